@@ -23,13 +23,16 @@ gather of the decoded (index, counts, ids, frames) over RCCL (gam_gather_ids, in
 Utterances are independent, so ranks own disjoint utterances with replicated weights.  Weights are random-init
 tensors of the exact architecture (gigaam_amd/synth.py; no checkpoints offline), arithmetic is fp32.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit,
+ms_per_step, dtype, ...); --dump-outputs DIR also writes what the last timed step returned (decoded ids / frames / counts,
+float32, padded with -1) as DIR/<name>.npy.  --full adds the legs that take runs of their own:
   roofline            the dominant kernel family (the GEMMs, incl. the implicit-GEMM stem conv), timed with HIP
                       events on the launch stream inside the timed region; achieved = algorithmic FLOP / event time
   roofline_f32_exact  the same steps re-timed with the dense contractions on exact-fp32 MFMA (the reference's own
                       arithmetic), so that figure is on the driver's clock too
   cpu_baseline        the REFERENCE's own modules (oracle/_ref, built by oracle/build_ref.py from /root/reference) on this
                       box's host cores (N=1 only), ids compared with the GPU's for every utterance of the sample
+  and board_power, pipelined, h2d, roofline_f16_fast, kernel_classes_ms_per_step (each still switchable off by its --no-* flag).
 """
 from __future__ import annotations
 
@@ -431,6 +434,24 @@ def ragged_host(dec):
     return rows
 
 
+def dump_outputs(path: str, rows) -> None:
+    """--dump-outputs: what the caller of the timed path received from its last step -- per utterance (or chunk) the decoded
+    ids and their frames (rows (ids, frames, ...); text, where the step also returns it, is a function of the ids) -- as
+    DIR/{ids,frames,counts}.npy, float32 (exact: ids and frames are far below 2**24), ids / frames padded with -1.  The
+    largest configuration (5: ~200 chunks x ~400 ids) writes well under 1 MB."""
+    import numpy as np
+    counts = np.array([len(r[0]) for r in rows], dtype=np.int64)
+    width = int(counts.max()) if len(rows) else 0
+    ids = np.full((len(rows), width), -1.0, dtype=np.float32)
+    frames = np.full((len(rows), width), -1.0, dtype=np.float32)
+    for k, r in enumerate(rows):
+        ids[k, :counts[k]] = r[0]
+        frames[k, :counts[k]] = r[1]
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("ids", ids), ("frames", frames), ("counts", counts.astype(np.float32))):
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def free_port() -> int:
     import socket
     with socket.socket() as so:
@@ -519,7 +540,7 @@ def main():
     ap.add_argument("--longform-seconds", type=int, default=3600, help="config 5")
     ap.add_argument("--fr-batch", type=int, default=16, help="config 5: chunks per batch (the reference's fr_batch_size default)")
     ap.add_argument("--layers", type=int, default=-1, help="debug only: fewer layers INVALIDATES the number")
-    ap.add_argument("--cpu-utts", type=int, default=-1, help="utterances in the CPU reference leg (0 = skip; default: 32 -- all of configs 2 / 3, "
+    ap.add_argument("--cpu-utts", type=int, default=-1, help="--full: utterances in the CPU reference leg (0 = skip; default: 32 -- all of configs 2 / 3, "
                     "the first batch of config 4, the first two batches of config 5)")
     ap.add_argument("--no-port-leg", action="store_true", help="config 2: do not time oracle/gigaam_oracle.py beside the reference")
     ap.add_argument("--rnnt-blank-bias", type=float, default=None,
@@ -538,6 +559,10 @@ def main():
     ap.add_argument("--gemm", default="f16x3", choices=["f16x3", "f32", "f16"],
                     help="dense-contraction arithmetic: split-fp16 MFMA (fp32-equivalent, default), exact fp32 MFMA, or the opt-in "
                          "one-term fp16 speed mode (the reference's GPU autocast contract; its line is marked, never the headline)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline: per-kernel HIP-event timing (roofline), "
+                    "board power, pipelined and host-memory re-timings, exact-fp32 and fp16 re-timings, the CPU reference baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (decoded ids / "
+                    "frames / counts as float32, padded with -1) to DIR/<name>.npy")
     ap.add_argument("--launch-selftest", action="store_true", help="CPU-only check of the rank plumbing (gloo); no GPU work")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="rehearsal on a box with fewer GPUs than ranks: ranks share devices (rank %% device_count) and "
@@ -843,9 +868,11 @@ def main():
     for _ in range(args.warmup):
         step()
     drain()
-    do_prof = not args.no_profile
+    do_prof = args.full and not args.no_profile
     dt, out = timed(args.steps, do_prof)
     timed_region = dict(timed_diag)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last5["res"] if cfgno == 5 else out)
     prof = prof_all = None
     if do_prof:
         prof = eng.profile_read()
@@ -858,7 +885,7 @@ def main():
 
     # board power and shader clock over ~2 s of untimed steps (one rank: the hwmon files are per board)
     power = None
-    if n_ranks == 1 and not args.no_power and cfgno in (2, 3):
+    if args.full and n_ranks == 1 and not args.no_power and cfgno in (2, 3):
         n_pw = max(5, int(2.0 / max(1e-3, dt / args.steps)))
         with PowerSampler(dev.index or 0) as ps:
             for _ in range(n_pw):
@@ -876,7 +903,7 @@ def main():
     # launched -- what transcribe_longform / shard.run_sharded do and what config 3's step already is; the D2H copy and the host-side list
     # building then run under the next batch's kernels.  Reported beside `value` (whose step ends with its own ids on the host), never as it.
     pipe_leg = None
-    if n_ranks == 1 and cfgno == 2 and not is_rnnt and not args.no_h2d_leg:
+    if args.full and n_ranks == 1 and cfgno == 2 and not is_rnnt and not args.no_h2d_leg:
         k_p = max(3, min(args.steps, 10))
         ragged_host(decode_dev(wav, wlen))
         barrier_sync()
@@ -895,7 +922,7 @@ def main():
                             "informational -- `value` ends every step with its own ids on the host"}
 
     h2d_leg = None
-    if n_ranks == 1 and cfgno == 2 and not args.no_h2d_leg:
+    if args.full and n_ranks == 1 and cfgno == 2 and not args.no_h2d_leg:
         from gigaam_amd.feeder import BatchFeeder
         wav_pin, len_pin = wav_h.pin_memory(), wlen_h.pin_memory()
         k_h = max(3, min(args.steps, 10))
@@ -938,7 +965,7 @@ def main():
 
     # exact-fp32 leg: the same steps with the dense contractions on v_mfma_f32_32x32x2_f32 (the reference's arithmetic)
     f32_leg = None
-    if args.gemm == "f16x3" and not args.no_f32_leg and cfgno in (2, 3):
+    if args.full and args.gemm == "f16x3" and not args.no_f32_leg and cfgno in (2, 3):
         eng.set_gemm_mode("f32")
         for _ in range(2):
             step()
@@ -952,7 +979,7 @@ def main():
     # opt-in speed mode leg: the same steps with ONE fp16 MFMA per product (GAM_GEMM_F16: the reference's own GPU contract, fp16
     # autocast) -- reported beside the headline with how the decoded ids compare and how wide the default mode's CTC margins are
     f16_leg = None
-    if args.gemm == "f16x3" and not args.no_f16_leg and n_ranks == 1 and cfgno in (2, 3):
+    if args.full and args.gemm == "f16x3" and not args.no_f16_leg and n_ranks == 1 and cfgno in (2, 3):
         eng.set_gemm_mode("f16")
         for _ in range(2):
             step()
@@ -1123,7 +1150,7 @@ def main():
             leg["ctc_margins"] = margins
         line["roofline_f16_fast"] = leg
     n_cpu = args.cpu_utts if args.cpu_utts >= 0 else 32
-    if n_ranks == 1 and n_cpu > 0 and cpu_sample is not None:
+    if args.full and n_ranks == 1 and n_cpu > 0 and cpu_sample is not None:
         try:
             cb, gidx = cpu_sample
             # at most n_cpu utterances: whole batches, the last one cut by ROWS only (the padded width -- what the reference's

@@ -29,7 +29,7 @@ def main():
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         for c in [int(x) for x in args.only.split(",")]:
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + EXTRA[c], capture_output=True, text=True)
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + EXTRA[c], capture_output=True, text=True)
             if r.returncode != 0:
                 print(f"config {c} failed:\n{r.stderr[-2000:]}")
                 continue

@@ -25,7 +25,7 @@ else
 fi
 run() {   # run <name> <bench args...>
   name=$1; shift
-  ( time timeout 900 python bench.py "$@" ) 2> "$out/$name.err" | grep -a '^{' | tail -1 > "$out/$name.json"
+  ( time timeout 900 python bench.py --full "$@" ) 2> "$out/$name.err" | grep -a '^{' | tail -1 > "$out/$name.json"
   if [ ! -s "$out/$name.json" ]; then echo "$name: NO LINE (see $out/$name.err)"; tail -5 "$out/$name.err"; fail=1; return; fi
   cat "$out/$name.json" >> "$out/scale8.jsonl"
   python - "$out/$name.json" "$name" <<'PY' || fail=1

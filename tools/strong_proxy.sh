@@ -10,7 +10,7 @@ C="--steps 30 --warmup 8 --no-f32-leg --no-h2d-leg --no-f16-leg --no-power --cpu
 rm -f $OUT/strong_proxy.jsonl
 for b in 32 16 8 4 2; do
   ( timeout 300 python bench.py --batch $b $C --no-profile ) 2> $OUT/b$b.err | grep -a '^{' > $OUT/b$b.json
-  ( timeout 300 python bench.py --batch $b $C ) 2>> $OUT/b$b.err | grep -a '^{' > $OUT/b${b}_profiled.json
+  ( timeout 300 python bench.py --batch $b $C --full ) 2>> $OUT/b$b.err | grep -a '^{' > $OUT/b${b}_profiled.json
   python - $OUT/b$b.json $OUT/b${b}_profiled.json $OUT/strong_proxy.jsonl <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read()); p = json.loads(open(sys.argv[2]).read())
