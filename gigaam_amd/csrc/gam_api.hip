@@ -23,7 +23,6 @@
 #include "gam_decode_cluster.h"
 #include "gam_frontend.h"
 #include "gam_gemm.h"
-#include "gam_gemm16.h"
 #include "gam_gemm_sp.h"
 #include "gam_norm.h"
 #include "gam_pack.h"
@@ -46,12 +45,10 @@ struct DevBuf {
   size_t cap = 0;  // floats
 };
 
-struct W16 {            // split-fp16 planes of one weight matrix (gam_gemm16.h)
-  _Float16* hi = nullptr;
-  _Float16* lo = nullptr;
-  _Float16* sp = nullptr;   // the same planes in the sp32 layout (gam_gemm_sp.h)
-  _Float16* h16 = nullptr;  // GAM_GEMM_F16: the hi plane as the one-term kernel walks it (= hi; a tap-permuted copy for the stem conv)
-  float inv = 1.0f;
+struct W16 {            // split-fp16 operand of one weight matrix (gam_gemm_sp.h): W * 2^s = hi + lo
+  _Float16* sp = nullptr;   // (hi, lo) in the sp32 layout
+  _Float16* h16 = nullptr;  // GAM_GEMM_F16: the hi plane as the one-term kernel walks it (row-major; a tap-permuted copy for the stem conv)
+  float inv = 1.0f;         // 2^-s
 };
 
 struct LayerW {
@@ -95,6 +92,7 @@ struct gam_handle {
   std::vector<LayerW> layers;
   float *rot_cos = nullptr, *rot_sin = nullptr;
   float* rel_pe = nullptr;  // rel_pos: sinusoid table, row r + (max_len-1) <-> relative position r
+  float* rel_pe_sp = nullptr;   // the same table in the sp32 layout (same bytes, same row offsets): linear_pos's split-fp16 A operand
   // heads
   float *ctc_w = nullptr, *ctc_b = nullptr;
   float *emo_w = nullptr, *emo_b = nullptr;
@@ -127,8 +125,6 @@ struct gam_handle {
 
   // workspace (grow-only)
   DevBuf wavp, spec, img, c2, xin, y1, x, y, yr, hbuf, qkv, ctx, ubuf, zbuf, tok, logits, encp, pbuf, aplanes;
-  int use_sp = 1;     // large-M GEMMs on the LDS-DMA sp32 kernel (GAM_SP=0 disables)
-  int sp_min_m = GAM_SP_MIN_M;   // GAM_SP_MIN_M overrides (tests force the sp path at small sizes)
   DevBuf op_planes, op_sp, splitk_ws;   // gam_op_gemm operand planes; split-K partial sums
   DevBuf dec_splitk_ws;                 // split-K partial sums of the DECODE class's GEMMs: a decode may run on a side stream beside
                                         // the next batch's encoder (r05), so it shares no scratch with it (tok / logits / encp / rnnt_x
@@ -245,9 +241,10 @@ float half_to_float(uint16_t x) {
 float half_bits_to_float(uint16_t x) { return half_to_float(x); }
 
 // W * 2^shift = hi + lo with hi, lo in fp16; the power-of-two scale puts max|W| near 2^8 so
-// that lo (~2^-11 |W|) stays in the normal fp16 range for all but negligible entries.
+// that lo (~2^-11 |W|) stays in the normal fp16 range for all but negligible entries.  K = the reduction length (row
+// pitch of W): the sp32 copy exists when K % 32 == 0.
 // conv_taps > 0 (K = conv_taps * C, k = tap * C + c): the sp32 copy orders its k-tiles (32-channel block, tap) -- taps
-// innermost, the order gam_gemm_sp_kernel walks an implicit-GEMM A operand in; the fp16 planes keep k as given.
+// innermost, the order gam_gemm_sp_kernel walks an implicit-GEMM A operand in; the h16 plane does the same with 64-channel blocks.
 int make_split(gam_handle* h, const std::vector<float>& w, W16& out, int K = 0, int conv_taps = 0) {
   float mx = 0.f;
   for (float v : w) mx = std::max(mx, fabsf(v));
@@ -262,32 +259,22 @@ int make_split(gam_handle* h, const std::vector<float>& w, W16& out, int K = 0, 
     hi[i] = hb;
     lo[i] = float_to_half_bits(v - half_bits_to_float(hb));
   }
-  const size_t bytes = std::max<size_t>(w.size(), 8) * 2 + 64;
-  void *dh = nullptr, *dl = nullptr;
-  if (hipMalloc(&dh, bytes) != hipSuccess || hipMalloc(&dl, bytes) != hipSuccess) return -2;
-  h->owned.push_back(dh);
-  h->owned.push_back(dl);
-  if (hipMemcpy(dh, hi.data(), w.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -2;
-  if (hipMemcpy(dl, lo.data(), w.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -2;
-  out.hi = (_Float16*)dh;
-  out.lo = (_Float16*)dl;
-  out.h16 = out.hi;
   out.inv = ldexpf(1.0f, -shift);
+  std::vector<uint16_t> hp(hi);
   if (conv_taps > 0 && K > 0 && (K / conv_taps) % 64 == 0 && w.size() % (size_t)K == 0) {
     // one-term kernel, implicit-GEMM A operand: k-tile = 64 channels of one tap, taps innermost within a 64-channel block
     const size_t C = (size_t)K / conv_taps, cb64 = C / 64;
-    std::vector<uint16_t> hp(w.size());
     for (size_t n = 0; n < w.size() / K; ++n)
       for (size_t cb = 0; cb < cb64; ++cb)
         for (size_t t = 0; t < (size_t)conv_taps; ++t)
           for (size_t j = 0; j < 64; ++j)
             hp[n * K + (cb * conv_taps + t) * 64 + j] = hi[n * K + t * C + cb * 64 + j];
-    void* dp = nullptr;
-    if (hipMalloc(&dp, hp.size() * 2 + 64) != hipSuccess) return -2;
-    h->owned.push_back(dp);
-    if (hipMemcpy(dp, hp.data(), hp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -2;
-    out.h16 = (_Float16*)dp;
   }
+  void* dp = nullptr;
+  if (hipMalloc(&dp, std::max<size_t>(w.size(), 8) * 2 + 64) != hipSuccess) return -2;
+  h->owned.push_back(dp);
+  if (hipMemcpy(dp, hp.data(), w.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -2;
+  out.h16 = (_Float16*)dp;
   if (K > 0 && K % 32 == 0 && w.size() % (size_t)K == 0) {
     // the same planes in the sp32 layout: row n, k-block kb -> [hi x32 | lo x32] (gam_gemm_sp.h)
     std::vector<uint16_t> sp(w.size() * 2);
@@ -372,7 +359,6 @@ int gemm(gam_handle* h, hipStream_t s, const GamGemmArgs& a_in, int act, int cls
   if (int r = flush_pending(h, s, defer)) return r;   // (an unconsumed deferral must not be overwritten: its C would stay unreduced)
   a.range_flag = h->use_range ? h->range_flag : nullptr;
   if (!split_mode(h)) a.c_guard = 0;   // fp32 consumers have no range limit
-  if (!split_mode(h) || w16 == nullptr || w16->hi == nullptr) a.a_rs = nullptr;   // exact-fp32 path: A is never scaled
   ProfScope ps(h, s, cls, 2.0 * (double)a.M * (double)a.N * (double)a.K);
   if (ps.ev) {   // unique bytes: A (overlapping rows counted once), W, C (+ residual)
     const double abytes = a.a_mode == 0 ? ((double)(a.M - 1) * (double)std::min<long>(a.lda, a.K) + a.K) * 4.0
@@ -380,10 +366,10 @@ int gemm(gam_handle* h, hipStream_t s, const GamGemmArgs& a_in, int act, int cls
     h->prof_bytes[cls] += abytes * (a.n_switch > 0 ? 2.0 : 1.0) + 4.0 * a.N * a.K + 4.0 * a.M * a.N * (a.R ? 2.0 : 1.0);   // (n_switch: two A operands)
   }
   hipError_t e;
-  const bool f16 = split_mode(h) && w16 != nullptr && w16->hi != nullptr;
-  if (f16 && a.Asp != nullptr) {
-    if (w16->sp == nullptr) return fail(h, -2, "sp32 A without sp32 W planes");
-    a.Whi = w16->hi; a.Wlo = w16->lo; a.wscale_inv = w16->inv;
+  if (a.Asp != nullptr) {   // split-fp16 operands: gam_gemm_sp_kernel
+    if (!split_mode(h)) return fail(h, -2, "sp32 A operand outside the split-fp16 GEMM mode");
+    if (w16 == nullptr || w16->sp == nullptr) return fail(h, -2, "sp32 A without sp32 W planes");
+    a.wscale_inv = w16->inv;
     a.Wsp = w16->sp;
     a.h16 = 0;
     if (a.a_fmt == 2) {
@@ -415,7 +401,9 @@ int gemm(gam_handle* h, hipStream_t s, const GamGemmArgs& a_in, int act, int cls
     }
     return 0;
   }
-  if (a.Asp != nullptr) return fail(h, -2, "sp32 A operand outside the split-fp16 GEMM mode");
+  // Everything else runs on the exact-fp32 kernel: the exact mode, the decode heads, and the split modes' GEMMs without sp32
+  // operands (shapes the LDS-DMA kernel cannot take).  Its A is never row-scaled and its C is fp32.
+  if (a.a_rs != nullptr || a.c_split) return fail(h, -2, "row-scaled A or split C without sp32 operands (M=%d N=%d K=%d)", a.M, a.N, a.K);
   // Split-K for grids that would leave most CUs idle (single clips, short batches: 126 tokens x 768
   // columns = 6 tiles): S slices of K write partial sums, a second pass sums them in a fixed order
   // (bit-reproducible) and applies the epilogue.
@@ -433,12 +421,7 @@ int gemm(gam_handle* h, hipStream_t s, const GamGemmArgs& a_in, int act, int cls
     if (int r = ensure(h, ws, (size_t)S * a.M * a.N + 64)) return r;
     a.splitk = S; a.ldw = a.K; a.K = a.K / S; a.partial = ws.p;
   }
-  if (f16) {
-    a.Whi = w16->hi; a.Wlo = w16->lo; a.wscale_inv = w16->inv;
-    e = gam_launch_gemm16(a, act, s);
-  } else {
-    e = gam_launch_gemm(a, act, s);
-  }
+  e = gam_launch_gemm(a, act, s);
   if (e != hipSuccess) return fail(h, -2, "gemm launch (M=%d N=%d K=%d): %s", a.M, a.N, a.K, hipGetErrorString(e));
   if (S > 1) {
     full.partial = a.partial;
@@ -507,8 +490,6 @@ int gam_create(const gam_config* cfg, int device_id, gam_handle** out) {
   h->cfg = *cfg;
   h->device = device_id;
   *out = h;
-  if (const char* e = getenv("GAM_SP")) h->use_sp = atoi(e);
-  if (const char* e = getenv("GAM_SP_MIN_M")) h->sp_min_m = atoi(e);
   if (const char* e = getenv("GAM_SPLITK")) h->use_splitk = atoi(e);
   if (const char* e = getenv("GAM_PACK")) h->use_pack = atoi(e);
   if (const char* e = getenv("GAM_FUSE_REDUCE")) h->fuse_reduce = atoi(e);
@@ -714,10 +695,10 @@ int gam_finalize(gam_handle* h) {
       for (int ci = 0; ci < C; ++ci)
         for (int k = 0; k < ks; ++k) r2[((size_t)n * ks + k) * C + ci] = w2->data[((size_t)n * C + ci) * ks + k];
     UP(h->c1_w, r0);
-    if (make_split(h, r0, h->s_c1)) return fail(h, -2, "split upload failed");
+    if (make_split(h, r0, h->s_c1, ks * F)) return fail(h, -2, "split upload failed");
     UP(h->c1_b, b0->data);
     UP(h->c2_w, r2);
-    if (make_split(h, r2, h->s_c2)) return fail(h, -2, "split upload failed");
+    if (make_split(h, r2, h->s_c2, ks * C)) return fail(h, -2, "split upload failed");
     UP(h->c2_b, b2->data);
   }
 
@@ -776,7 +757,7 @@ int gam_finalize(gam_handle* h) {
       NEED(pu, p + "self_attn.pos_bias_u", D);
       NEED(pv, p + "self_attn.pos_bias_v", D);
       UP(L.wpos, wp->data);
-      if (make_split(h, wp->data, L.s_wpos)) return fail(h, -2, "split upload failed");
+      if (make_split(h, wp->data, L.s_wpos, D)) return fail(h, -2, "split upload failed");
       UP(L.pos_u, pu->data);
       UP(L.pos_v, pv->data);
     }
@@ -841,6 +822,13 @@ int gam_finalize(gam_handle* h) {
       }
     }
     UP(h->rel_pe, pe);
+    // its sp32 copy, split by the kernel that splits every other fp32 operand (D % 32 == 0: a row starts on a 32-element block)
+    HIPCHK(h, hipMalloc(&h->rel_pe_sp, pe.size() * sizeof(float)));
+    h->owned.push_back(h->rel_pe_sp);
+    hipLaunchKernelGGL(gam_to_sp32_kernel, dim3((int)std::min<size_t>((pe.size() / 4 + 255) / 256, 4096)), dim3(256), 0, nullptr, h->rel_pe,
+                       reinterpret_cast<_Float16*>(h->rel_pe_sp), pe.size() / 4, (const float*)nullptr, D);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(nullptr));
   }
 
   h->has_encoder = build_encoder;
@@ -1071,10 +1059,10 @@ static int encode_impl(gam_handle* h, const float* feat, const int64_t* feat_len
     }
   }
 
-  // Large batches: every big GEMM runs on the LDS-DMA kernel of gam_gemm_sp.h, and the kernels that
+  // Split-fp16 modes: every encoder GEMM runs on the LDS-DMA kernel of gam_gemm_sp.h, and the kernels that
   // produce its A operands (LayerNorm, SiLU epilogue, attention, conv module, stem) write them in the
   // sp32 split layout instead of fp32 -- same bytes, no conversion pass.
-  const bool sp = split_mode(h) && h->use_sp && N >= h->sp_min_m && D % 32 == 0 && DFF % 32 == 0;
+  const bool sp = split_mode(h) && D % 32 == 0 && DFF % 32 == 0;
   // operand format the producers write (gam_common.h gam_store4).  Format 2 (plain fp16, GAM_GEMM_F16) packs 64 k-values into
   // the 128-byte line of a k-tile, so every reduction length / row pitch must be a multiple of 64; a model whose d_model or
   // FFN width is 32 x an odd number keeps the three-term kernels for its GEMMs in that mode (as gam_op_gemm does)
@@ -1121,20 +1109,28 @@ static int encode_impl(gam_handle* h, const float* feat, const int64_t* feat_len
     const int T1a = std::max(T1, (int)((T + 2 * pad + 1) / 2));
     if (int r = ensure(h, h->xin, ((size_t)B * 2 * T1a + 8) * F)) return r;
     if (int r = ensure(h, h->y1, ((size_t)B * 2 * Ta + 8) * C)) return r;
+    // Both GEMMs read overlapping rows (lda = 2F / 2C < K).  In the split modes xin and y1 hold sp32 (a row starts on a 32-element
+    // block of the flat buffer, F % 32 == 0), and both GEMMs are three-term in the one-term mode too.  All-zero bits are an sp32 zero.
+    const bool sp_stem = sp && F % 32 == 0;
     {
       ProfScope ps(h, s, GAM_PF_STEM, (double)B * T * F * 8.0);
       HIPCHK(h, hipMemsetAsync(h->xin.p, 0, ((size_t)B * 2 * T1a + 8) * F * sizeof(float), s));
       HIPCHK(h, hipMemsetAsync(h->y1.p, 0, ((size_t)B * 2 * Ta + 8) * C * sizeof(float), s));
       dim3 grid(gam_cdiv(T, 32), gam_cdiv(F, 32), B);
-      hipLaunchKernelGGL(gam_feat_to_rows_kernel, grid, dim3(256), 0, s, feat, h->xin.p, len0, B, F, (int)T, 2 * T1a, pad);
+      int* const rf = h->use_range ? h->range_flag : nullptr;
+      if (sp_stem) hipLaunchKernelGGL(gam_feat_to_rows_kernel<1>, grid, dim3(256), 0, s, feat, h->xin.p, len0, B, F, (int)T, 2 * T1a, pad, rf);
+      else hipLaunchKernelGGL(gam_feat_to_rows_kernel<0>, grid, dim3(256), 0, s, feat, h->xin.p, len0, B, F, (int)T, 2 * T1a, pad, rf);
       HIPCHK(h, hipGetLastError());
     }
     GamGemmArgs g1 = gemm_args(h->xin.p, 2L * F, h->c1_w, h->c1_b, h->y1.p, C, B * T1a, C, ks * F);
     g1.lens = len1; g1.rpb = T1a; g1.fdiv = 1;
     g1.remap = 1; g1.out_rpb = 2 * Ta; g1.out_shift = pad; g1.rows_valid = std::min(T1a, 2 * Ta - pad);
+    if (sp_stem) { g1.Asp = reinterpret_cast<const _Float16*>(g1.A); g1.a_fmt = 1; g1.c_split = 1; }
+    g1.c_guard = 1;
     if (int r = gemm(h, s, g1, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c1)) return r;
     GamGemmArgs g2 = gemm_args(h->y1.p, 2L * C, h->c2_w, h->c2_b, packed ? h->y.p : h->x.p, D, N, D, ks * C);
     g2.lens = len2; g2.rpb = Ta; g2.fdiv = 1;
+    if (sp_stem) { g2.Asp = reinterpret_cast<const _Float16*>(g2.A); g2.a_fmt = 1; }
     if (int r = gemm(h, s, g2, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c2)) return r;
   }
   if (packed) {   // the stem's padded rows -> packed rows (the only copy the layout costs: 2 x NR x D x 4 bytes)
@@ -1155,8 +1151,8 @@ static int encode_impl(gam_handle* h, const float* feat, const int64_t* feat_len
   memset(&ln, 0, sizeof ln);
   ln.rows = NR; ln.d = D; ln.ta = Ta; ln.row_t = row_t; ln.dk = dk; ln.eps = 1e-5f; ln.rcos = h->rot_cos; ln.rsin = h->rot_sin;
   ln.rope_rows = c.pos_emb_max_len;
-  // split-fp16 modes: every LayerNorm hands its GEMMs a per-row power-of-two scale (gam_row_scale)
-  float* const rs = split_mode(h) && h->use_rowscale ? h->rsbuf.p : nullptr;
+  // sp32 operands: every LayerNorm hands its GEMMs a per-row power-of-two scale (gam_row_scale; the exact-fp32 kernel undoes none)
+  float* const rs = sp && h->use_rowscale ? h->rsbuf.p : nullptr;
   ln.rs = rs;
   if (nl > 0) {
     GamLnArgs a = ln;
@@ -1197,15 +1193,16 @@ static int encode_impl(gam_handle* h, const float* feat, const int64_t* feat_len
         if (int r = gemm(h, s, gq, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wqkv)) return r;
         W16 wv16 = L.s_wqkv;   // rows 2D .. 3D of the same planes
         const size_t off = (size_t)2 * D * D;
-        if (wv16.hi) { wv16.hi += off; wv16.lo += off; }
+        wv16.h16 += off;
         if (wv16.sp) wv16.sp += 2 * off;
         GamGemmArgs gv = gemm_args(h->y.p, D, L.wqkv + off, L.bqkv + 2 * D, h->qkv.p + 2 * D, 3 * D, NR, D, D);
         sp_a(gv); gv.a_rs = rs; gv.c_guard = 1;
         if (int r = gemm(h, s, gv, GAM_ACT_NONE, GAM_PF_GEMM, &wv16)) return r;
       }
       if (rel) {  // P = linear_pos(pos_emb) for relative positions -(T'-1) .. T'-1 (no bias)
-        const float* pe0 = h->rel_pe + (size_t)(c.pos_emb_max_len - 1 - (Tv - 1)) * D;
-        GamGemmArgs gp = gemm_args(pe0, D, L.wpos, nullptr, h->pbuf.p, D, 2 * Tv - 1, D, D);
+        const size_t pe0 = (size_t)(c.pos_emb_max_len - 1 - (Tv - 1)) * D;
+        GamGemmArgs gp = gemm_args(h->rel_pe + pe0, D, L.wpos, nullptr, h->pbuf.p, D, 2 * Tv - 1, D, D);
+        if (sp) { gp.Asp = reinterpret_cast<const _Float16*>(h->rel_pe_sp + pe0); gp.a_fmt = 1; }   // (three-term in the one-term mode too)
         if (int r = gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wpos)) return r;
       }
       GamAttnArgs at;
@@ -1641,51 +1638,36 @@ int gam_op_gemm(gam_handle* h, const float* A, const float* W, const float* bias
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->device));
   GamGemmArgs g = gemm_args(A, K, W, bias, C, N, M, N, K);
-  if (!split_mode(h)) return gemm(h, (hipStream_t)stream, g, act);
-  // split-fp16 mode: the W planes are rebuilt on the device (unit scale) on every call -- a cache keyed
-  // on the W pointer returned stale planes when an allocator handed the same address to a new matrix
-  // of the same size.  This is a test / microbenchmark entry; the HIP-event profile class times only
-  // the GEMM launch below, not these conversions.
   hipStream_t s = (hipStream_t)stream;
-  const size_t count = ((size_t)N * K + 7) / 8 * 8;
-  {
-    if (int r = ensure(h, h->op_planes, count + 64)) return r;
-    _Float16* hi = (_Float16*)h->op_planes.p;
-    hipLaunchKernelGGL(gam_split_kernel, dim3((int)std::min<size_t>((count / 4 + 255) / 256, 4096)), dim3(256), 0, s, W, hi,
-                       hi + count + 8, count / 4);
-  }
-  W16 w16;
-  w16.hi = (_Float16*)h->op_planes.p; w16.lo = w16.hi + count + 8; w16.inv = 1.0f;
-  w16.h16 = w16.hi;
+  // the exact-fp32 kernel: the exact mode, and the shapes the LDS-DMA kernel cannot take (its epilogue moves 4-column pieces)
+  if (!split_mode(h) || K % 32 != 0 || N % 4 != 0) return gemm(h, s, g, act);
+  // split-fp16 modes: both operands converted by pre-passes on every call (in the encoder the producing kernels write sp32
+  // directly and the weight planes are built at gam_finalize) -- a cache keyed on the W pointer returned stale planes when an
+  // allocator handed the same address to a new matrix of the same size.  This is a test / microbenchmark entry; the HIP-event
+  // profile class times only the GEMM launch, not these conversions.
+  const size_t wn = (size_t)N * K, an = (size_t)M * K;
+  W16 w16;   // unit scale
+  if (int r = ensure(h, h->op_sp, wn + 64)) return r;
+  hipLaunchKernelGGL(gam_to_sp32_kernel, dim3((int)std::min<size_t>((wn / 4 + 255) / 256, 4096)), dim3(256), 0, s, W,
+                     (_Float16*)h->op_sp.p, wn / 4, (const float*)nullptr, K);
+  w16.sp = (_Float16*)h->op_sp.p;
   // per-row power-of-two scale of A, as the LayerNorm kernels provide it inside the encoder
   if (int r = ensure(h, h->op_rs, (size_t)M + 64)) return r;
   hipLaunchKernelGGL(gam_rowscale_kernel, dim3(gam_cdiv(M, 4)), dim3(256), 0, s, A, h->op_rs.p, M, K, (long)K);
   g.a_rs = h->op_rs.p;
-  if (h->use_sp && K % 32 == 0 && N % 4 == 0 && M >= h->sp_min_m) {
-    // sp32 operands by pre-passes (in the encoder the producing kernels write sp32 directly and the
-    // weight planes are built at gam_finalize)
-    const size_t wn = (size_t)N * K, an = (size_t)M * K;
-    if (int r = ensure(h, h->op_sp, wn + 64)) return r;
-    hipLaunchKernelGGL(gam_to_sp32_kernel, dim3((int)std::min<size_t>((wn / 4 + 255) / 256, 4096)), dim3(256), 0, s, W,
-                       (_Float16*)h->op_sp.p, wn / 4, (const float*)nullptr, K);
-    if (int r = ensure(h, h->aplanes, an + 64)) return r;
-    g.a_fmt = (h->gemm_mode == GAM_GEMM_F16 && K % 64 == 0) ? 2 : 1;   // (other K: the three-term kernels, whatever the mode)
-    if (g.a_fmt == 2)
-      hipLaunchKernelGGL(gam_to_h16_kernel, dim3((int)std::min<size_t>((an / 4 + 255) / 256, 8192)), dim3(256), 0, s, A,
-                         (_Float16*)h->aplanes.p, an / 4, (const float*)h->op_rs.p, K);
-    else
-      hipLaunchKernelGGL(gam_to_sp32_kernel, dim3((int)std::min<size_t>((an / 4 + 255) / 256, 8192)), dim3(256), 0, s, A,
-                         (_Float16*)h->aplanes.p, an / 4, (const float*)h->op_rs.p, K);
-    w16.sp = (_Float16*)h->op_sp.p;
-    g.Asp = (const _Float16*)h->aplanes.p;
-  } else if (K % 4 == 0) {   // 128x128 kernel: a row-scaled fp32 copy of A (what the LayerNorm kernels write inside the encoder)
-    const size_t an = (size_t)M * K;
-    if (int r = ensure(h, h->aplanes, an + 64)) return r;
-    hipLaunchKernelGGL(gam_scale_rows_kernel, dim3((int)std::min<size_t>((an / 4 + 255) / 256, 8192)), dim3(256), 0, s, A,
-                       h->aplanes.p, an / 4, (const float*)h->op_rs.p, K);
-    g.A = h->aplanes.p;
+  if (int r = ensure(h, h->aplanes, an + 64)) return r;
+  g.Asp = (const _Float16*)h->aplanes.p;
+  g.a_fmt = (h->gemm_mode == GAM_GEMM_F16 && K % 64 == 0) ? 2 : 1;   // (other K: the three-term kernel, whatever the mode)
+  if (g.a_fmt == 2) {
+    if (int r = ensure(h, h->op_planes, wn / 2 + 64)) return r;
+    w16.h16 = (_Float16*)h->op_planes.p;
+    hipLaunchKernelGGL(gam_to_h16_kernel, dim3((int)std::min<size_t>((wn / 4 + 255) / 256, 4096)), dim3(256), 0, s, W, w16.h16,
+                       wn / 4, (const float*)nullptr, K);
+    hipLaunchKernelGGL(gam_to_h16_kernel, dim3((int)std::min<size_t>((an / 4 + 255) / 256, 8192)), dim3(256), 0, s, A,
+                       (_Float16*)h->aplanes.p, an / 4, (const float*)h->op_rs.p, K);
   } else {
-    g.a_rs = nullptr;
+    hipLaunchKernelGGL(gam_to_sp32_kernel, dim3((int)std::min<size_t>((an / 4 + 255) / 256, 8192)), dim3(256), 0, s, A,
+                       (_Float16*)h->aplanes.p, an / 4, (const float*)h->op_rs.p, K);
   }
   return gemm(h, s, g, act, GAM_PF_GEMM, &w16);
 }

@@ -1,5 +1,5 @@
 // gam_attn16.h -- the fused attention of gam_attn.h with both small GEMMs evaluated as
-// three-term fp16 splits on the fp16 matrix cores (see gam_gemm16.h for the numerics):
+// three-term fp16 splits on the fp16 matrix cores (see gam_gemm_sp.h for the numerics):
 //   S^T = K.Q^T        ~  K_hi.Q_hi + K_hi.Q_lo + K_lo.Q_hi
 //   O^T = V^T.P^T      ~  V_hi.P_hi + V_hi.P_lo + V_lo.P_hi        (fp32 accumulate)
 // d_k = 48 is contracted as one v_mfma_f32_16x16x32_f16 (d 0..31) + one
@@ -11,7 +11,6 @@
 // an odd number of 16-byte slots).  Same work decomposition as gam_attn_f32_kernel.
 #pragma once
 #include "gam_attn.h"
-#include "gam_gemm16.h"
 
 #define GAM_A16_KLD 56   // halfs per K-plane row  (112 B = 7 x 16 B)
 #define GAM_A16_VLD 72   // halfs per V^T-plane row (144 B = 9 x 16 B)

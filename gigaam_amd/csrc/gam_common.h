@@ -50,7 +50,7 @@ typedef _Float16 gam_half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 gam_half8 __attribute__((ext_vector_type(8)));
 typedef unsigned gam_u32x4 __attribute__((ext_vector_type(4)));
 
-// x = hi + lo, hi = fp16(x), lo = fp16(x - hi): the split-fp16 operand format (gam_gemm16.h).
+// x = hi + lo, hi = fp16(x), lo = fp16(x - hi): the split-fp16 operand format (gam_gemm_sp.h).
 // Two elements cost 4 VALU instructions: one packed convert for the hi pair, one v_fma_mix_f32 per element for x - hi (the
 // mixed-precision FMA reads the fp16 half in place: no convert back), one packed convert for the lo pair.  hipcc's own code for
 // the C expression is 13 instructions per 4 elements (it converts every hi back to fp32 first); the split sits in VALU-bound

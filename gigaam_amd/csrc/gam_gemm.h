@@ -53,9 +53,6 @@ struct GamGemmArgs {
   // packed-row batches (gam_pack.h): the stem still runs on the padded layout, but a row tile that lies wholly inside ONE utterance's
   // padding frames (t >= lens[b] for all its rows) produces nothing the gather behind the stem reads -- gam_gemm_sp_kernel returns at once
   int skip_pad;
-  // split-fp16 operand planes of W (gam_gemm16.h): W * 2^wshift = Whi + Wlo (+ ~2^-22 |W|)
-  const _Float16* Whi;
-  const _Float16* Wlo;
   // both operands in the sp32 layout of gam_gemm_sp.h (row pitch = lda / K elements, 4 B each)
   const _Float16* Asp;
   const _Float16* Wsp;
@@ -68,7 +65,7 @@ struct GamGemmArgs {
   // full row pitch of W; slice s reads columns [s*K, (s+1)*K) and writes its raw partial sums to
   // partial[s][M][N]; gam_splitk_reduce_kernel applies the epilogue.  0 / 1 = off.
   int splitk;
-  long ldw;             // row pitch of W / Whi / Wlo in elements (0 = K)
+  long ldw;             // row pitch of W in elements (0 = K)
   float* partial;
   int sp_mt, sp_nw;     // LDS-DMA GEMM: the plan's tile shape (gam_gemm_sp_plan); 0 = let the launcher plan (no split-K)
   int sp_ns;            // LDS stages of the plan (2 or 3)
@@ -94,16 +91,13 @@ struct GamGemmArgs {
 #define GAM_GEMM_BN 128
 #define GAM_GEMM_BK 32
 #define GAM_GEMM_LD 36
-#define GAM_GEMM_SMEM(NBUF) ((NBUF) * (GAM_GEMM_BM + GAM_GEMM_BN) * GAM_GEMM_LD * 4)
+#define GAM_GEMM_SMEM ((GAM_GEMM_BM + GAM_GEMM_BN) * GAM_GEMM_LD * 4)
 
-// ---- shared epilogue.  C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5)
+// ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5)
 template <int ACT>
 __device__ __forceinline__ void gam_gemm_epilogue(const GamGemmArgs& g, const f32x16& acc00, const f32x16& acc01,
                                                   const f32x16& acc10, const f32x16& acc11, int m0, int n0, int wm,
-                                                  int wn, int lane, float accscale, const float* rs_lds = nullptr) {
-  // rs_lds: the tile's per-row A-operand factors (a_rs[m0 + i]) staged in LDS by the caller, or null (none).  (They were
-  // first loaded into a 16-register array per 32-row slab here: +32 VGPRs, and the pipelined 128x128 kernel dropped
-  // from 3 to 2 waves per SIMD -- a single 5 s clip went from 3.6 to 4.6 ms.)
+                                                  int wn, int lane) {
   const int lcol = lane & 31;
   const int lrow4 = 4 * (lane >> 5);
   if (g.partial != nullptr) {   // split-K slice: raw partial sums, the reduce kernel finishes
@@ -118,8 +112,7 @@ __device__ __forceinline__ void gam_gemm_epilogue(const GamGemmArgs& g, const f3
         for (int tn = 0; tn < 2; ++tn) {
           const int col = n0 + wn * 64 + tn * 32 + lcol;
           if (col < g.N)
-            P[(size_t)row * g.N + col] = (tm == 0 ? (tn == 0 ? acc00[r] : acc01[r]) : (tn == 0 ? acc10[r] : acc11[r])) *
-                                         (accscale * (rs_lds != nullptr ? rs_lds[row - m0] : 1.0f));
+            P[(size_t)row * g.N + col] = tm == 0 ? (tn == 0 ? acc00[r] : acc01[r]) : (tn == 0 ? acc10[r] : acc11[r]);
         }
       }
     return;
@@ -140,12 +133,11 @@ __device__ __forceinline__ void gam_gemm_epilogue(const GamGemmArgs& g, const f3
           orow = (long)bb * g.out_rpb + tt + g.out_shift;
         }
       }
-      const float rowscale = rs_lds != nullptr ? accscale * rs_lds[row - m0] : accscale;
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
         const int col = n0 + wn * 64 + tn * 32 + lcol;
         if (col >= g.N) continue;
-        float v = (tm == 0 ? (tn == 0 ? acc00[r] : acc01[r]) : (tn == 0 ? acc10[r] : acc11[r])) * rowscale;
+        float v = tm == 0 ? (tn == 0 ? acc00[r] : acc01[r]) : (tn == 0 ? acc10[r] : acc11[r]);
         if (g.bias != nullptr) v += g.bias[col];
         if (ACT == GAM_ACT_SILU) v = gam_silu(v);
         if (ACT == GAM_ACT_RELU) v = fmaxf(v, 0.0f);
@@ -159,13 +151,13 @@ __device__ __forceinline__ void gam_gemm_epilogue(const GamGemmArgs& g, const f3
   }
 }
 
-template <int ACT, int NBUF>
-__global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gam_gemm_f32_kernel(GamGemmArgs g) {
+template <int ACT>
+__global__ __launch_bounds__(256, 3) void gam_gemm_f32_kernel(GamGemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) float gam_smem[];
   if (g.splitk > 1) { const size_t ko = (size_t)blockIdx.y * (size_t)g.K; g.A += ko; g.W += ko; }
   constexpr int BM = GAM_GEMM_BM, BN = GAM_GEMM_BN, BK = GAM_GEMM_BK, LD = GAM_GEMM_LD;
   float* As = gam_smem;
-  float* Bs = gam_smem + NBUF * BM * LD;
+  float* Bs = gam_smem + BM * LD;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -232,10 +224,10 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gam_gemm_f32_kernel(Ga
     vb2 = *reinterpret_cast<const float4*>(pw2 + k0_);                          \
     vb3 = *reinterpret_cast<const float4*>(pw3 + k0_);                          \
   }
-#define GAM_LSTORE(BUF)                                                         \
+#define GAM_LSTORE()                                                            \
   {                                                                             \
-    float* a_ = As + (BUF) * BM * LD + lrow * LD + lc4;                         \
-    float* b_ = Bs + (BUF) * BN * LD + lrow * LD + lc4;                         \
+    float* a_ = As + lrow * LD + lc4;                                           \
+    float* b_ = Bs + lrow * LD + lc4;                                           \
     *reinterpret_cast<float4*>(a_) = va0;                                       \
     *reinterpret_cast<float4*>(a_ + 32 * LD) = va1;                             \
     *reinterpret_cast<float4*>(a_ + 64 * LD) = va2;                             \
@@ -247,11 +239,6 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gam_gemm_f32_kernel(Ga
   }
 #define GAM_MFMA(AV, BV, ACC) ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(AV, BV, ACC, 0, 0, 0)
 
-  // One LDS tile set (36 KB -> 3 workgroups per CU, i.e. 768 resident tiles: the
-  // 126 x 6 = 756 tiles of an N = 768 GEMM at the bench shape run in ONE round), the
-  // next k-tile travels through registers while the current one is multiplied:
-  //   barrier | regs -> LDS | barrier | issue global loads of tile kt+1 | 64 MFMAs
-  // The two barriers per k-tile are covered by the other resident workgroups' MFMAs.
   const int frag = (lane & 31) * LD + (lane >> 5) * 4;
 #define GAM_COMPUTE(AB, BB)                                                                     \
   _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                               \
@@ -265,61 +252,34 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gam_gemm_f32_kernel(Ga
     GAM_MFMA(a0.z, b0.z, acc00); GAM_MFMA(a0.z, b1.z, acc01); GAM_MFMA(a1.z, b0.z, acc10); GAM_MFMA(a1.z, b1.z, acc11); \
     GAM_MFMA(a0.w, b0.w, acc00); GAM_MFMA(a0.w, b1.w, acc01); GAM_MFMA(a1.w, b0.w, acc10); GAM_MFMA(a1.w, b1.w, acc11); \
   }
-  if constexpr (NBUF == 1) {
-    // One LDS tile set (36 KB -> 3 workgroups per CU, i.e. 768 resident tiles: the
-    // 126 x 6 = 756 tiles of an N = 768 GEMM at the bench shape run in ONE round); the
-    // next k-tile travels through registers while the current one is multiplied:
-    //   barrier | regs -> LDS | barrier | issue global loads of tile kt+1 | 64 MFMAs
-    // The two barriers per k-tile are covered by the other resident workgroups' MFMAs.
-    GAM_GLOAD(0);
-    const float* Ab = As + wm * 64 * LD + frag;
-    const float* Bb = Bs + wn * 64 * LD + frag;
-    for (int kt = 0; kt < nk; ++kt) {
-      __syncthreads();
-      GAM_LSTORE(0);
-      __syncthreads();
-      if (kt + 1 < nk) GAM_GLOAD(kt + 1);
-      GAM_COMPUTE(Ab, Bb);
-    }
-  } else {
-    // Two LDS tile sets (72 KB -> 2 workgroups per CU), one barrier per k-tile.
-    GAM_GLOAD(0);
-    GAM_LSTORE(0);
+  // One LDS tile set (36 KB -> 3 workgroups per CU, i.e. 768 resident tiles: the
+  // 126 x 6 = 756 tiles of an N = 768 GEMM at the bench shape run in ONE round); the
+  // next k-tile travels through registers while the current one is multiplied:
+  //   barrier | regs -> LDS | barrier | issue global loads of tile kt+1 | 64 MFMAs
+  // The two barriers per k-tile are covered by the other resident workgroups' MFMAs.
+  GAM_GLOAD(0);
+  const float* Ab = As + wm * 64 * LD + frag;
+  const float* Bb = Bs + wn * 64 * LD + frag;
+  for (int kt = 0; kt < nk; ++kt) {
     __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int buf = kt & 1;
-      const bool more = kt + 1 < nk;
-      if (more) GAM_GLOAD(kt + 1);
-      const float* Ab = As + buf * BM * LD + wm * 64 * LD + frag;
-      const float* Bb = Bs + buf * BN * LD + wn * 64 * LD + frag;
-      GAM_COMPUTE(Ab, Bb);
-      if (more) GAM_LSTORE(buf ^ 1);
-      __syncthreads();
-    }
+    GAM_LSTORE();
+    __syncthreads();
+    if (kt + 1 < nk) GAM_GLOAD(kt + 1);
+    GAM_COMPUTE(Ab, Bb);
   }
 #undef GAM_COMPUTE
 #undef GAM_GLOAD
 #undef GAM_LSTORE
 #undef GAM_MFMA
 
-  gam_gemm_epilogue<ACT>(g, acc00, acc01, acc10, acc11, m0, n0, wm, wn, lane, 1.0f);
+  gam_gemm_epilogue<ACT>(g, acc00, acc01, acc10, acc11, m0, n0, wm, wn, lane);
 }
 
-template <int ACT, int NBUF>
+template <int ACT>
 static inline void gam_launch_gemm_t(const GamGemmArgs& a, int grid, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_devs{0};
-  if (gam_set_max_lds(reinterpret_cast<const void*>(gam_gemm_f32_kernel<ACT, NBUF>), GAM_GEMM_SMEM(NBUF), attr_devs) != hipSuccess) return;
-  hipLaunchKernelGGL((gam_gemm_f32_kernel<ACT, NBUF>), dim3(grid, a.splitk > 1 ? a.splitk : 1), dim3(256), GAM_GEMM_SMEM(NBUF), stream, a);
-}
-
-// GAM_GEMM_NBUF=2 selects the double-buffered variant (A/B measurements only)
-static inline int gam_gemm_nbuf() {
-  static int v = 0;
-  if (v == 0) {
-    const char* e = getenv("GAM_GEMM_NBUF");
-    v = (e && e[0] == '2') ? 2 : 1;
-  }
-  return v;
+  if (gam_set_max_lds(reinterpret_cast<const void*>(gam_gemm_f32_kernel<ACT>), GAM_GEMM_SMEM, attr_devs) != hipSuccess) return;
+  hipLaunchKernelGGL((gam_gemm_f32_kernel<ACT>), dim3(grid, a.splitk > 1 ? a.splitk : 1), dim3(256), GAM_GEMM_SMEM, stream, a);
 }
 
 static inline hipError_t gam_launch_gemm(const GamGemmArgs& a_in, int act, hipStream_t stream) {
@@ -328,17 +288,10 @@ static inline hipError_t gam_launch_gemm(const GamGemmArgs& a_in, int act, hipSt
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
   if (a.K % GAM_GEMM_BK != 0 || a.K <= 0) return hipErrorInvalidValue;
   const int grid = gam_cdiv(a.M, GAM_GEMM_BM) * gam_cdiv(a.N, GAM_GEMM_BN);
-  const bool one = gam_gemm_nbuf() == 1;
   switch (act) {
-    case GAM_ACT_SILU:
-      if (one) gam_launch_gemm_t<GAM_ACT_SILU, 1>(a, grid, stream); else gam_launch_gemm_t<GAM_ACT_SILU, 2>(a, grid, stream);
-      break;
-    case GAM_ACT_RELU:
-      if (one) gam_launch_gemm_t<GAM_ACT_RELU, 1>(a, grid, stream); else gam_launch_gemm_t<GAM_ACT_RELU, 2>(a, grid, stream);
-      break;
-    default:
-      if (one) gam_launch_gemm_t<GAM_ACT_NONE, 1>(a, grid, stream); else gam_launch_gemm_t<GAM_ACT_NONE, 2>(a, grid, stream);
-      break;
+    case GAM_ACT_SILU: gam_launch_gemm_t<GAM_ACT_SILU>(a, grid, stream); break;
+    case GAM_ACT_RELU: gam_launch_gemm_t<GAM_ACT_RELU>(a, grid, stream); break;
+    default: gam_launch_gemm_t<GAM_ACT_NONE>(a, grid, stream); break;
   }
   return hipGetLastError();
 }

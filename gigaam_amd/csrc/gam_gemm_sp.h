@@ -1,9 +1,18 @@
-// gam_gemm_sp.h -- the large-M split-fp16 GEMM: (64 MT) x (64 NW) block tiles fed entirely by
-// LDS-DMA (global_load_lds_dwordx4), two LDS stages (<= 64 KB each), one barrier per k-tile.
+// gam_gemm_sp.h -- the split-fp16 GEMM: (64 MT) x (64 NW) block tiles fed entirely by
+// LDS-DMA (global_load_lds_dwordx4), two or three LDS stages, one barrier per k-tile.
 //
-// Same arithmetic as gam_gemm16.h (a.w ~= (a_hi.w_hi + a_hi.w_lo + a_lo.w_hi) 2^-s on
-// v_mfma_f32_32x32x16_f16, fp32 accumulate) but both operands arrive already split, in the
-// "sp32" layout that the producing kernels write instead of fp32:
+// Three-term split ("f16x3") on the fp16 matrix cores (v_mfma_f32_32x32x16_f16, 16x the
+// per-instruction rate of the fp32 MFMA), fp32 accumulate:
+//
+//   a = a_hi + a_lo,  w * 2^s = w_hi + w_lo      (hi = fp16(x), lo = fp16(x - hi))
+//   a.w ~= (a_hi.w_hi + a_hi.w_lo + a_lo.w_hi) * 2^-s
+//
+// fp16 carries 11 significant bits, so hi+lo keeps 22 of fp32's 24 and the dropped a_lo.w_lo
+// term is ~2^-22 relative: on the full 16-layer encoder the split path is as close to an fp64
+// evaluation as plain fp32 is.  The power-of-two pre-scale of each weight
+// matrix (exact, undone in the epilogue, gam_api.hip make_split) keeps w_lo clear of the fp16
+// subnormal range.  Both operands arrive already split, in the "sp32" layout that the producing
+// kernels write instead of fp32:
 //
 //   element (row, k)  ->  halfs  row*2K + (k/32)*64 + (k%32)        hi = fp16(x)
 //                                row*2K + (k/32)*64 + 32 + (k%32)   lo = fp16(x - hi)
@@ -11,7 +20,7 @@
 // i.e. the 4 bytes an fp32 element would occupy hold its (hi, lo) pair, regrouped so that one
 // row's share of a 32-deep k-tile is ONE 128-byte line [hi x32 | lo x32].  A k-tile of a block is
 // then (BM + 256) full lines; a wave-wide global_load_lds_dwordx4 moves 8 of them (1 KiB) straight
-// into LDS -- no staging registers, no ds_write pass, no conversion in the GEMM.  (The 128x128
+// into LDS -- no staging registers, no ds_write pass, no conversion in the GEMM.  (A 128x128
 // register-staged kernel measured TD/TCP-bound on exactly that traffic: profiles/r01_f16x3_*.)
 //
 // LDS image: rows of 128 B (8 slots of 16 B), slot' = slot ^ ((row >> 1) & 7).  LDS-DMA writes
@@ -21,11 +30,12 @@
 //
 // 2 (M) x NW (N) waves; a wave owns (32 MT) x 64 outputs = MT x 2 MFMA tiles, 3 MFMAs per tile per
 // k16-step.  At NW = 4 (256-wide tiles, one workgroup per CU) the bytes moved per FLOP are half
-// those of the 128x128 kernel; the k-tile after next lands while the current one is multiplied.
+// those of a 128 x 128 tile; the k-tile after next lands while the current one is multiplied.
 // MT in {2,3,4} and NW in {2,4} are picked per launch (gam_gemm_sp_pick) to minimise the tail of the
 // last round of tiles.
 #pragma once
-#include "gam_gemm16.h"
+#include "gam_gemm.h"
+#include <type_traits>
 #if defined(GAM_SP_INSTRUMENT) && GAM_SP_INSTRUMENT
 #include <algorithm>
 #include <vector>
@@ -51,9 +61,6 @@
 #else
 #define GAM_SP_TL(i)
 #endif
-
-#define GAM_SP_MIN_M 1      // rows from which the encoder runs on this kernel family: all (with split-K for small grids it beats the
-                            // 128x128 register-staged kernels from one 5 s clip up, profiles/r03_smallm_sweep.txt); GAM_SP_MIN_M overrides
 
 template <int MT, int NW, int NS = 2>
 struct GamGemmSpCfg {
@@ -725,14 +732,6 @@ __global__ __launch_bounds__(256) void gam_to_h16_kernel(const float* __restrict
     if (rs != nullptr) v = v * (1.0f / rs[(i * 4) / (size_t)K]);
     reinterpret_cast<gam_half4*>(y)[i] = __builtin_convertvector(v, gam_half4);
   }
-}
-
-// fp32 [rows, K] -> fp32 copy with row r multiplied by 2^e_r = 1 / rs[r] (the 128x128 kernel's scaled operand)
-__global__ __launch_bounds__(256) void gam_scale_rows_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n4,
-                                                             const float* __restrict__ rs, int K) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
-    reinterpret_cast<f32x4*>(y)[i] = reinterpret_cast<const f32x4*>(x)[i] * (1.0f / rs[(i * 4) / (size_t)K]);
 }
 
 // rs[row] = 2^-e with max|row| 2^e in [2^7, 2^8): one wave per row of an fp32 [rows, K] matrix (row pitch lda)

@@ -93,9 +93,11 @@ __global__ __launch_bounds__(256) void gam_conv2d1_kernel(GamConv1Args a) {
 // ---------------------------------------------------------------------------------
 // v3 stem input: feat [B,F,T] -> time-major, masked, zero-padded rows
 // xin[b][pad + t][f] inside a per-utterance stride of `rows` rows (Conv1d k=5, p=2).
+// FMT 1: xin in the sp32 GEMM-operand layout (F % 32 == 0); a value beyond fp16's range sets *range_flag (may be null).
 // ---------------------------------------------------------------------------------
+template <int FMT>
 __global__ __launch_bounds__(256) void gam_feat_to_rows_kernel(const float* feat, float* xin, const int* len0,
-                                                               int B, int F, int T, int rows, int pad) {
+                                                               int B, int F, int T, int rows, int pad, int* range_flag) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
@@ -109,7 +111,11 @@ __global__ __launch_bounds__(256) void gam_feat_to_rows_kernel(const float* feat
   __syncthreads();
   for (int i = ty; i < 32; i += 8) {
     const int t = t0 + i, f = f0 + tx;
-    if (t < T && f < F) xin[((size_t)b * rows + pad + t) * F + f] = tile[tx][i];
+    if (t < T && f < F) {
+      const float v = tile[tx][i];
+      if (FMT != 0) gam_range_note(range_flag, v, 0.f, 0.f, 0.f);   // (the GEMM reads xin unscaled)
+      gam_store1(xin, ((size_t)b * rows + pad + t) * F, f, v, FMT);
+    }
   }
 }
 

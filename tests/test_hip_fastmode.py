@@ -18,19 +18,10 @@ TOL_ENC_F16 = 3e-2
 TOL_ATT_F16 = 5e-3
 
 
-def _engine(ck, sp=True):
-    import os
+def _engine(ck):
     from gigaam_amd.engine import HipEngine, build_config
     cfg = ck["cfg"]
-    old = os.environ.get("GAM_SP_MIN_M")
-    os.environ["GAM_SP_MIN_M"] = "1" if sp else str(1 << 30)
-    try:
-        return HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg.get("head")), ck["state_dict"], torch.device("cuda:0"))
-    finally:
-        if old is None:
-            del os.environ["GAM_SP_MIN_M"]
-        else:
-            os.environ["GAM_SP_MIN_M"] = old
+    return HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg.get("head")), ck["state_dict"], torch.device("cuda:0"))
 
 
 def test_default_mode_is_not_the_speed_mode():

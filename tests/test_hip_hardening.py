@@ -256,8 +256,8 @@ def test_rnnt_decode_is_not_perturbed_by_another_streams_gemm(exclusive):
     launch stream runs the small-tile GEMM came out with a perturbed predictor state in 1-30 % of the launches.  r06 found the mechanism: hipcc
     had packed pairs of gate-row FMA chains into v_pk_fma_f32 with op_sel:[0,1,0], whose low result is wrong in lanes 48..63 whenever another
     wave on the SIMD issues MFMAs (tools/pkfma_rule.hip).  The library holds no such instruction any more (gigaam_amd/build.py), so the decode
-    must be bit-identical to the one that had the GPU to itself BOTH with the r05 protection (workgroups claim their CU's whole LDS,
-    exclusive = 1, the default) and without it (GAM_RNNT_EXCLUSIVE=0: decode workgroups share CUs with the GEMM's).  With the r05 library the
+    must be bit-identical to the one that had the GPU to itself BOTH with the r05 protection (GAM_RNNT_EXCLUSIVE=1: workgroups claim their
+    CU's whole LDS) and without it (exclusive = 0, the default: decode workgroups share CUs with the GEMM's).  With the r05 library the
     exclusive = 0 leg fails with probability > 0.95 (cluster size 1: 34 of 3000 decodes differed)."""
     import os
     from gigaam_amd import synth

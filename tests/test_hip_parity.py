@@ -14,34 +14,17 @@ SUPPORTED = list(CASES)
 
 
 # Every arithmetic mode of the dense contractions must hold the same bars: "f16x3" = the product's default (three-term split on the
-# LDS-DMA kernels of gam_gemm_sp.h at every size; the v3 conv1d stem and v1's rel-pos projection reach the register-staged
-# gam_gemm16.h kernels inside it, DESIGN.md "reachable shapes"), "f32" = exact-fp32 MFMA.
-# "f16x3-legacy" FORCES the register-staged 128 x 128 family for every GEMM (GAM_SP_MIN_M = 2^30) -- what a model whose d_model is not a
-# multiple of 32, or GAM_SP=0, would run.  r05 ran the whole matrix in it (a third of the GPU suite on kernels the product never launches
-# for the published shapes); it now covers the kernel-level GEMM test and one end-to-end case.
+# LDS-DMA kernels of gam_gemm_sp.h; the v3 conv1d stem and v1's rel-pos projection included), "f32" = exact-fp32 MFMA.
 MODES = ["f16x3", "f32"]
-LEGACY = "f16x3-legacy"
 
 
 def _make_engine(cfg, state_dict, mode, head=True):
-    """mode "f16x3": the product's default family; "f16x3-legacy": the register-staged 128 x 128 split-fp16 kernels forced for every GEMM;
-    "f32": exact-fp32 MFMA."""
-    import os
+    """mode "f16x3": the product's default; "f32": exact-fp32 MFMA."""
     from gigaam_amd.engine import HipEngine, build_config
-    old = os.environ.get("GAM_SP_MIN_M")
-    if mode.endswith("-legacy"):
-        os.environ["GAM_SP_MIN_M"] = str(1 << 30)   # read when the handle is created
-    try:
-        eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg.get("head") if head else None), state_dict,
-                        torch.device("cuda:0"))
-    finally:
-        if mode.endswith("-legacy"):
-            if old is None:
-                del os.environ["GAM_SP_MIN_M"]
-            else:
-                os.environ["GAM_SP_MIN_M"] = old
-    eng.set_gemm_mode(mode.split("-")[0])
-    assert eng.gemm_mode == mode.split("-")[0]
+    eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg.get("head") if head else None), state_dict,
+                    torch.device("cuda:0"))
+    eng.set_gemm_mode(mode)
+    assert eng.gemm_mode == mode
     return eng
 
 
@@ -49,13 +32,13 @@ def _engine(ck, mode="f16x3"):
     return _make_engine(ck["cfg"], ck["state_dict"], mode)
 
 
-@pytest.mark.parametrize("mode", MODES + [LEGACY])
+@pytest.mark.parametrize("mode", MODES)
 def test_gemm_kernel_shapes_and_epilogues(mode):
     from gigaam_amd import synth
     eng = _make_engine(synth.model_cfg("v2_ctc"), {}, mode, head=False)
     g = torch.Generator().manual_seed(0)
     # asymmetric operands, ragged M/N edges, all activations (transposes / layout slips cannot hide)
-    # the last three shapes reach the many-tile variant (128x128 phase-separated)
+    # N % 4 != 0 ((257, 34, 768), (1, 1, 32)): the exact-fp32 kernel in every mode (the LDS-DMA epilogue moves 4-column pieces)
     for (m, n, k, act) in [(128, 128, 32, 0), (300, 200, 64, 0), (1000, 768, 768, 1), (257, 34, 768, 0), (515, 1536, 96, 2), (1, 1, 32, 0),
                            (16064, 768, 64, 0), (16064, 3072, 64, 1), (33000, 1536, 32, 2),
                            # steady-state k-loop of the large-batch kernel (192x256 / 256x256 tiles, LDS-DMA)
@@ -123,7 +106,7 @@ def test_frontend_matches_oracle(case, mode):
     assert float(((feat.cpu()[:, ::7, ::13] - torch.from_numpy(gold["feat_probe"])).abs() * keep).max()) < TOL_FEAT
 
 
-@pytest.mark.parametrize("case,mode", [(c, m) for c in SUPPORTED for m in MODES] + [("v2_ctc_l2", LEGACY)])
+@pytest.mark.parametrize("case,mode", [(c, m) for c in SUPPORTED for m in MODES])
 def test_encoder_matches_reference_golden(case, mode):
     ck, wav, wlen, gold = load_case(case)
     eng = _engine(ck, mode)

@@ -1,7 +1,7 @@
 """r06: the one-switch reproducer of the RNN-T cluster decode's co-residency perturbation.
 A dense, near-tie-rich batch (v2_rnnt, 2 layers, blank bias 13.5: up to 10 symbols per frame) is decoded on the engine's side stream while the
 launch stream runs the small-tile LDS-DMA GEMM; ids are compared with the decode that had the GPU to itself at the SAME cluster size.
-    GAM_RNNT_EXCLUSIVE=0 [GIGAAM_HIP_LIB=...] python tools/coresidency_repro.py <clusters e.g. 2,1> <reps> [neighbour=gemm640|legacy|attention|none]
+    GAM_RNNT_EXCLUSIVE=0 [GIGAAM_HIP_LIB=...] python tools/coresidency_repro.py <clusters e.g. 2,1> <reps> [neighbour=gemm640|attention|none]
 prints one line per cluster size: decodes that differ / decodes run."""
 import os
 import sys
@@ -39,7 +39,7 @@ for cluster in clusters:
     t0.record()
     for _ in range(reps):
         dec = eng.rnnt_greedy(enc, elen, 10, overlap=True)
-        if beside in ("gemm640", "legacy"):
+        if beside == "gemm640":
             for _ in range(30):
                 out = eng.op_gemm(xa, wa)
             gemm_bad += not torch.equal(out, ref_gemm)

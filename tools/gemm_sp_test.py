@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel-only timing (HIP events around the launch) and fp64 error of the sp32 LDS-DMA GEMM
-(gam_gemm_sp.h) against the 128x128 register-staged kernel, through gam_op_gemm."""
+(gam_gemm_sp.h), through gam_op_gemm."""
 import os
 import sys
 
@@ -12,8 +12,7 @@ from gigaam_amd import synth  # noqa: E402
 from gigaam_amd.engine import HipEngine, build_config  # noqa: E402
 
 
-def engine(sp, mt=None):
-    os.environ["GAM_SP"] = str(sp)
+def engine(mt=None):
     if mt:
         os.environ["GAM_SP_MT"] = str(mt)
     cfg = synth.model_cfg("v2_ctc")
@@ -27,9 +26,7 @@ def main():
         shapes = shapes[:3]
     elif len(sys.argv) > 1:      # "M,N,K,act;M,N,K,act;..."
         shapes = [tuple(int(v) for v in t.split(",")) for t in sys.argv[1].split(";") if t]
-    engs = [("base", engine(0)), ("sp", engine(1))]
-    if os.environ.get("GAM_SP_DBG"):
-        engs = engs[1:]
+    engs = [("sp", engine())]
     tlog = bool(os.environ.get("GAM_SP_TLOG"))    # instrumented library + GAM_SP_DBG=16: the launcher prints a timeline per call
     torch.manual_seed(0)
     for (m, n, k, act) in shapes:

@@ -57,7 +57,7 @@ def aggr_lib(kind):
         if kind == "gemm640":
             for _ in range(110):
                 eng.op_gemm(x640, w768)
-        elif kind == "gemm16k":
+        elif kind == "gemm_16k":
             for _ in range(40):
                 eng.op_gemm(x16k, w768)
         elif kind == "attention":
@@ -70,7 +70,7 @@ def aggr_lib(kind):
 AGGRESSORS = [("none", lambda: None), ("own: LDS-DMA stream (HBM)", aggr_own(0)), ("own: LDS-DMA stream (L2-hot)", aggr_own(1)),
               ("own: plain 16 B load stream", aggr_own(2)), ("own: MFMA loop", aggr_own(3)), ("own: LDS rw loop", aggr_own(4)),
               ("own: LDS-DMA + MFMA", aggr_own(5)), ("lib: op_gemm 640 x 768 x 768 (small-tile LDS-DMA)", aggr_lib("gemm640")),
-              ("lib: op_gemm 16064 x 768 x 768", aggr_lib("gemm16k")), ("lib: op_attention", aggr_lib("attention"))]
+              ("lib: op_gemm 16064 x 768 x 768", aggr_lib("gemm_16k")), ("lib: op_attention", aggr_lib("attention"))]
 FLAVOURS = ["plain", "nt", "sc1", "sc0 sc1"]
 
 

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Per-shape kernel time (HIP events around gemm(): the GEMM launch + its split-K reduce) of the Conformer layer's GEMM
 shapes at the row counts of the strong-scaling points (2 / 4 / 8 / 16 utterances of 20 s per GPU, one 5 s clip):
-  base      the 128x128 register-staged kernels + split-K (what runs below GAM_SP_MIN_M rows)
   sp        the LDS-DMA sp32 kernel as planned by gam_gemm_sp_plan (tile shape + split-K from its time model)
   sweep     with --calib: EVERY (MT, NW, S) of the sp kernel through the gam_tune_sp hook -- the data the plan's model is fitted to
     python tools/smallm_sweep.py [--calib] > profiles/r03_smallm_sweep.txt"""
@@ -17,8 +16,7 @@ from gigaam_amd import synth  # noqa: E402
 from gigaam_amd.engine import HipEngine, build_config  # noqa: E402
 
 
-def engine(sp_min):
-    os.environ["GAM_SP_MIN_M"] = str(sp_min)
+def engine():
     cfg = synth.model_cfg("v2_ctc")
     return HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], None), {}, torch.device("cuda:0"))
 
@@ -41,7 +39,7 @@ def main():
     stages = "--stages" in sys.argv       # r04: every configuration also with three LDS stages where the tile has that build
     rows_arg = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--rows=")), None)
     m_list = [int(v) for v in rows_arg.split(",")] if rows_arg else [126, 1004, 2008, 4016, 8032, 16064]
-    base, sp = engine(1 << 30), engine(1)
+    sp = engine()
     lib = sp.lib
     torch.manual_seed(0)
     rows = []
@@ -56,8 +54,8 @@ def main():
             lib.gam_tune_sp(0, 0, 0)
             lib.gam_tune_sp_stages(0)
             err = float((sp.op_gemm(a, w, b, act).double() - ref).abs().max() / ref.abs().max())
-            rec = {"M": m, "N": n, "K": k, "base": timed(base, a, w, b, act), "sp": timed(sp, a, w, b, act), "rel_err": err}
-            line = (f"M={m:5d} N={n:5d} K={k:6d} act={act}  ideal@360TF {2.0*m*n*k/360e6:6.1f} us | base {rec['base']:7.1f} | "
+            rec = {"M": m, "N": n, "K": k, "sp": timed(sp, a, w, b, act), "rel_err": err}
+            line = (f"M={m:5d} N={n:5d} K={k:6d} act={act}  ideal@360TF {2.0*m*n*k/360e6:6.1f} us | "
                     f"sp(plan) {rec['sp']:7.1f} us  rel.err {err:.1e}")
             if calib:
                 allc = {}
