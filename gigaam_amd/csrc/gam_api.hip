@@ -1688,6 +1688,30 @@ int gam_op_attention(gam_handle* h, const float* q, const float* k, const float*
   return 0;
 }
 
+int gam_op_attention_ex(gam_handle* h, const float* q, const float* k, const float* v, int64_t ldq, float* ctx, const int32_t* lens,
+                        const int32_t* cu, int B, int Ta, int Tv, int H, const float* pbuf, const float* pos_u, const float* pos_v,
+                        void* stream) {
+  if (!h) return -1;
+  const int D = H * GAM_ATT_DK;
+  if (B <= 0 || Ta <= 0 || Tv <= 0 || H <= 0) return fail(h, -1, "bad attention shape");
+  if (cu == nullptr && Tv > Ta) return fail(h, -1, "attention: Tv %d > Ta %d in the padded layout", Tv, Ta);
+  if (ldq < D || ldq % 4 != 0) return fail(h, -1, "attention: row stride %ld (H*48 = %d, multiple of 4)", (long)ldq, D);
+  if (pbuf != nullptr && (pos_u == nullptr || pos_v == nullptr)) return fail(h, -1, "attention: pbuf without pos_u / pos_v");
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };   // (float4 loads and stores)
+  if (!al16(q) || !al16(k) || !al16(v) || !al16(ctx) || (pbuf && (!al16(pbuf) || !al16(pos_u) || !al16(pos_v))))
+    return fail(h, -1, "attention: operands must be 16-byte aligned");
+  HIPCHK(h, hipSetDevice(h->device));
+  GamAttnArgs at;
+  memset(&at, 0, sizeof at);
+  at.q = q; at.k = k; at.v = v; at.ctx = ctx; at.lens = lens; at.cu = cu;
+  at.B = B; at.Ta = Ta; at.Tv = Tv; at.H = H; at.ldq = ldq; at.ldv = ldq; at.ldo = D;
+  at.scale = 1.0f / sqrtf((float)GAM_ATT_DK);
+  at.pbuf = pbuf; at.pos_u = pos_u; at.pos_v = pos_v; at.ldp = D;
+  hipError_t e = gam_launch_attn_mode(at, GAM_ATT_DK, split_mode(h), (hipStream_t)stream, h->gemm_mode == GAM_GEMM_F16 ? 1 : 3, h->ncu);
+  if (e != hipSuccess) return fail(h, -2, "attention launch: %s", hipGetErrorString(e));
+  return 0;
+}
+
 int gam_set_gemm_mode(gam_handle* h, int mode) {
   if (!h || (mode != GAM_GEMM_F32 && mode != GAM_GEMM_F16X3 && mode != GAM_GEMM_F16)) return fail(h, -1, "unknown GEMM mode %d", mode);
   h->gemm_mode = mode;

@@ -580,11 +580,16 @@ static inline double gam_gemm_sp_model(int M, int N, int K, int a_mode, int t, i
 }
 static inline GamSpPlan gam_gemm_sp_plan(int M, int N, int K, int a_mode = 0, int ncu = 256) {
   GamSpForce& frc = gam_sp_force();
-  const int f_mt = frc.mt.load(std::memory_order_relaxed), f_nw = frc.nw.load(std::memory_order_relaxed), f_s = frc.s.load(std::memory_order_relaxed);
-  const int f_ns = frc.ns.load(std::memory_order_relaxed);
+  const int f_mt = frc.mt.load(std::memory_order_relaxed), f_nw = frc.nw.load(std::memory_order_relaxed);
+  int f_s = frc.s.load(std::memory_order_relaxed), f_ns = frc.ns.load(std::memory_order_relaxed);
   GamSpPlan best = {3, 4, 1, 2};
   double bt = 1e30;
   const int nk = K / 32;
+  // A force this launch cannot take degrades in its own dimension only -- a split-K factor K does not divide into >= 4 whole k-tiles
+  // to S = 1, three stages on the implicit-GEMM conv (two-stage tiles only) to 2 -- instead of emptying the candidate set, which left
+  // the default {3, 4, 1, 2} and silently dropped a forced tile shape too.
+  if (f_s > 1 && (f_s > 8 || nk % f_s != 0 || nk / f_s < 4)) f_s = 1;
+  if (f_ns == 3 && a_mode != 0) f_ns = 2;
   for (int w = 4; w >= 2; w -= 2) {
     if ((f_nw == 2 || f_nw == 4) && w != f_nw) continue;
     for (int t = (w == 2 ? 3 : 4); t >= 2; --t) {

@@ -522,6 +522,23 @@ class HipEngine:
         self._check(rc, "gam_op_attention")
         return out
 
+    def op_attention_ex(self, q: Tensor, k: Tensor, v: Tensor, B: int, Ta: int, Tv: int, H: int, lens: Optional[Tensor] = None,
+                        cu: Optional[Tensor] = None, pbuf: Optional[Tensor] = None, pos_u: Optional[Tensor] = None,
+                        pos_v: Optional[Tensor] = None) -> Tensor:
+        """gam_op_attention_ex: q, k, v [rows, ldq] views sharing one row stride (columns of one [rows, 3*H*48] buffer allowed)
+        -> ctx [rows, H*48]; cu = first packed row of every utterance, pbuf / pos_u / pos_v select relative-position attention."""
+        ldq = q.stride(0)
+        if not (q.is_cuda and k.is_cuda and v.is_cuda) or k.stride(0) != ldq or v.stride(0) != ldq or any(t.stride(1) != 1 for t in (q, k, v)):
+            raise GigaAMHipError("op_attention_ex: q, k, v must be CUDA row views with one row stride")
+        lens_d, cu_d = (None if t is None else self._dev(t, torch.int32) for t in (lens, cu))
+        pbuf, pos_u, pos_v = (None if t is None else self._dev(t, torch.float32) for t in (pbuf, pos_u, pos_v))
+        out = torch.full((q.shape[0], H * 48), float("nan"), dtype=torch.float32, device=self.device)   # (rows no utterance owns stay NaN)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_attention_ex(self._h, _ptr(q), _ptr(k), _ptr(v), ldq, _ptr(out), _ptr(lens_d), _ptr(cu_d), B, Ta, Tv, H,
+                                              _ptr(pbuf), _ptr(pos_u), _ptr(pos_v), self._stream())
+        self._check(rc, "gam_op_attention_ex")
+        return out
+
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on=True) -> None:
         """True/1: time every launch; 2: GEMM family only; False/0: off."""

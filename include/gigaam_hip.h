@@ -209,6 +209,17 @@ int gam_op_gemm(gam_handle* h, const float* A, const float* W, const float* bias
  * ctx = softmax(q.k^T / sqrt(48) over keys < len).v per head (arithmetic = current mode). */
 int gam_op_attention(gam_handle* h, const float* q, const float* k, const float* v, float* ctx,
                      const int32_t* lens, int B, int T, int H, void* stream);
+/* Test hook: gam_op_attention with every variant the encoder launches.  q, k, v: rows of `ldq` floats (ldq >= H*48,
+ * ldq % 4 == 0; q, k, v may be column offsets into one [rows, 3*H*48] buffer, as in gam_encode); ctx dense [rows, H*48].
+ * Ta query rows per utterance, Tv <= Ta keys (klen_b = min(lens[b], Tv), or Tv if lens is NULL); query rows t >= klen_b
+ * of a padded layout are written but carry no defined value.  cu (DEVICE i32 [B], may be NULL): packed rows -- utterance
+ * b is rows cu[b] .. cu[b] + klen_b - 1 (Ta >= every klen_b: it sizes the grid); NULL = rows b*Ta .. b*Ta + Ta - 1.
+ * pbuf (may be NULL) selects relative-position attention: pbuf f32 [2*Tv-1, H*48], row n = P(n - (Tv-1)), the projected
+ * position embedding of relative position (query index - key index); pos_u / pos_v f32 [H*48] the two position biases:
+ * score(i, j) = ((q_i + u).k_j + (q_i + v).P(i - j)) / sqrt(48). */
+int gam_op_attention_ex(gam_handle* h, const float* q, const float* k, const float* v, int64_t ldq, float* ctx,
+                        const int32_t* lens, const int32_t* cu, int B, int Ta, int Tv, int H, const float* pbuf,
+                        const float* pos_u, const float* pos_v, void* stream);
 
 /* Tuning hook of the large-M GEMM (tools/smallm_sweep.py): force the tile shape (mt in 2..4 rows of 64, nw in {2, 4}
  * columns of 64) and / or the split-K factor of every following launch in this process; 0 = planned per launch (default). */

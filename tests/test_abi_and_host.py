@@ -333,6 +333,36 @@ def test_gemm_plan_invariants():
     assert lib.gam_tune_sp_stages(0) == 0
 
 
+def test_forced_plan_degrades_only_where_it_cannot_be_honoured():
+    """A forced split-K factor that K cannot take (not a divisor of the k-tile count, fewer than four k-tiles per slice, > 8) must
+    fall back to S = 1 and KEEP the forced tile shape and stages; it used to empty the candidate set and return the default 3x4
+    tile, so a sweep or test forcing 2x2 silently measured 3x4."""
+    import ctypes as C
+    from gigaam_amd import _lib
+    lib = _lib.load_library()
+
+    def plan_ex(m, n, k):
+        mt, nw, s, ns = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        assert lib.gam_plan_sp_ex(m, n, k, 256, C.byref(mt), C.byref(nw), C.byref(s), C.byref(ns)) == 0
+        return mt.value, nw.value, s.value, ns.value
+
+    try:
+        for (mt, nw, ns) in [(2, 2, 2), (2, 2, 3), (3, 2, 3), (2, 4, 3), (4, 4, 2)]:
+            assert lib.gam_tune_sp_stages(ns) == 0
+            for s_bad, k in [(5, 768), (7, 768), (8, 768), (16, 3072), (2, 192), (3, 32)]:   # 24 % 5, 24 % 7, 24 / 8 < 4, > 8, 6 / 2 < 4
+                assert lib.gam_tune_sp(mt, nw, s_bad) == 0
+                assert plan_ex(2008, 772, k) == (mt, nw, 1, ns), (mt, nw, ns, s_bad, k)
+            for s_ok, k in [(4, 768), (8, 3072), (1, 32)]:                                   # honoured as given
+                assert lib.gam_tune_sp(mt, nw, s_ok) == 0
+                assert plan_ex(2008, 772, k) == (mt, nw, s_ok, ns), (mt, nw, ns, s_ok, k)
+        # three stages on a tile without a three-stage build: stages drop to 2, tile and S stay
+        assert lib.gam_tune_sp_stages(3) == 0 and lib.gam_tune_sp(3, 4, 2) == 0
+        assert plan_ex(2008, 772, 768) == (3, 4, 2, 2)
+    finally:
+        lib.gam_tune_sp(0, 0, 0)
+        lib.gam_tune_sp_stages(0)
+
+
 def test_decoded_object_carries_flag_and_event_explicitly():
     """r05: what a decode returns is ONE object whose hidden companions are explicit fields -- nothing hangs off
     a tensor view any more, so a slice / cat / unpack cannot silently drop the range flag.  CPU tensors: the plain collect path."""
