@@ -51,6 +51,8 @@ SIGNATURES = {
     "gam_last_encode_rows": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "gam_ctc_head": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P]),
     "gam_ctc_greedy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
+    "gam_ctc_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gam_op_ctc_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_rnnt_greedy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
     "gam_emo_probs": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P]),
     "gam_rnnt_predict": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),

@@ -1,0 +1,289 @@
+// gam_align.h -- CTC forced alignment and transcript log-likelihood (gam_ctc_align / gam_op_ctc_align).
+//
+// For utterance b with log-probs lp[t, v] (t < T = enc_len[b], torch.log_softmax units), target y[0..U) and blank = V-1, the
+// extended label sequence l = (blank, y0, blank, y1, ..., blank) has S = 2U + 1 states.  ONE sweep over t computes both
+//   Viterbi  d_t(s) = lp[t, l_s] + max(d_{t-1}(s), d_{t-1}(s-1), d_{t-1}(s-2) if l_s != blank and l_s != l_{s-2})
+//   forward  a_t(s) = the same recursion with log-sum-exp instead of max
+// with score = max(d_{T-1}(S-1), d_{T-1}(S-2)) and log-likelihood = logsumexp(a_{T-1}(S-1), a_{T-1}(S-2)) (= -ctc_loss).
+//
+// Shape: one workgroup per utterance, states across the lanes (state s = i * blockDim + tid, i < spt <= 3), t the sequential
+// loop with ONE barrier per step (d / a double-buffered in LDS).  The emission row of frame t + GAM_ALIGN_PF is loaded while
+// frame t is computed.  Precision: every step subtracts the previous step's maximum (of d and of a separately, read from the
+// per-wave maxima of that step) and carries the offsets in fp64, so the stored values stay O(one frame's log-prob) and their
+// fp32 ulp far below the top-1 / top-2 margins of real frames.  Backpointers: 2 bits per (t, s) as two 64-bit ballots per
+// 64-state chunk; in LDS when T' x chunks x 16 B fit beside the rest of the workgroup's LDS (BP_LDS), else in a global scratch
+// buffer the handle owns.  The backtrack runs in the same kernel (one lane walks the 2-bit pointers, then every lane writes).
+//
+// Tie rule (deterministic, shared with tests/ctc_align_ref.py): among equal predecessors prefer s over s-1 over s-2; at the
+// end prefer S-1 over S-2.
+// Limits: U <= GAM_ALIGN_MAX_U (S <= 2049) tokens, T' <= GAM_ALIGN_MAX_T frames (the host entry points fail beyond them).
+// Infeasible utterances -- T < U + #{i : y_i == y_{i-1}}, a target id outside [0, V-2], target_len outside [0, Umax], or no
+// path of finite score -- get status 0, score = loglik = -inf, frame labels and token frames -1; target entries past
+// target_len[b] are never read.  U = 0 is the all-blank path; T = 0 with U = 0 scores 0.
+#pragma once
+#include "gam_common.h"
+
+#define GAM_ALIGN_MAX_U 1024
+#define GAM_ALIGN_MAX_T 8192
+#define GAM_ALIGN_MAX_NT 1024
+#define GAM_ALIGN_MAX_SPT 3
+#define GAM_ALIGN_PF 4          // emission rows in flight ahead of the step that uses them
+#define GAM_ALIGN_LDS_MAX (160 * 1024)
+
+struct GamAlignArgs {
+  const float* lp;           // [B, Tp, V]
+  const int* enc_len;        // [B]
+  const int* targets;        // [B, Umax] (may be NULL when Umax == 0)
+  const int* target_len;     // [B]
+  int Tp, V, Umax;
+  int spt;                   // states per thread: S_max <= spt * blockDim
+  int nchunk;                // 64-state backpointer chunks per frame: ceil(S_max / 64)
+  uint4* bp_glob;            // !BP_LDS: [B, Tp, nchunk] chunks of {bit0 lo, bit0 hi, bit1 lo, bit1 hi}
+  int* frame_labels;         // [B, Tp]
+  int* tok_first;            // [B, Umax]
+  int* tok_last;             // [B, Umax]
+  float* score;              // [B]
+  float* loglik;             // [B]
+  int* status;               // [B]
+};
+
+// LDS bytes of one workgroup (host and device carve it the same way)
+static inline size_t gam_align_lds_bytes(bool bp_lds, int Tp, int nchunk, int spt, int nt) {
+  const size_t sp = (size_t)spt * nt + 2;
+  return (bp_lds ? (size_t)Tp * nchunk * 16 : 0) + 16 * sp + 64 * sizeof(float) + 64 + (((size_t)Tp * 2 + 15) & ~(size_t)15);
+}
+
+// The forward recursion's log-sum-exp on the hardware transcendentals (v_exp_f32 / v_log_f32, ~1 ulp): arguments of exp are <= 0,
+// the sum of the three terms lies in [1, 3], so each step adds an absolute error of ~1e-7 (measured loglik errors: DESIGN.md section 4.8).
+__device__ __forceinline__ float gam_align_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
+__device__ __forceinline__ float gam_align_log(float x) { return __builtin_amdgcn_logf(x) * 0.693147180559945309f; }
+
+// Wave maximum by DPP (row quad-perms and mirrors, then the two GFX9 row broadcasts): the per-step renormalisation needs two of
+// these on the sequential path, where the ds_bpermute chain of gam_wave_max costs six LDS round trips each.  Result in lane 63.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float gam_align_dpp_max(float v) {
+  const int o = __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
+  return fmaxf(v, __int_as_float(o));
+}
+__device__ __forceinline__ float gam_align_wave_max(float v) {
+  v = gam_align_dpp_max<0xb1, 0xf>(v);    // quad_perm [1,0,3,2]
+  v = gam_align_dpp_max<0x4e, 0xf>(v);    // quad_perm [2,3,0,1]
+  v = gam_align_dpp_max<0x141, 0xf>(v);   // row_half_mirror
+  v = gam_align_dpp_max<0x140, 0xf>(v);   // row_mirror: every lane holds its row's maximum
+  v = gam_align_dpp_max<0x142, 0xa>(v);   // row_bcast:15 -> rows 1, 3
+  v = gam_align_dpp_max<0x143, 0xc>(v);   // row_bcast:31 -> rows 2, 3
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+template <bool BP_LDS>
+__global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlignArgs a) {
+  extern __shared__ uint4 gam_smem_align[];
+  unsigned char* smem = reinterpret_cast<unsigned char*>(gam_smem_align);
+  const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+  const int b = blockIdx.x;
+  const int Tp = a.Tp, V = a.V, blank = V - 1;
+  const int sp = a.spt * nt + 2;                 // floats per state buffer: two -inf sentinels (s - 1, s - 2 of s = 0), then states
+  size_t off = BP_LDS ? (size_t)Tp * a.nchunk * 16 : 0;
+  uint4* bpl = gam_smem_align;
+  float* D = reinterpret_cast<float*>(smem + off);     // D[buf][2 + s], buf = t & 1
+  float* A = D + 2 * sp;
+  float* wm = A + 2 * sp;                              // per-wave maxima of the step: wm[(buf * 2 + {0: d, 1: a}) * 16 + wave]
+  int* misc = reinterpret_cast<int*>(wm + 64);         // repeats, bad id, path found
+  // the six output pointers, parked in LDS across the sweep: held in SGPRs through it they made the kernel spill SGPRs
+  void** outp = reinterpret_cast<void**>(misc + 4);
+  unsigned short* path = reinterpret_cast<unsigned short*>(misc + 16);
+
+  int T = a.enc_len[b];
+  T = T < 0 ? 0 : (T > Tp ? Tp : T);
+  const int U = a.target_len[b];
+  const bool ulen_ok = U >= 0 && U <= a.Umax;
+  const int* y = a.targets + (size_t)b * a.Umax;
+  if (tid < 4) misc[tid] = 0;
+  if (tid == 0) {
+    outp[0] = a.frame_labels; outp[1] = a.tok_first; outp[2] = a.tok_last;
+    outp[3] = a.score; outp[4] = a.loglik; outp[5] = a.status;
+  }
+  __syncthreads();
+  if (ulen_ok) {
+    int reps = 0, bad = 0;
+    for (int u = tid; u < U; u += nt) {
+      const int v = y[u];
+      bad |= (v < 0 || v > V - 2);
+      reps += (u > 0 && y[u - 1] == v);
+    }
+    if (reps) atomicAdd(&misc[0], reps);
+    if (bad) atomicOr(&misc[1], 1);
+  }
+  __syncthreads();
+  const int S = 2 * U + 1;
+  int* fl = a.frame_labels + (size_t)b * Tp;
+  int* tf = a.tok_first + (size_t)b * a.Umax;
+  int* tl = a.tok_last + (size_t)b * a.Umax;
+  const bool feasible = ulen_ok && misc[1] == 0 && T >= U + misc[0];
+  if (!feasible || T == 0) {      // (T == 0 and feasible: U == 0, the empty path)
+    for (int t = tid; t < Tp; t += nt) fl[t] = -1;
+    for (int u = tid; u < a.Umax; u += nt) tf[u] = tl[u] = -1;
+    if (tid == 0) {
+      a.score[b] = feasible ? 0.f : -INFINITY;
+      a.loglik[b] = feasible ? 0.f : -INFINITY;
+      a.status[b] = feasible ? 1 : 0;
+    }
+    return;
+  }
+
+  // this thread's states: label, whether the s-2 skip is allowed
+  int lab[GAM_ALIGN_MAX_SPT];
+  bool act[GAM_ALIGN_MAX_SPT], skip[GAM_ALIGN_MAX_SPT];
+#pragma unroll
+  for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) {
+    const int s = i * nt + tid;
+    act[i] = i < a.spt && s < S;
+    const bool tok = act[i] && (s & 1);
+    lab[i] = tok ? y[(s - 1) >> 1] : blank;
+    skip[i] = tok && s >= 3 && y[(s - 1) >> 1] != y[(s - 3) >> 1];
+  }
+  // t = -1: a virtual start that only state 0 holds (then d_0(0) = lp[0, blank], d_0(1) = lp[0, y0], the rest -inf)
+  for (int k = tid; k < 2 * sp; k += nt) {
+    D[k] = -INFINITY;
+    A[k] = -INFINITY;
+  }
+  if (tid < 64) wm[tid] = -INFINITY;
+  __syncthreads();
+  if (tid == 0) {
+    D[sp + 2] = 0.f;
+    A[sp + 2] = 0.f;
+  }
+  __syncthreads();
+
+  // Emission loads are unconditional (a row index clamped to T - 1, inactive states read the blank column): a load under a branch makes
+  // hipcc wait for every load in flight at its first use, which would serialise the prefetch.
+  const float* lpb = a.lp + (size_t)b * Tp * V;
+  float e[GAM_ALIGN_PF][GAM_ALIGN_MAX_SPT];
+#pragma unroll
+  for (int k = 0; k < GAM_ALIGN_PF; ++k)
+#pragma unroll
+    for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) e[k][i] = lpb[(size_t)(k < T ? k : T - 1) * V + lab[i]];
+
+  double offD = 0.0, offA = 0.0;   // what the renormalisations subtracted so far
+  for (int t0 = 0; t0 < T; t0 += GAM_ALIGN_PF) {
+#pragma unroll
+    for (int k = 0; k < GAM_ALIGN_PF; ++k) {
+      const int t = t0 + k;
+      if (t >= T) break;
+      const int cur = t & 1, prv = cur ^ 1;
+      const float* Dp = D + prv * sp + 2;
+      const float* Ap = A + prv * sp + 2;
+      float* Dc = D + cur * sp + 2;
+      float* Ac = A + cur * sp + 2;
+      float mD = -INFINITY, mA = -INFINITY;
+#pragma unroll
+      for (int w = 0; w < 16; w += 4) {   // (all 16 slots: those of absent waves hold -inf)
+        const float4 xd = *reinterpret_cast<const float4*>(wm + (prv * 2) * 16 + w);
+        const float4 xa = *reinterpret_cast<const float4*>(wm + (prv * 2 + 1) * 16 + w);
+        mD = fmaxf(mD, fmaxf(fmaxf(xd.x, xd.y), fmaxf(xd.z, xd.w)));
+        mA = fmaxf(mA, fmaxf(fmaxf(xa.x, xa.y), fmaxf(xa.z, xa.w)));
+      }
+      if (mD == -INFINITY) mD = 0.f;
+      if (mA == -INFINITY) mA = 0.f;
+      offD += (double)mD;
+      offA += (double)mA;
+      float lmD = -INFINITY, lmA = -INFINITY;
+      unsigned bpv[GAM_ALIGN_MAX_SPT];
+#pragma unroll
+      for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) {
+        const int s = i * nt + tid;
+        unsigned bp = 0;
+        if (act[i]) {
+          const float d0 = Dp[s], d1 = Dp[s - 1], d2 = skip[i] ? Dp[s - 2] : -INFINITY;
+          float best = d0;
+          if (d1 > best) { best = d1; bp = 1; }
+          if (d2 > best) { best = d2; bp = 2; }
+          const float nd = (best - mD) + e[k][i];
+          const float a0 = Ap[s], a1 = Ap[s - 1], a2 = skip[i] ? Ap[s - 2] : -INFINITY;
+          const float M = fmaxf(fmaxf(a0, a1), a2);
+          float na = -INFINITY;
+          if (M > -INFINITY) na = ((M - mA) + gam_align_log(gam_align_exp(a0 - M) + gam_align_exp(a1 - M) + gam_align_exp(a2 - M))) + e[k][i];
+          Dc[s] = nd;
+          Ac[s] = na;
+          lmD = fmaxf(lmD, nd);
+          lmA = fmaxf(lmA, na);
+        }
+        bpv[i] = bp;
+      }
+      // the row t + PF replaces the one just used (its load is in flight during the next PF - 1 steps)
+      const int tn = t + GAM_ALIGN_PF < T ? t + GAM_ALIGN_PF : T - 1;
+#pragma unroll
+      for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) e[k][i] = lpb[(size_t)tn * V + lab[i]];
+      lmD = gam_align_wave_max(lmD);
+      lmA = gam_align_wave_max(lmA);
+#pragma unroll
+      for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) {
+        if (i >= a.spt) break;
+        const unsigned long long m1 = __ballot(bpv[i] & 1u), m2 = __ballot(bpv[i] >> 1);
+        const int c = i * nw + wave;
+        if (lane == 0 && c < a.nchunk) {
+          const uint4 w = make_uint4((unsigned)m1, (unsigned)(m1 >> 32), (unsigned)m2, (unsigned)(m2 >> 32));
+          if (BP_LDS) bpl[(size_t)t * a.nchunk + c] = w;
+          else a.bp_glob[((size_t)b * Tp + t) * a.nchunk + c] = w;
+        }
+      }
+      if (lane == 0) {
+        wm[(cur * 2) * 16 + wave] = lmD;
+        wm[(cur * 2 + 1) * 16 + wave] = lmA;
+      }
+      __syncthreads();
+    }
+  }
+
+  fl = reinterpret_cast<int*>(outp[0]) + (size_t)b * Tp;
+  tf = reinterpret_cast<int*>(outp[1]) + (size_t)b * a.Umax;
+  tl = reinterpret_cast<int*>(outp[2]) + (size_t)b * a.Umax;
+  if (tid == 0) {
+    float* score = reinterpret_cast<float*>(outp[3]);
+    float* loglik = reinterpret_cast<float*>(outp[4]);
+    int* status = reinterpret_cast<int*>(outp[5]);
+    const int fb = (T - 1) & 1;
+    const float* Df = D + fb * sp + 2;
+    const float* Af = A + fb * sp + 2;
+    int s = S - 1;
+    float best = Df[S - 1];
+    if (S >= 2 && Df[S - 2] > best) { best = Df[S - 2]; s = S - 2; }
+    const float a1 = Af[S - 1], a2 = S >= 2 ? Af[S - 2] : -INFINITY;
+    const float M = fmaxf(a1, a2);
+    const bool found = best > -INFINITY;
+    score[b] = found ? (float)((double)best + offD) : -INFINITY;
+    loglik[b] = found && M > -INFINITY ? (float)((double)(M + logf(expf(a1 - M) + expf(a2 - M))) + offA) : -INFINITY;
+    status[b] = found ? 1 : 0;
+    misc[2] = found ? 1 : 0;
+    if (found) {
+      for (int t = T - 1; t >= 0; --t) {
+        path[t] = (unsigned short)s;
+        if (t == 0) break;
+        const uint4 w = BP_LDS ? bpl[(size_t)t * a.nchunk + (s >> 6)] : a.bp_glob[((size_t)b * Tp + t) * a.nchunk + (s >> 6)];
+        const int sh = s & 31;
+        const unsigned lo = (s & 32) ? w.y : w.x, hi = (s & 32) ? w.w : w.z;
+        s -= (int)(((lo >> sh) & 1u) | (((hi >> sh) & 1u) << 1));
+      }
+    }
+  }
+  __syncthreads();
+  if (!misc[2]) {
+    for (int t = tid; t < Tp; t += nt) fl[t] = -1;
+    for (int u = tid; u < a.Umax; u += nt) tf[u] = tl[u] = -1;
+    return;
+  }
+  for (int t = tid; t < Tp; t += nt) {
+    int out = -1;
+    if (t < T) {
+      const int s = path[t];
+      out = (s & 1) ? y[(s - 1) >> 1] : blank;
+      if (s & 1) {
+        const int u = (s - 1) >> 1;
+        if (t == 0 || path[t - 1] != s) tf[u] = t;
+        if (t == T - 1 || path[t + 1] != s) tl[u] = t;
+      }
+    }
+    fl[t] = out;
+  }
+  for (int u = U + tid; u < a.Umax; u += nt) tf[u] = tl[u] = -1;
+}

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/gigaam_hip.h"
+#include "gam_align.h"
 #include "gam_attn.h"
 #include "gam_attn16.h"
 #include "gam_comm.h"
@@ -126,6 +127,7 @@ struct gam_handle {
   // workspace (grow-only)
   DevBuf wavp, spec, img, c2, xin, y1, x, y, yr, hbuf, qkv, ctx, ubuf, zbuf, tok, logits, encp, pbuf, aplanes;
   DevBuf op_planes, op_sp, splitk_ws;   // gam_op_gemm operand planes; split-K partial sums
+  DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
   DevBuf dec_splitk_ws;                 // split-K partial sums of the DECODE class's GEMMs: a decode may run on a side stream beside
                                         // the next batch's encoder (r05), so it shares no scratch with it (tok / logits / encp / rnnt_x
                                         // are the decode's alone already)
@@ -1402,6 +1404,74 @@ int gam_ctc_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, 
   hipLaunchKernelGGL(gam_ctc_greedy_kernel, dim3(B), dim3(GAM_CTC_NT), sm, s, h->logits.p, enc_len, (int)Tp, V, ids, frames, counts);
   HIPCHK(h, hipGetLastError());
   return 0;
+}
+
+// CTC forced alignment over log-probs [B, Tp, V] (gam_align.h): one workgroup per utterance.  Decode class (the caller holds a DecodeScope):
+// the backpointer scratch is the handle's.
+static int ctc_align_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
+                            const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last,
+                            float* score, float* loglik, int32_t* status, hipStream_t s) {
+  if (B <= 0 || Tp <= 0 || V < 2) return fail(h, -1, "CTC alignment: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
+  if (Tp > GAM_ALIGN_MAX_T) return fail(h, -1, "CTC alignment: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_ALIGN_MAX_T);
+  if (Umax < 0 || Umax > GAM_ALIGN_MAX_U) return fail(h, -1, "CTC alignment: Umax=%d tokens outside [0, %d]", Umax, GAM_ALIGN_MAX_U);
+  if (!lp || !enc_len || !target_len || !frame_labels || !score || !loglik || !status ||
+      (Umax > 0 && (!targets || !tok_first || !tok_last)))
+    return fail(h, -1, "CTC alignment: NULL buffer");
+  const int smax = 2 * Umax + 1;
+  const int nt = std::min(GAM_ALIGN_MAX_NT, std::max(64, (smax + 63) / 64 * 64));
+  const int spt = (smax + nt - 1) / nt;
+  const int nchunk = (smax + 63) / 64;
+  const bool bp_lds = gam_align_lds_bytes(true, (int)Tp, nchunk, spt, nt) <= GAM_ALIGN_LDS_MAX;
+  const size_t sm = gam_align_lds_bytes(bp_lds, (int)Tp, nchunk, spt, nt);
+  if (sm > GAM_ALIGN_LDS_MAX) return fail(h, -1, "CTC alignment: T'=%lld x Umax=%d needs %zu bytes of LDS", (long long)Tp, Umax, sm);
+  GamAlignArgs a;
+  a.lp = lp; a.enc_len = enc_len; a.targets = targets; a.target_len = target_len;
+  a.Tp = (int)Tp; a.V = V; a.Umax = Umax; a.spt = spt; a.nchunk = nchunk; a.bp_glob = nullptr;
+  a.frame_labels = frame_labels; a.tok_first = tok_first; a.tok_last = tok_last; a.score = score; a.loglik = loglik; a.status = status;
+  if (!bp_lds) {
+    if (int r = ensure(h, h->align_bp, (size_t)B * Tp * nchunk * 4 + 64)) return r;
+    a.bp_glob = reinterpret_cast<uint4*>(h->align_bp.p);
+  }
+  static std::atomic<unsigned long long> lds_set[2];
+  const void* kern = bp_lds ? (const void*)gam_ctc_align_kernel<true> : (const void*)gam_ctc_align_kernel<false>;
+  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds(kern, GAM_ALIGN_LDS_MAX, lds_set[bp_lds ? 1 : 0]));
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * smax * 4.0);
+  if (bp_lds) hipLaunchKernelGGL(gam_ctc_align_kernel<true>, dim3(B), dim3(nt), sm, s, a);
+  else hipLaunchKernelGGL(gam_ctc_align_kernel<false>, dim3(B), dim3(nt), sm, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_ctc_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                  const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
+                  float* loglik, int32_t* status, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
+  DecodeScope ds(h, s);
+  if (Tp > GAM_ALIGN_MAX_T || Umax < 0 || Umax > GAM_ALIGN_MAX_U)
+    return fail(h, -1, "CTC alignment: T'=%lld / Umax=%d beyond the limits (%d / %d)", (long long)Tp, Umax, GAM_ALIGN_MAX_T, GAM_ALIGN_MAX_U);
+  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
+  const int V = h->cfg.num_classes, rows = (int)(B * Tp);
+  {
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
+    // in place: each row is read whole by its wave before that wave writes it
+    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
+    HIPCHK(h, hipGetLastError());
+  }
+  return ctc_align_launch(h, h->logits.p, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score,
+                          loglik, status, s);
+}
+
+int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
+                     const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
+                     float* loglik, int32_t* status, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return ctc_align_launch(h, log_probs, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score, loglik,
+                          status, s);
 }
 
 #if GAM_RC_AUDIT

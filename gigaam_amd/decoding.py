@@ -27,6 +27,21 @@ class Tokenizer:
             self.model = SentencePieceProcessor()
             self.model.load(model_path)
 
+    def encode(self, text: str) -> List[int]:
+        """Text -> token ids (the inverse of ``decode``): one id per character of a char-wise vocabulary -- a ``ValueError`` names
+        every character it does not hold, nothing is normalised -- or the SentencePiece model's ``EncodeAsIds``."""
+        if not self.charwise:
+            return list(self.model.EncodeAsIds(text))
+        index = getattr(self, "_index", None)
+        if index is None:
+            index = self._index = {}
+            for i, c in enumerate(self.vocab):
+                index.setdefault(c, i)
+        unknown = sorted({c for c in text if c not in index})
+        if unknown:
+            raise ValueError(f"characters not in the vocabulary: {', '.join(repr(c) for c in unknown)}")
+        return [index[c] for c in text]
+
     def decode(self, tokens: List[int]) -> str:
         if self.charwise:
             return "".join(self.vocab[t] for t in tokens)
@@ -78,6 +93,32 @@ class CTCGreedyDecoding:
     @torch.inference_mode()
     def decode(self, head: CTCHead, encoded: Tensor, lengths: Tensor) -> List[Tuple[str, List[int], List[int]]]:
         return self.finish(self.decode_device(head, encoded, lengths))
+
+    MAX_ALIGN_TOKENS = 1024     # include/gigaam_hip.h gam_ctc_align
+
+    @torch.inference_mode()
+    def align(self, head: CTCHead, encoded: Tensor, lengths: Tensor, targets: List[List[int]]):
+        """CTC forced alignment of known token ids (one list per utterance) on the device (gam_ctc_align), ONE D2H for the
+        result.  Returns per utterance ``(ids, first_frames, last_frames, score, loglik, feasible)``: the first / last encoder frame
+        of each token's run on the best path, that path's log-prob, log p(ids | audio) (= -ctc_loss) and whether any path exists
+        (if not: empty frame lists, -inf scores).  Raises ``RangeOverflow`` like ``finish``."""
+        c = head.num_classes
+        assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
+        targets = [[int(t) for t in ids] for ids in targets]
+        too_long = [len(t) for t in targets if len(t) > self.MAX_ALIGN_TOKENS]
+        if too_long:
+            raise ValueError(f"forced alignment takes at most {self.MAX_ALIGN_TOKENS} tokens per utterance (got {max(too_long)})")
+        h = head.engine.ctc_align(encoded, lengths, targets).host()
+        if h["flag"]:
+            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        out = []
+        for i, ids in enumerate(targets):
+            ok = bool(h["status"][i])
+            n = len(ids)
+            first = h["tok_first"][i, :n].tolist() if ok else []
+            last = h["tok_last"][i, :n].tolist() if ok else []
+            out.append((ids, first, last, float(h["score"][i]), float(h["loglik"][i]), ok))
+        return out
 
 
 class RNNTGreedyDecoding:

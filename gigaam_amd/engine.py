@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Any, Dict, Mapping, Optional, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -109,6 +110,54 @@ class Decoded(tuple):
     def flag_word(self) -> Optional[Tensor]:
         """The device word (i32 [1]) that received the range flag of this decode, or None."""
         return None if self.ext is None else self.ext[-1:]
+
+
+class Aligned:
+    """What ``ctc_align`` / ``op_ctc_align`` return: every output of the alignment kernel as a view of ONE i32 device buffer
+    (``whole``) that reaches the host in ONE copy (``host``), like ``Decoded.whole``.  Layout: frame_labels [B, T'] | tok_first
+    [B, Umax] | tok_last [B, Umax] | status [B] | score [B] (f32 bits) | loglik [B] (f32 bits) | range flag word."""
+
+    def __init__(self, whole: Tensor, b: int, tp: int, umax: int, event=None, stream=None):
+        self.whole, self.b, self.tp, self.umax, self.event, self.stream = whole, b, tp, umax, event, stream
+        o = 0
+
+        def take(n: int) -> Tensor:
+            nonlocal o
+            o += n
+            return whole[o - n: o]
+
+        self.frame_labels = take(b * tp).view(b, tp)
+        self.tok_first = take(b * umax).view(b, umax)
+        self.tok_last = take(b * umax).view(b, umax)
+        self.status = take(b)
+        self.score = take(b).view(torch.float32)
+        self.loglik = take(b).view(torch.float32)
+        self.ext = take(1)
+
+    def host(self) -> Dict[str, Any]:
+        """One blocking D2H of the whole result, on the collect stream behind the alignment's own completion event -> numpy arrays
+        (``frame_labels``, ``tok_first``, ``tok_last``, ``status``, ``score``, ``loglik``) and ``flag`` (the split-fp16
+        range flag of the encoder run that produced the log-probs: True = repeat under GAM_GEMM_F32)."""
+        side = HipEngine._collect_stream(self.whole.device)
+        with torch.cuda.stream(side):
+            if self.event is not None:
+                side.wait_event(self.event)
+            else:
+                side.wait_stream(torch.cuda.current_stream(self.whole.device))
+            arr = self.whole.cpu().numpy()
+        self.whole.record_stream(side)
+        b, tp, um = self.b, self.tp, self.umax
+        o = [0]
+
+        def take(n: int):
+            o[0] += n
+            return arr[o[0] - n: o[0]]
+
+        out = {"frame_labels": take(b * tp).reshape(b, tp), "tok_first": take(b * um).reshape(b, um),
+               "tok_last": take(b * um).reshape(b, um), "status": take(b),
+               "score": take(b).view(np.float32), "loglik": take(b).view(np.float32)}
+        out["flag"] = HipEngine._flag_of(int(take(1)[0]))
+        return out
 
 
 def _ptr(t: Optional[Tensor]) -> C.c_void_p:
@@ -393,6 +442,58 @@ class HipEngine:
             self._check(rc, "gam_ctc_greedy")
             evt, st = self._fetch_flag(ext)
         return Decoded(ids, frames, counts, ext, evt, st, whole=whole)
+
+    def _align_buffers(self, b: int, tp: int, targets, target_len):
+        """targets: [B, Umax] ints or a list of B int lists; target_len [B] (None: the rows' lengths) -> device i32 tensors + Aligned buffer."""
+        if isinstance(targets, Tensor):
+            tgt = targets.reshape(b, -1)
+            tlen = torch.full((b,), tgt.shape[1], dtype=torch.int32) if target_len is None else target_len
+        else:
+            if len(targets) != b:
+                raise GigaAMHipError(f"{len(targets)} targets for a batch of {b}")
+            um = max([len(t) for t in targets] + [0])
+            tgt = torch.zeros((b, um), dtype=torch.int32)
+            for i, t in enumerate(targets):
+                if len(t):
+                    tgt[i, : len(t)] = torch.as_tensor(list(t), dtype=torch.int32)
+            tlen = torch.tensor([len(t) for t in targets], dtype=torch.int32) if target_len is None else target_len
+        tgt, tlen = self._dev(tgt, torch.int32), self._dev(tlen, torch.int32)
+        um = tgt.shape[1]
+        whole = torch.empty((b * tp + 2 * b * um + 3 * b + 1,), dtype=torch.int32, device=self.device)
+        return tgt, tlen, Aligned(whole, b, tp, um)
+
+    def _launch_align(self, fn, first, enc_len: Tensor, b: int, tp: int, extra, tgt: Tensor, tlen: Tensor, out: Aligned, what: str) -> None:
+        rc = fn(self._h, _ptr(first), _ptr(enc_len), b, tp, *extra, _ptr(tgt), _ptr(tlen), out.umax, _ptr(out.frame_labels),
+                _ptr(out.tok_first), _ptr(out.tok_last), _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
+        self._check(rc, what)
+
+    def ctc_align(self, encoded: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None) -> Aligned:
+        """CTC forced alignment of known targets (gam_ctc_align): the CTC head, its log-softmax and the alignment kernel, no host sync.
+        ``targets``: i32 [B, Umax] (entries past ``target_len[b]`` are ignored) or a list of B token-id lists.  The split-fp16 range
+        flag is CONSUMED as ``ctc_greedy`` does: it lands in the result's last word (``Aligned.host()['flag']``)."""
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        tgt, tlen, out = self._align_buffers(b, tp, targets, target_len)
+        with torch.cuda.device(self.device):
+            self._launch_align(self.lib.gam_ctc_align, encoded, enc_len, b, tp, (), tgt, tlen, out, "gam_ctc_align")
+            out.event, out.stream = self._fetch_flag(out.ext)
+        return out
+
+    def op_ctc_align(self, log_probs: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None) -> Aligned:
+        """gam_op_ctc_align: the alignment kernel alone on caller-supplied log-probs [B, T', V] (used as they are).  The result's flag
+        word is 0 (no encoder ran)."""
+        log_probs = self._dev(log_probs, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, v = log_probs.shape
+        tgt, tlen, out = self._align_buffers(b, tp, targets, target_len)
+        with torch.cuda.device(self.device):
+            out.ext.zero_()
+            self._launch_align(self.lib.gam_op_ctc_align, log_probs, enc_len, b, tp, (v,), tgt, tlen, out, "gam_op_ctc_align")
+            st = torch.cuda.current_stream(self.device)
+            out.event, out.stream = torch.cuda.Event(), st
+            out.event.record(st)
+        return out
 
     def set_rnnt_cluster(self, n: int) -> None:
         """Workgroups per utterance of the cluster decode kernel (gam_set_rnnt_cluster): -1 auto, 0 one-workgroup kernel, 1..8."""

@@ -7,7 +7,7 @@ handle per model.
 """
 from __future__ import annotations
 
-from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor, nn
@@ -18,7 +18,7 @@ from . import encoder as _encoder
 from . import preprocess as _preprocess
 from .engine import HipEngine, build_config
 from .preprocess import SAMPLE_RATE, load_audio
-from .types import LongformTranscriptionResult, Segment, TranscriptionResult, Word
+from .types import AlignmentResult, LongformTranscriptionResult, Segment, TranscriptionResult, Word
 
 LONGFORM_THRESHOLD = 25 * SAMPLE_RATE
 
@@ -303,6 +303,52 @@ class GigaAMASR(GigaAM):
         """Batched twin of ``transcribe`` on an already collated batch (wav [B,L] zero
         padded, len [B]) -- the unit bench.py and the longform driver iterate."""
         return self._with_f32_fallback(lambda: self.collect_batch(self.launch_batch(wav, lengths), word_timestamps), "this batch was")
+
+    # ---- CTC forced alignment: a KNOWN transcript placed on the audio, and its log-likelihood (gam_ctc_align)
+    def _require_ctc(self) -> None:
+        if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
+            raise TypeError("forced alignment needs a CTC head")
+
+    @torch.inference_mode()
+    def align(self, wav_file: str, text: Union[str, List[int]]) -> AlignmentResult:
+        """Align ``text`` (a string in the model's vocabulary, or token ids) to a clip of at most 25 s.  Words are built as
+        ``transcribe(word_timestamps=True)`` builds them, from each token's first frame on the best path.  Raises ``ValueError``
+        for a longer clip, for characters outside the vocabulary, or for a text that no alignment can fit into the clip."""
+        self._require_ctc()
+        wav, length = self._prepare_wav_f32(wav_file)
+        if length.item() > LONGFORM_THRESHOLD:
+            raise ValueError("Too long wav file for forced alignment (at most 25 s).")
+        res = self.align_batch(wav, length, [text])[0]
+        if not res.feasible:
+            raise ValueError(f"the text ({len(res.token_ids)} tokens) cannot be aligned to this audio: too long for it")
+        return res
+
+    @torch.inference_mode()
+    def align_batch(self, wav: Tensor, lengths: Tensor, texts: Sequence[Union[str, List[int]]]) -> List[AlignmentResult]:
+        """Batched ``align`` on a collated batch (wav [B,L] zero padded, len [B]); ``texts`` holds a ``str`` or token ids per
+        utterance.  An utterance no alignment fits gets ``feasible=False`` (empty words, -inf scores) instead of an error."""
+        self._require_ctc()
+        if len(texts) != wav.shape[0]:
+            raise ValueError(f"{len(texts)} texts for a batch of {wav.shape[0]}")
+        tok = self.decoding.tokenizer
+        targets = [tok.encode(t) if isinstance(t, str) else [int(i) for i in t] for t in texts]
+
+        def run():
+            # as launch_batch: sample counts on the host give a ragged batch packed rows
+            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
+            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            return self.decoding.align(self.head, encoded, encoded_len, targets), encoded_len
+
+        rows, encoded_len = self._with_f32_fallback(run, "this batch was")
+        from .timestamps_utils import compute_frame_shift, frames_to_words
+
+        wl, el = lengths.tolist(), encoded_len.tolist()
+        out: List[AlignmentResult] = []
+        for i, (ids, first, _last, score, loglik, ok) in enumerate(rows):
+            words = frames_to_words(tok, ids, first, compute_frame_shift(int(wl[i]), int(el[i]))) if ok else []
+            out.append(AlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_frames=first, score=score,
+                                       log_likelihood=loglik, feasible=ok))
+        return out
 
     @torch.inference_mode()
     def transcribe_longform(self, wav_file: str, word_timestamps: bool = False, fr_batch_size: int = 16,

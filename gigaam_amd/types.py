@@ -23,6 +23,24 @@ class TranscriptionResult:
 
 
 @dataclass
+class AlignmentResult:
+    """``GigaAMASR.align``: a known transcript placed on the audio by CTC forced alignment.  ``token_frames``: the first encoder
+    frame of each token on the best path; ``score``: that path's log-prob; ``log_likelihood``: log p(text | audio) over all paths
+    (= -CTC loss); ``feasible``: False when no path exists (the text is too long for the audio) -- then ``words`` and
+    ``token_frames`` are empty and both scores are -inf."""
+    text: str
+    words: List[Word]
+    token_ids: List[int]
+    token_frames: List[int]
+    score: float
+    log_likelihood: float
+    feasible: bool
+
+    def __str__(self) -> str:
+        return self.text
+
+
+@dataclass
 class Segment:
     text: str
     start: float

@@ -11,6 +11,7 @@
  *   gam_encode       <- ConformerEncoder.forward          gigaam/encoder.py:605-647
  *   gam_ctc_head     <- CTCHead.forward                   gigaam/decoder.py:18-21
  *   gam_ctc_greedy   <- CTCGreedyDecoding.decode          gigaam/decoding.py:56-96
+ *   gam_ctc_align    (no reference counterpart: CTC forced alignment + log-likelihood of a given transcript)
  *   gam_rnnt_greedy  <- RNNTGreedyDecoding.decode         gigaam/decoding.py:128-207
  *                        (+ RNNTDecoder.predict decoder.py:85-102, RNNTJoint.joint :41-47)
  *   gam_emo_probs    <- GigaAMEmo.get_probs (pool+head)    gigaam/model.py:272-285
@@ -118,6 +119,26 @@ int gam_ctc_head(gam_handle* h, const float* encoded, int B, int64_t Tp, float* 
 /* CTCGreedyDecoding.decode: -> ids i32 [B,T'], frames i32 [B,T'] (first counts[b] valid), counts i32 [B]. */
 int gam_ctc_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp,
                    int32_t* ids, int32_t* frames, int32_t* counts, void* stream);
+
+/* CTC forced alignment and transcript scoring (gigaam_amd/csrc/gam_align.h).  Runs the CTC head, its log-softmax and ONE alignment
+ * kernel (a workgroup per utterance: Viterbi best path + forward log-likelihood in one sweep over t, backtrack in the same kernel).
+ *   targets i32 [B, Umax] (entries past target_len[b] are never read), target_len i32 [B], 0 <= Umax <= 1024; blank = V - 1.
+ *   frame_labels i32 [B, T']: the best path's label per frame (token id or blank), -1 at t >= enc_len[b].
+ *   tok_first / tok_last i32 [B, Umax]: first / last frame of each token's run on that path, -1 past target_len[b].
+ *   score f32 [B]: the best path's log-prob (sum over frames); loglik f32 [B]: log p(target | audio) = -ctc_loss.
+ *   status i32 [B]: 1 aligned, 0 infeasible -- enc_len[b] < U + (adjacent repeats), a target id outside [0, V-2], target_len[b]
+ *   outside [0, Umax], or no path of finite score; then score = loglik = -inf and frames / token frames are -1.
+ * Ties: among equal predecessors the path keeps the state (s) over s-1 over s-2; it ends in the last token's state (S-1) over the
+ * trailing blank (S-2) when both score the same.  Limits: Umax <= 1024, T' <= 8192 (an error beyond them).
+ * Decode class, like gam_ctc_greedy; no host synchronisation.  Consumers of the range flag fetch it behind this call. */
+int gam_ctc_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                  const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
+                  float* loglik, int32_t* status, void* stream);
+/* The same from caller-supplied log-probs f32 [B, T', V] (read as they are: no normalisation), for op-level tests and callers that
+ * bring their own CTC posteriors. */
+int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
+                     const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
+                     float* loglik, int32_t* status, void* stream);
 
 /* RNNTGreedyDecoding.decode: ids/frames i32 [B, T'*max_symbols], counts i32 [B].
  * Optional dump of the log-softmax of every joint evaluation, in order, per utterance:
