@@ -16,6 +16,7 @@
 #include "../../include/gigaam_hip.h"
 #include "gam_align.h"
 #include "gam_attn.h"
+#include "gam_beam.h"
 #include "gam_attn16.h"
 #include "gam_comm.h"
 #include "gam_common.h"
@@ -128,6 +129,11 @@ struct gam_handle {
   DevBuf wavp, spec, img, c2, xin, y1, x, y, yr, hbuf, qkv, ctx, ubuf, zbuf, tok, logits, encp, pbuf, aplanes;
   DevBuf op_planes, op_sp, splitk_ws;   // gam_op_gemm operand planes; split-K partial sums
   DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
+  DevBuf beam_nodes;                    // CTC beam search prefix-trie nodes, B x T' x W (gam_beam.h)
+  int* hw_trie = nullptr;               // hotword trie of gam_set_hotwords (CSR, gam_beam.h): offsets | edges; NULL = no hotwords
+  size_t hw_cap = 0;                    // ints allocated at hw_trie
+  int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
+  float hw_boost = 0.f;
   DevBuf dec_splitk_ws;                 // split-K partial sums of the DECODE class's GEMMs: a decode may run on a side stream beside
                                         // the next batch's encoder (r05), so it shares no scratch with it (tok / logits / encp / rnnt_x
                                         // are the decode's alone already)
@@ -545,6 +551,8 @@ void gam_destroy(gam_handle* h) {
     if (b->p) hipFree(b->p);
   if (h->lens) hipFree(h->lens);
   if (h->range_flag) hipFree(h->range_flag);
+  if (h->beam_nodes.p) hipFree(h->beam_nodes.p);
+  if (h->hw_trie) hipFree(h->hw_trie);
   for (auto& e : h->prof_events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (auto& g : h->graphs)
     if (g.second.exec) hipGraphExecDestroy(g.second.exec);
@@ -1472,6 +1480,131 @@ int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_l
   DecodeScope ds(h, s);
   return ctc_align_launch(h, log_probs, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score, loglik,
                           status, s);
+}
+
+// CTC prefix beam search over log-probs [B, Tp, V] (gam_beam.h): one workgroup per utterance.  Decode class (the caller holds a
+// DecodeScope): the prefix-trie nodes are the handle's.
+static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
+                           int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s) {
+  if (B <= 0 || Tp <= 0 || V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "CTC beam search: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
+  if (Tp > GAM_ALIGN_MAX_T) return fail(h, -1, "CTC beam search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_ALIGN_MAX_T);
+  if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "CTC beam search: beam width W=%d outside [1, %d]", W, GAM_BEAM_MAX_W);
+  if (!lp || !enc_len || !ids || !frames || !counts || !score || !logp) return fail(h, -1, "CTC beam search: NULL buffer");
+  if (h->hw_trie && h->hw_max_tok > V - 2)
+    return fail(h, -1, "CTC beam search: hotword token id %d outside [0, %d] for V=%d", h->hw_max_tok, V - 2, V);
+  const int K = std::min(W, V - 1);
+  const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
+  const size_t sm = gam_beam_lds_bytes(W, K, V, hw_lds ? h->hw_words : 0);
+  if (int r = ensure(h, h->beam_nodes, (size_t)B * Tp * W * 2 + 64)) return r;
+  GamBeamArgs a;
+  a.lp = lp; a.enc_len = enc_len; a.Tp = (int)Tp; a.V = V; a.W = W; a.K = K;
+  a.hw = h->hw_trie; a.hw_nodes = h->hw_nodes; a.hw_words = h->hw_words; a.hw_lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
+  a.nodes = reinterpret_cast<int2*>(h->beam_nodes.p);
+  a.ids = ids; a.frames = frames; a.counts = counts; a.score = score; a.logp = logp;
+  static std::atomic<unsigned long long> lds_set;
+  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds((const void*)gam_ctc_beam_kernel, (int)sm, lds_set));
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * W * (K + 1) * 4.0);
+  hipLaunchKernelGGL(gam_ctc_beam_kernel, dim3(B), dim3(GAM_BEAM_NT), sm, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
+                 int32_t* counts, float* score, float* logp, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
+  DecodeScope ds(h, s);
+  if (Tp > GAM_ALIGN_MAX_T || W < 1 || W > GAM_BEAM_MAX_W)
+    return fail(h, -1, "CTC beam search: T'=%lld / W=%d beyond the limits (%d / [1, %d])", (long long)Tp, W, GAM_ALIGN_MAX_T, GAM_BEAM_MAX_W);
+  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
+  const int V = h->cfg.num_classes, rows = (int)(B * Tp);
+  {
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
+    // in place: each row is read whole by its wave before that wave writes it
+    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
+    HIPCHK(h, hipGetLastError());
+  }
+  return ctc_beam_launch(h, h->logits.p, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s);
+}
+
+int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
+                    int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return ctc_beam_launch(h, log_probs, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s);
+}
+
+int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offsets, int n_phrases, float boost) {
+  if (!h) return -1;
+  if (n_phrases < 0 || n_phrases > GAM_BEAM_MAX_PHRASES)
+    return fail(h, -1, "hotwords: %d phrases outside [0, %d]", n_phrases, GAM_BEAM_MAX_PHRASES);
+  if (n_phrases > 0 && (!tokens || !offsets)) return fail(h, -1, "hotwords: NULL buffer");
+  if (!std::isfinite(boost)) return fail(h, -1, "hotwords: boost is not finite");
+  // the trie on the host: children per node (token -> child), phrase ends
+  std::vector<std::map<int, int>> kids(1);
+  std::vector<char> end(1, 0);
+  int max_tok = -1;
+  if (n_phrases > 0) {
+    if (offsets[0] != 0) return fail(h, -1, "hotwords: offsets[0] = %d, expected 0", offsets[0]);
+    const int hi = h->cfg.head_type == GAM_HEAD_CTC && h->cfg.num_classes >= 2 ? h->cfg.num_classes - 2 : GAM_BEAM_MAX_V - 2;
+    for (int i = 0; i < n_phrases; ++i) {
+      const int a = offsets[i], e = offsets[i + 1];
+      if (e <= a) return fail(h, -1, "hotwords: phrase %d is empty or its offsets decrease", i);
+      if (e > GAM_BEAM_MAX_HW_TOKENS) return fail(h, -1, "hotwords: more than %d tokens in all", GAM_BEAM_MAX_HW_TOKENS);
+      int n = 0;
+      for (int k = a; k < e; ++k) {
+        const int c = tokens[k];
+        if (c < 0 || c > hi) return fail(h, -1, "hotwords: token id %d of phrase %d outside [0, %d]", c, i, hi);
+        max_tok = std::max(max_tok, c);
+        auto it = kids[n].find(c);
+        if (it == kids[n].end()) {
+          kids.emplace_back();
+          end.push_back(0);
+          it = kids[n].emplace(c, (int)kids.size() - 1).first;
+        }
+        n = it->second;
+      }
+      end[n] = 1;
+    }
+  }
+  // CSR: offsets [nodes + 1], then each node's edges in token order (token | end << 11 | child << 12)
+  const int nn = (int)kids.size();
+  std::vector<int> flat((size_t)nn + 1);
+  int ne = 0;
+  for (int n = 0; n < nn; ++n) {
+    flat[n] = ne;
+    ne += (int)kids[n].size();
+  }
+  flat[nn] = ne;
+  for (int n = 0; n < nn; ++n)
+    for (const auto& kv : kids[n]) flat.push_back(kv.first | (end[kv.second] << 11) | (kv.second << 12));
+  HIPCHK(h, hipSetDevice(h->device));
+  // a decode-class kernel still in flight may read the current trie
+  if (h->dec_evt != nullptr && h->dec_evt_set) HIPCHK(h, hipEventSynchronize(h->dec_evt));
+  if (n_phrases == 0) {
+    h->hw_nodes = h->hw_words = 0;
+    h->hw_max_tok = -1;
+    if (h->hw_trie) HIPCHK(h, hipFree(h->hw_trie));
+    h->hw_trie = nullptr;
+    h->hw_cap = 0;
+    return 0;
+  }
+  if (flat.size() > h->hw_cap) {
+    if (h->hw_trie) HIPCHK(h, hipFree(h->hw_trie));
+    h->hw_trie = nullptr;
+    h->hw_cap = 0;
+    HIPCHK(h, hipMalloc(&h->hw_trie, flat.size() * sizeof(int)));
+    h->hw_cap = flat.size();
+  }
+  HIPCHK(h, hipMemcpy(h->hw_trie, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+  h->hw_nodes = nn;
+  h->hw_words = (int)flat.size();
+  h->hw_max_tok = max_tok;
+  h->hw_boost = boost;
+  return 0;
 }
 
 #if GAM_RC_AUDIT

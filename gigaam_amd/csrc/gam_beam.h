@@ -1,0 +1,423 @@
+// gam_beam.h -- CTC prefix beam search with hotword boosting (gam_ctc_beam / gam_op_ctc_beam).
+//
+// The algorithm (shared with tests/ctc_beam_ref.py, which holds real prefix tuples): for utterance b with log-probs lp[t, v]
+// (t < T = enc_len[b], blank = V - 1), beam width W and K = min(W, V - 1) candidate tokens per frame (the top-K non-blank ids of
+// lp[t], ties to the lower id), every beam entry y (last token l; p_b / p_nb: log-probs of the paths ending in blank / non-blank)
+// contributes, with (+) = log-add-exp:
+//   stay    y.p_b      (+)= (p_b (+) p_nb) + lp[t, blank]
+//   repeat  y.p_nb     (+)= p_nb + lp[t, l]                             (y non-empty, whether or not l is a candidate)
+//   extend  (y+c).p_nb (+)= (c == l ? p_b : p_b (+) p_nb) + lp[t, c]   for each candidate c
+// Candidates naming the same prefix merge -- the only way two can is an extension y_j + c that equals another entry y_i; if that
+// extension's term outweighs the entry's own stay + repeat mass, the prefix's last token re-enters the beam at t (its frame becomes t,
+// so a token's frame is where the dominant extension entered: the first frame of its run on the best path).  The new
+// beam is the top W by rank = (p_b (+) p_nb) + bonus; equal ranks go by the origin key (source entry's position, -1 for stay /
+// repeat else c) ascending, a merged prefix taking its smaller key.  Candidates of rank -inf are dropped.
+//
+// Hotwords: a trie of token-id phrases with one boost beta per matched token.  Only an extension by c moves an entry's state
+// (node, acc): to node's child for c (acc += beta; at a phrase end acc is committed and reset; the walk stays on the child if it has
+// children, else returns to the root), else the pending acc is rolled back and the walk restarts from the root's child for c.
+// There are no failure links: with the phrase "a a b", the text "a a a b" is not boosted -- the third "a" finds no child of "a a",
+// rolls back and restarts at "a", then "b" is no child of "a".  bonus = committed + acc; the state depends on y alone, so merged
+// candidates agree on it.  The final pick drops the pending acc: best (p_b (+) p_nb) + committed, ties to the lower beam position.
+//
+// Shape: one workgroup of GAM_BEAM_NT threads per utterance, t the sequential loop, TWO barriers per frame:
+//   phase 1 (every thread)  one candidate per thread and step: stay / repeat of entry j (q = j (K + 1) + K) or the extension of
+//                            entry j by the s-th top-K id (q = j (K + 1) + s); its rank, origin key and index packed into one
+//                            64-bit key (orderable rank bits | 0xffff - origin | q), 0 for no candidate.          -- barrier A
+//   phase 2 (wave 0)        top W of the <= W (K + 1) <= 1056 keys: each lane holds <= 17 in registers; W wave maxima (DPP),
+//                            the winner removed each time.  Then the new beam: lane i builds entry i, extensions get a prefix-trie
+//                            node, and each entry finds its parent prefix in the new beam (a hash compare per entry: O(W))
+//                            -- the child masks with which phase 1 finds merges.
+//           (wave 1)        the top K of frame t + 1 (the same wave maxima over the row, <= 17 values per lane), and the row
+//                            itself into LDS (blank and repeat terms); the row of frame t + 2 is loaded meanwhile.  -- barrier B
+// Prefix identity: (length, 64-bit polynomial hash h(y + c) = h(y) * P + c + 1).  A collision would merge two different prefixes;
+// it is accepted (2^-64 per compare) and the reference, with real tuples, cannot show one.
+// Precision: every frame subtracts the best kept rank from p_b / p_nb and adds it to an fp64 offset, so the stored values stay
+// O(one frame's log-probs); the log-add-exp runs on the hardware transcendentals (gam_align_exp / gam_align_log, ~1 ulp).
+// Prefix trie: only surviving extensions (and re-entries) create a node {parent, token << 13 | frame}, in a grow-only handle workspace of
+// B x T' x W nodes (at most W per frame).  The backtrack runs in the same kernel and writes ids / frames / count / score / logp.
+// Hotword trie: CSR -- offsets [n_nodes + 1], then edges (token | end << 11 | child << 12) sorted by token per node, searched by
+// binary search; copied to LDS when it fits (GAM_BEAM_HW_LDS_MAX bytes), else read from global memory (L2-resident).
+// Limits (host errors beyond them): W <= 32, T' <= GAM_ALIGN_MAX_T, V <= 1025, <= 1024 phrases, <= 16384 phrase tokens.
+#pragma once
+#include "gam_align.h"
+
+#define GAM_BEAM_MAX_W 32
+#define GAM_BEAM_MAX_V 1025
+#define GAM_BEAM_RPL 17                  // values per lane: ceil(max(1025, 32 * 33) / 64)
+#define GAM_BEAM_NT 256
+#define GAM_BEAM_MAX_PHRASES 1024
+#define GAM_BEAM_MAX_HW_TOKENS 16384
+#define GAM_BEAM_HW_LDS_MAX (64 * 1024)
+#define GAM_BEAM_KEY_STRIDE 1026         // origin key = source position * 1026 + (stay ? 0 : c + 1), < 2^16
+#define GAM_BEAM_HASH_P 0x100000001b3ull
+
+struct GamBeamArgs {
+  const float* lp;       // [B, Tp, V] log-probs
+  const int* enc_len;    // [B]
+  int Tp, V, W, K;
+  const int* hw;         // hotword trie (NULL: none): offsets [hw_nodes + 1] | edges
+  int hw_nodes, hw_words, hw_lds;
+  float beta;
+  int2* nodes;           // [B, Tp * W] prefix-trie nodes
+  int* ids;              // [B, Tp]
+  int* frames;           // [B, Tp]
+  int* counts;           // [B]
+  float* score;          // [B]
+  float* logp;           // [B]
+};
+
+// LDS carve (host and device): beam state [2][32] (hash, parent hash: u64; p_b, p_nb, acc, committed: f32; len, last, prefix node,
+// hotword node, parent, child mask: i32), top-K ids / values [2][32], beam sizes, candidate keys u64 [NC], candidate p_b, p_nb, acc,
+// committed, hotword node [NC], the emission row [V], the hotword trie when it lies in LDS.
+static inline size_t gam_beam_lds_bytes(int W, int K, int V, int hw_lds_words) {
+  const size_t nc = (size_t)W * (K + 1);
+  return 2 * 2 * 32 * 8 + 2 * 4 * 32 * 4 + 2 * 6 * 32 * 4 + 2 * 2 * 32 * 4 + 16 + nc * 8 + nc * 5 * 4 + (((size_t)V + 3) & ~(size_t)3) * 4 +
+         (size_t)hw_lds_words * 4;
+}
+
+__device__ __forceinline__ float gam_beam_lse(float a, float b) {
+  const float m = fmaxf(a, b);
+  if (m == -INFINITY) return -INFINITY;
+  return m + gam_align_log(1.0f + gam_align_exp(fminf(a, b) - m));
+}
+__device__ __forceinline__ unsigned gam_beam_ord(float f) {     // float -> unsigned, order preserving
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float gam_beam_unord(unsigned u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// Wave maximum of a 64-bit key by DPP (the pattern of gam_align_wave_max on both halves), read from lane 63: uniform.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long gam_beam_dpp_max(unsigned long long v) {
+  const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+  const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
+  const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
+  const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
+  return o > v ? o : v;
+}
+__device__ __forceinline__ unsigned long long gam_beam_wave_max(unsigned long long v) {
+  v = gam_beam_dpp_max<0xb1, 0xf>(v);
+  v = gam_beam_dpp_max<0x4e, 0xf>(v);
+  v = gam_beam_dpp_max<0x141, 0xf>(v);
+  v = gam_beam_dpp_max<0x140, 0xf>(v);
+  v = gam_beam_dpp_max<0x142, 0xa>(v);
+  v = gam_beam_dpp_max<0x143, 0xc>(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// The n largest of the keys k[0..nr) of the wave (n <= 64, keys unique or 0): the i-th largest lands in lane i's `out`.  Returns
+// how many non-zero keys were found (<= n).
+__device__ __forceinline__ int gam_beam_wave_topn(unsigned long long (&k)[GAM_BEAM_RPL], int nr, int n, int lane,
+                                                  unsigned long long& out) {
+  unsigned long long loc = 0;
+#pragma unroll
+  for (int r = 0; r < GAM_BEAM_RPL; ++r)
+    if (r < nr) loc = k[r] > loc ? k[r] : loc;
+  int found = 0;
+  out = 0;
+  for (; found < n; ++found) {
+    const unsigned long long m = gam_beam_wave_max(loc);
+    if (m == 0) break;
+    if (lane == found) out = m;
+    loc = 0;
+#pragma unroll
+    for (int r = 0; r < GAM_BEAM_RPL; ++r) {
+      if (r < nr) {
+        if (k[r] == m) k[r] = 0;
+        loc = k[r] > loc ? k[r] : loc;
+      }
+    }
+  }
+  return found;
+}
+
+// Edge of hotword node `node` for token c (edges sorted by token), or -1.
+__device__ __forceinline__ int gam_beam_hw_find(const int* hw, int n_nodes, int node, int c) {
+  const int* E = hw + n_nodes + 1;
+  int lo = hw[node];
+  const int end = hw[node + 1];
+  int hi = end;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((E[mid] & 2047) < c) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < end && (E[lo] & 2047) == c) ? E[lo] : -1;
+}
+
+// The hotword state after an extension by c.
+__device__ __forceinline__ void gam_beam_hw_step(const int* hw, int n_nodes, float beta, int c, int& node, float& acc, float& cb) {
+  int e = gam_beam_hw_find(hw, n_nodes, node, c);
+  if (e < 0 && node != 0) {          // roll back the pending part, restart from the root
+    acc = 0.f;
+    node = 0;
+    e = gam_beam_hw_find(hw, n_nodes, 0, c);
+  }
+  if (e < 0) {                       // (at the root acc is 0)
+    node = 0;
+    acc = 0.f;
+    return;
+  }
+  acc += beta;
+  const int child = e >> 12;
+  if ((e >> 11) & 1) {
+    cb += acc;
+    acc = 0.f;
+  }
+  node = hw[child + 1] > hw[child] ? child : 0;
+}
+
+__global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a) {
+  extern __shared__ uint4 gam_smem_beam[];
+  unsigned char* p = reinterpret_cast<unsigned char*>(gam_smem_beam);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
+  const int Tp = a.Tp, V = a.V, W = a.W, K = a.K, blank = V - 1, K1 = K + 1;
+  const int NC = W * K1;
+  auto take = [&](size_t n) { unsigned char* r = p; p += n; return r; };
+  unsigned long long* bh = reinterpret_cast<unsigned long long*>(take(2 * 32 * 8));    // [buf * 32 + i]
+  unsigned long long* bph = reinterpret_cast<unsigned long long*>(take(2 * 32 * 8));
+  float* bpb = reinterpret_cast<float*>(take(2 * 32 * 4));
+  float* bpnb = reinterpret_cast<float*>(take(2 * 32 * 4));
+  float* bacc = reinterpret_cast<float*>(take(2 * 32 * 4));
+  float* bcb = reinterpret_cast<float*>(take(2 * 32 * 4));
+  int* blen = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* blast = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* bnode = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* bhn = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* bpar = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* bcm = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* cid = reinterpret_cast<int*>(take(2 * 32 * 4));        // top-K ids of frame t at [(t & 1) * 32 + s]
+  float* cval = reinterpret_cast<float*>(take(2 * 32 * 4));
+  int* nbuf = reinterpret_cast<int*>(take(16));                // beam sizes [buf]
+  unsigned long long* ckey = reinterpret_cast<unsigned long long*>(take((size_t)NC * 8));
+  float* cpb = reinterpret_cast<float*>(take((size_t)NC * 4));
+  float* cpnb = reinterpret_cast<float*>(take((size_t)NC * 4));
+  float* cacc = reinterpret_cast<float*>(take((size_t)NC * 4));
+  float* ccb = reinterpret_cast<float*>(take((size_t)NC * 4));
+  int* chn = reinterpret_cast<int*>(take((size_t)NC * 4));
+  float* row = reinterpret_cast<float*>(take((((size_t)V + 3) & ~(size_t)3) * 4));
+  int* hw_sh = reinterpret_cast<int*>(p);
+
+  int T = a.enc_len[b];
+  T = T < 0 ? 0 : (T > Tp ? Tp : T);
+  if (T == 0) {
+    if (tid == 0) {
+      a.counts[b] = 0;
+      a.score[b] = 0.f;
+      a.logp[b] = 0.f;
+    }
+    return;
+  }
+  const int* hw = a.hw;
+  if (hw != nullptr && a.hw_lds) {
+    for (int i = tid; i < a.hw_words; i += GAM_BEAM_NT) hw_sh[i] = a.hw[i];
+    hw = hw_sh;
+  }
+  if (tid == 0) {       // the empty prefix: p_b = 0, p_nb = -inf, hotword state (root, 0)
+    bh[0] = bph[0] = 0ull;
+    bpb[0] = 0.f; bpnb[0] = -INFINITY; bacc[0] = 0.f; bcb[0] = 0.f;
+    blen[0] = 0; blast[0] = -1; bnode[0] = -1; bhn[0] = 0; bpar[0] = -1; bcm[0] = 0;
+    nbuf[0] = 1;
+  }
+
+  const float* lpb = a.lp + (size_t)b * Tp * V;
+  const int nrv = (V + 63) >> 6;
+  float nxt[GAM_BEAM_RPL];       // wave 1: the row of the frame after the one whose top K it takes next
+  // wave 1: the top K of the row in `x` (frame f) into cid / cval [(f & 1)], the row into LDS
+  auto topk = [&](const float (&x)[GAM_BEAM_RPL], int f) {
+    unsigned long long k[GAM_BEAM_RPL];
+#pragma unroll
+    for (int r = 0; r < GAM_BEAM_RPL; ++r) {
+      const int v = lane + 64 * r;
+      k[r] = (r < nrv && v < V - 1) ? (((unsigned long long)gam_beam_ord(x[r]) << 32) | (unsigned)(0xffff - v)) : 0ull;
+      if (r < nrv && v < V) row[v] = x[r];
+    }
+    unsigned long long out;
+    gam_beam_wave_topn(k, nrv, K, lane, out);
+    if (lane < K) {
+      cid[(f & 1) * 32 + lane] = 0xffff - (int)(out & 0xffff);
+      cval[(f & 1) * 32 + lane] = gam_beam_unord((unsigned)(out >> 32));
+    }
+  };
+  if (wave == 1) {
+    float x[GAM_BEAM_RPL];
+#pragma unroll
+    for (int r = 0; r < GAM_BEAM_RPL; ++r) {
+      const int v = min(lane + 64 * r, V - 1);
+      if (r < nrv) x[r] = lpb[v];
+    }
+    const int t1 = T > 1 ? 1 : 0;
+#pragma unroll
+    for (int r = 0; r < GAM_BEAM_RPL; ++r) {
+      const int v = min(lane + 64 * r, V - 1);
+      if (r < nrv) nxt[r] = lpb[(size_t)t1 * V + v];
+    }
+    topk(x, 0);
+  }
+  __syncthreads();
+
+  double off = 0.0;                  // wave 0: what the renormalisations subtracted so far
+  int ncount = 0;                    // wave 0: prefix-trie nodes of this utterance so far
+  int2* nodes = a.nodes + (size_t)b * Tp * W;
+  for (int t = 0; t < T; ++t) {
+    const int cur = t & 1, nx = cur ^ 1;
+    const int nb = nbuf[cur];
+    const int N = nb * K1;
+    const int* tk = cid + cur * 32;
+    const float* tv = cval + cur * 32;
+    // ---- phase 1: candidates
+    for (int q = tid; q < N; q += GAM_BEAM_NT) {
+      const int j = q / K1, s = q - j * K1;
+      const int o = cur * 32 + j;
+      const float pbj = bpb[o], pnbj = bpnb[o];
+      const int lastj = blast[o], lenj = blen[o];
+      const float tot = gam_beam_lse(pbj, pnbj);
+      float pb, pnb, acc = bacc[o], cb = bcb[o];
+      int hn = bhn[o], key;
+      bool valid = true, reenter = false;
+      if (s == K) {        // stay / repeat, and the extension of this entry's parent prefix by its last token
+        pb = tot + row[blank];
+        pnb = lenj > 0 ? pnbj + row[lastj] : -INFINITY;
+        key = j * GAM_BEAM_KEY_STRIDE;
+        const int par = bpar[o];
+        if (par >= 0) {
+          int sl = -1;
+          for (int u = 0; u < K; ++u)
+            if (tk[u] == lastj) sl = u;
+          if (sl >= 0) {
+            const int op = cur * 32 + par;
+            const float pe = ((blen[op] > 0 && blast[op] == lastj) ? bpb[op] : gam_beam_lse(bpb[op], bpnb[op])) + tv[sl];
+            reenter = pe > gam_beam_lse(pb, pnb);
+            pnb = gam_beam_lse(pnb, pe);
+            key = min(key, par * GAM_BEAM_KEY_STRIDE + lastj + 1);
+          }
+        }
+      } else {
+        const int c = tk[s];
+        for (unsigned m = (unsigned)bcm[o]; m; m &= m - 1)     // merged into the entry that already is y_j + c
+          if (blast[cur * 32 + __builtin_ctz(m)] == c) valid = false;
+        pb = -INFINITY;
+        pnb = ((lenj > 0 && c == lastj) ? pbj : tot) + tv[s];
+        if (hw != nullptr) gam_beam_hw_step(hw, a.hw_nodes, a.beta, c, hn, acc, cb);
+        key = j * GAM_BEAM_KEY_STRIDE + c + 1;
+      }
+      const float rank = gam_beam_lse(pb, pnb) + (cb + acc);
+      valid = valid && rank > -INFINITY;
+      ckey[q] = valid ? (((unsigned long long)gam_beam_ord(rank) << 32) | ((unsigned)(0xffff - key) << 16) | (unsigned)q) : 0ull;
+      cpb[q] = pb;
+      cpnb[q] = pnb;
+      cacc[q] = acc;
+      ccb[q] = cb;
+      chn[q] = hn << 1 | (reenter ? 1 : 0);
+    }
+    __syncthreads();
+    if (wave == 0) {
+      // ---- phase 2: the top W, then the new beam (lane i: entry i)
+      unsigned long long k[GAM_BEAM_RPL];
+      const int nr = (N + 63) >> 6;
+#pragma unroll
+      for (int r = 0; r < GAM_BEAM_RPL; ++r) {
+        const int q = lane + 64 * r;
+        k[r] = (r < nr && q < N) ? ckey[q] : 0ull;
+      }
+      unsigned long long sel;
+      const int ns = gam_beam_wave_topn(k, nr, W, lane, sel);
+      if (ns > 0) {
+        const float M = gam_beam_unord((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), 0));
+        off += (double)M;
+        const bool act = lane < ns;
+        const int q = act ? (int)(sel & 0xffff) : 0;
+        const int j = q / K1, s = q - j * K1;
+        const int o = cur * 32 + j;
+        const bool ext = act && s != K;
+        const int hnre = chn[q];
+        const bool re = act && s == K && (hnre & 1);     // a stay whose merged extension outweighs it: its last token re-enters at t
+        const unsigned long long hj = bh[o];
+        const int c = ext ? tk[s] : blast[o];
+        const unsigned long long h = ext ? hj * GAM_BEAM_HASH_P + (unsigned long long)(c + 1) : hj;
+        const unsigned long long ph = ext ? hj : bph[o];
+        const int len = blen[o] + (ext ? 1 : 0);
+        int pnode = re ? bnode[cur * 32 + bpar[o]] : bnode[o];
+        const unsigned long long em = __ballot(ext || re);
+        if (ext || re) {
+          const int idx = ncount + __popcll(em & ((1ull << lane) - 1));
+          nodes[idx] = make_int2(pnode, (c << 13) | t);
+          pnode = idx;
+        }
+        ncount += __popcll(em);
+        int par = -1;
+        for (int i = 0; i < ns; ++i) {
+          const unsigned long long hi = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(h >> 32), i) << 32) |
+                                        (unsigned)__builtin_amdgcn_readlane((int)(unsigned)h, i);
+          const int li = __builtin_amdgcn_readlane(len, i);
+          if (par < 0 && len > 0 && li == len - 1 && hi == ph) par = i;
+        }
+        int cm = 0;
+        for (int i = 0; i < ns; ++i) {
+          const unsigned long long bm = __ballot(act && par == i);
+          if (lane == i) cm = (int)(unsigned)bm;
+        }
+        if (act) {
+          const int d = nx * 32 + lane;
+          bh[d] = h; bph[d] = ph;
+          bpb[d] = cpb[q] - M; bpnb[d] = cpnb[q] - M; bacc[d] = cacc[q]; bcb[d] = ccb[q];
+          blen[d] = len; blast[d] = c; bnode[d] = pnode; bhn[d] = hnre >> 1; bpar[d] = par; bcm[d] = cm;
+        }
+      }
+      if (lane == 0) nbuf[nx] = ns;
+    } else if (wave == 1 && t + 1 < T) {
+      // ---- the top K of frame t + 1 (its row arrived during this frame); load the row of frame t + 2
+      float x[GAM_BEAM_RPL];
+#pragma unroll
+      for (int r = 0; r < GAM_BEAM_RPL; ++r) x[r] = nxt[r];
+      const int t2 = t + 2 < T ? t + 2 : T - 1;
+#pragma unroll
+      for (int r = 0; r < GAM_BEAM_RPL; ++r) {
+        const int v = min(lane + 64 * r, V - 1);
+        if (r < nrv) nxt[r] = lpb[(size_t)t2 * V + v];
+      }
+      topk(x, t + 1);
+    }
+    __syncthreads();
+  }
+
+  // ---- final pick (pending hotword bonus dropped) and backtrack
+  if (wave == 0) {
+    const int fb = T & 1;
+    const int nb = nbuf[fb];
+    const int d = fb * 32 + lane;
+    const float lse = lane < nb ? gam_beam_lse(bpb[d], bpnb[d]) : -INFINITY;
+    const float val = lane < nb ? lse + bcb[d] : -INFINITY;
+    const unsigned long long key = lane < nb ? (((unsigned long long)gam_beam_ord(val) << 32) | (unsigned)(0xffff - lane)) : 0ull;
+    const unsigned long long m = gam_beam_wave_max(key);
+    const int best = m ? 0xffff - (int)(m & 0xffff) : -1;
+    if (best < 0) {
+      if (lane == 0) {
+        a.counts[b] = 0;
+        a.score[b] = -INFINITY;
+        a.logp[b] = -INFINITY;
+      }
+    } else if (lane == best) {
+      const double lp_ = (double)lse + off;
+      a.logp[b] = (float)lp_;
+      a.score[b] = (float)(lp_ + (double)bcb[d]);
+      const int n = blen[d];
+      a.counts[b] = n;
+      int* ids = a.ids + (size_t)b * Tp;
+      int* fr = a.frames + (size_t)b * Tp;
+      int node = bnode[d];
+      for (int i = n - 1; i >= 0; --i) {
+        const int2 e = nodes[node];
+        ids[i] = e.y >> 13;
+        fr[i] = e.y & 8191;
+        node = e.x;
+      }
+    }
+  }
+}

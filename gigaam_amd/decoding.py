@@ -94,6 +94,42 @@ class CTCGreedyDecoding:
     def decode(self, head: CTCHead, encoded: Tensor, lengths: Tensor) -> List[Tuple[str, List[int], List[int]]]:
         return self.finish(self.decode_device(head, encoded, lengths))
 
+    def hotword_ids(self, hotwords) -> List[List[int]]:
+        """Hotwords (each a string in the vocabulary -- ``Tokenizer.encode`` -- or token ids) -> token-id lists, the strings'
+        encodings cached."""
+        cache = self.__dict__.setdefault("_hotword_cache", {})
+        out = []
+        for w in hotwords or ():
+            if isinstance(w, str):
+                if w not in cache:
+                    cache[w] = self.tokenizer.encode(w)
+                out.append(cache[w])
+            else:
+                out.append([int(i) for i in w])
+        return out
+
+    @torch.inference_mode()
+    def decode_beam_device(self, head: CTCHead, encoded: Tensor, lengths: Tensor, beam_size: int = 8, hotwords=None,
+                           hotword_boost: float = 2.0):
+        """The device half of ``decode_beam``: CTC prefix beam search (gam_ctc_beam), no host sync.  Returns an
+        ``engine.BeamDecoded``: ``finish`` takes it as it takes a greedy decode; its ``host()`` also brings the scores.  The
+        hotword set is uploaded only when it differs from the one the engine holds."""
+        c = head.num_classes
+        assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
+        head.engine.set_hotwords(self.hotword_ids(hotwords), hotword_boost)
+        return head.engine.ctc_beam(encoded, lengths, beam_size)
+
+    @torch.inference_mode()
+    def decode_beam(self, head: CTCHead, encoded: Tensor, lengths: Tensor, beam_size: int = 8, hotwords=None,
+                    hotword_boost: float = 2.0) -> List[Tuple[str, List[int], List[int], float, float]]:
+        """Beam search decode -> per utterance ``(text, ids, frames, score, logp)``: ``frames`` the frame at which each token entered
+        the beam, ``score`` log p + committed hotword bonus, ``logp`` log p over the paths the beam kept.  ONE D2H copy; raises
+        ``RangeOverflow`` like ``finish``."""
+        h = self.decode_beam_device(head, encoded, lengths, beam_size, hotwords, hotword_boost).host()
+        if h["flag"]:
+            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        return [(self.tokenizer.decode(i), i, f, float(h["score"][k]), float(h["logp"][k])) for k, (i, f) in enumerate(h["rows"])]
+
     MAX_ALIGN_TOKENS = 1024     # include/gigaam_hip.h gam_ctc_align
 
     @torch.inference_mode()

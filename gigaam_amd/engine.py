@@ -160,6 +160,40 @@ class Aligned:
         return out
 
 
+class BeamDecoded(Decoded):
+    """What ``ctc_beam`` / ``op_ctc_beam`` return: a ``Decoded`` (ids, frames, counts + range flag word: ``collect``, ``finish`` and the
+    word builder take it as they take a greedy decode) whose buffer goes on with ``score`` and ``logp`` f32 [B] (``buf``: ids [B, T'] |
+    frames [B, T'] | counts [B] | flag word | score bits [B] | logp bits [B]).  ``host`` brings all of it to the host in ONE copy."""
+
+    def __new__(cls, buf: Tensor, b: int, tp: int, event=None, stream=None):
+        n0 = 2 * b * tp + b + 1
+        ids, frames, ext = buf[: b * tp].view(b, tp), buf[b * tp: 2 * b * tp].view(b, tp), buf[2 * b * tp: n0]
+        self = Decoded.__new__(cls, ids, frames, ext[:b], ext, event, stream, whole=buf[:n0])
+        self.buf = buf
+        self.score = buf[n0: n0 + b].view(torch.float32)
+        self.logp = buf[n0 + b: n0 + 2 * b].view(torch.float32)
+        return self
+
+    def host(self) -> Dict[str, Any]:
+        """One blocking D2H of the whole result, on the collect stream behind the beam search's own completion event -> ``rows``
+        [(ids, frames)] host lists, ``score`` / ``logp`` numpy f32 [B] and ``flag`` (the split-fp16 range flag, as ``collect``)."""
+        side = HipEngine._collect_stream(self.buf.device)
+        with torch.cuda.stream(side):
+            if self.event is not None:
+                side.wait_event(self.event)
+            else:
+                side.wait_stream(torch.cuda.current_stream(self.buf.device))
+            arr = self.buf.cpu().numpy()
+        self.buf.record_stream(side)
+        b, tp = self.ids.shape
+        n0 = 2 * b * tp + b + 1
+        n = arr[2 * b * tp: n0 - 1].tolist()
+        ids_h, fr_h = arr[: b * tp].reshape(b, tp), arr[b * tp: 2 * b * tp].reshape(b, tp)
+        return {"rows": [(ids_h[i, :c].tolist(), fr_h[i, :c].tolist()) for i, c in enumerate(n)],
+                "score": arr[n0: n0 + b].view(np.float32).copy(), "logp": arr[n0 + b: n0 + 2 * b].view(np.float32).copy(),
+                "flag": HipEngine._flag_of(int(arr[n0 - 1]))}
+
+
 def _ptr(t: Optional[Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -494,6 +528,57 @@ class HipEngine:
             out.event, out.stream = torch.cuda.Event(), st
             out.event.record(st)
         return out
+
+    MAX_BEAM = 32     # include/gigaam_hip.h gam_ctc_beam
+
+    def _launch_beam(self, fn, first, enc_len: Tensor, b: int, tp: int, extra, beam_size: int, what: str) -> BeamDecoded:
+        if not 1 <= int(beam_size) <= self.MAX_BEAM:
+            raise GigaAMHipError(f"beam_size {beam_size} outside [1, {self.MAX_BEAM}]")
+        out = BeamDecoded(torch.empty((2 * b * tp + 3 * b + 1,), dtype=torch.int32, device=self.device), b, tp)
+        rc = fn(self._h, _ptr(first), _ptr(enc_len), b, tp, *extra, int(beam_size), _ptr(out.ids), _ptr(out.frames), _ptr(out.counts),
+                _ptr(out.score), _ptr(out.logp), self._stream())
+        self._check(rc, what)
+        return out
+
+    def ctc_beam(self, encoded: Tensor, enc_len: Tensor, beam_size: int) -> BeamDecoded:
+        """CTC prefix beam search (gam_ctc_beam): the CTC head, its log-softmax and the beam kernel, no host sync; the hotword set of
+        ``set_hotwords`` applies.  The split-fp16 range flag is CONSUMED as ``ctc_greedy`` does: it lands in the flag word."""
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        with torch.cuda.device(self.device):
+            out = self._launch_beam(self.lib.gam_ctc_beam, encoded, enc_len, b, tp, (), beam_size, "gam_ctc_beam")
+            out.event, out.stream = self._fetch_flag(out.ext)
+        return out
+
+    def op_ctc_beam(self, log_probs: Tensor, enc_len: Tensor, beam_size: int) -> BeamDecoded:
+        """gam_op_ctc_beam: the beam kernel alone on caller-supplied log-probs [B, T', V] (used as they are).  The flag word is 0."""
+        log_probs = self._dev(log_probs, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, v = log_probs.shape
+        with torch.cuda.device(self.device):
+            out = self._launch_beam(self.lib.gam_op_ctc_beam, log_probs, enc_len, b, tp, (v,), beam_size, "gam_op_ctc_beam")
+            out.ext[b:].zero_()
+            st = torch.cuda.current_stream(self.device)
+            out.event, out.stream = torch.cuda.Event(), st
+            out.event.record(st)
+        return out
+
+    def set_hotwords(self, phrases, boost: float = 2.0) -> None:
+        """Hotword phrases (token-id lists) for the beam search, each matched token worth ``boost`` (gam_set_hotwords); an empty
+        list clears the set.  Re-uploads only when the set or the boost changed; a setup call that waits for in-flight decodes."""
+        key = (tuple(tuple(int(c) for c in p) for p in phrases), float(boost))
+        prev = getattr(self, "_hotwords_key", None)
+        if key == prev or (not key[0] and (prev is None or not prev[0])):     # (no set and none uploaded: nothing to clear)
+            return
+        flat = [c for p in key[0] for c in p]
+        offs = [0]
+        for p in key[0]:
+            offs.append(offs[-1] + len(p))
+        tok = (C.c_int32 * max(len(flat), 1))(*flat)
+        off = (C.c_int32 * len(offs))(*offs)
+        self._check(self.lib.gam_set_hotwords(self._h, tok, off, len(key[0]), C.c_float(key[1])), "gam_set_hotwords")
+        self._hotwords_key = key
 
     def set_rnnt_cluster(self, n: int) -> None:
         """Workgroups per utterance of the cluster decode kernel (gam_set_rnnt_cluster): -1 auto, 0 one-workgroup kernel, 1..8."""

@@ -12,6 +12,7 @@
  *   gam_ctc_head     <- CTCHead.forward                   gigaam/decoder.py:18-21
  *   gam_ctc_greedy   <- CTCGreedyDecoding.decode          gigaam/decoding.py:56-96
  *   gam_ctc_align    (no reference counterpart: CTC forced alignment + log-likelihood of a given transcript)
+ *   gam_ctc_beam     (no reference counterpart: CTC prefix beam search with hotword boosting)
  *   gam_rnnt_greedy  <- RNNTGreedyDecoding.decode         gigaam/decoding.py:128-207
  *                        (+ RNNTDecoder.predict decoder.py:85-102, RNNTJoint.joint :41-47)
  *   gam_emo_probs    <- GigaAMEmo.get_probs (pool+head)    gigaam/model.py:272-285
@@ -139,6 +140,27 @@ int gam_ctc_align(gam_handle* h, const float* encoded, const int32_t* enc_len, i
 int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
                      const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
                      float* loglik, int32_t* status, void* stream);
+
+/* CTC prefix beam search with hotword boosting (gigaam_amd/csrc/gam_beam.h).  Runs the CTC head, its log-softmax and ONE beam
+ * kernel (a workgroup per utterance, t the sequential loop, backtrack in the same kernel).  Beam width 1 <= W <= 32; per frame the
+ * top min(W, V - 1) non-blank ids are the candidate tokens; blank = V - 1.  Ties follow a fixed rule (gam_beam.h), so the result is
+ * deterministic.  The hotword set of gam_set_hotwords (if any) boosts the hypotheses that spell its phrases.
+ *   ids / frames i32 [B, T']: the best prefix's token ids and the frame at which each token entered the beam (the first frame of its
+ *   run), counts i32 [B] of them (entries past counts[b] are not written).
+ *   score f32 [B]: log p of the prefix (over the paths the beam kept) + its committed hotword bonus; logp f32 [B]: that log p alone.
+ *   enc_len[b] = 0 gives an empty result with score = logp = 0.
+ * Limits: W <= 32, T' <= 8192 (an error beyond them).  Decode class, like gam_ctc_greedy; no host synchronisation. */
+int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
+                 int32_t* counts, float* score, float* logp, void* stream);
+/* The same from caller-supplied log-probs f32 [B, T', V] (read as they are), 2 <= V <= 1025. */
+int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
+                    int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
+/* Hotword phrases for the beam search: phrase i is tokens[offsets[i] .. offsets[i + 1]) (host arrays; offsets has n_phrases + 1
+ * entries, offsets[0] = 0), every matched token worth `boost` in the ranking; a partial match is rolled back when the prefix leaves
+ * the phrase, and only complete phrases count in the final score.  Ids outside [0, V - 2], empty phrases, more than 1024 phrases or
+ * 16384 tokens are errors; n_phrases = 0 clears the set.  A setup call, like gam_set_weight: it waits for the handle's in-flight
+ * decode-class work before it replaces the set. */
+int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offsets, int n_phrases, float boost);
 
 /* RNNTGreedyDecoding.decode: ids/frames i32 [B, T'*max_symbols], counts i32 [B].
  * Optional dump of the log-softmax of every joint evaluation, in order, per utterance:
