@@ -134,6 +134,11 @@ struct gam_handle {
   size_t hw_cap = 0;                    // ints allocated at hw_trie
   int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
   float hw_boost = 0.f;
+  // the n-gram LM of gam_set_lm (gam_beam.h): token classes [lm_V], word / n-gram table slots; lm_ng NULL = no LM
+  int* lm_cls = nullptr;
+  void *lm_wt = nullptr, *lm_ng = nullptr;
+  int lm_V = 0, lm_wslots = 0, lm_wprobe = 0, lm_nslots = 0, lm_nprobe = 0, lm_order = 0, lm_bos = 0, lm_eos = 0, lm_unk = 0;
+  float lm_unk_logp = 0.f, lm_alpha = 0.f, lm_beta = 0.f;
   DevBuf dec_splitk_ws;                 // split-K partial sums of the DECODE class's GEMMs: a decode may run on a side stream beside
                                         // the next batch's encoder (r05), so it shares no scratch with it (tok / logits / encp / rnnt_x
                                         // are the decode's alone already)
@@ -553,6 +558,9 @@ void gam_destroy(gam_handle* h) {
   if (h->range_flag) hipFree(h->range_flag);
   if (h->beam_nodes.p) hipFree(h->beam_nodes.p);
   if (h->hw_trie) hipFree(h->hw_trie);
+  if (h->lm_cls) hipFree(h->lm_cls);
+  if (h->lm_wt) hipFree(h->lm_wt);
+  if (h->lm_ng) hipFree(h->lm_ng);
   for (auto& e : h->prof_events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (auto& g : h->graphs)
     if (g.second.exec) hipGraphExecDestroy(g.second.exec);
@@ -1493,18 +1501,28 @@ static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_le
   if (h->hw_trie && h->hw_max_tok > V - 2)
     return fail(h, -1, "CTC beam search: hotword token id %d outside [0, %d] for V=%d", h->hw_max_tok, V - 2, V);
   const int K = std::min(W, V - 1);
+  const bool lm = h->lm_ng != nullptr;
+  if (lm && h->lm_V != V) return fail(h, -1, "CTC beam search: the LM's token classes are for V=%d, the log-probs have V=%d", h->lm_V, V);
   const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
-  const size_t sm = gam_beam_lds_bytes(W, K, V, hw_lds ? h->hw_words : 0);
+  const size_t sm = gam_beam_lds_bytes(W, K, V, hw_lds ? h->hw_words : 0, lm);
   if (int r = ensure(h, h->beam_nodes, (size_t)B * Tp * W * 2 + 64)) return r;
   GamBeamArgs a;
   a.lp = lp; a.enc_len = enc_len; a.Tp = (int)Tp; a.V = V; a.W = W; a.K = K;
   a.hw = h->hw_trie; a.hw_nodes = h->hw_nodes; a.hw_words = h->hw_words; a.hw_lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
   a.nodes = reinterpret_cast<int2*>(h->beam_nodes.p);
   a.ids = ids; a.frames = frames; a.counts = counts; a.score = score; a.logp = logp;
-  static std::atomic<unsigned long long> lds_set;
-  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds((const void*)gam_ctc_beam_kernel, (int)sm, lds_set));
+  a.lm_cls = h->lm_cls;
+  a.lm_wt = reinterpret_cast<const uint4*>(h->lm_wt);
+  a.lm_ng = reinterpret_cast<const uint4*>(h->lm_ng);
+  a.lm_wmask = h->lm_wslots - 1; a.lm_wprobe = h->lm_wprobe; a.lm_nmask = h->lm_nslots - 1; a.lm_nprobe = h->lm_nprobe;
+  a.lm_m = h->lm_order - 1; a.lm_bos = h->lm_bos; a.lm_eos = h->lm_eos; a.lm_unk = h->lm_unk;
+  a.lm_unk_logp = h->lm_unk_logp; a.lm_alpha = h->lm_alpha; a.lm_beta = h->lm_beta;
+  static std::atomic<unsigned long long> lds_set, lds_set_lm;
+  const void* kern = lm ? (const void*)gam_ctc_beam_kernel<true> : (const void*)gam_ctc_beam_kernel<false>;
+  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds(kern, (int)sm, lm ? lds_set_lm : lds_set));
   ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * W * (K + 1) * 4.0);
-  hipLaunchKernelGGL(gam_ctc_beam_kernel, dim3(B), dim3(GAM_BEAM_NT), sm, s, a);
+  if (lm) hipLaunchKernelGGL(gam_ctc_beam_kernel<true>, dim3(B), dim3(GAM_BEAM_NT), sm, s, a);
+  else hipLaunchKernelGGL(gam_ctc_beam_kernel<false>, dim3(B), dim3(GAM_BEAM_NT), sm, s, a);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -1604,6 +1622,61 @@ int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offset
   h->hw_words = (int)flat.size();
   h->hw_max_tok = max_tok;
   h->hw_boost = boost;
+  return 0;
+}
+
+static void lm_free(gam_handle* h) {
+  if (h->lm_cls) (void)hipFree(h->lm_cls);
+  if (h->lm_wt) (void)hipFree(h->lm_wt);
+  if (h->lm_ng) (void)hipFree(h->lm_ng);
+  h->lm_cls = nullptr;
+  h->lm_wt = h->lm_ng = nullptr;
+  h->lm_V = 0;
+}
+
+int gam_set_lm(gam_handle* h, const int32_t* token_class, int V, const void* word_table, int64_t word_slots, int word_probe,
+               const void* ngram_table, int64_t ngram_slots, int ngram_probe, int order, int bos, int eos, int unk, float unk_logp,
+               float weight, float word_bonus) {
+  if (!h) return -1;
+  if (ngram_slots != 0) {
+    const int64_t max_slots = (int64_t)1 << 30;
+    auto pow2 = [](int64_t n) { return n > 0 && (n & (n - 1)) == 0; };
+    if (order < 1 || order > GAM_BEAM_LM_MAX_ORDER) return fail(h, -1, "LM: order %d outside [1, %d]", order, GAM_BEAM_LM_MAX_ORDER);
+    if (V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "LM: token classes for V=%d outside [2, %d]", V, GAM_BEAM_MAX_V);
+    if (!token_class || !word_table || !ngram_table) return fail(h, -1, "LM: NULL buffer");
+    for (int v = 0; v < V; ++v)
+      if (token_class[v] < 0 || token_class[v] > 2) return fail(h, -1, "LM: token class %d of token %d outside [0, 2]", token_class[v], v);
+    if (!pow2(word_slots) || !pow2(ngram_slots) || word_slots > max_slots || ngram_slots > max_slots)
+      return fail(h, -1, "LM: table slots %lld / %lld must be powers of two <= 2^30", (long long)word_slots, (long long)ngram_slots);
+    if (word_probe < 1 || word_probe > word_slots || ngram_probe < 1 || ngram_probe > ngram_slots)
+      return fail(h, -1, "LM: probe bounds %d / %d outside [1, slots]", word_probe, ngram_probe);
+    if (bos < 0 || eos < 0 || unk < 0 || bos >= (1 << 30) || eos >= (1 << 30) || unk >= (1 << 30))
+      return fail(h, -1, "LM: word ids bos=%d eos=%d unk=%d outside [0, 2^30)", bos, eos, unk);
+    if (!std::isfinite(unk_logp) || !std::isfinite(weight) || !std::isfinite(word_bonus))
+      return fail(h, -1, "LM: unk_logp, weight and word bonus must be finite");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  // a decode-class kernel still in flight may read the current tables
+  if (h->dec_evt != nullptr && h->dec_evt_set) HIPCHK(h, hipEventSynchronize(h->dec_evt));
+  lm_free(h);
+  if (ngram_slots == 0) return 0;
+  const size_t wb = (size_t)word_slots * 16, nbytes = (size_t)ngram_slots * 16;
+  if (hipMalloc(&h->lm_cls, (size_t)V * sizeof(int)) != hipSuccess || hipMalloc(&h->lm_wt, wb) != hipSuccess ||
+      hipMalloc(&h->lm_ng, nbytes) != hipSuccess) {
+    lm_free(h);
+    return fail(h, -1, "LM: cannot allocate %zu bytes of device tables", (size_t)V * 4 + wb + nbytes);
+  }
+  if (hipMemcpy(h->lm_cls, token_class, (size_t)V * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->lm_wt, word_table, wb, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->lm_ng, ngram_table, nbytes, hipMemcpyHostToDevice) != hipSuccess) {
+    lm_free(h);
+    return fail(h, -1, "LM: copying the tables to the device failed");
+  }
+  h->lm_V = V;
+  h->lm_wslots = (int)word_slots; h->lm_wprobe = word_probe;
+  h->lm_nslots = (int)ngram_slots; h->lm_nprobe = ngram_probe;
+  h->lm_order = order; h->lm_bos = bos; h->lm_eos = eos; h->lm_unk = unk;
+  h->lm_unk_logp = unk_logp; h->lm_alpha = weight; h->lm_beta = word_bonus;
   return 0;
 }
 

@@ -39,6 +39,27 @@
 // Hotword trie: CSR -- offsets [n_nodes + 1], then edges (token | end << 11 | child << 12) sorted by token per node, searched by
 // binary search; copied to LDS when it fits (GAM_BEAM_HW_LDS_MAX bytes), else read from global memory (L2-resident).
 // Limits (host errors beyond them): W <= 32, T' <= GAM_ALIGN_MAX_T, V <= 1025, <= 1024 phrases, <= 16384 phrase tokens.
+//
+// Word n-gram LM (template <bool LM>; gam_ctc_beam_kernel<false> is the kernel without it, unchanged; tests/ctc_lm_ref.py is the
+// float64 reference, gigaam_amd/lm.py builds the tables).  Every token has a class: 0 continues the current word, 1 starts a new word
+// (a SentencePiece piece beginning with U+2581; the token belongs to the new word), 2 is a separator (the " " of a char-wise
+// vocabulary; it belongs to no word).  An entry's partial word is its token ids since the last class-1/2 token, identified by the
+// spelling hash wh = h(ids) (h as for prefixes, from 0; 0 = empty); its LM state is the word ids of its last order - 1 completed
+// words (<s> at the start).  An extension of y by a class-1/2 token completes y's partial word w when it is non-empty: the entry's
+// `lm` grows by alpha ln P(w | state) + beta and w enters the state.  P is ARPA back-off (natural log; a word outside the word table
+// is <unk>, which scores unk_logp when the ARPA has no <unk> unigram).  Partial words are not scored.  All of it depends on the prefix
+// alone, so merged candidates agree on it.  rank = (p_b (+) p_nb) + bonus + lm.  Final pick: the last partial word is completed, then
+// alpha ln P(</s> | state) is added: best (p_b (+) p_nb) + committed + lm.  score = log p + committed + lm; logp is unchanged.
+//   Cost: one LM query per NEW beam entry and frame, not per candidate -- the completion term d(y) = alpha ln P(w | state) + beta
+//   and w's id are the same whichever boundary token completes w, so wave 0 computes them in phase 2 for each new entry whose
+//   partial word changed (an extension; a stay keeps its entry's) and phase 1 only adds them.  A query is two rounds of global loads
+//   (the tables stay L2 / Infinity-Cache resident): the word (word table) together with the back-off weights of the state's suffixes
+//   (n-gram table; their keys are known before the word id), then the n-grams (suffix, w) of every order together.  Renormalisation
+//   subtracts the best rank minus its lm, so p_b / p_nb stay O(one frame) however large lm grows.
+// Tables: 16-byte slots {u64 key, 2 x 32 bit} (word table: word id; n-gram table: ln p, ln back-off as f32), open addressing,
+// linear probing, a power-of-two slot count < 2^30, load <= 0.5; key = mix64(h) (splitmix64 finaliser, 0 -> 1), 0 = free slot;
+// n-gram h = n, then h = h * P + (id + 1) per word, oldest first.  A probe reads at most the host's longest chain.  Full 64-bit keys
+// are compared: a collision is accepted (2^-64 per compare), as for prefixes.  Limits: order <= 5.
 #pragma once
 #include "gam_align.h"
 
@@ -65,15 +86,30 @@ struct GamBeamArgs {
   int* counts;           // [B]
   float* score;          // [B]
   float* logp;           // [B]
+  // the n-gram LM (gam_ctc_beam_kernel<true> only)
+  const int* lm_cls;     // [V] token classes
+  const uint4* lm_wt;    // word table slots
+  const uint4* lm_ng;    // n-gram table slots
+  int lm_wmask, lm_wprobe, lm_nmask, lm_nprobe;   // slots - 1, longest probe chain
+  int lm_m, lm_bos, lm_eos, lm_unk;               // order - 1, word ids
+  float lm_unk_logp, lm_alpha, lm_beta;
 };
+
+#define GAM_BEAM_LM_MAX_ORDER 5
 
 // LDS carve (host and device): beam state [2][32] (hash, parent hash: u64; p_b, p_nb, acc, committed: f32; len, last, prefix node,
 // hotword node, parent, child mask: i32), top-K ids / values [2][32], beam sizes, candidate keys u64 [NC], candidate p_b, p_nb, acc,
-// committed, hotword node [NC], the emission row [V], the hotword trie when it lies in LDS.
-static inline size_t gam_beam_lds_bytes(int W, int K, int V, int hw_lds_words) {
+// committed, hotword node [NC], the emission row [V], the hotword trie when it lies in LDS; with the LM, from the next 16-byte
+// boundary: beam LM state [2][32] (partial-word hash u64, state int4, lm, d, completed word id), top-K classes [2][32], classes [V] i8.
+__host__ __device__ static inline size_t gam_beam_lds_base(int W, int K, int V, int hw_lds_words) {
   const size_t nc = (size_t)W * (K + 1);
   return 2 * 2 * 32 * 8 + 2 * 4 * 32 * 4 + 2 * 6 * 32 * 4 + 2 * 2 * 32 * 4 + 16 + nc * 8 + nc * 5 * 4 + (((size_t)V + 3) & ~(size_t)3) * 4 +
          (size_t)hw_lds_words * 4;
+}
+static inline size_t gam_beam_lds_bytes(int W, int K, int V, int hw_lds_words, bool lm = false) {
+  const size_t base = gam_beam_lds_base(W, K, V, hw_lds_words);
+  if (!lm) return base;
+  return ((base + 15) & ~(size_t)15) + 2 * 32 * (8 + 16 + 3 * 4) + 2 * 32 * 4 + (((size_t)V + 3) & ~(size_t)3);
 }
 
 __device__ __forceinline__ float gam_beam_lse(float a, float b) {
@@ -172,6 +208,92 @@ __device__ __forceinline__ void gam_beam_hw_step(const int* hw, int n_nodes, flo
   node = hw[child + 1] > hw[child] ? child : 0;
 }
 
+// ---- the n-gram LM
+__device__ __forceinline__ unsigned long long gam_lm_mix(unsigned long long x) {
+  x ^= x >> 30;
+  x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27;
+  x *= 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return x ? x : 1ull;
+}
+
+// Linear probes of up to NQ keys at once (bit q of `live`: query q runs; query 0 in table t0 of mask m0, the others in t of mask
+// m); every round issues the loads of all open queries before it compares any.  Returns the found bits; val[q] is the found slot's
+// third word (q == 0 or !FOURTH) or its fourth.
+template <int NQ, bool FOURTH>
+__device__ __forceinline__ unsigned gam_lm_probe(const uint4* t0, int m0, const uint4* t, int m, int maxp,
+                                                 const unsigned long long (&key)[NQ], unsigned live, unsigned (&val)[NQ]) {
+  unsigned open = live, found = 0;
+  for (int i = 0; i < maxp && open; ++i) {
+    uint4 e[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const unsigned sl = (unsigned)(key[q] + (unsigned)i) & (unsigned)(q == 0 ? m0 : m);
+      e[q] = ((open >> q) & 1) ? (q == 0 ? t0 : t)[sl] : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const unsigned long long k = ((unsigned long long)e[q].y << 32) | e[q].x;
+      const bool hit = ((open >> q) & 1) && k == key[q];
+      if (hit) found |= 1u << q;
+      val[q] = hit ? ((FOURTH && q != 0) ? e[q].w : e[q].z) : val[q];
+      if (hit || k == 0ull) open &= ~(1u << q);
+    }
+  }
+  return found;
+}
+
+// ln P(w | s) by ARPA back-off, s = (s.x most recent, s.y, s.z, s.w), -1 = no word; the first lm_m of them are the context.  With
+// `word`, w is the word table's id for spelling hash wh (lm_unk when it has none).  Returns ln P and sets w.
+__device__ __forceinline__ float gam_lm_query(const GamBeamArgs& a, bool word, unsigned long long wh, int& w, int4 s4) {
+  constexpr int NQ = GAM_BEAM_LM_MAX_ORDER;
+  const int m = a.lm_m;
+  const int s[4] = {s4.x, s4.y, s4.z, s4.w};
+  // round A: the word (slot 0, word table), and the back-off contexts B_k = (s[k-1] .. s[0]), k = 1..m (slot k, n-gram table)
+  unsigned long long kA[NQ];
+  unsigned vA[NQ] = {0, 0, 0, 0, 0};
+  unsigned live = word ? 1u : 0u;
+  kA[0] = gam_lm_mix(wh);
+#pragma unroll
+  for (int k = 1; k < NQ; ++k) {
+    unsigned long long h = (unsigned long long)k;
+#pragma unroll
+    for (int i = k - 1; i >= 0; --i) h = h * GAM_BEAM_HASH_P + (unsigned long long)(s[i] + 1);
+    kA[k] = gam_lm_mix(h);
+    if (k <= m && s[k - 1] >= 0) live |= 1u << k;
+  }
+  const unsigned fA = gam_lm_probe<NQ, true>(a.lm_wt, a.lm_wmask, a.lm_ng, a.lm_nmask, max(a.lm_wprobe, a.lm_nprobe), kA, live, vA);
+  if (word) w = (fA & 1) ? (int)vA[0] : a.lm_unk;
+  // round B: the n-grams P_k = (s[k-1] .. s[0], w), k = 0..m
+  unsigned long long kB[NQ];
+  unsigned vB[NQ] = {0, 0, 0, 0, 0};
+  live = 0;
+#pragma unroll
+  for (int k = 0; k < NQ; ++k) {
+    unsigned long long h = (unsigned long long)(k + 1);
+#pragma unroll
+    for (int i = k - 1; i >= 0; --i) h = h * GAM_BEAM_HASH_P + (unsigned long long)(s[i] + 1);
+    h = h * GAM_BEAM_HASH_P + (unsigned long long)(w + 1);
+    kB[k] = gam_lm_mix(h);
+    if (k <= m && (k == 0 || s[k - 1] >= 0)) live |= 1u << k;
+  }
+  const unsigned fB = gam_lm_probe<NQ, false>(a.lm_ng, a.lm_nmask, a.lm_ng, a.lm_nmask, a.lm_nprobe, kB, live, vB);
+  // the longest context that has (context, w), plus the back-offs of the longer ones; no unigram: unk_logp
+  float bo = 0.f, lp = a.lm_unk_logp;
+  bool got = false;
+#pragma unroll
+  for (int k = NQ - 1; k >= 0; --k) {
+    if (!got && ((fB >> k) & 1)) {
+      lp = __uint_as_float(vB[k]) + bo;
+      got = true;
+    }
+    if (!got && k >= 1 && ((fA >> k) & 1)) bo += __uint_as_float(vA[k]);
+  }
+  return lp;
+}
+
+template <bool LM>
 __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a) {
   extern __shared__ uint4 gam_smem_beam[];
   unsigned char* p = reinterpret_cast<unsigned char*>(gam_smem_beam);
@@ -203,6 +325,23 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
   int* chn = reinterpret_cast<int*>(take((size_t)NC * 4));
   float* row = reinterpret_cast<float*>(take((((size_t)V + 3) & ~(size_t)3) * 4));
   int* hw_sh = reinterpret_cast<int*>(p);
+  // the LM's carve (gam_beam_lds_bytes): from the first 16-byte boundary after the hotword trie
+  unsigned long long* bwh = nullptr;
+  int4* bctx = nullptr;
+  float *blm = nullptr, *bdl = nullptr;
+  int *bcw = nullptr, *ccls = nullptr;
+  signed char* cls_sh = nullptr;
+  if constexpr (LM) {
+    p = reinterpret_cast<unsigned char*>(gam_smem_beam) +
+        ((gam_beam_lds_base(W, K, V, a.hw != nullptr && a.hw_lds ? a.hw_words : 0) + 15) & ~(size_t)15);
+    bwh = reinterpret_cast<unsigned long long*>(take(2 * 32 * 8));
+    bctx = reinterpret_cast<int4*>(take(2 * 32 * 16));
+    blm = reinterpret_cast<float*>(take(2 * 32 * 4));
+    bdl = reinterpret_cast<float*>(take(2 * 32 * 4));
+    bcw = reinterpret_cast<int*>(take(2 * 32 * 4));
+    ccls = reinterpret_cast<int*>(take(2 * 32 * 4));       // classes of the top-K ids, beside cid
+    cls_sh = reinterpret_cast<signed char*>(p);
+  }
 
   int T = a.enc_len[b];
   T = T < 0 ? 0 : (T > Tp ? Tp : T);
@@ -224,6 +363,11 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
     bpb[0] = 0.f; bpnb[0] = -INFINITY; bacc[0] = 0.f; bcb[0] = 0.f;
     blen[0] = 0; blast[0] = -1; bnode[0] = -1; bhn[0] = 0; bpar[0] = -1; bcm[0] = 0;
     nbuf[0] = 1;
+    if constexpr (LM) {   // an empty partial word, the state <s>, lm 0
+      bwh[0] = 0ull;
+      bctx[0] = make_int4(a.lm_m > 0 ? a.lm_bos : -1, -1, -1, -1);
+      blm[0] = 0.f; bdl[0] = 0.f; bcw[0] = -1;
+    }
   }
 
   const float* lpb = a.lp + (size_t)b * Tp * V;
@@ -243,9 +387,12 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
     if (lane < K) {
       cid[(f & 1) * 32 + lane] = 0xffff - (int)(out & 0xffff);
       cval[(f & 1) * 32 + lane] = gam_beam_unord((unsigned)(out >> 32));
+      if constexpr (LM) ccls[(f & 1) * 32 + lane] = cls_sh[min(0xffff - (int)(out & 0xffff), V - 1)];
     }
   };
   if (wave == 1) {
+    if constexpr (LM)     // (wave 1 alone reads the class table: its own LDS writes are ordered before its reads)
+      for (int v = lane; v < V; v += 64) cls_sh[v] = (signed char)a.lm_cls[v];
     float x[GAM_BEAM_RPL];
 #pragma unroll
     for (int r = 0; r < GAM_BEAM_RPL; ++r) {
@@ -307,7 +454,12 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
         if (hw != nullptr) gam_beam_hw_step(hw, a.hw_nodes, a.beta, c, hn, acc, cb);
         key = j * GAM_BEAM_KEY_STRIDE + c + 1;
       }
-      const float rank = gam_beam_lse(pb, pnb) + (cb + acc);
+      float rank = gam_beam_lse(pb, pnb) + (cb + acc);
+      if constexpr (LM) {   // the lm of the candidate's prefix: y_j's, plus d(y_j) when c completes y_j's partial word
+        float lmv = blm[o];
+        if (s != K && ccls[cur * 32 + s] != 0 && bwh[o] != 0ull) lmv += bdl[o];
+        rank += lmv;
+      }
       valid = valid && rank > -INFINITY;
       ckey[q] = valid ? (((unsigned long long)gam_beam_ord(rank) << 32) | ((unsigned)(0xffff - key) << 16) | (unsigned)q) : 0ull;
       cpb[q] = pb;
@@ -329,8 +481,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
       unsigned long long sel;
       const int ns = gam_beam_wave_topn(k, nr, W, lane, sel);
       if (ns > 0) {
-        const float M = gam_beam_unord((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), 0));
-        off += (double)M;
+        float M = gam_beam_unord((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), 0));
         const bool act = lane < ns;
         const int q = act ? (int)(sel & 0xffff) : 0;
         const int j = q / K1, s = q - j * K1;
@@ -340,6 +491,27 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
         const bool re = act && s == K && (hnre & 1);     // a stay whose merged extension outweighs it: its last token re-enters at t
         const unsigned long long hj = bh[o];
         const int c = ext ? tk[s] : blast[o];
+        unsigned long long lwh = 0ull;
+        int4 lcx = make_int4(-1, -1, -1, -1);
+        float llm = 0.f, ldl = 0.f;
+        int lcw = -1;
+        if constexpr (LM) {   // the new entry's LM state; an extension whose partial word is non-empty queries d and its word id
+          const unsigned long long whj = bwh[o];
+          const int4 cj = bctx[o];
+          const int cl = ext ? ccls[cur * 32 + s] : 0;
+          const bool done = ext && cl != 0 && whj != 0ull;      // c completes y_j's partial word
+          llm = done ? blm[o] + bdl[o] : blm[o];
+          lcx = done ? make_int4(bcw[o], cj.x, cj.y, cj.z) : cj;
+          lwh = !ext ? whj : (cl == 0 ? whj * GAM_BEAM_HASH_P + (unsigned long long)(c + 1) : (cl == 1 ? (unsigned long long)(c + 1) : 0ull));
+          if (!ext) {
+            ldl = bdl[o];
+            lcw = bcw[o];
+          } else if (lwh != 0ull) {
+            ldl = a.lm_alpha * gam_lm_query(a, true, lwh, lcw, lcx) + a.lm_beta;
+          }
+          M -= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(llm), 0));     // (p_b / p_nb keep O(one frame))
+        }
+        off += (double)M;
         const unsigned long long h = ext ? hj * GAM_BEAM_HASH_P + (unsigned long long)(c + 1) : hj;
         const unsigned long long ph = ext ? hj : bph[o];
         const int len = blen[o] + (ext ? 1 : 0);
@@ -368,6 +540,9 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
           bh[d] = h; bph[d] = ph;
           bpb[d] = cpb[q] - M; bpnb[d] = cpnb[q] - M; bacc[d] = cacc[q]; bcb[d] = ccb[q];
           blen[d] = len; blast[d] = c; bnode[d] = pnode; bhn[d] = hnre >> 1; bpar[d] = par; bcm[d] = cm;
+          if constexpr (LM) {
+            bwh[d] = lwh; bctx[d] = lcx; blm[d] = llm; bdl[d] = ldl; bcw[d] = lcw;
+          }
         }
       }
       if (lane == 0) nbuf[nx] = ns;
@@ -393,7 +568,21 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
     const int nb = nbuf[fb];
     const int d = fb * 32 + lane;
     const float lse = lane < nb ? gam_beam_lse(bpb[d], bpnb[d]) : -INFINITY;
-    const float val = lane < nb ? lse + bcb[d] : -INFINITY;
+    float val = lane < nb ? lse + bcb[d] : -INFINITY;
+    float lmf = 0.f;
+    if constexpr (LM) {   // complete the last partial word, then </s>
+      if (lane < nb) {
+        int4 cx = bctx[d];
+        lmf = blm[d];
+        if (bwh[d] != 0ull) {
+          lmf += bdl[d];
+          cx = make_int4(bcw[d], cx.x, cx.y, cx.z);
+        }
+        int w = a.lm_eos;
+        lmf += a.lm_alpha * gam_lm_query(a, false, 0ull, w, cx);
+        val += lmf;
+      }
+    }
     const unsigned long long key = lane < nb ? (((unsigned long long)gam_beam_ord(val) << 32) | (unsigned)(0xffff - lane)) : 0ull;
     const unsigned long long m = gam_beam_wave_max(key);
     const int best = m ? 0xffff - (int)(m & 0xffff) : -1;
@@ -406,7 +595,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
     } else if (lane == best) {
       const double lp_ = (double)lse + off;
       a.logp[b] = (float)lp_;
-      a.score[b] = (float)(lp_ + (double)bcb[d]);
+      a.score[b] = LM ? (float)(lp_ + (double)bcb[d] + (double)lmf) : (float)(lp_ + (double)bcb[d]);
       const int n = blen[d];
       a.counts[b] = n;
       int* ids = a.ids + (size_t)b * Tp;

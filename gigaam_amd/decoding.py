@@ -6,6 +6,7 @@ launch per batch; only the final ragged ids/frames cross PCIe, once.
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Tuple
 
 import torch
@@ -108,24 +109,40 @@ class CTCGreedyDecoding:
                 out.append([int(i) for i in w])
         return out
 
+    def language_model(self, lm):
+        """``lm`` (an ``lm.NgramLM``, a path to an ARPA or ``.npz`` file, or None) -> an ``NgramLM`` or None; a path is read once."""
+        if lm is None:
+            return None
+        from .lm import NgramLM
+        if isinstance(lm, NgramLM):
+            return lm
+        cache = self.__dict__.setdefault("_lm_cache", {})
+        key = os.fspath(lm)
+        if key not in cache:
+            cache[key] = NgramLM.open(key)
+        return cache[key]
+
     @torch.inference_mode()
     def decode_beam_device(self, head: CTCHead, encoded: Tensor, lengths: Tensor, beam_size: int = 8, hotwords=None,
-                           hotword_boost: float = 2.0):
+                           hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0):
         """The device half of ``decode_beam``: CTC prefix beam search (gam_ctc_beam), no host sync.  Returns an
         ``engine.BeamDecoded``: ``finish`` takes it as it takes a greedy decode; its ``host()`` also brings the scores.  The
-        hotword set is uploaded only when it differs from the one the engine holds."""
+        hotword set and the LM are uploaded only when they differ from the ones the engine holds."""
         c = head.num_classes
         assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
         head.engine.set_hotwords(self.hotword_ids(hotwords), hotword_boost)
+        head.engine.set_lm(self.language_model(lm), self.tokenizer, lm_weight, word_bonus)
         return head.engine.ctc_beam(encoded, lengths, beam_size)
 
     @torch.inference_mode()
     def decode_beam(self, head: CTCHead, encoded: Tensor, lengths: Tensor, beam_size: int = 8, hotwords=None,
-                    hotword_boost: float = 2.0) -> List[Tuple[str, List[int], List[int], float, float]]:
+                    hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5,
+                    word_bonus: float = 1.0) -> List[Tuple[str, List[int], List[int], float, float]]:
         """Beam search decode -> per utterance ``(text, ids, frames, score, logp)``: ``frames`` the frame at which each token entered
-        the beam, ``score`` log p + committed hotword bonus, ``logp`` log p over the paths the beam kept.  ONE D2H copy; raises
-        ``RangeOverflow`` like ``finish``."""
-        h = self.decode_beam_device(head, encoded, lengths, beam_size, hotwords, hotword_boost).host()
+        the beam, ``score`` log p + committed hotword bonus + LM term, ``logp`` log p over the paths the beam kept.  ``lm`` (an
+        ``NgramLM`` or a path) fuses a word n-gram LM: ``lm_weight`` * ln P(word | history) + ``word_bonus`` per word (gam_set_lm).
+        ONE D2H copy; raises ``RangeOverflow`` like ``finish``."""
+        h = self.decode_beam_device(head, encoded, lengths, beam_size, hotwords, hotword_boost, lm, lm_weight, word_bonus).host()
         if h["flag"]:
             raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
         return [(self.tokenizer.decode(i), i, f, float(h["score"][k]), float(h["logp"][k])) for k, (i, f) in enumerate(h["rows"])]

@@ -580,6 +580,25 @@ class HipEngine:
         self._check(self.lib.gam_set_hotwords(self._h, tok, off, len(key[0]), C.c_float(key[1])), "gam_set_hotwords")
         self._hotwords_key = key
 
+    def set_lm(self, lm=None, tokenizer=None, weight: float = 0.5, word_bonus: float = 1.0) -> None:
+        """An n-gram LM (``lm.NgramLM``) for the beam search, its words spelt by ``tokenizer`` (gam_set_lm); None clears it.
+        Re-uploads only when the model, the tokenizer or a parameter changed; a setup call that waits for in-flight decodes."""
+        key = None if lm is None else (id(lm), id(tokenizer), float(weight), float(word_bonus), lm.unk_logp)
+        prev = getattr(self, "_lm_key", None)
+        if key == prev:
+            return
+        if lm is None:
+            rc = self.lib.gam_set_lm(self._h, None, 0, None, 0, 0, None, 0, 0, 0, 0, 0, 0, C.c_float(0), C.c_float(0), C.c_float(0))
+        else:
+            t = lm.device_tables(tokenizer)
+            cls = np.ascontiguousarray(t["classes"], dtype=np.int32)
+            wt, ng = np.ascontiguousarray(t["words"]), np.ascontiguousarray(t["ngrams"])
+            rc = self.lib.gam_set_lm(self._h, cls.ctypes.data, int(cls.shape[0]), wt.ctypes.data, int(wt.shape[0]), int(t["word_probe"]),
+                                     ng.ctypes.data, int(ng.shape[0]), int(t["ngram_probe"]), int(lm.order), int(lm.bos), int(lm.eos),
+                                     int(lm.unk), C.c_float(lm.unk_logp), C.c_float(weight), C.c_float(word_bonus))
+        self._check(rc, "gam_set_lm")
+        self._lm_key, self._lm_ref = key, (lm, tokenizer)     # (the references keep the ids of the key unique)
+
     def set_rnnt_cluster(self, n: int) -> None:
         """Workgroups per utterance of the cluster decode kernel (gam_set_rnnt_cluster): -1 auto, 0 one-workgroup kernel, 1..8."""
         self._check(self.lib.gam_set_rnnt_cluster(self._h, int(n)), "gam_set_rnnt_cluster")

@@ -273,28 +273,30 @@ class GigaAMASR(GigaAM):
 
     # ---- the launch / collect pair every transcribe path is built from (public: a driver -- bench.py, shard.run_sharded,
     #      a test -- can interleave them, or replace them to script the decode)
-    def _beam_width(self, beam_size: Optional[int], hotwords) -> Optional[int]:
-        """The beam width of a transcribe call: None (greedy) when neither option is given, 8 for hotwords alone."""
-        if beam_size is None and hotwords is None:
+    def _beam_width(self, beam_size: Optional[int], hotwords, lm=None) -> Optional[int]:
+        """The beam width of a transcribe call: None (greedy) when no option is given, 8 for hotwords or an LM alone."""
+        if beam_size is None and hotwords is None and lm is None:
             return None
         if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
             raise TypeError("beam search needs a CTC head")
         return 8 if beam_size is None else int(beam_size)
 
     def launch_batch(self, wav: Tensor, lengths: Tensor, overlap: bool = False, host_lengths=None, *, beam_size: Optional[int] = None,
-                     hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0):
+                     hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
+                     lm_weight: float = 0.5, word_bonus: float = 1.0):
         """Device half of ``transcribe_batch``: frontend + encoder + greedy decode of a collated batch (wav [B,L] zero
         padded, len [B]) launched on the current stream, NO host sync.  Returns an opaque handle for ``collect_batch``.
         ``overlap=True`` says another ``launch_batch`` follows before this one is collected: an RNN-T decode then runs on
         the decode side stream BESIDE the next batch's encoder (decoding.RNNTGreedyDecoding.decode_device).
-        ``beam_size`` / ``hotwords`` (CTC heads only) decode by prefix beam search instead (decoding.decode_beam_device)."""
-        width = self._beam_width(beam_size, hotwords)
+        ``beam_size`` / ``hotwords`` / ``lm`` (CTC heads only) decode by prefix beam search instead (decoding.decode_beam_device)."""
+        width = self._beam_width(beam_size, hotwords, lm)
         # sample counts on the host (given, or ``lengths`` itself still a CPU tensor): a ragged batch then runs on its valid frames only
         host = host_lengths if host_lengths is not None else (lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None)
         wav, lengths = wav.to(self._device), lengths.to(self._device)
         encoded, encoded_len = self._encode(wav, lengths, host)
         if width is not None:
-            return self.decoding.decode_beam_device(self.head, encoded, encoded_len, width, hotwords, hotword_boost), lengths, encoded_len
+            return (self.decoding.decode_beam_device(self.head, encoded, encoded_len, width, hotwords, hotword_boost, lm, lm_weight, word_bonus),
+                    lengths, encoded_len)
         return self.decoding.decode_device(self.head, encoded, encoded_len, overlap=overlap), lengths, encoded_len
 
     def collect_batch(self, handle, word_timestamps: bool = False) -> List[Tuple[str, Optional[List[Word]]]]:
@@ -305,25 +307,29 @@ class GigaAMASR(GigaAM):
 
     @torch.inference_mode()
     def transcribe(self, wav_file: str, word_timestamps: bool = False, *, beam_size: Optional[int] = None,
-                   hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0) -> TranscriptionResult:
+                   hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
+                   lm_weight: float = 0.5, word_bonus: float = 1.0) -> TranscriptionResult:
         """``beam_size`` (1..32) decodes by CTC prefix beam search; ``hotwords`` (strings in the vocabulary or token ids; alone
-        they mean ``beam_size=8``) bias it toward those phrases, ``hotword_boost`` per matched token.  CTC heads only (TypeError)."""
-        self._beam_width(beam_size, hotwords)
+        they mean ``beam_size=8``) bias it toward those phrases, ``hotword_boost`` per matched token.  ``lm`` (an ``NgramLM`` or a
+        path to an ARPA / ``.npz`` file; alone it means ``beam_size=8``) fuses a word n-gram LM: ``lm_weight`` * ln P(word |
+        history) + ``word_bonus`` per word.  CTC heads only (TypeError)."""
+        self._beam_width(beam_size, hotwords, lm)
         wav, length = self._prepare_wav_f32(wav_file)
         if length.item() > LONGFORM_THRESHOLD:
             raise ValueError("Too long wav file, use 'transcribe_longform' method.")
         text, words = self.transcribe_batch(wav, length, word_timestamps, beam_size=beam_size, hotwords=hotwords,
-                                            hotword_boost=hotword_boost)[0]
+                                            hotword_boost=hotword_boost, lm=lm, lm_weight=lm_weight, word_bonus=word_bonus)[0]
         return TranscriptionResult(text=text, words=words)
 
     @torch.inference_mode()
     def transcribe_batch(self, wav: Tensor, lengths: Tensor, word_timestamps: bool = False, *, beam_size: Optional[int] = None,
-                         hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0):
+                         hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
+                         lm_weight: float = 0.5, word_bonus: float = 1.0):
         """Batched twin of ``transcribe`` on an already collated batch (wav [B,L] zero
         padded, len [B]) -- the unit bench.py and the longform driver iterate."""
-        if self._beam_width(beam_size, hotwords) is None:
+        if self._beam_width(beam_size, hotwords, lm) is None:
             return self._with_f32_fallback(lambda: self.collect_batch(self.launch_batch(wav, lengths), word_timestamps), "this batch was")
-        kw = dict(beam_size=beam_size, hotwords=hotwords, hotword_boost=hotword_boost)
+        kw = dict(beam_size=beam_size, hotwords=hotwords, hotword_boost=hotword_boost, lm=lm, lm_weight=lm_weight, word_bonus=word_bonus)
         return self._with_f32_fallback(lambda: self.collect_batch(self.launch_batch(wav, lengths, **kw), word_timestamps), "this batch was")
 
     # ---- CTC forced alignment: a KNOWN transcript placed on the audio, and its log-likelihood (gam_ctc_align)
@@ -375,8 +381,8 @@ class GigaAMASR(GigaAM):
     @torch.inference_mode()
     def transcribe_longform(self, wav_file: str, word_timestamps: bool = False, fr_batch_size: int = 16,
                             fr_num_workers: int = 0, *, beam_size: Optional[int] = None,
-                            hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0,
-                            **kwargs: Any) -> LongformTranscriptionResult:
+                            hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
+                            lm_weight: float = 0.5, word_bonus: float = 1.0, **kwargs: Any) -> LongformTranscriptionResult:
         """Segment -> zero-padded batches of ``fr_batch_size`` -> transcribe -> stitch
         (reference model.py:195-259).  The reference segments with pyannote's VAD
         (gated third-party model, not installable here); pass ``speech_regions=[(s,e),..]``,
@@ -388,11 +394,13 @@ class GigaAMASR(GigaAM):
         ``DataLoader`` whose workers only run ``collate`` (model.py:219-229); here that role is the pinned,
         double-buffered ``feeder.BatchFeeder`` (one staging thread is enough to keep the GPU busy).
 
-        ``beam_size`` / ``hotwords`` / ``hotword_boost``: as for ``transcribe`` (CTC prefix beam search on every chunk)."""
+        ``beam_size`` / ``hotwords`` / ``hotword_boost`` / ``lm`` / ``lm_weight`` / ``word_bonus``: as for ``transcribe`` (CTC prefix
+        beam search on every chunk; each chunk starts its own LM history at <s>)."""
         from .vad_utils import EnergyVAD, segment_audio_file
 
-        beam_kw = {} if self._beam_width(beam_size, hotwords) is None else dict(beam_size=beam_size, hotwords=hotwords,
-                                                                                 hotword_boost=hotword_boost)
+        beam_kw = {} if self._beam_width(beam_size, hotwords, lm) is None else dict(beam_size=beam_size, hotwords=hotwords,
+                                                                                     hotword_boost=hotword_boost, lm=lm,
+                                                                                     lm_weight=lm_weight, word_bonus=word_bonus)
 
         if kwargs.get("vad") == "energy":   # stand-in detector on the HIP frontend (NOT pyannote)
             kwargs["vad"] = EnergyVAD(self.preprocessor)

@@ -12,7 +12,7 @@
  *   gam_ctc_head     <- CTCHead.forward                   gigaam/decoder.py:18-21
  *   gam_ctc_greedy   <- CTCGreedyDecoding.decode          gigaam/decoding.py:56-96
  *   gam_ctc_align    (no reference counterpart: CTC forced alignment + log-likelihood of a given transcript)
- *   gam_ctc_beam     (no reference counterpart: CTC prefix beam search with hotword boosting)
+ *   gam_ctc_beam     (no reference counterpart: CTC prefix beam search with hotword boosting and n-gram LM fusion)
  *   gam_rnnt_greedy  <- RNNTGreedyDecoding.decode         gigaam/decoding.py:128-207
  *                        (+ RNNTDecoder.predict decoder.py:85-102, RNNTJoint.joint :41-47)
  *   gam_emo_probs    <- GigaAMEmo.get_probs (pool+head)    gigaam/model.py:272-285
@@ -144,10 +144,12 @@ int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_l
 /* CTC prefix beam search with hotword boosting (gigaam_amd/csrc/gam_beam.h).  Runs the CTC head, its log-softmax and ONE beam
  * kernel (a workgroup per utterance, t the sequential loop, backtrack in the same kernel).  Beam width 1 <= W <= 32; per frame the
  * top min(W, V - 1) non-blank ids are the candidate tokens; blank = V - 1.  Ties follow a fixed rule (gam_beam.h), so the result is
- * deterministic.  The hotword set of gam_set_hotwords (if any) boosts the hypotheses that spell its phrases.
+ * deterministic.  The hotword set of gam_set_hotwords (if any) boosts the hypotheses that spell its phrases; the n-gram LM of
+ * gam_set_lm (if any) adds weight * ln P(word | history) + word_bonus for every completed word.
  *   ids / frames i32 [B, T']: the best prefix's token ids and the frame at which each token entered the beam (the first frame of its
  *   run), counts i32 [B] of them (entries past counts[b] are not written).
- *   score f32 [B]: log p of the prefix (over the paths the beam kept) + its committed hotword bonus; logp f32 [B]: that log p alone.
+ *   score f32 [B]: log p of the prefix (over the paths the beam kept) + its committed hotword bonus + its LM term (every word
+ *   including the last, and weight * ln P(</s> | history)); logp f32 [B]: that log p alone.
  *   enc_len[b] = 0 gives an empty result with score = logp = 0.
  * Limits: W <= 32, T' <= 8192 (an error beyond them).  Decode class, like gam_ctc_greedy; no host synchronisation. */
 int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
@@ -161,6 +163,19 @@ int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_le
  * 16384 tokens are errors; n_phrases = 0 clears the set.  A setup call, like gam_set_weight: it waits for the handle's in-flight
  * decode-class work before it replaces the set. */
 int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offsets, int n_phrases, float boost);
+/* A word n-gram LM for the beam search (host arrays, copied; gigaam_amd/lm.py builds them, gam_beam.h holds the rules):
+ *   token_class i32 [V] (V = the log-probs' V, blank included): 0 continues the current word, 1 starts a new word (the token belongs
+ *   to it), 2 separates words (belongs to none).  A word is completed when a class-1/2 token follows a non-empty partial word.
+ *   word_table: word_slots 16-byte slots {u64 key, i32 LM word id, i32 0}, keyed by the hash of the word's token ids;
+ *   ngram_table: ngram_slots slots {u64 key, f32 ln p, f32 ln back-off}, keyed by the hash of the word-id tuple.  Open addressing
+ *   with linear probing: slot counts are powers of two <= 2^30 (load <= 0.5 advised), word_probe / ngram_probe the longest probe
+ *   chains.  order 1..5; bos / eos / unk the ids of <s>, </s>, <unk> (unk may name a word with no unigram: it then scores
+ *   unk_logp).  weight (alpha) scales ln P, word_bonus (beta) is added per completed word.  ngram_slots = 0 clears the LM.
+ * Token classes outside [0, 2], a bad order, slot count or probe bound are errors; a search whose V differs from the classes' is
+ * an error.  A setup call: it waits for the handle's in-flight decode-class work before it replaces the tables. */
+int gam_set_lm(gam_handle* h, const int32_t* token_class, int V, const void* word_table, int64_t word_slots, int word_probe,
+               const void* ngram_table, int64_t ngram_slots, int ngram_probe, int order, int bos, int eos, int unk, float unk_logp,
+               float weight, float word_bonus);
 
 /* RNNTGreedyDecoding.decode: ids/frames i32 [B, T'*max_symbols], counts i32 [B].
  * Optional dump of the log-softmax of every joint evaluation, in order, per utterance:
