@@ -17,6 +17,7 @@
 #include "gam_align.h"
 #include "gam_attn.h"
 #include "gam_beam.h"
+#include "gam_rnnt_beam.h"
 #include "gam_attn16.h"
 #include "gam_comm.h"
 #include "gam_common.h"
@@ -130,6 +131,7 @@ struct gam_handle {
   DevBuf op_planes, op_sp, splitk_ws;   // gam_op_gemm operand planes; split-K partial sums
   DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
   DevBuf beam_nodes;                    // CTC beam search prefix-trie nodes, B x T' x W (gam_beam.h)
+  DevBuf rb_ws, rb_nodes;               // RNN-T beam search: predictor-state slots + logit rows, prefix-trie nodes (gam_rnnt_beam.h)
   int* hw_trie = nullptr;               // hotword trie of gam_set_hotwords (CSR, gam_beam.h): offsets | edges; NULL = no hotwords
   size_t hw_cap = 0;                    // ints allocated at hw_trie
   int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
@@ -557,6 +559,8 @@ void gam_destroy(gam_handle* h) {
   if (h->lens) hipFree(h->lens);
   if (h->range_flag) hipFree(h->range_flag);
   if (h->beam_nodes.p) hipFree(h->beam_nodes.p);
+  if (h->rb_ws.p) hipFree(h->rb_ws.p);
+  if (h->rb_nodes.p) hipFree(h->rb_nodes.p);
   if (h->hw_trie) hipFree(h->hw_trie);
   if (h->lm_cls) hipFree(h->lm_cls);
   if (h->lm_wt) hipFree(h->lm_wt);
@@ -1840,6 +1844,77 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
     }
   }
   return launch_single(0);
+}
+
+// RNN-T beam search over the encoder projection encp [B, Tp, JH] (gam_rnnt_beam.h): one workgroup per utterance.  Decode class (the
+// caller holds a DecodeScope): the state slots, logit rows and prefix-trie nodes are the handle's.
+static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols,
+                            int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s) {
+  const gam_config& c = h->cfg;
+  const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden, L = c.pred_rnn_layers;
+  if (B <= 0 || Tp <= 0) return fail(h, -1, "RNN-T beam search: bad shape B=%d T'=%lld", B, (long long)Tp);
+  if (Tp > GAM_RB_MAX_T) return fail(h, -1, "RNN-T beam search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_RB_MAX_T);
+  if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "RNN-T beam search: beam width W=%d outside [1, %d]", W, GAM_BEAM_MAX_W);
+  if (max_symbols < 1 || max_symbols > GAM_RB_MAX_S)
+    return fail(h, -1, "RNN-T beam search: max_symbols S=%d outside [1, %d]", max_symbols, GAM_RB_MAX_S);
+  if (V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "RNN-T beam search: V=%d outside [2, %d]", V, GAM_BEAM_MAX_V);
+  if (H > GAM_RB_MAX_H || JH > GAM_RB_MAX_H || H % 16 != 0 || JH % 16 != 0)
+    return fail(h, -1, "RNN-T beam search: H=%d / JH=%d must be multiples of 16 up to %d", H, JH, GAM_RB_MAX_H);
+  if (!encp || !enc_len || !ids || !frames || !counts || !score || !logp) return fail(h, -1, "RNN-T beam search: NULL buffer");
+  if (h->hw_trie && h->hw_max_tok > V - 2)
+    return fail(h, -1, "RNN-T beam search: hotword token id %d outside [0, %d] for V=%d", h->hw_max_tok, V - 2, V);
+  const int K = std::min(W, V - 1);
+  const size_t base = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, 0);
+  if (base > 160 * 1024) return fail(h, -1, "RNN-T beam search: W=%d, S=%d, H=%d, L=%d need %zu bytes of LDS (> 160 KiB)", W, max_symbols, H, L, base);
+  const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX && base + (size_t)h->hw_words * 4 <= 160 * 1024;
+  const size_t sm = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, hw_lds ? h->hw_words : 0);
+  const size_t per = (gam_rb_ws_floats(W, max_symbols, V, H, JH, L) + 63) & ~(size_t)63;
+  if (int r = ensure(h, h->rb_ws, per * B + 64)) return r;
+  if (int r = ensure(h, h->rb_nodes, (size_t)B * Tp * max_symbols * W * 2 + 64)) return r;
+  GamRnntBeamArgs a;
+  memset(&a, 0, sizeof a);
+  a.encp = encp; a.enc_len = enc_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wpred_t = h->jn_pred_t; a.bpred = h->jn_pred_b;
+  a.wout = h->jn_out_w; a.bout = h->jn_out_b; a.wih_x = h->lstm_wih_x; a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x;
+  a.Tp = (int)Tp; a.V = V; a.H = H; a.JH = JH; a.L = L; a.W = W; a.K = K; a.S = max_symbols;
+  a.hw = h->hw_trie; a.hw_nodes = h->hw_nodes; a.hw_words = h->hw_words; a.hw_lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
+  a.ws = h->rb_ws.p; a.ws_stride = per;
+  a.nodes = reinterpret_cast<int2*>(h->rb_nodes.p);
+  a.ids = ids; a.frames = frames; a.cap = (int)Tp * max_symbols; a.counts = counts; a.score = score; a.logp = logp;
+  static std::atomic<unsigned long long> lds_set;
+  HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_beam_kernel), 160 * 1024, lds_set));
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * ((double)V * JH + 4.0 * H * H) * 4.0);
+  hipLaunchKernelGGL(gam_rnnt_beam_kernel, dim3(B), dim3(GAM_RB_NT), sm, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
+                  int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
+  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
+  DecodeScope ds(h, s);
+  if (B <= 0 || Tp <= 0 || Tp > GAM_RB_MAX_T || W < 1 || W > GAM_BEAM_MAX_W || max_symbols < 1 || max_symbols > GAM_RB_MAX_S)
+    return fail(h, -1, "RNN-T beam search: B=%d T'=%lld / W=%d / S=%d beyond the limits (%d / [1, %d] / [1, %d])", B, (long long)Tp, W,
+                max_symbols, GAM_RB_MAX_T, GAM_BEAM_MAX_W, GAM_RB_MAX_S);
+  const gam_config& c = h->cfg;
+  const int D = c.d_model, JH = c.joint_hidden;
+  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
+  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
+  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
+  if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  return rnnt_beam_launch(h, h->encp.p, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s);
+}
+
+int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
+                     int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
+  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s);
 }
 
 int gam_rnnt_predict(gam_handle* h, const int32_t* labels, const float* h_in, const float* c_in, int B, float* g_out,

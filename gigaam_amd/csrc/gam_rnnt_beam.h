@@ -1,0 +1,577 @@
+// gam_rnnt_beam.h -- RNN-T beam search with hotword boosting (gam_rnnt_beam / gam_op_rnnt_beam).
+//
+// The contract (shared with tests/rnnt_beam_ref.py, which holds real token tuples).  For utterance b: T = enc_len[b], blank = V - 1,
+// beam width W (1..32), K = min(W, V - 1) candidate tokens per joint row, S = max_symbols (1..16).  A hypothesis h has its token
+// sequence y, the predictor state after feeding y (the empty y: predict(None, None), gate_tab row V, as in gam_rnnt_greedy_kernel),
+// pp(y) = W_pred g(y) + b_pred, a score (log-prob) and a hotword state (node, acc, committed) with the rules of gam_beam.h.
+//   lp(t, y) = log_softmax(W_out relu(encp[t] + pp(y)) + b_out);   rank = score + committed + acc.
+//
+//   beam = {empty: score 0}
+//   for t in 0 .. T-1:
+//     B = {}; A_0 = beam
+//     for s in 0 .. S:
+//       if s < S: for a in A_s (position p): lp = lp(t, a.y)
+//                   blank candidate  (a.y, a.score + lp[blank]), origin key (s, p, 0)          -> merged into B
+//                   for v in the top-K non-blank ids of lp (ties to the lower id):
+//                     extension (a.y + v, a.score + lp[v]), emitted at frame t, key (s, p, v + 1), hotword step -> C_s
+//       else:     for a in A_S: (a.y, a.score), key (S, p, 0) -> merged into B    (forced advance without a joint: greedy's rule)
+//       theta = the W-th highest rank in B, or -inf while |B| < W
+//       A_{s+1} = top W of {c in C_s : rank(c) > theta}; the frame ends when it is empty
+//       one predictor step for A_{s+1}'s new last tokens (all rows together), then W_pred
+//     beam = top W of B
+//   final: the entry of beam with the best score + committed (ties: lower position)
+// Merging in B: entries with equal y are log-add-exp'd; the merged entry keeps the prefix node (its frames) and the predictor state of
+// the contributor with the higher score (= higher rank: the hotword state depends on y alone), ties to the earlier (smaller key)
+// contributor, and the key of its first contributor.  Within one C_s sequences are distinct.  Every top-W selection breaks rank ties
+// by the smaller origin key.  The theta cut is part of the contract: without it C_s is never empty and every frame runs S joints and S
+// predictor steps; with it a blank-dominant frame ends after one joint.
+// Hypothesis identity: (length, 64-bit polynomial hash h(y + v) = h(y) P + v + 1), as in gam_beam.h.
+//
+// Shape: one workgroup of GAM_RB_NT threads per utterance; t the sequential loop; the backtrack at the end of the same kernel.
+//   joint   z [rows][JH] = relu(encp[t] + pp) in LDS; logits = z W_out^T + b_out on the matrix cores (v_mfma_f32_16x16x4_f32, rows
+//           padded to 16 or 32, W_out read from L2 ONCE per call for all rows) into a per-utterance global scratch slice; then one
+//           wave per row: log-sum-exp, blank and the top K (64-bit keys, wave maxima: gam_beam_wave_topn).
+//   merge   wave 0: blank / forced candidates into B (hash compare), theta, the top W extensions -> A_{s+1} (prefix-trie nodes,
+//           predictor-state slots from a free list).
+//   predict gates = gate_tab[v] + W_hh h (layer 0; layers above take the new h of the layer below through W_ih) for all rows at once,
+//           four gate tiles of 16 hidden units per MFMA pass so the LSTM cell runs on the accumulators; then pp = W_pred g + b_pred.
+//           The states live in global slots [L][h | c] | pp of a per-utterance pool of (S + 1) W slots: the beam holds <= W, each
+//           A_{s+1} takes <= W fresh ones, and the free list is rebuilt from the new beam at the end of every frame.
+// Arithmetic: exact fp32 (MFMA f32, expf / logf), no fp16 terms.  Every row's sums run in the same order whatever its position, so
+// one y always gets bit-identical predictor outputs.  Renormalisation: each frame subtracts the best kept rank from the scores and adds
+// it to an fp64 offset.  Limits (host errors beyond them): W <= 32, S <= 16, T' <= 8192, V <= 1025, H and JH <= 512 (multiples of 16).
+#pragma once
+#include "gam_beam.h"
+
+#define GAM_RB_NT 256
+#define GAM_RB_MAX_S 16
+#define GAM_RB_MAX_H 512
+#define GAM_RB_MAX_T 8192
+
+struct GamRnntBeamArgs {
+  const float* encp;     // [B*Tp, JH]
+  const int* enc_len;    // [B]
+  const float* gate_tab; // [V+1, 4H]
+  const float* whh_t;    // [H, 4H]
+  const float* wpred_t;  // [H, JH]
+  const float* bpred;    // [JH]
+  const float* wout;     // [V, JH]
+  const float* bout;     // [V]
+  const float* wih_x;    // [L-1][H][4H]
+  const float* whh_x;    // [L-1][H][4H]
+  const float* bias_x;   // [L-1][4H]
+  int Tp, V, H, JH, L, W, K, S;
+  const int* hw;         // hotword trie (NULL: none)
+  int hw_nodes, hw_words, hw_lds;
+  float beta;
+  float* ws;             // [B][slots (S+1) W x SS | logits Wp x LGS] floats
+  size_t ws_stride;      // floats per utterance
+  int2* nodes;           // [B][Tp S W]
+  int* ids;              // [B, cap]
+  int* frames;           // [B, cap]
+  int cap;
+  int* counts;           // [B]
+  float* score;          // [B]
+  float* logp;           // [B]
+};
+
+// LDS carve (host and device), in bytes, in this order: A lists [2][32] (hash u64; len, score, hotword node, acc, committed, prefix
+// node, slot, token, parent slot: i32 / f32), row blank log-probs [32], counters [16], B list [P] (hash u64; len, score, best
+// contributor score, key, slot, node, hotword node, acc, committed), free list [P], slot mask [(P + 31) / 32], then from a 16-byte
+// boundary the union region U (joint rows z [Wp][JH + 4] | candidates [W K] (key u64; score, acc, committed, hotword node) | hidden
+// rows [1 or 2][Wp][H + 4]), then the hotword trie when it lies in LDS.
+__host__ __device__ static inline size_t gam_rb_pool(int W, int S) { return (size_t)(S + 1) * W; }
+__host__ __device__ static inline size_t gam_rb_fixed_bytes(int W, int S) {
+  const size_t P = gam_rb_pool(W, S);
+  const size_t f = 2 * 32 * 8 + 2 * 32 * 9 * 4 + 32 * 4 + 16 * 4 + P * 8 + P * 9 * 4 + P * 4 + ((P + 31) / 32) * 4;
+  return (f + 15) & ~(size_t)15;
+}
+__host__ __device__ static inline size_t gam_rb_union_bytes(int W, int K, int H, int JH, int L) {
+  const size_t Wp = (size_t)((W + 15) / 16) * 16;
+  size_t u = Wp * (JH + 4) * 4;
+  const size_t c = (size_t)W * K * (8 + 4 * 4);
+  const size_t hb = (size_t)(L > 1 ? 2 : 1) * Wp * (H + 4) * 4;
+  u = u > c ? u : c;
+  u = u > hb ? u : hb;
+  return (u + 15) & ~(size_t)15;
+}
+static inline size_t gam_rb_lds_bytes(int W, int K, int S, int H, int JH, int L, int hw_lds_words) {
+  return gam_rb_fixed_bytes(W, S) + gam_rb_union_bytes(W, K, H, JH, L) + (size_t)hw_lds_words * 4;
+}
+// floats of one utterance's global workspace: the state slots and the logit rows
+static inline size_t gam_rb_ws_floats(int W, int S, int V, int H, int JH, int L) {
+  const size_t Wp = (size_t)((W + 15) / 16) * 16;
+  return gam_rb_pool(W, S) * ((size_t)L * 2 * H + JH) + Wp * (size_t)((V + 3) & ~3);
+}
+
+__device__ __forceinline__ f32x4 gam_rb_lds4(const float* p) {
+  return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>((__attribute__((address_space(3))) const void*)(p));
+}
+
+// acc[g][rt] += A[16 rt + i][k] * Wt[k][g * H + j0 + c] over k < H: A rows from LDS (row stride H + 4), Wt k-major with 4H columns.
+// MFMA lane (i = lane & 15, q = lane >> 4): A row i, weight column j0 + i, k = k0 + 4 q + e in the e-th MFMA of a group of four.
+template <int RT>
+__device__ __forceinline__ void gam_rb_gates_mm(f32x4 (&acc)[4][2], const float* A, const float* __restrict__ Wt, int H, int j0, int li,
+                                                int lg4) {
+  const int G = 4 * H, ALD = H + 4;
+  for (int k0 = 0; k0 < H; k0 += 16) {
+    float w[4][4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) w[g][e] = Wt[(size_t)(k0 + 4 * lg4 + e) * G + g * H + j0 + li];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const f32x4 a = gam_rb_lds4(A + (16 * rt + li) * ALD + k0 + 4 * lg4);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[g][0], acc[g][rt], 0, 0, 0);
+        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[g][1], acc[g][rt], 0, 0, 0);
+        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[g][2], acc[g][rt], 0, 0, 0);
+        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[g][3], acc[g][rt], 0, 0, 0);
+      }
+    }
+  }
+}
+
+template <int RT>
+__device__ void gam_rb_body(const GamRnntBeamArgs& a);
+
+__global__ __launch_bounds__(GAM_RB_NT) void gam_rnnt_beam_kernel(GamRnntBeamArgs a) {
+  if (a.W > 16) gam_rb_body<2>(a);
+  else gam_rb_body<1>(a);
+}
+
+template <int RT>
+__device__ void gam_rb_body(const GamRnntBeamArgs& a) {
+  extern __shared__ uint4 gam_smem_rbeam[];
+  unsigned char* p = reinterpret_cast<unsigned char*>(gam_smem_rbeam);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lg4 = lane >> 4;
+  const int b = blockIdx.x;
+  const int Tp = a.Tp, V = a.V, H = a.H, JH = a.JH, L = a.L, W = a.W, K = a.K, S = a.S, blank = V - 1;
+  const int Wp = 16 * RT, G = 4 * H;
+  const int P = (S + 1) * W;
+  const size_t SS = (size_t)L * 2 * H + JH;        // slot: [L][h | c] | pp
+  const int LGS = (V + 3) & ~3;
+  auto take = [&](size_t n) { unsigned char* r = p; p += n; return r; };
+  unsigned long long* ah = reinterpret_cast<unsigned long long*>(take(2 * 32 * 8));   // A lists [buf * 32 + i]
+  int* alen = reinterpret_cast<int*>(take(2 * 32 * 4));
+  float* asc = reinterpret_cast<float*>(take(2 * 32 * 4));
+  int* ahn = reinterpret_cast<int*>(take(2 * 32 * 4));
+  float* aacc = reinterpret_cast<float*>(take(2 * 32 * 4));
+  float* acb = reinterpret_cast<float*>(take(2 * 32 * 4));
+  int* anode = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* aslot = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* atok = reinterpret_cast<int*>(take(2 * 32 * 4));
+  int* apar = reinterpret_cast<int*>(take(2 * 32 * 4));
+  float* rlpb = reinterpret_cast<float*>(take(32 * 4));
+  int* cnt = reinterpret_cast<int*>(take(16 * 4));      // [0], [1]: sizes of the A lists
+  unsigned long long* bh = reinterpret_cast<unsigned long long*>(take((size_t)P * 8));
+  int* blen = reinterpret_cast<int*>(take((size_t)P * 4));
+  float* bsc = reinterpret_cast<float*>(take((size_t)P * 4));
+  float* bcs = reinterpret_cast<float*>(take((size_t)P * 4));
+  int* bkey = reinterpret_cast<int*>(take((size_t)P * 4));
+  int* bslot = reinterpret_cast<int*>(take((size_t)P * 4));
+  int* bnode = reinterpret_cast<int*>(take((size_t)P * 4));
+  int* bhn = reinterpret_cast<int*>(take((size_t)P * 4));
+  float* bacc = reinterpret_cast<float*>(take((size_t)P * 4));
+  float* bcb = reinterpret_cast<float*>(take((size_t)P * 4));
+  int* freel = reinterpret_cast<int*>(take((size_t)P * 4));
+  int* smask = reinterpret_cast<int*>(take((size_t)((P + 31) / 32) * 4));
+  p = reinterpret_cast<unsigned char*>(gam_smem_rbeam) + gam_rb_fixed_bytes(W, S);
+  unsigned char* U = p;
+  // the union region: joint rows | candidates | hidden rows
+  float* zr = reinterpret_cast<float*>(U);
+  const int NC = W * K;
+  unsigned long long* ckey = reinterpret_cast<unsigned long long*>(U);
+  float* csc = reinterpret_cast<float*>(U + (size_t)NC * 8);
+  float* cacc = csc + NC;
+  float* ccb = cacc + NC;
+  int* chn = reinterpret_cast<int*>(ccb + NC);
+  float* hx = reinterpret_cast<float*>(U);                       // [Wp][H + 4]: the layer's input x (layers above the first)
+  float* hr = L > 1 ? hx + (size_t)Wp * (H + 4) : hx;            // [Wp][H + 4]: the recurrent h (and g for W_pred)
+  int* hw_sh = reinterpret_cast<int*>(U + gam_rb_union_bytes(W, K, H, JH, L));
+
+  int T = a.enc_len[b];
+  T = T < 0 ? 0 : (T > Tp ? Tp : T);
+  if (T == 0) {
+    if (tid == 0) {
+      a.counts[b] = 0;
+      a.score[b] = 0.f;
+      a.logp[b] = 0.f;
+    }
+    return;
+  }
+  const int* hw = a.hw;
+  if (hw != nullptr && a.hw_lds) {
+    for (int i = tid; i < a.hw_words; i += GAM_RB_NT) hw_sh[i] = a.hw[i];
+    hw = hw_sh;
+  }
+  float* slots = a.ws + (size_t)b * a.ws_stride;
+  float* lg = slots + (size_t)P * SS;                              // [Wp][LGS] logits
+  int2* nodes = a.nodes + (size_t)b * Tp * S * W;
+  const float* encb = a.encp + (size_t)b * Tp * JH;
+
+  // wave 0: rebuild the free list from the slots the A[0] list (the beam) holds
+  auto rebuild_free = [&](int nb) {
+    for (int i = lane; i < (P + 31) / 32; i += 64) smask[i] = 0;
+    __builtin_amdgcn_wave_barrier();
+    if (lane < nb) atomicOr(&smask[aslot[lane] >> 5], 1 << (aslot[lane] & 31));
+    __builtin_amdgcn_wave_barrier();
+    int n = 0;
+    for (int base = 0; base < P; base += 64) {
+      const int sl = base + lane;
+      const bool fr = sl < P && !((smask[sl >> 5] >> (sl & 31)) & 1);
+      const unsigned long long m = __ballot(fr);
+      if (fr) freel[n + __popcll(m & ((1ull << lane) - 1ull))] = sl;
+      n += __popcll(m);
+    }
+  };
+
+  // ---- one predictor step for the n rows of A list `buf`: new slot aslot[i] <- LSTM(atok[i], slot apar[i]); pp = W_pred g + b_pred
+  auto predict = [&](int buf, int n) {
+    const int* tok = atok + buf * 32;
+    const int* par = apar + buf * 32;
+    const int* dst = aslot + buf * 32;
+    for (int l = 0; l < L; ++l) {
+      // stage the rows: recurrent h of layer l of the parent (zero for the empty y's parent -1); x = the new h of layer l - 1
+      for (int e = tid; e < Wp * H; e += GAM_RB_NT) {
+        const int i = e / H, k = e - i * H;
+        float hv = 0.f, xv = 0.f;
+        if (i < n) {
+          const int ps = par[i];
+          hv = ps >= 0 ? slots[(size_t)ps * SS + (size_t)l * 2 * H + k] : 0.f;
+          if (l > 0) xv = slots[(size_t)dst[i] * SS + (size_t)(l - 1) * 2 * H + k];
+        }
+        hr[i * (H + 4) + k] = hv;
+        if (l > 0) hx[i * (H + 4) + k] = xv;
+      }
+      __syncthreads();
+      for (int jt = wave; jt * 16 < H; jt += 4) {
+        const int j0 = jt * 16;
+        f32x4 acc[4][2];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = 16 * rt + 4 * lg4 + r;
+            const int tk = row < n ? tok[row] : V;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              acc[g][rt][r] = l == 0 ? a.gate_tab[(size_t)tk * G + g * H + j0 + li] : a.bias_x[(size_t)(l - 1) * G + g * H + j0 + li];
+          }
+        if (l > 0) gam_rb_gates_mm<RT>(acc, hx, a.wih_x + (size_t)(l - 1) * H * G, H, j0, li, lg4);
+        gam_rb_gates_mm<RT>(acc, hr, l == 0 ? a.whh_t : a.whh_x + (size_t)(l - 1) * H * G, H, j0, li, lg4);
+        // the LSTM cell on the accumulators: row 16 rt + 4 q + r, hidden unit j0 + i (gate order i, f, g, o)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = 16 * rt + 4 * lg4 + r;
+            if (row < n) {
+              const int ps = par[row];
+              const float c0 = ps >= 0 ? slots[(size_t)ps * SS + (size_t)l * 2 * H + H + j0 + li] : 0.f;
+              const float ig = gam_sigmoid_exact(acc[0][rt][r]), fg = gam_sigmoid_exact(acc[1][rt][r]);
+              const float gg = tanhf(acc[2][rt][r]), og = gam_sigmoid_exact(acc[3][rt][r]);
+              const float c2 = fg * c0 + ig * gg;
+              float* sd = slots + (size_t)dst[row] * SS + (size_t)l * 2 * H;
+              sd[H + j0 + li] = c2;
+              sd[j0 + li] = og * tanhf(c2);
+            }
+          }
+      }
+      __syncthreads();
+    }
+    // pp = W_pred g + b_pred, g = the top layer's new h
+    for (int e = tid; e < Wp * H; e += GAM_RB_NT) {
+      const int i = e / H, k = e - i * H;
+      hr[i * (H + 4) + k] = i < n ? slots[(size_t)dst[i] * SS + (size_t)(L - 1) * 2 * H + k] : 0.f;
+    }
+    __syncthreads();
+    for (int ct = wave; ct * 16 < JH; ct += 4) {
+      const int c0 = ct * 16;
+      f32x4 acc[2];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        const float bv = a.bpred[c0 + li];
+        acc[rt] = (f32x4){bv, bv, bv, bv};
+      }
+      for (int k0 = 0; k0 < H; k0 += 16) {
+        float w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] = a.wpred_t[(size_t)(k0 + 4 * lg4 + e) * JH + c0 + li];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+          const f32x4 av = gam_rb_lds4(hr + (16 * rt + li) * (H + 4) + k0 + 4 * lg4);
+          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, w[0], acc[rt], 0, 0, 0);
+          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, w[1], acc[rt], 0, 0, 0);
+          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, w[2], acc[rt], 0, 0, 0);
+          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, w[3], acc[rt], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * rt + 4 * lg4 + r;
+          if (row < n) slots[(size_t)dst[row] * SS + (size_t)L * 2 * H + c0 + li] = acc[rt][r];
+        }
+    }
+    __syncthreads();
+  };
+
+  // ---- the empty hypothesis: predict(None, None) into slot 0
+  if (tid == 0) {
+    ah[0] = 0ull; alen[0] = 0; asc[0] = 0.f; ahn[0] = 0; aacc[0] = 0.f; acb[0] = 0.f; anode[0] = -1;
+    aslot[0] = 0; atok[0] = V; apar[0] = -1;
+    cnt[0] = 1;
+  }
+  __syncthreads();
+  predict(0, 1);
+  if (wave == 0) rebuild_free(1);
+  __syncthreads();
+
+  double off = 0.0;        // wave 0: what the renormalisations subtracted so far
+  int ncount = 0;          // wave 0: prefix-trie nodes of this utterance so far
+  for (int t = 0; t < T; ++t) {
+    int nB = 0;            // wave 0: entries of B
+    int fptr = 0;          // wave 0: free slots taken this frame
+    const float* et = encb + (size_t)t * JH;
+    for (int s = 0; s <= S; ++s) {
+      const int cur = s & 1, nx = cur ^ 1;
+      const int n = cnt[cur];
+      int nc = 0;          // candidates of C_s (n K, or 0 at s = S)
+      if (s < S) {
+        nc = n * K;
+        // ---- joint rows: z = relu(encp[t] + pp), rows >= n zero
+        for (int e = tid; e < Wp * JH; e += GAM_RB_NT) {
+          const int i = e / JH, k = e - i * JH;
+          zr[i * (JH + 4) + k] = i < n ? fmaxf(et[k] + slots[(size_t)aslot[cur * 32 + i] * SS + (size_t)L * 2 * H + k], 0.f) : 0.f;
+        }
+        __syncthreads();
+        // ---- logits = z W_out^T + b_out: one 16-class tile per MFMA chain, W_out read once for all rows
+        for (int nt = wave; nt * 16 < V; nt += 4) {
+          const int v = nt * 16 + li;
+          const int vc = v < V ? v : V - 1;
+          const float* wr = a.wout + (size_t)vc * JH + 4 * lg4;
+          f32x4 acc[2];
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) acc[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          for (int k0 = 0; k0 < JH; k0 += 16) {
+            const f32x4 wf = *reinterpret_cast<const f32x4*>(wr + k0);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+              const f32x4 zf = gam_rb_lds4(zr + (16 * rt + li) * (JH + 4) + k0 + 4 * lg4);
+              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.x, wf.x, acc[rt], 0, 0, 0);
+              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.y, wf.y, acc[rt], 0, 0, 0);
+              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.z, wf.z, acc[rt], 0, 0, 0);
+              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.w, wf.w, acc[rt], 0, 0, 0);
+            }
+          }
+          if (v < V) {
+            const float bo = a.bout[v];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int row = 16 * rt + 4 * lg4 + r;
+                if (row < n) lg[(size_t)row * LGS + v] = acc[rt][r] + bo;
+              }
+          }
+        }
+        __syncthreads();
+        // ---- one wave per row: log-sum-exp, blank, the top K -> the candidates of C_s
+        const int nrv = (V + 63) >> 6;
+        for (int r = wave; r < n; r += 4) {
+          const float* xr = lg + (size_t)r * LGS;
+          float x[GAM_BEAM_RPL];
+          float mx = -INFINITY;
+#pragma unroll
+          for (int j = 0; j < GAM_BEAM_RPL; ++j) {
+            const int v = lane + 64 * j;
+            x[j] = (j < nrv && v < V) ? xr[v] : -INFINITY;
+            mx = fmaxf(mx, x[j]);
+          }
+          mx = gam_wave_max(mx);
+          float se = 0.f;
+#pragma unroll
+          for (int j = 0; j < GAM_BEAM_RPL; ++j)
+            if (j < nrv) se += expf(x[j] - mx);
+          se = gam_wave_sum(se);
+          const float lse = mx + logf(se);
+          unsigned long long k[GAM_BEAM_RPL];
+#pragma unroll
+          for (int j = 0; j < GAM_BEAM_RPL; ++j) {
+            const int v = lane + 64 * j;
+            k[j] = (j < nrv && v < V - 1) ? (((unsigned long long)gam_beam_ord(x[j]) << 32) | (unsigned)(0xffff - v)) : 0ull;
+          }
+          unsigned long long out;
+          gam_beam_wave_topn(k, nrv, K, lane, out);
+          const int o = cur * 32 + r;
+          if (lane == 0) rlpb[r] = xr[blank] - lse;
+          if (lane < K) {
+            const int v = 0xffff - (int)(out & 0xffff);
+            const float sc = asc[o] + (gam_beam_unord((unsigned)(out >> 32)) - lse);
+            int hn = ahn[o];
+            float acc = aacc[o], cb = acb[o];
+            if (hw != nullptr) gam_beam_hw_step(hw, a.hw_nodes, a.beta, v, hn, acc, cb);
+            const float rank = sc + (cb + acc);
+            const int q = r * K + lane;
+            const int key = r * GAM_BEAM_KEY_STRIDE + v + 1;
+            ckey[q] = rank > -INFINITY ? (((unsigned long long)gam_beam_ord(rank) << 32) | ((unsigned)(0xffff - key) << 16) | (unsigned)q) : 0ull;
+            csc[q] = sc;
+            cacc[q] = acc;
+            ccb[q] = cb;
+            chn[q] = hn;
+          }
+        }
+        __syncthreads();
+      }
+      if (wave == 0) {
+        // ---- blank candidates (s < S) or forced advances (s = S) of A_s into B
+        {
+          const int o = cur * 32 + lane;
+          const bool act = lane < n;
+          const float sc = act ? (s < S ? asc[o] + rlpb[lane] : asc[o]) : -INFINITY;
+          const unsigned long long h = act ? ah[o] : 0ull;
+          const int len = act ? alen[o] : -1;
+          int f = -1;
+          for (int i = 0; i < nB; ++i)
+            if (f < 0 && blen[i] == len && bh[i] == h) f = i;
+          const bool valid = act && sc > -INFINITY;
+          if (valid && f >= 0) {
+            bsc[f] = gam_beam_lse(bsc[f], sc);
+            if (sc > bcs[f]) {
+              bcs[f] = sc;
+              bslot[f] = aslot[o];
+              bnode[f] = anode[o];
+            }
+          }
+          const bool add = valid && f < 0;
+          const unsigned long long m = __ballot(add);
+          if (add) {
+            const int d = nB + __popcll(m & ((1ull << lane) - 1ull));
+            bh[d] = h; blen[d] = len; bsc[d] = sc; bcs[d] = sc; bkey[d] = s * 32 + lane;
+            bslot[d] = aslot[o]; bnode[d] = anode[o]; bhn[d] = ahn[o]; bacc[d] = aacc[o]; bcb[d] = acb[o];
+          }
+          nB += __popcll(m);
+        }
+        // ---- theta, then A_{s+1} = top W of the candidates above it
+        int ns = 0;
+        if (nc > 0) {
+          unsigned ord_theta = 0u;     // (every finite or +inf rank orders above it)
+          unsigned long long k[GAM_BEAM_RPL];
+          if (nB >= W) {
+            const int nr = (nB + 63) >> 6;
+#pragma unroll
+            for (int j = 0; j < GAM_BEAM_RPL; ++j) {
+              const int i = lane + 64 * j;
+              k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(bsc[i] + (bcb[i] + bacc[i])) << 32) |
+                                           ((unsigned)(0xffff - bkey[i]) << 16) | (unsigned)i)
+                                        : 0ull;
+            }
+            unsigned long long sel;
+            gam_beam_wave_topn(k, nr, W, lane, sel);
+            ord_theta = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), W - 1);
+          }
+          const int nr = (nc + 63) >> 6;
+#pragma unroll
+          for (int j = 0; j < GAM_BEAM_RPL; ++j) {
+            const int q = lane + 64 * j;
+            const unsigned long long kq = (j < nr && q < nc) ? ckey[q] : 0ull;
+            k[j] = (unsigned)(kq >> 32) > ord_theta ? kq : 0ull;
+          }
+          unsigned long long sel;
+          ns = gam_beam_wave_topn(k, nr, W, lane, sel);
+          if (lane < ns) {
+            const int q = (int)(sel & 0xffff);
+            const int r = q / K;
+            const int key = 0xffff - (int)((sel >> 16) & 0xffff);
+            const int v = key - r * GAM_BEAM_KEY_STRIDE - 1;
+            const int o = cur * 32 + r, d = nx * 32 + lane;
+            const int idx = ncount + lane;
+            nodes[idx] = make_int2(anode[o], (v << 13) | t);
+            ah[d] = ah[o] * GAM_BEAM_HASH_P + (unsigned long long)(v + 1);
+            alen[d] = alen[o] + 1;
+            asc[d] = csc[q];
+            ahn[d] = chn[q]; aacc[d] = cacc[q]; acb[d] = ccb[q];
+            anode[d] = idx;
+            aslot[d] = freel[fptr + lane];
+            atok[d] = v;
+            apar[d] = aslot[o];
+          }
+          ncount += ns;
+          fptr += ns;
+        }
+        if (lane == 0) cnt[nx] = ns;
+      }
+      __syncthreads();
+      const int nn = cnt[nx];
+      if (nn == 0) break;
+      predict(nx, nn);
+    }
+    // ---- the new beam: top W of B -> A list 0, renormalised; the free list from its slots
+    if (wave == 0) {
+      unsigned long long k[GAM_BEAM_RPL];
+      const int nr = (nB + 63) >> 6;
+#pragma unroll
+      for (int j = 0; j < GAM_BEAM_RPL; ++j) {
+        const int i = lane + 64 * j;
+        k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(bsc[i] + (bcb[i] + bacc[i])) << 32) |
+                                     ((unsigned)(0xffff - bkey[i]) << 16) | (unsigned)i)
+                                  : 0ull;
+      }
+      unsigned long long sel;
+      const int nb = gam_beam_wave_topn(k, nr, W, lane, sel);
+      if (nb > 0) {
+        const float M = gam_beam_unord((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), 0));
+        off += (double)M;
+        if (lane < nb) {
+          const int i = (int)(sel & 0xffff);
+          ah[lane] = bh[i]; alen[lane] = blen[i]; asc[lane] = bsc[i] - M;
+          ahn[lane] = bhn[i]; aacc[lane] = bacc[i]; acb[lane] = bcb[i];
+          anode[lane] = bnode[i]; aslot[lane] = bslot[i];
+        }
+      }
+      if (lane == 0) cnt[0] = nb;
+      __builtin_amdgcn_wave_barrier();
+      rebuild_free(nb);
+    }
+    __syncthreads();
+    if (cnt[0] == 0) break;      // (every candidate -inf: cannot happen with finite log-probs)
+  }
+
+  // ---- final pick (pending hotword bonus dropped), backtrack
+  if (wave == 0) {
+    const int nb = cnt[0];
+    const float val = lane < nb ? asc[lane] + acb[lane] : -INFINITY;
+    const unsigned long long key = lane < nb ? (((unsigned long long)gam_beam_ord(val) << 32) | (unsigned)(0xffff - lane)) : 0ull;
+    const unsigned long long m = gam_beam_wave_max(key);
+    const int best = m ? 0xffff - (int)(m & 0xffff) : -1;
+    if (best < 0) {
+      if (lane == 0) {
+        a.counts[b] = 0;
+        a.score[b] = -INFINITY;
+        a.logp[b] = -INFINITY;
+      }
+    } else if (lane == best) {
+      const double lp_ = (double)asc[lane] + off;
+      a.logp[b] = (float)lp_;
+      a.score[b] = (float)(lp_ + (double)acb[lane]);
+      const int n = alen[lane] < a.cap ? alen[lane] : a.cap;
+      a.counts[b] = n;
+      int* ids = a.ids + (size_t)b * a.cap;
+      int* fr = a.frames + (size_t)b * a.cap;
+      int node = anode[lane];
+      for (int i = alen[lane] - 1; i >= 0; --i) {
+        const int2 e = nodes[node];
+        if (i < n) {
+          ids[i] = e.y >> 13;
+          fr[i] = e.y & 8191;
+        }
+        node = e.x;
+      }
+    }
+  }
+}

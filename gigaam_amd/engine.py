@@ -161,11 +161,12 @@ class Aligned:
 
 
 class BeamDecoded(Decoded):
-    """What ``ctc_beam`` / ``op_ctc_beam`` return: a ``Decoded`` (ids, frames, counts + range flag word: ``collect``, ``finish`` and the
-    word builder take it as they take a greedy decode) whose buffer goes on with ``score`` and ``logp`` f32 [B] (``buf``: ids [B, T'] |
-    frames [B, T'] | counts [B] | flag word | score bits [B] | logp bits [B]).  ``host`` brings all of it to the host in ONE copy."""
+    """What ``ctc_beam`` / ``op_ctc_beam`` / ``rnnt_beam`` / ``op_rnnt_beam`` return: a ``Decoded`` (ids, frames, counts + range flag word: ``collect``, ``finish`` and the
+    word builder take it as they take a greedy decode) whose buffer goes on with ``score`` and ``logp`` f32 [B] (``buf``: ids [B, cap] |
+    frames [B, cap] | counts [B] | flag word | score bits [B] | logp bits [B]).  ``host`` brings all of it to the host in ONE copy."""
 
     def __new__(cls, buf: Tensor, b: int, tp: int, event=None, stream=None):
+        # (tp: the width of ids / frames -- T' for CTC, T' * max_symbols for RNN-T)
         n0 = 2 * b * tp + b + 1
         ids, frames, ext = buf[: b * tp].view(b, tp), buf[b * tp: 2 * b * tp].view(b, tp), buf[2 * b * tp: n0]
         self = Decoded.__new__(cls, ids, frames, ext[:b], ext, event, stream, whole=buf[:n0])
@@ -558,6 +559,50 @@ class HipEngine:
         b, tp, v = log_probs.shape
         with torch.cuda.device(self.device):
             out = self._launch_beam(self.lib.gam_op_ctc_beam, log_probs, enc_len, b, tp, (v,), beam_size, "gam_op_ctc_beam")
+            out.ext[b:].zero_()
+            st = torch.cuda.current_stream(self.device)
+            out.event, out.stream = torch.cuda.Event(), st
+            out.event.record(st)
+        return out
+
+    MAX_SYMBOLS_BEAM = 16     # include/gigaam_hip.h gam_rnnt_beam
+
+    def _rnnt_beam_out(self, b: int, tp: int, beam_size: int, max_symbols: int) -> BeamDecoded:
+        if not 1 <= int(beam_size) <= self.MAX_BEAM:
+            raise GigaAMHipError(f"beam_size {beam_size} outside [1, {self.MAX_BEAM}]")
+        if not 1 <= int(max_symbols) <= self.MAX_SYMBOLS_BEAM:
+            raise GigaAMHipError(f"max_symbols {max_symbols} outside [1, {self.MAX_SYMBOLS_BEAM}] for the RNN-T beam search")
+        cap = tp * int(max_symbols)
+        return BeamDecoded(torch.empty((2 * b * cap + 3 * b + 1,), dtype=torch.int32, device=self.device), b, cap)
+
+    def rnnt_beam(self, encoded: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int) -> BeamDecoded:
+        """RNN-T beam search (gam_rnnt_beam): the encoder projection GEMM and the beam kernel, no host sync; the hotword set of
+        ``set_hotwords`` applies.  ids / frames are [B, T' * max_symbols].  The split-fp16 range flag is CONSUMED as ``rnnt_greedy``
+        does: it lands in the flag word."""
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        with torch.cuda.device(self.device):
+            out = self._rnnt_beam_out(b, tp, beam_size, max_symbols)
+            rc = self.lib.gam_rnnt_beam(self._h, _ptr(encoded), _ptr(enc_len), b, tp, int(beam_size), int(max_symbols), _ptr(out.ids),
+                                        _ptr(out.frames), _ptr(out.counts), _ptr(out.score), _ptr(out.logp), self._stream())
+            self._check(rc, "gam_rnnt_beam")
+            out.event, out.stream = self._fetch_flag(out.ext)
+        return out
+
+    def op_rnnt_beam(self, encp: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int) -> BeamDecoded:
+        """gam_op_rnnt_beam: the beam kernel alone on a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with this
+        engine's predictor and joint weights.  The flag word is 0."""
+        encp = self._dev(encp, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, jh = encp.shape
+        if jh != self.cfg.joint_hidden:
+            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        with torch.cuda.device(self.device):
+            out = self._rnnt_beam_out(b, tp, beam_size, max_symbols)
+            rc = self.lib.gam_op_rnnt_beam(self._h, _ptr(encp), _ptr(enc_len), b, tp, int(beam_size), int(max_symbols), _ptr(out.ids),
+                                           _ptr(out.frames), _ptr(out.counts), _ptr(out.score), _ptr(out.logp), self._stream())
+            self._check(rc, "gam_op_rnnt_beam")
             out.ext[b:].zero_()
             st = torch.cuda.current_stream(self.device)
             out.event, out.stream = torch.cuda.Event(), st
