@@ -1846,8 +1846,9 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
   return launch_single(0);
 }
 
-// RNN-T beam search over the encoder projection encp [B, Tp, JH] (gam_rnnt_beam.h): one workgroup per utterance.  Decode class (the
-// caller holds a DecodeScope): the state slots, logit rows and prefix-trie nodes are the handle's.
+// RNN-T beam search over the encoder projection encp [B, Tp, JH] (gam_rnnt_beam.h): one workgroup per utterance; with the handle's LM
+// (gam_set_lm) gam_rnnt_beam_kernel<true>.  Decode class (the caller holds a DecodeScope): the state slots, logit rows and prefix-trie
+// nodes are the handle's.
 static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols,
                             int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s) {
   const gam_config& c = h->cfg;
@@ -1863,11 +1864,16 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
   if (!encp || !enc_len || !ids || !frames || !counts || !score || !logp) return fail(h, -1, "RNN-T beam search: NULL buffer");
   if (h->hw_trie && h->hw_max_tok > V - 2)
     return fail(h, -1, "RNN-T beam search: hotword token id %d outside [0, %d] for V=%d", h->hw_max_tok, V - 2, V);
+  const bool lm = h->lm_ng != nullptr;
+  if (lm && h->lm_V != V)
+    return fail(h, -1, "RNN-T beam search: the LM's token classes are for V=%d, the model has V=%d", h->lm_V, V);
   const int K = std::min(W, V - 1);
-  const size_t base = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, 0);
-  if (base > 160 * 1024) return fail(h, -1, "RNN-T beam search: W=%d, S=%d, H=%d, L=%d need %zu bytes of LDS (> 160 KiB)", W, max_symbols, H, L, base);
+  const size_t base = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, 0, lm ? V : 0);
+  if (base > 160 * 1024)
+    return fail(h, -1, "RNN-T beam search: W=%d, S=%d, H=%d, L=%d%s need %zu bytes of LDS (> 160 KiB)", W, max_symbols, H, L,
+                lm ? " with the LM" : "", base);
   const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX && base + (size_t)h->hw_words * 4 <= 160 * 1024;
-  const size_t sm = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, hw_lds ? h->hw_words : 0);
+  const size_t sm = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, hw_lds ? h->hw_words : 0, lm ? V : 0);
   const size_t per = (gam_rb_ws_floats(W, max_symbols, V, H, JH, L) + 63) & ~(size_t)63;
   if (int r = ensure(h, h->rb_ws, per * B + 64)) return r;
   if (int r = ensure(h, h->rb_nodes, (size_t)B * Tp * max_symbols * W * 2 + 64)) return r;
@@ -1880,10 +1886,18 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
   a.ws = h->rb_ws.p; a.ws_stride = per;
   a.nodes = reinterpret_cast<int2*>(h->rb_nodes.p);
   a.ids = ids; a.frames = frames; a.cap = (int)Tp * max_symbols; a.counts = counts; a.score = score; a.logp = logp;
-  static std::atomic<unsigned long long> lds_set;
-  HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_beam_kernel), 160 * 1024, lds_set));
+  a.lm_cls = h->lm_cls;
+  a.lm_wt = reinterpret_cast<const uint4*>(h->lm_wt);
+  a.lm_ng = reinterpret_cast<const uint4*>(h->lm_ng);
+  a.lm_wmask = h->lm_wslots - 1; a.lm_wprobe = h->lm_wprobe; a.lm_nmask = h->lm_nslots - 1; a.lm_nprobe = h->lm_nprobe;
+  a.lm_m = h->lm_order - 1; a.lm_bos = h->lm_bos; a.lm_eos = h->lm_eos; a.lm_unk = h->lm_unk;
+  a.lm_unk_logp = h->lm_unk_logp; a.lm_alpha = h->lm_alpha; a.lm_beta = h->lm_beta;
+  static std::atomic<unsigned long long> lds_set, lds_set_lm;
+  const void* kern = lm ? (const void*)gam_rnnt_beam_kernel<true> : (const void*)gam_rnnt_beam_kernel<false>;
+  HIPCHK(h, gam_set_max_lds(kern, 160 * 1024, lm ? lds_set_lm : lds_set));
   ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * ((double)V * JH + 4.0 * H * H) * 4.0);
-  hipLaunchKernelGGL(gam_rnnt_beam_kernel, dim3(B), dim3(GAM_RB_NT), sm, s, a);
+  if (lm) hipLaunchKernelGGL(gam_rnnt_beam_kernel<true>, dim3(B), dim3(GAM_RB_NT), sm, s, a);
+  else hipLaunchKernelGGL(gam_rnnt_beam_kernel<false>, dim3(B), dim3(GAM_RB_NT), sm, s, a);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -245,8 +245,10 @@ __device__ __forceinline__ unsigned gam_lm_probe(const uint4* t0, int m0, const 
 }
 
 // ln P(w | s) by ARPA back-off, s = (s.x most recent, s.y, s.z, s.w), -1 = no word; the first lm_m of them are the context.  With
-// `word`, w is the word table's id for spelling hash wh (lm_unk when it has none).  Returns ln P and sets w.
-__device__ __forceinline__ float gam_lm_query(const GamBeamArgs& a, bool word, unsigned long long wh, int& w, int4 s4) {
+// `word`, w is the word table's id for spelling hash wh (lm_unk when it has none).  Returns ln P and sets w.  Args: any argument
+// struct with the lm_* fields of GamBeamArgs (GamBeamArgs, GamRnntBeamArgs of gam_rnnt_beam.h).
+template <class Args>
+__device__ __forceinline__ float gam_lm_query(const Args& a, bool word, unsigned long long wh, int& w, int4 s4) {
   constexpr int NQ = GAM_BEAM_LM_MAX_ORDER;
   const int m = a.lm_m;
   const int s[4] = {s4.x, s4.y, s4.z, s4.w};

@@ -40,6 +40,24 @@
 // Arithmetic: exact fp32 (MFMA f32, expf / logf), no fp16 terms.  Every row's sums run in the same order whatever its position, so
 // one y always gets bit-identical predictor outputs.  Renormalisation: each frame subtracts the best kept rank from the scores and adds
 // it to an fp64 offset.  Limits (host errors beyond them): W <= 32, S <= 16, T' <= 8192, V <= 1025, H and JH <= 512 (multiples of 16).
+//
+// Word n-gram LM (template <bool LM>; gam_rnnt_beam_kernel<false> is the kernel without it, unchanged; tests/rnnt_lm_ref.py is the
+// float64 reference).  The word rules of gam_beam.h, applied to hypotheses: token classes from gam_set_lm (0 continues the current
+// word, 1 starts a new word, 2 separates; blank is class 0 and never extends y).  A hypothesis carries the spelling hash of its
+// partial word (0 = empty), its last order - 1 completed word ids (<s> at the start) and lm, the LM term so far.
+//   rank = score + committed + acc + lm.
+//   An extension a.y + v with class(v) in {1, 2} whose a has a non-empty partial word completes that word: it adds
+//   d(a) = alpha ln P(w | state) + beta and w enters the state; class 0 appends v to the partial word, class 1 starts the partial
+//   word [v], class 2 leaves it empty.  Blank candidates and the forced advance at s = S leave the LM state as it is.
+//   Equal y means equal LM state, so the merge in B is unchanged (it keeps the first contributor's state).  The theta cut and every
+//   top-W selection use this rank.
+//   Final pick: the last partial word is completed, then alpha ln P(</s> | state) is added: best score + committed + lm.
+//   score = log p + committed + lm (final); logp is unchanged.  Renormalisation subtracts the best rank minus its lm.
+//   With alpha = beta = 0 every lm and d is +0, so ids, frames, score and logp are bit-identical to the kernel without the LM.
+// Cost: one LM query per NEW hypothesis, not per candidate: d(a) and w's id depend on a alone, so wave 0 queries them for every entry
+// of A_{s+1} whose partial word is non-empty, right after its top-W selection, and the next joint phase only adds d to the
+// extensions by class-1/2 tokens (the split of gam_beam.h).  The LM state of the A lists and of B (36 B per entry) and the class
+// table [V] i8 lie in LDS after the union region (gam_rb_lm_bytes): 22.4 KiB at W = 32, S = 16, V = 1025.
 #pragma once
 #include "gam_beam.h"
 
@@ -73,13 +91,22 @@ struct GamRnntBeamArgs {
   int* counts;           // [B]
   float* score;          // [B]
   float* logp;           // [B]
+  // the n-gram LM (gam_rnnt_beam_kernel<true> only; the fields and meanings of GamBeamArgs, read by gam_lm_query)
+  const int* lm_cls;     // [V] token classes
+  const uint4* lm_wt;    // word table slots
+  const uint4* lm_ng;    // n-gram table slots
+  int lm_wmask, lm_wprobe, lm_nmask, lm_nprobe;   // slots - 1, longest probe chain
+  int lm_m, lm_bos, lm_eos, lm_unk;               // order - 1, word ids
+  float lm_unk_logp, lm_alpha, lm_beta;
 };
 
 // LDS carve (host and device), in bytes, in this order: A lists [2][32] (hash u64; len, score, hotword node, acc, committed, prefix
 // node, slot, token, parent slot: i32 / f32), row blank log-probs [32], counters [16], B list [P] (hash u64; len, score, best
 // contributor score, key, slot, node, hotword node, acc, committed), free list [P], slot mask [(P + 31) / 32], then from a 16-byte
 // boundary the union region U (joint rows z [Wp][JH + 4] | candidates [W K] (key u64; score, acc, committed, hotword node) | hidden
-// rows [1 or 2][Wp][H + 4]), then the hotword trie when it lies in LDS.
+// rows [1 or 2][Wp][H + 4]), then with the LM (gam_rb_lm_bytes) the LM state of the A lists [2][32] and of the B list [P] (index
+// buf * 32 + i and 64 + i: word state int4, partial-word hash u64, lm, d, completed word id) and the classes [V] i8, then the hotword
+// trie when it lies in LDS.
 __host__ __device__ static inline size_t gam_rb_pool(int W, int S) { return (size_t)(S + 1) * W; }
 __host__ __device__ static inline size_t gam_rb_fixed_bytes(int W, int S) {
   const size_t P = gam_rb_pool(W, S);
@@ -95,8 +122,14 @@ __host__ __device__ static inline size_t gam_rb_union_bytes(int W, int K, int H,
   u = u > hb ? u : hb;
   return (u + 15) & ~(size_t)15;
 }
-static inline size_t gam_rb_lds_bytes(int W, int K, int S, int H, int JH, int L, int hw_lds_words) {
-  return gam_rb_fixed_bytes(W, S) + gam_rb_union_bytes(W, K, H, JH, L) + (size_t)hw_lds_words * 4;
+__host__ __device__ static inline size_t gam_rb_lm_bytes(int W, int S, int V) {
+  const size_t n = 64 + gam_rb_pool(W, S);
+  return (n * (16 + 8 + 3 * 4) + (size_t)V + 15) & ~(size_t)15;
+}
+// lm_V: the class table's V with the LM, 0 without
+static inline size_t gam_rb_lds_bytes(int W, int K, int S, int H, int JH, int L, int hw_lds_words, int lm_V = 0) {
+  return gam_rb_fixed_bytes(W, S) + gam_rb_union_bytes(W, K, H, JH, L) + (lm_V > 0 ? gam_rb_lm_bytes(W, S, lm_V) : 0) +
+         (size_t)hw_lds_words * 4;
 }
 // floats of one utterance's global workspace: the state slots and the logit rows
 static inline size_t gam_rb_ws_floats(int W, int S, int V, int H, int JH, int L) {
@@ -134,16 +167,17 @@ __device__ __forceinline__ void gam_rb_gates_mm(f32x4 (&acc)[4][2], const float*
   }
 }
 
-template <int RT>
-__device__ void gam_rb_body(const GamRnntBeamArgs& a);
+template <int RT, bool LM>
+__device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a);
 
+template <bool LM>
 __global__ __launch_bounds__(GAM_RB_NT) void gam_rnnt_beam_kernel(GamRnntBeamArgs a) {
-  if (a.W > 16) gam_rb_body<2>(a);
-  else gam_rb_body<1>(a);
+  if (a.W > 16) gam_rb_body<2, LM>(a);
+  else gam_rb_body<1, LM>(a);
 }
 
-template <int RT>
-__device__ void gam_rb_body(const GamRnntBeamArgs& a) {
+template <int RT, bool LM>
+__device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
   extern __shared__ uint4 gam_smem_rbeam[];
   unsigned char* p = reinterpret_cast<unsigned char*>(gam_smem_rbeam);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -191,7 +225,25 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
   int* chn = reinterpret_cast<int*>(ccb + NC);
   float* hx = reinterpret_cast<float*>(U);                       // [Wp][H + 4]: the layer's input x (layers above the first)
   float* hr = L > 1 ? hx + (size_t)Wp * (H + 4) : hx;            // [Wp][H + 4]: the recurrent h (and g for W_pred)
-  int* hw_sh = reinterpret_cast<int*>(U + gam_rb_union_bytes(W, K, H, JH, L));
+  size_t hw_off = gam_rb_union_bytes(W, K, H, JH, L);
+  // the LM's carve: word state, partial-word hash, lm, d, completed word id [64 + P] (A lists at buf * 32 + i, B at 64 + i), classes
+  int4* mctx = nullptr;
+  unsigned long long* mwh = nullptr;
+  float *mlm = nullptr, *mdl = nullptr;
+  int* mcw = nullptr;
+  signed char* cls_sh = nullptr;
+  if constexpr (LM) {
+    p = U + hw_off;
+    const size_t n = 64 + (size_t)P;
+    mctx = reinterpret_cast<int4*>(take(n * 16));
+    mwh = reinterpret_cast<unsigned long long*>(take(n * 8));
+    mlm = reinterpret_cast<float*>(take(n * 4));
+    mdl = reinterpret_cast<float*>(take(n * 4));
+    mcw = reinterpret_cast<int*>(take(n * 4));
+    cls_sh = reinterpret_cast<signed char*>(p);
+    hw_off += gam_rb_lm_bytes(W, S, V);
+  }
+  int* hw_sh = reinterpret_cast<int*>(U + hw_off);
 
   int T = a.enc_len[b];
   T = T < 0 ? 0 : (T > Tp ? Tp : T);
@@ -322,16 +374,27 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
   };
 
   // ---- the empty hypothesis: predict(None, None) into slot 0
+  if constexpr (LM)
+    for (int v = tid; v < V; v += GAM_RB_NT) cls_sh[v] = (signed char)a.lm_cls[v];
   if (tid == 0) {
     ah[0] = 0ull; alen[0] = 0; asc[0] = 0.f; ahn[0] = 0; aacc[0] = 0.f; acb[0] = 0.f; anode[0] = -1;
     aslot[0] = 0; atok[0] = V; apar[0] = -1;
     cnt[0] = 1;
+    if constexpr (LM) {   // an empty partial word, the state <s>, lm 0
+      mctx[0] = make_int4(a.lm_m > 0 ? a.lm_bos : -1, -1, -1, -1);
+      mwh[0] = 0ull; mlm[0] = 0.f; mdl[0] = 0.f; mcw[0] = -1;
+    }
   }
   __syncthreads();
   predict(0, 1);
   if (wave == 0) rebuild_free(1);
   __syncthreads();
 
+  auto brank = [&](int i) {   // rank of B entry i
+    float r = bsc[i] + (bcb[i] + bacc[i]);
+    if constexpr (LM) r += mlm[64 + i];
+    return r;
+  };
   double off = 0.0;        // wave 0: what the renormalisations subtracted so far
   int ncount = 0;          // wave 0: prefix-trie nodes of this utterance so far
   for (int t = 0; t < T; ++t) {
@@ -416,7 +479,12 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
             int hn = ahn[o];
             float acc = aacc[o], cb = acb[o];
             if (hw != nullptr) gam_beam_hw_step(hw, a.hw_nodes, a.beta, v, hn, acc, cb);
-            const float rank = sc + (cb + acc);
+            float rank = sc + (cb + acc);
+            if constexpr (LM) {   // a's lm, plus d(a) when v completes a's partial word
+              float lmv = mlm[o];
+              if (cls_sh[v] != 0 && mwh[o] != 0ull) lmv += mdl[o];
+              rank += lmv;
+            }
             const int q = r * K + lane;
             const int key = r * GAM_BEAM_KEY_STRIDE + v + 1;
             ckey[q] = rank > -INFINITY ? (((unsigned long long)gam_beam_ord(rank) << 32) | ((unsigned)(0xffff - key) << 16) | (unsigned)q) : 0ull;
@@ -454,6 +522,9 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
             const int d = nB + __popcll(m & ((1ull << lane) - 1ull));
             bh[d] = h; blen[d] = len; bsc[d] = sc; bcs[d] = sc; bkey[d] = s * 32 + lane;
             bslot[d] = aslot[o]; bnode[d] = anode[o]; bhn[d] = ahn[o]; bacc[d] = aacc[o]; bcb[d] = acb[o];
+            if constexpr (LM) {
+              mctx[64 + d] = mctx[o]; mwh[64 + d] = mwh[o]; mlm[64 + d] = mlm[o]; mdl[64 + d] = mdl[o]; mcw[64 + d] = mcw[o];
+            }
           }
           nB += __popcll(m);
         }
@@ -467,7 +538,7 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
 #pragma unroll
             for (int j = 0; j < GAM_BEAM_RPL; ++j) {
               const int i = lane + 64 * j;
-              k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(bsc[i] + (bcb[i] + bacc[i])) << 32) |
+              k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(brank(i)) << 32) |
                                            ((unsigned)(0xffff - bkey[i]) << 16) | (unsigned)i)
                                         : 0ull;
             }
@@ -500,6 +571,20 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
             aslot[d] = freel[fptr + lane];
             atok[d] = v;
             apar[d] = aslot[o];
+            if constexpr (LM) {   // the new entry's LM state; a non-empty partial word queries d and its word id
+              const unsigned long long wh = mwh[o];
+              const int4 cx = mctx[o];
+              const int cl = cls_sh[v];
+              const bool done = cl != 0 && wh != 0ull;      // v completes a's partial word
+              const int4 ncx = done ? make_int4(mcw[o], cx.x, cx.y, cx.z) : cx;
+              const unsigned long long nwh =
+                  cl == 0 ? wh * GAM_BEAM_HASH_P + (unsigned long long)(v + 1) : (cl == 1 ? (unsigned long long)(v + 1) : 0ull);
+              int w = -1;
+              float dl = 0.f;
+              if (nwh != 0ull) dl = a.lm_alpha * gam_lm_query(a, true, nwh, w, ncx) + a.lm_beta;
+              mlm[d] = done ? mlm[o] + mdl[o] : mlm[o];
+              mctx[d] = ncx; mwh[d] = nwh; mdl[d] = dl; mcw[d] = w;
+            }
           }
           ncount += ns;
           fptr += ns;
@@ -518,20 +603,24 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
 #pragma unroll
       for (int j = 0; j < GAM_BEAM_RPL; ++j) {
         const int i = lane + 64 * j;
-        k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(bsc[i] + (bcb[i] + bacc[i])) << 32) |
+        k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(brank(i)) << 32) |
                                      ((unsigned)(0xffff - bkey[i]) << 16) | (unsigned)i)
                                   : 0ull;
       }
       unsigned long long sel;
       const int nb = gam_beam_wave_topn(k, nr, W, lane, sel);
       if (nb > 0) {
-        const float M = gam_beam_unord((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), 0));
+        float M = gam_beam_unord((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), 0));
+        if constexpr (LM) M -= mlm[64 + __builtin_amdgcn_readlane((int)(sel & 0xffff), 0)];     // (scores keep O(one frame))
         off += (double)M;
         if (lane < nb) {
           const int i = (int)(sel & 0xffff);
           ah[lane] = bh[i]; alen[lane] = blen[i]; asc[lane] = bsc[i] - M;
           ahn[lane] = bhn[i]; aacc[lane] = bacc[i]; acb[lane] = bcb[i];
           anode[lane] = bnode[i]; aslot[lane] = bslot[i];
+          if constexpr (LM) {
+            mctx[lane] = mctx[64 + i]; mwh[lane] = mwh[64 + i]; mlm[lane] = mlm[64 + i]; mdl[lane] = mdl[64 + i]; mcw[lane] = mcw[64 + i];
+          }
         }
       }
       if (lane == 0) cnt[0] = nb;
@@ -542,10 +631,24 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
     if (cnt[0] == 0) break;      // (every candidate -inf: cannot happen with finite log-probs)
   }
 
-  // ---- final pick (pending hotword bonus dropped), backtrack
+  // ---- final pick (pending hotword bonus dropped; with the LM the last word and </s> added), backtrack
   if (wave == 0) {
     const int nb = cnt[0];
-    const float val = lane < nb ? asc[lane] + acb[lane] : -INFINITY;
+    float val = lane < nb ? asc[lane] + acb[lane] : -INFINITY;
+    float lmf = 0.f;
+    if constexpr (LM) {
+      if (lane < nb) {
+        int4 cx = mctx[lane];
+        lmf = mlm[lane];
+        if (mwh[lane] != 0ull) {
+          lmf += mdl[lane];
+          cx = make_int4(mcw[lane], cx.x, cx.y, cx.z);
+        }
+        int w = a.lm_eos;
+        lmf += a.lm_alpha * gam_lm_query(a, false, 0ull, w, cx);
+        val += lmf;
+      }
+    }
     const unsigned long long key = lane < nb ? (((unsigned long long)gam_beam_ord(val) << 32) | (unsigned)(0xffff - lane)) : 0ull;
     const unsigned long long m = gam_beam_wave_max(key);
     const int best = m ? 0xffff - (int)(m & 0xffff) : -1;
@@ -558,7 +661,8 @@ __device__ void gam_rb_body(const GamRnntBeamArgs& a) {
     } else if (lane == best) {
       const double lp_ = (double)asc[lane] + off;
       a.logp[b] = (float)lp_;
-      a.score[b] = (float)(lp_ + (double)acb[lane]);
+      if constexpr (LM) a.score[b] = (float)(lp_ + (double)acb[lane] + (double)lmf);
+      else a.score[b] = (float)(lp_ + (double)acb[lane]);
       const int n = alen[lane] < a.cap ? alen[lane] : a.cap;
       a.counts[b] = n;
       int* ids = a.ids + (size_t)b * a.cap;

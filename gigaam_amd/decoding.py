@@ -198,13 +198,16 @@ class RNNTGreedyDecoding:
 
 
 class RNNTBeamDecoding(RNNTGreedyDecoding):
-    """RNN-T beam search with hotword boosting (gam_rnnt_beam; the contract is in gigaam_amd/csrc/gam_rnnt_beam.h).  A ``cfg.decoding``
-    target like the greedy one, so a config naming ``gigaam.decoding.RNNTBeamDecoding`` loads a model that decodes by beam, and
-    ``GigaAMASR.set_decoding`` switches to it.  ``beam_size`` 1..32; ``hotwords`` (strings in the vocabulary -- ``Tokenizer.encode``
-    -- or token ids) bias the search toward those phrases, ``hotword_boost`` per matched token.  ``max_symbols_per_step`` 1..16."""
+    """RNN-T beam search with hotword boosting and word n-gram LM fusion (gam_rnnt_beam; the contract is in
+    gigaam_amd/csrc/gam_rnnt_beam.h).  A ``cfg.decoding`` target like the greedy one, so a config naming
+    ``gigaam.decoding.RNNTBeamDecoding`` loads a model that decodes by beam, and ``GigaAMASR.set_decoding`` switches to it.
+    ``beam_size`` 1..32; ``hotwords`` (strings in the vocabulary -- ``Tokenizer.encode`` -- or token ids) bias the search toward those
+    phrases, ``hotword_boost`` per matched token.  ``lm`` (an ``lm.NgramLM`` or a path to an ARPA / ``.arpa.gz`` / ``.npz`` file)
+    adds ``lm_weight`` * ln P(word | history) + ``word_bonus`` per completed word, and ln P(</s> | history) at the end.
+    ``max_symbols_per_step`` 1..16."""
 
     def __init__(self, vocabulary: List[str], model_path: Optional[str] = None, max_symbols_per_step: int = 10, beam_size: int = 4,
-                 hotwords=None, hotword_boost: float = 2.0):
+                 hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0):
         super().__init__(vocabulary, model_path, max_symbols_per_step)
         if not 1 <= int(beam_size) <= 32:
             raise ValueError(f"beam_size {beam_size} outside [1, 32]")
@@ -213,8 +216,15 @@ class RNNTBeamDecoding(RNNTGreedyDecoding):
         self.beam_size = int(beam_size)
         self.hotwords = list(hotwords) if hotwords else []
         self.hotword_boost = float(hotword_boost)
+        self.set_lm(lm, lm_weight, word_bonus)
 
     hotword_ids = CTCGreedyDecoding.hotword_ids
+    language_model = CTCGreedyDecoding.language_model
+
+    def set_lm(self, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0) -> None:
+        """The LM of every later search (None: none); a path is read here, once."""
+        self.lm = self.language_model(lm)
+        self.lm_weight, self.word_bonus = float(lm_weight), float(word_bonus)
 
     @torch.inference_mode()
     def decode_device(self, head: RNNTHead, encoded: Tensor, enc_len: Tensor, overlap: bool = False, beam_size: Optional[int] = None,
@@ -222,17 +232,20 @@ class RNNTBeamDecoding(RNNTGreedyDecoding):
         """The device half of ``decode``: an ``engine.BeamDecoded``, no host sync; ``finish`` takes it as it takes a greedy decode.
         ``overlap`` is accepted for signature symmetry and ignored: the search runs on the current stream (the side-stream overlap of
         the greedy decode relies on its small clusters).  ``beam_size`` / ``hotwords`` / ``hotword_boost`` override this object's
-        settings for one call; the hotword set is uploaded only when it differs from the one the engine holds."""
+        settings for one call; the hotword set and the LM (this object's, or none) are uploaded only when they differ from the ones
+        the engine holds."""
         hw = self.hotwords if hotwords is None else hotwords
         boost = self.hotword_boost if hotword_boost is None else hotword_boost
         head.engine.set_hotwords(self.hotword_ids(hw), boost)
+        head.engine.set_lm(self.lm, self.tokenizer, self.lm_weight, self.word_bonus)
         return head.engine.rnnt_beam(encoded, enc_len, self.beam_size if beam_size is None else beam_size, self.max_symbols)
 
     @torch.inference_mode()
     def decode_beam(self, head: RNNTHead, encoded: Tensor, enc_len: Tensor, beam_size: Optional[int] = None, hotwords=None,
                     hotword_boost: Optional[float] = None) -> List[Tuple[str, List[int], List[int], float, float]]:
         """Beam search decode -> per utterance ``(text, ids, frames, score, logp)``: ``frames`` the frame at which each token was
-        emitted, ``score`` log p + committed hotword bonus, ``logp`` log p summed over the alignments the beam merged.  Per-call
+        emitted, ``score`` log p + committed hotword bonus + LM term (every word and </s>), ``logp`` log p summed over the
+        alignments the beam merged.  Per-call
         ``beam_size`` / ``hotwords`` / ``hotword_boost`` default to this object's.  ONE D2H copy; raises ``RangeOverflow`` like
         ``finish``."""
         h = self.decode_device(head, encoded, enc_len, beam_size=beam_size, hotwords=hotwords, hotword_boost=hotword_boost).host()

@@ -577,8 +577,8 @@ class HipEngine:
 
     def rnnt_beam(self, encoded: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int) -> BeamDecoded:
         """RNN-T beam search (gam_rnnt_beam): the encoder projection GEMM and the beam kernel, no host sync; the hotword set of
-        ``set_hotwords`` applies.  ids / frames are [B, T' * max_symbols].  The split-fp16 range flag is CONSUMED as ``rnnt_greedy``
-        does: it lands in the flag word."""
+        ``set_hotwords`` and the LM of ``set_lm`` apply.  ids / frames are [B, T' * max_symbols].  The split-fp16 range flag is
+        CONSUMED as ``rnnt_greedy`` does: it lands in the flag word."""
         encoded = self._dev(encoded, torch.float32)
         enc_len = self._dev(enc_len, torch.int32)
         b, _, tp = encoded.shape
@@ -592,7 +592,7 @@ class HipEngine:
 
     def op_rnnt_beam(self, encp: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int) -> BeamDecoded:
         """gam_op_rnnt_beam: the beam kernel alone on a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with this
-        engine's predictor and joint weights.  The flag word is 0."""
+        engine's predictor and joint weights (and the hotwords / LM set on it).  The flag word is 0."""
         encp = self._dev(encp, torch.float32)
         enc_len = self._dev(enc_len, torch.int32)
         b, tp, jh = encp.shape

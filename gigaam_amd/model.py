@@ -273,18 +273,20 @@ class GigaAMASR(GigaAM):
         return self._with_words(self.decoding.decode(self.head, encoded, encoded_len), wav_lens, encoded_len, word_timestamps)
 
     def set_decoding(self, beam_size: Optional[int] = None, hotwords: Optional[Sequence[Union[str, List[int]]]] = None,
-                     hotword_boost: float = 2.0) -> None:
+                     hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0) -> None:
         """RNN-T models: switch the decoding object (``cfg.decoding``'s role; NeMo's ``change_decoding_strategy``).  ``beam_size``
-        (1..32) and / or ``hotwords`` (strings in the vocabulary or token ids; alone they mean ``beam_size=4``) select
-        ``decoding.RNNTBeamDecoding``; with neither, ``RNNTGreedyDecoding`` again.  The vocabulary and ``max_symbols_per_step`` stay.
-        Every transcribe path then decodes that way.  CTC heads take the beam options per call instead (TypeError here)."""
+        (1..32), ``hotwords`` (strings in the vocabulary or token ids) and / or ``lm`` (an ``NgramLM`` or a path to an ARPA / ``.npz``
+        file: ``lm_weight`` * ln P(word | history) + ``word_bonus`` per word) select ``decoding.RNNTBeamDecoding``; hotwords or an LM
+        alone mean ``beam_size=4``.  With none of them, ``RNNTGreedyDecoding`` again.  The vocabulary and ``max_symbols_per_step``
+        stay.  Every transcribe path then decodes that way (each longform segment starts its LM history at <s>).  CTC heads take
+        the beam options per call instead (TypeError here)."""
         dec = self.decoding
         if not isinstance(dec, _decoding.RNNTGreedyDecoding):
             raise TypeError("set_decoding is for RNN-T heads; CTC heads take beam_size / hotwords per call")
         if beam_size is not None and not 1 <= int(beam_size) <= 32:
             raise ValueError(f"beam_size {beam_size} outside [1, 32]")
         new = _decoding.RNNTGreedyDecoding.__new__(
-            _decoding.RNNTGreedyDecoding if beam_size is None and hotwords is None else _decoding.RNNTBeamDecoding)
+            _decoding.RNNTGreedyDecoding if beam_size is None and hotwords is None and lm is None else _decoding.RNNTBeamDecoding)
         new.tokenizer, new.blank_id, new.max_symbols = dec.tokenizer, dec.blank_id, dec.max_symbols
         if isinstance(new, _decoding.RNNTBeamDecoding):
             if not 1 <= new.max_symbols <= 16:
@@ -292,6 +294,7 @@ class GigaAMASR(GigaAM):
             new.beam_size = 4 if beam_size is None else int(beam_size)
             new.hotwords = list(hotwords) if hotwords else []
             new.hotword_boost = float(hotword_boost)
+            new.set_lm(lm, lm_weight, word_bonus)
         self.decoding = new
 
     # ---- the launch / collect pair every transcribe path is built from (public: a driver -- bench.py, shard.run_sharded,

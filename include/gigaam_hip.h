@@ -14,7 +14,7 @@
  *   gam_ctc_align    (no reference counterpart: CTC forced alignment + log-likelihood of a given transcript)
  *   gam_ctc_beam     (no reference counterpart: CTC prefix beam search with hotword boosting and n-gram LM fusion)
  *   gam_rnnt_greedy  <- RNNTGreedyDecoding.decode         gigaam/decoding.py:128-207
- *   gam_rnnt_beam    (no reference counterpart: RNN-T beam search with hotword boosting)
+ *   gam_rnnt_beam    (no reference counterpart: RNN-T beam search with hotword boosting and n-gram LM fusion)
  *                        (+ RNNTDecoder.predict decoder.py:85-102, RNNTJoint.joint :41-47)
  *   gam_emo_probs    <- GigaAMEmo.get_probs (pool+head)    gigaam/model.py:272-285
  *   gam_set_weight   <- nn.Module.load_state_dict         gigaam/__init__.py:185
@@ -185,20 +185,25 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
                     int max_symbols, int32_t* ids, int32_t* frames, int32_t* counts,
                     float* logits_dump, int32_t* dump_count, int dump_cap, void* stream);
 
-/* RNN-T beam search with hotword boosting (gigaam_amd/csrc/gam_rnnt_beam.h holds the contract).  Runs the encoder projection GEMM
- * that gam_rnnt_greedy runs, then ONE beam kernel (a workgroup per utterance, t the sequential loop, backtrack in the same kernel).
- * Beam width 1 <= W <= 32; each joint row proposes its top min(W, V - 1) non-blank ids; at most max_symbols (1..16) tokens per frame,
- * then the frame advances without a joint (greedy's rule).  Ties follow a fixed rule, so the result is deterministic.  The hotword
- * set of gam_set_hotwords (shared with the CTC search) boosts the hypotheses that spell its phrases; an id >= V - 1 is an error here.
+/* RNN-T beam search with hotword boosting and n-gram LM fusion (gigaam_amd/csrc/gam_rnnt_beam.h holds the contract).  Runs the
+ * encoder projection GEMM that gam_rnnt_greedy runs, then ONE beam kernel (a workgroup per utterance, t the sequential loop,
+ * backtrack in the same kernel).  Beam width 1 <= W <= 32; each joint row proposes its top min(W, V - 1) non-blank ids; at most
+ * max_symbols (1..16) tokens per frame, then the frame advances without a joint (greedy's rule).  Ties follow a fixed rule, so the
+ * result is deterministic.  The hotword set of gam_set_hotwords (shared with the CTC search) boosts the hypotheses that spell its
+ * phrases; an id >= V - 1 is an error here.  The n-gram LM of gam_set_lm (if any; shared with the CTC search) adds
+ * weight * ln P(word | history) + word_bonus for every completed word, under the word rules of gam_ctc_beam; its token classes must
+ * be for the model's V (an error otherwise).
  *   ids / frames i32 [B, T' * max_symbols]: the best hypothesis's token ids and the frame at which each was emitted (greedy's
  *   meaning), counts i32 [B] of them.  score f32 [B]: its log p (summed over the alignments the beam merged) + its committed hotword
- *   bonus; logp f32 [B]: that log p alone.  enc_len[b] = 0 gives an empty result with score = logp = 0.
- * Limits: W <= 32, max_symbols <= 16, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512 (an error beyond them).  Decode
- * class, like gam_rnnt_greedy; no host synchronisation. */
+ *   bonus + its LM term (every word including the last, and weight * ln P(</s> | history)); logp f32 [B]: that log p alone.
+ *   enc_len[b] = 0 gives an empty result with score = logp = 0.
+ * Limits: W <= 32, max_symbols <= 16, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512, at most 160 KiB of LDS for the
+ * search state (an error beyond them; every W and max_symbols fits at pred_hidden = joint_hidden = 320 with or without the LM).
+ * Decode class, like gam_rnnt_greedy; no host synchronisation. */
 int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
                   int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
 /* The beam kernel alone on a caller-supplied encoder projection encp f32 [B, T', joint_hidden] (W_enc f + b_enc), with the handle's
- * predictor and joint weights. */
+ * predictor and joint weights, hotwords and LM. */
 int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
                      int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
 
