@@ -132,11 +132,11 @@ struct gam_handle {
   DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
   DevBuf beam_nodes;                    // CTC beam search prefix-trie nodes, B x T' x W (gam_beam.h)
   DevBuf rb_ws, rb_nodes;               // RNN-T beam search: predictor-state slots + logit rows, prefix-trie nodes (gam_rnnt_beam.h)
-  int* hw_trie = nullptr;               // hotword trie of gam_set_hotwords (CSR, gam_beam.h): offsets | edges; NULL = no hotwords
+  int* hw_trie = nullptr;               // hotword trie of gam_set_hotwords (CSR, gam_search.h): offsets | edges; NULL = no hotwords
   size_t hw_cap = 0;                    // ints allocated at hw_trie
   int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
   float hw_boost = 0.f;
-  // the n-gram LM of gam_set_lm (gam_beam.h): token classes [lm_V], word / n-gram table slots; lm_ng NULL = no LM
+  // the n-gram LM of gam_set_lm (gam_search.h): token classes [lm_V], word / n-gram table slots; lm_ng NULL = no LM
   int* lm_cls = nullptr;
   void *lm_wt = nullptr, *lm_ng = nullptr;
   int lm_V = 0, lm_wslots = 0, lm_wprobe = 0, lm_nslots = 0, lm_nprobe = 0, lm_order = 0, lm_bos = 0, lm_eos = 0, lm_unk = 0;
@@ -1494,41 +1494,64 @@ int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_l
                           status, s);
 }
 
-// CTC prefix beam search over log-probs [B, Tp, V] (gam_beam.h): one workgroup per utterance.  Decode class (the caller holds a
-// DecodeScope): the prefix-trie nodes are the handle's.
-static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
-                           int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s) {
-  if (B <= 0 || Tp <= 0 || V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "CTC beam search: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
-  if (Tp > GAM_ALIGN_MAX_T) return fail(h, -1, "CTC beam search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_ALIGN_MAX_T);
-  if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "CTC beam search: beam width W=%d outside [1, %d]", W, GAM_BEAM_MAX_W);
-  if (!lp || !enc_len || !ids || !frames || !counts || !score || !logp) return fail(h, -1, "CTC beam search: NULL buffer");
-  if (h->hw_trie && h->hw_max_tok > V - 2)
-    return fail(h, -1, "CTC beam search: hotword token id %d outside [0, %d] for V=%d", h->hw_max_tok, V - 2, V);
-  const int K = std::min(W, V - 1);
-  const bool lm = h->lm_ng != nullptr;
-  if (lm && h->lm_V != V) return fail(h, -1, "CTC beam search: the LM's token classes are for V=%d, the log-probs have V=%d", h->lm_V, V);
-  const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
-  const size_t sm = gam_beam_lds_bytes(W, K, V, hw_lds ? h->hw_words : 0, lm);
-  if (int r = ensure(h, h->beam_nodes, (size_t)B * Tp * W * 2 + 64)) return r;
-  GamBeamArgs a;
-  a.lp = lp; a.enc_len = enc_len; a.Tp = (int)Tp; a.V = V; a.W = W; a.K = K;
-  a.hw = h->hw_trie; a.hw_nodes = h->hw_nodes; a.hw_words = h->hw_words; a.hw_lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
-  a.nodes = reinterpret_cast<int2*>(h->beam_nodes.p);
-  a.ids = ids; a.frames = frames; a.counts = counts; a.score = score; a.logp = logp;
+// ---- what the two beam searches share (gam_search.h): the handle's hotwords and LM as kernel arguments, the common checks, the launch
+static GamHwArgs hw_args(const gam_handle* h, bool hw_lds) {
+  GamHwArgs a;
+  a.trie = h->hw_trie; a.nodes = h->hw_nodes; a.words = h->hw_words; a.lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
+  return a;
+}
+static GamLmArgs lm_args(const gam_handle* h) {
+  GamLmArgs a;
   a.lm_cls = h->lm_cls;
   a.lm_wt = reinterpret_cast<const uint4*>(h->lm_wt);
   a.lm_ng = reinterpret_cast<const uint4*>(h->lm_ng);
   a.lm_wmask = h->lm_wslots - 1; a.lm_wprobe = h->lm_wprobe; a.lm_nmask = h->lm_nslots - 1; a.lm_nprobe = h->lm_nprobe;
   a.lm_m = h->lm_order - 1; a.lm_bos = h->lm_bos; a.lm_eos = h->lm_eos; a.lm_unk = h->lm_unk;
   a.lm_unk_logp = h->lm_unk_logp; a.lm_alpha = h->lm_alpha; a.lm_beta = h->lm_beta;
-  static std::atomic<unsigned long long> lds_set, lds_set_lm;
-  const void* kern = lm ? (const void*)gam_ctc_beam_kernel<true> : (const void*)gam_ctc_beam_kernel<false>;
-  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds(kern, (int)sm, lm ? lds_set_lm : lds_set));
-  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * W * (K + 1) * 4.0);
-  if (lm) hipLaunchKernelGGL(gam_ctc_beam_kernel<true>, dim3(B), dim3(GAM_BEAM_NT), sm, s, a);
-  else hipLaunchKernelGGL(gam_ctc_beam_kernel<false>, dim3(B), dim3(GAM_BEAM_NT), sm, s, a);
-  HIPCHK(h, hipGetLastError());
+  return a;
+}
+// Width, buffers, and the handle's hotwords and LM against V.  `name` opens the messages; `lm_fmt` is the search's own LM message
+// (the LM's V, the search's V).
+static int beam_check(gam_handle* h, const char* name, int W, int V, bool null_buffer, const char* lm_fmt) {
+  if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "%s: beam width W=%d outside [1, %d]", name, W, GAM_BEAM_MAX_W);
+  if (null_buffer) return fail(h, -1, "%s: NULL buffer", name);
+  if (h->hw_trie && h->hw_max_tok > V - 2)
+    return fail(h, -1, "%s: hotword token id %d outside [0, %d] for V=%d", name, h->hw_max_tok, V - 2, V);
+  if (h->lm_ng && h->lm_V != V) return fail(h, -1, lm_fmt, h->lm_V, V);
   return 0;
+}
+// Launch one instantiation of a beam kernel; its LDS limit is raised once (`once`: one word per instantiation) when it needs > 64 KiB.
+static int beam_launch(gam_handle* h, const void* kern, std::atomic<unsigned long long>& once, size_t max_lds, int B, int nt, size_t sm,
+                       hipStream_t s, void* args) {
+  if (max_lds > 64 * 1024) HIPCHK(h, gam_set_max_lds(kern, (int)max_lds, once));
+  HIPCHK(h, hipLaunchKernel(kern, dim3(B), dim3(nt), &args, sm, s));
+  return 0;
+}
+
+// CTC prefix beam search over log-probs [B, Tp, V] (gam_beam.h): one workgroup per utterance.  Decode class (the caller holds a
+// DecodeScope): the prefix-trie nodes are the handle's.
+static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
+                           int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s) {
+  if (B <= 0 || Tp <= 0 || V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "CTC beam search: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
+  if (Tp > GAM_ALIGN_MAX_T) return fail(h, -1, "CTC beam search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_ALIGN_MAX_T);
+  if (int r = beam_check(h, "CTC beam search", W, V, !lp || !enc_len || !ids || !frames || !counts || !score || !logp,
+                         "CTC beam search: the LM's token classes are for V=%d, the log-probs have V=%d"))
+    return r;
+  const int K = std::min(W, V - 1);
+  const bool lm = h->lm_ng != nullptr;
+  const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
+  const size_t sm = gam_beam_lds_bytes(W, K, V, hw_lds ? h->hw_words : 0, lm);
+  if (int r = ensure(h, h->beam_nodes, (size_t)B * Tp * W * 2 + 64)) return r;
+  GamBeamArgs a;
+  a.lp = lp; a.enc_len = enc_len; a.Tp = (int)Tp; a.V = V; a.W = W; a.K = K;
+  a.hw = hw_args(h, hw_lds);
+  a.lm = lm_args(h);
+  a.nodes = reinterpret_cast<int2*>(h->beam_nodes.p);
+  a.ids = ids; a.frames = frames; a.counts = counts; a.score = score; a.logp = logp;
+  static std::atomic<unsigned long long> lds_set[2];
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * W * (K + 1) * 4.0);
+  return beam_launch(h, lm ? (const void*)gam_ctc_beam_kernel<true> : (const void*)gam_ctc_beam_kernel<false>, lds_set[lm], sm, B,
+                     GAM_BEAM_NT, sm, s, &a);
 }
 
 int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
@@ -1855,18 +1878,15 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
   const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden, L = c.pred_rnn_layers;
   if (B <= 0 || Tp <= 0) return fail(h, -1, "RNN-T beam search: bad shape B=%d T'=%lld", B, (long long)Tp);
   if (Tp > GAM_RB_MAX_T) return fail(h, -1, "RNN-T beam search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_RB_MAX_T);
-  if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "RNN-T beam search: beam width W=%d outside [1, %d]", W, GAM_BEAM_MAX_W);
   if (max_symbols < 1 || max_symbols > GAM_RB_MAX_S)
     return fail(h, -1, "RNN-T beam search: max_symbols S=%d outside [1, %d]", max_symbols, GAM_RB_MAX_S);
   if (V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "RNN-T beam search: V=%d outside [2, %d]", V, GAM_BEAM_MAX_V);
   if (H > GAM_RB_MAX_H || JH > GAM_RB_MAX_H || H % 16 != 0 || JH % 16 != 0)
     return fail(h, -1, "RNN-T beam search: H=%d / JH=%d must be multiples of 16 up to %d", H, JH, GAM_RB_MAX_H);
-  if (!encp || !enc_len || !ids || !frames || !counts || !score || !logp) return fail(h, -1, "RNN-T beam search: NULL buffer");
-  if (h->hw_trie && h->hw_max_tok > V - 2)
-    return fail(h, -1, "RNN-T beam search: hotword token id %d outside [0, %d] for V=%d", h->hw_max_tok, V - 2, V);
+  if (int r = beam_check(h, "RNN-T beam search", W, V, !encp || !enc_len || !ids || !frames || !counts || !score || !logp,
+                         "RNN-T beam search: the LM's token classes are for V=%d, the model has V=%d"))
+    return r;
   const bool lm = h->lm_ng != nullptr;
-  if (lm && h->lm_V != V)
-    return fail(h, -1, "RNN-T beam search: the LM's token classes are for V=%d, the model has V=%d", h->lm_V, V);
   const int K = std::min(W, V - 1);
   const size_t base = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, 0, lm ? V : 0);
   if (base > 160 * 1024)
@@ -1882,24 +1902,15 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
   a.encp = encp; a.enc_len = enc_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wpred_t = h->jn_pred_t; a.bpred = h->jn_pred_b;
   a.wout = h->jn_out_w; a.bout = h->jn_out_b; a.wih_x = h->lstm_wih_x; a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x;
   a.Tp = (int)Tp; a.V = V; a.H = H; a.JH = JH; a.L = L; a.W = W; a.K = K; a.S = max_symbols;
-  a.hw = h->hw_trie; a.hw_nodes = h->hw_nodes; a.hw_words = h->hw_words; a.hw_lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
+  a.hw = hw_args(h, hw_lds);
+  a.lm = lm_args(h);
   a.ws = h->rb_ws.p; a.ws_stride = per;
   a.nodes = reinterpret_cast<int2*>(h->rb_nodes.p);
   a.ids = ids; a.frames = frames; a.cap = (int)Tp * max_symbols; a.counts = counts; a.score = score; a.logp = logp;
-  a.lm_cls = h->lm_cls;
-  a.lm_wt = reinterpret_cast<const uint4*>(h->lm_wt);
-  a.lm_ng = reinterpret_cast<const uint4*>(h->lm_ng);
-  a.lm_wmask = h->lm_wslots - 1; a.lm_wprobe = h->lm_wprobe; a.lm_nmask = h->lm_nslots - 1; a.lm_nprobe = h->lm_nprobe;
-  a.lm_m = h->lm_order - 1; a.lm_bos = h->lm_bos; a.lm_eos = h->lm_eos; a.lm_unk = h->lm_unk;
-  a.lm_unk_logp = h->lm_unk_logp; a.lm_alpha = h->lm_alpha; a.lm_beta = h->lm_beta;
-  static std::atomic<unsigned long long> lds_set, lds_set_lm;
-  const void* kern = lm ? (const void*)gam_rnnt_beam_kernel<true> : (const void*)gam_rnnt_beam_kernel<false>;
-  HIPCHK(h, gam_set_max_lds(kern, 160 * 1024, lm ? lds_set_lm : lds_set));
+  static std::atomic<unsigned long long> lds_set[2];
   ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * ((double)V * JH + 4.0 * H * H) * 4.0);
-  if (lm) hipLaunchKernelGGL(gam_rnnt_beam_kernel<true>, dim3(B), dim3(GAM_RB_NT), sm, s, a);
-  else hipLaunchKernelGGL(gam_rnnt_beam_kernel<false>, dim3(B), dim3(GAM_RB_NT), sm, s, a);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return beam_launch(h, lm ? (const void*)gam_rnnt_beam_kernel<true> : (const void*)gam_rnnt_beam_kernel<false>, lds_set[lm], 160 * 1024, B,
+                     GAM_RB_NT, sm, s, &a);
 }
 
 int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,

@@ -13,12 +13,8 @@
 // beam is the top W by rank = (p_b (+) p_nb) + bonus; equal ranks go by the origin key (source entry's position, -1 for stay /
 // repeat else c) ascending, a merged prefix taking its smaller key.  Candidates of rank -inf are dropped.
 //
-// Hotwords: a trie of token-id phrases with one boost beta per matched token.  Only an extension by c moves an entry's state
-// (node, acc): to node's child for c (acc += beta; at a phrase end acc is committed and reset; the walk stays on the child if it has
-// children, else returns to the root), else the pending acc is rolled back and the walk restarts from the root's child for c.
-// There are no failure links: with the phrase "a a b", the text "a a a b" is not boosted -- the third "a" finds no child of "a a",
-// rolls back and restarts at "a", then "b" is no child of "a".  bonus = committed + acc; the state depends on y alone, so merged
-// candidates agree on it.  The final pick drops the pending acc: best (p_b (+) p_nb) + committed, ties to the lower beam position.
+// Hotwords: the rules and the trie of gam_search.h.  The final pick drops the pending acc: best (p_b (+) p_nb) + committed, ties to the
+// lower beam position.
 //
 // Shape: one workgroup of GAM_BEAM_NT threads per utterance, t the sequential loop, TWO barriers per frame:
 //   phase 1 (every thread)  one candidate per thread and step: stay / repeat of entry j (q = j (K + 1) + K) or the extension of
@@ -30,72 +26,40 @@
 //                            -- the child masks with which phase 1 finds merges.
 //           (wave 1)        the top K of frame t + 1 (the same wave maxima over the row, <= 17 values per lane), and the row
 //                            itself into LDS (blank and repeat terms); the row of frame t + 2 is loaded meanwhile.  -- barrier B
-// Prefix identity: (length, 64-bit polynomial hash h(y + c) = h(y) * P + c + 1).  A collision would merge two different prefixes;
-// it is accepted (2^-64 per compare) and the reference, with real tuples, cannot show one.
+// Prefix identity: (length, 64-bit hash), gam_search.h.
 // Precision: every frame subtracts the best kept rank from p_b / p_nb and adds it to an fp64 offset, so the stored values stay
 // O(one frame's log-probs); the log-add-exp runs on the hardware transcendentals (gam_align_exp / gam_align_log, ~1 ulp).
 // Prefix trie: only surviving extensions (and re-entries) create a node {parent, token << 13 | frame}, in a grow-only handle workspace of
 // B x T' x W nodes (at most W per frame).  The backtrack runs in the same kernel and writes ids / frames / count / score / logp.
-// Hotword trie: CSR -- offsets [n_nodes + 1], then edges (token | end << 11 | child << 12) sorted by token per node, searched by
-// binary search; copied to LDS when it fits (GAM_BEAM_HW_LDS_MAX bytes), else read from global memory (L2-resident).
-// Limits (host errors beyond them): W <= 32, T' <= GAM_ALIGN_MAX_T, V <= 1025, <= 1024 phrases, <= 16384 phrase tokens.
+// Limits (host errors beyond them): those of gam_search.h and T' <= GAM_ALIGN_MAX_T.
 //
-// Word n-gram LM (template <bool LM>; gam_ctc_beam_kernel<false> is the kernel without it, unchanged; tests/ctc_lm_ref.py is the
-// float64 reference, gigaam_amd/lm.py builds the tables).  Every token has a class: 0 continues the current word, 1 starts a new word
-// (a SentencePiece piece beginning with U+2581; the token belongs to the new word), 2 is a separator (the " " of a char-wise
-// vocabulary; it belongs to no word).  An entry's partial word is its token ids since the last class-1/2 token, identified by the
-// spelling hash wh = h(ids) (h as for prefixes, from 0; 0 = empty); its LM state is the word ids of its last order - 1 completed
-// words (<s> at the start).  An extension of y by a class-1/2 token completes y's partial word w when it is non-empty: the entry's
-// `lm` grows by alpha ln P(w | state) + beta and w enters the state.  P is ARPA back-off (natural log; a word outside the word table
-// is <unk>, which scores unk_logp when the ARPA has no <unk> unigram).  Partial words are not scored.  All of it depends on the prefix
-// alone, so merged candidates agree on it.  rank = (p_b (+) p_nb) + bonus + lm.  Final pick: the last partial word is completed, then
-// alpha ln P(</s> | state) is added: best (p_b (+) p_nb) + committed + lm.  score = log p + committed + lm; logp is unchanged.
-//   Cost: one LM query per NEW beam entry and frame, not per candidate -- the completion term d(y) = alpha ln P(w | state) + beta
-//   and w's id are the same whichever boundary token completes w, so wave 0 computes them in phase 2 for each new entry whose
-//   partial word changed (an extension; a stay keeps its entry's) and phase 1 only adds them.  A query is two rounds of global loads
-//   (the tables stay L2 / Infinity-Cache resident): the word (word table) together with the back-off weights of the state's suffixes
-//   (n-gram table; their keys are known before the word id), then the n-grams (suffix, w) of every order together.  Renormalisation
-//   subtracts the best rank minus its lm, so p_b / p_nb stay O(one frame) however large lm grows.
-// Tables: 16-byte slots {u64 key, 2 x 32 bit} (word table: word id; n-gram table: ln p, ln back-off as f32), open addressing,
-// linear probing, a power-of-two slot count < 2^30, load <= 0.5; key = mix64(h) (splitmix64 finaliser, 0 -> 1), 0 = free slot;
-// n-gram h = n, then h = h * P + (id + 1) per word, oldest first.  A probe reads at most the host's longest chain.  Full 64-bit keys
-// are compared: a collision is accepted (2^-64 per compare), as for prefixes.  Limits: order <= 5.
+// Word n-gram LM (template <bool LM>; gam_ctc_beam_kernel<false> is the kernel without it, unchanged; tests/ctc_beam_ref.py with an
+// LMSpec is the float64 reference).  The word rules, the cost split and the tables of gam_search.h, applied to prefixes:
+// rank = (p_b (+) p_nb) + bonus + lm.  Final pick: best (p_b (+) p_nb) + committed + lm with the last word and </s> added.
+// score = log p + committed + lm; logp is unchanged.  Wave 0 computes d and the word id in phase 2 for each new entry whose partial
+// word changed (an extension; a stay keeps its entry's) and phase 1 only adds them.  Renormalisation subtracts the best rank minus its
+// lm, so p_b / p_nb stay O(one frame) however large lm grows.
 #pragma once
-#include "gam_align.h"
+#include "gam_search.h"
 
-#define GAM_BEAM_MAX_W 32
-#define GAM_BEAM_MAX_V 1025
-#define GAM_BEAM_RPL 17                  // values per lane: ceil(max(1025, 32 * 33) / 64)
 #define GAM_BEAM_NT 256
-#define GAM_BEAM_MAX_PHRASES 1024
-#define GAM_BEAM_MAX_HW_TOKENS 16384
-#define GAM_BEAM_HW_LDS_MAX (64 * 1024)
-#define GAM_BEAM_KEY_STRIDE 1026         // origin key = source position * 1026 + (stay ? 0 : c + 1), < 2^16
-#define GAM_BEAM_HASH_P 0x100000001b3ull
 
 struct GamBeamArgs {
   const float* lp;       // [B, Tp, V] log-probs
   const int* enc_len;    // [B]
   int Tp, V, W, K;
-  const int* hw;         // hotword trie (NULL: none): offsets [hw_nodes + 1] | edges
-  int hw_nodes, hw_words, hw_lds;
-  float beta;
+  GamHwArgs hw;
   int2* nodes;           // [B, Tp * W] prefix-trie nodes
   int* ids;              // [B, Tp]
   int* frames;           // [B, Tp]
   int* counts;           // [B]
   float* score;          // [B]
   float* logp;           // [B]
-  // the n-gram LM (gam_ctc_beam_kernel<true> only)
-  const int* lm_cls;     // [V] token classes
-  const uint4* lm_wt;    // word table slots
-  const uint4* lm_ng;    // n-gram table slots
-  int lm_wmask, lm_wprobe, lm_nmask, lm_nprobe;   // slots - 1, longest probe chain
-  int lm_m, lm_bos, lm_eos, lm_unk;               // order - 1, word ids
-  float lm_unk_logp, lm_alpha, lm_beta;
+  GamLmArgs lm;
 };
-
-#define GAM_BEAM_LM_MAX_ORDER 5
+// (the kernel argument layout the fields had before the two blocks were structs of their own)
+static_assert(sizeof(GamBeamArgs) == 176 && offsetof(GamBeamArgs, hw) == 32 && offsetof(GamBeamArgs, nodes) == 56 &&
+              offsetof(GamBeamArgs, lm) == 104, "GamBeamArgs layout");
 
 // LDS carve (host and device): beam state [2][32] (hash, parent hash: u64; p_b, p_nb, acc, committed: f32; len, last, prefix node,
 // hotword node, parent, child mask: i32), top-K ids / values [2][32], beam sizes, candidate keys u64 [NC], candidate p_b, p_nb, acc,
@@ -110,189 +74,6 @@ static inline size_t gam_beam_lds_bytes(int W, int K, int V, int hw_lds_words, b
   const size_t base = gam_beam_lds_base(W, K, V, hw_lds_words);
   if (!lm) return base;
   return ((base + 15) & ~(size_t)15) + 2 * 32 * (8 + 16 + 3 * 4) + 2 * 32 * 4 + (((size_t)V + 3) & ~(size_t)3);
-}
-
-__device__ __forceinline__ float gam_beam_lse(float a, float b) {
-  const float m = fmaxf(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + gam_align_log(1.0f + gam_align_exp(fminf(a, b) - m));
-}
-__device__ __forceinline__ unsigned gam_beam_ord(float f) {     // float -> unsigned, order preserving
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float gam_beam_unord(unsigned u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-// Wave maximum of a 64-bit key by DPP (the pattern of gam_align_wave_max on both halves), read from lane 63: uniform.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned long long gam_beam_dpp_max(unsigned long long v) {
-  const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-  const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-  const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-  const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
-  return o > v ? o : v;
-}
-__device__ __forceinline__ unsigned long long gam_beam_wave_max(unsigned long long v) {
-  v = gam_beam_dpp_max<0xb1, 0xf>(v);
-  v = gam_beam_dpp_max<0x4e, 0xf>(v);
-  v = gam_beam_dpp_max<0x141, 0xf>(v);
-  v = gam_beam_dpp_max<0x140, 0xf>(v);
-  v = gam_beam_dpp_max<0x142, 0xa>(v);
-  v = gam_beam_dpp_max<0x143, 0xc>(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// The n largest of the keys k[0..nr) of the wave (n <= 64, keys unique or 0): the i-th largest lands in lane i's `out`.  Returns
-// how many non-zero keys were found (<= n).
-__device__ __forceinline__ int gam_beam_wave_topn(unsigned long long (&k)[GAM_BEAM_RPL], int nr, int n, int lane,
-                                                  unsigned long long& out) {
-  unsigned long long loc = 0;
-#pragma unroll
-  for (int r = 0; r < GAM_BEAM_RPL; ++r)
-    if (r < nr) loc = k[r] > loc ? k[r] : loc;
-  int found = 0;
-  out = 0;
-  for (; found < n; ++found) {
-    const unsigned long long m = gam_beam_wave_max(loc);
-    if (m == 0) break;
-    if (lane == found) out = m;
-    loc = 0;
-#pragma unroll
-    for (int r = 0; r < GAM_BEAM_RPL; ++r) {
-      if (r < nr) {
-        if (k[r] == m) k[r] = 0;
-        loc = k[r] > loc ? k[r] : loc;
-      }
-    }
-  }
-  return found;
-}
-
-// Edge of hotword node `node` for token c (edges sorted by token), or -1.
-__device__ __forceinline__ int gam_beam_hw_find(const int* hw, int n_nodes, int node, int c) {
-  const int* E = hw + n_nodes + 1;
-  int lo = hw[node];
-  const int end = hw[node + 1];
-  int hi = end;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if ((E[mid] & 2047) < c) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < end && (E[lo] & 2047) == c) ? E[lo] : -1;
-}
-
-// The hotword state after an extension by c.
-__device__ __forceinline__ void gam_beam_hw_step(const int* hw, int n_nodes, float beta, int c, int& node, float& acc, float& cb) {
-  int e = gam_beam_hw_find(hw, n_nodes, node, c);
-  if (e < 0 && node != 0) {          // roll back the pending part, restart from the root
-    acc = 0.f;
-    node = 0;
-    e = gam_beam_hw_find(hw, n_nodes, 0, c);
-  }
-  if (e < 0) {                       // (at the root acc is 0)
-    node = 0;
-    acc = 0.f;
-    return;
-  }
-  acc += beta;
-  const int child = e >> 12;
-  if ((e >> 11) & 1) {
-    cb += acc;
-    acc = 0.f;
-  }
-  node = hw[child + 1] > hw[child] ? child : 0;
-}
-
-// ---- the n-gram LM
-__device__ __forceinline__ unsigned long long gam_lm_mix(unsigned long long x) {
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x ? x : 1ull;
-}
-
-// Linear probes of up to NQ keys at once (bit q of `live`: query q runs; query 0 in table t0 of mask m0, the others in t of mask
-// m); every round issues the loads of all open queries before it compares any.  Returns the found bits; val[q] is the found slot's
-// third word (q == 0 or !FOURTH) or its fourth.
-template <int NQ, bool FOURTH>
-__device__ __forceinline__ unsigned gam_lm_probe(const uint4* t0, int m0, const uint4* t, int m, int maxp,
-                                                 const unsigned long long (&key)[NQ], unsigned live, unsigned (&val)[NQ]) {
-  unsigned open = live, found = 0;
-  for (int i = 0; i < maxp && open; ++i) {
-    uint4 e[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const unsigned sl = (unsigned)(key[q] + (unsigned)i) & (unsigned)(q == 0 ? m0 : m);
-      e[q] = ((open >> q) & 1) ? (q == 0 ? t0 : t)[sl] : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const unsigned long long k = ((unsigned long long)e[q].y << 32) | e[q].x;
-      const bool hit = ((open >> q) & 1) && k == key[q];
-      if (hit) found |= 1u << q;
-      val[q] = hit ? ((FOURTH && q != 0) ? e[q].w : e[q].z) : val[q];
-      if (hit || k == 0ull) open &= ~(1u << q);
-    }
-  }
-  return found;
-}
-
-// ln P(w | s) by ARPA back-off, s = (s.x most recent, s.y, s.z, s.w), -1 = no word; the first lm_m of them are the context.  With
-// `word`, w is the word table's id for spelling hash wh (lm_unk when it has none).  Returns ln P and sets w.  Args: any argument
-// struct with the lm_* fields of GamBeamArgs (GamBeamArgs, GamRnntBeamArgs of gam_rnnt_beam.h).
-template <class Args>
-__device__ __forceinline__ float gam_lm_query(const Args& a, bool word, unsigned long long wh, int& w, int4 s4) {
-  constexpr int NQ = GAM_BEAM_LM_MAX_ORDER;
-  const int m = a.lm_m;
-  const int s[4] = {s4.x, s4.y, s4.z, s4.w};
-  // round A: the word (slot 0, word table), and the back-off contexts B_k = (s[k-1] .. s[0]), k = 1..m (slot k, n-gram table)
-  unsigned long long kA[NQ];
-  unsigned vA[NQ] = {0, 0, 0, 0, 0};
-  unsigned live = word ? 1u : 0u;
-  kA[0] = gam_lm_mix(wh);
-#pragma unroll
-  for (int k = 1; k < NQ; ++k) {
-    unsigned long long h = (unsigned long long)k;
-#pragma unroll
-    for (int i = k - 1; i >= 0; --i) h = h * GAM_BEAM_HASH_P + (unsigned long long)(s[i] + 1);
-    kA[k] = gam_lm_mix(h);
-    if (k <= m && s[k - 1] >= 0) live |= 1u << k;
-  }
-  const unsigned fA = gam_lm_probe<NQ, true>(a.lm_wt, a.lm_wmask, a.lm_ng, a.lm_nmask, max(a.lm_wprobe, a.lm_nprobe), kA, live, vA);
-  if (word) w = (fA & 1) ? (int)vA[0] : a.lm_unk;
-  // round B: the n-grams P_k = (s[k-1] .. s[0], w), k = 0..m
-  unsigned long long kB[NQ];
-  unsigned vB[NQ] = {0, 0, 0, 0, 0};
-  live = 0;
-#pragma unroll
-  for (int k = 0; k < NQ; ++k) {
-    unsigned long long h = (unsigned long long)(k + 1);
-#pragma unroll
-    for (int i = k - 1; i >= 0; --i) h = h * GAM_BEAM_HASH_P + (unsigned long long)(s[i] + 1);
-    h = h * GAM_BEAM_HASH_P + (unsigned long long)(w + 1);
-    kB[k] = gam_lm_mix(h);
-    if (k <= m && (k == 0 || s[k - 1] >= 0)) live |= 1u << k;
-  }
-  const unsigned fB = gam_lm_probe<NQ, false>(a.lm_ng, a.lm_nmask, a.lm_ng, a.lm_nmask, a.lm_nprobe, kB, live, vB);
-  // the longest context that has (context, w), plus the back-offs of the longer ones; no unigram: unk_logp
-  float bo = 0.f, lp = a.lm_unk_logp;
-  bool got = false;
-#pragma unroll
-  for (int k = NQ - 1; k >= 0; --k) {
-    if (!got && ((fB >> k) & 1)) {
-      lp = __uint_as_float(vB[k]) + bo;
-      got = true;
-    }
-    if (!got && k >= 1 && ((fA >> k) & 1)) bo += __uint_as_float(vA[k]);
-  }
-  return lp;
 }
 
 template <bool LM>
@@ -335,7 +116,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
   signed char* cls_sh = nullptr;
   if constexpr (LM) {
     p = reinterpret_cast<unsigned char*>(gam_smem_beam) +
-        ((gam_beam_lds_base(W, K, V, a.hw != nullptr && a.hw_lds ? a.hw_words : 0) + 15) & ~(size_t)15);
+        ((gam_beam_lds_base(W, K, V, a.hw.trie != nullptr && a.hw.lds ? a.hw.words : 0) + 15) & ~(size_t)15);
     bwh = reinterpret_cast<unsigned long long*>(take(2 * 32 * 8));
     bctx = reinterpret_cast<int4*>(take(2 * 32 * 16));
     blm = reinterpret_cast<float*>(take(2 * 32 * 4));
@@ -355,9 +136,9 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
     }
     return;
   }
-  const int* hw = a.hw;
-  if (hw != nullptr && a.hw_lds) {
-    for (int i = tid; i < a.hw_words; i += GAM_BEAM_NT) hw_sh[i] = a.hw[i];
+  const int* hw = a.hw.trie;
+  if (hw != nullptr && a.hw.lds) {
+    for (int i = tid; i < a.hw.words; i += GAM_BEAM_NT) hw_sh[i] = a.hw.trie[i];
     hw = hw_sh;
   }
   if (tid == 0) {       // the empty prefix: p_b = 0, p_nb = -inf, hotword state (root, 0)
@@ -367,7 +148,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
     nbuf[0] = 1;
     if constexpr (LM) {   // an empty partial word, the state <s>, lm 0
       bwh[0] = 0ull;
-      bctx[0] = make_int4(a.lm_m > 0 ? a.lm_bos : -1, -1, -1, -1);
+      bctx[0] = make_int4(a.lm.lm_m > 0 ? a.lm.lm_bos : -1, -1, -1, -1);
       blm[0] = 0.f; bdl[0] = 0.f; bcw[0] = -1;
     }
   }
@@ -394,7 +175,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
   };
   if (wave == 1) {
     if constexpr (LM)     // (wave 1 alone reads the class table: its own LDS writes are ordered before its reads)
-      for (int v = lane; v < V; v += 64) cls_sh[v] = (signed char)a.lm_cls[v];
+      for (int v = lane; v < V; v += 64) cls_sh[v] = (signed char)a.lm.lm_cls[v];
     float x[GAM_BEAM_RPL];
 #pragma unroll
     for (int r = 0; r < GAM_BEAM_RPL; ++r) {
@@ -453,7 +234,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
           if (blast[cur * 32 + __builtin_ctz(m)] == c) valid = false;
         pb = -INFINITY;
         pnb = ((lenj > 0 && c == lastj) ? pbj : tot) + tv[s];
-        if (hw != nullptr) gam_beam_hw_step(hw, a.hw_nodes, a.beta, c, hn, acc, cb);
+        if (hw != nullptr) gam_beam_hw_step(hw, a.hw.nodes, a.hw.beta, c, hn, acc, cb);
         key = j * GAM_BEAM_KEY_STRIDE + c + 1;
       }
       float rank = gam_beam_lse(pb, pnb) + (cb + acc);
@@ -463,7 +244,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
         rank += lmv;
       }
       valid = valid && rank > -INFINITY;
-      ckey[q] = valid ? (((unsigned long long)gam_beam_ord(rank) << 32) | ((unsigned)(0xffff - key) << 16) | (unsigned)q) : 0ull;
+      ckey[q] = valid ? gam_beam_key(gam_beam_ord(rank), key, q) : 0ull;
       cpb[q] = pb;
       cpnb[q] = pnb;
       cacc[q] = acc;
@@ -509,7 +290,7 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
             ldl = bdl[o];
             lcw = bcw[o];
           } else if (lwh != 0ull) {
-            ldl = a.lm_alpha * gam_lm_query(a, true, lwh, lcw, lcx) + a.lm_beta;
+            ldl = a.lm.lm_alpha * gam_lm_query(a.lm, true, lwh, lcw, lcx) + a.lm.lm_beta;
           }
           M -= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(llm), 0));     // (p_b / p_nb keep O(one frame))
         }
@@ -580,8 +361,8 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
           lmf += bdl[d];
           cx = make_int4(bcw[d], cx.x, cx.y, cx.z);
         }
-        int w = a.lm_eos;
-        lmf += a.lm_alpha * gam_lm_query(a, false, 0ull, w, cx);
+        int w = a.lm.lm_eos;
+        lmf += a.lm.lm_alpha * gam_lm_query(a.lm, false, 0ull, w, cx);
         val += lmf;
       }
     }

@@ -3,7 +3,7 @@
 // The contract (shared with tests/rnnt_beam_ref.py, which holds real token tuples).  For utterance b: T = enc_len[b], blank = V - 1,
 // beam width W (1..32), K = min(W, V - 1) candidate tokens per joint row, S = max_symbols (1..16).  A hypothesis h has its token
 // sequence y, the predictor state after feeding y (the empty y: predict(None, None), gate_tab row V, as in gam_rnnt_greedy_kernel),
-// pp(y) = W_pred g(y) + b_pred, a score (log-prob) and a hotword state (node, acc, committed) with the rules of gam_beam.h.
+// pp(y) = W_pred g(y) + b_pred, a score (log-prob) and a hotword state (node, acc, committed) with the rules of gam_search.h.
 //   lp(t, y) = log_softmax(W_out relu(encp[t] + pp(y)) + b_out);   rank = score + committed + acc.
 //
 //   beam = {empty: score 0}
@@ -25,7 +25,7 @@
 // contributor, and the key of its first contributor.  Within one C_s sequences are distinct.  Every top-W selection breaks rank ties
 // by the smaller origin key.  The theta cut is part of the contract: without it C_s is never empty and every frame runs S joints and S
 // predictor steps; with it a blank-dominant frame ends after one joint.
-// Hypothesis identity: (length, 64-bit polynomial hash h(y + v) = h(y) P + v + 1), as in gam_beam.h.
+// Hypothesis identity: (length, 64-bit hash), gam_search.h.
 //
 // Shape: one workgroup of GAM_RB_NT threads per utterance; t the sequential loop; the backtrack at the end of the same kernel.
 //   joint   z [rows][JH] = relu(encp[t] + pp) in LDS; logits = z W_out^T + b_out on the matrix cores (v_mfma_f32_16x16x4_f32, rows
@@ -41,8 +41,8 @@
 // one y always gets bit-identical predictor outputs.  Renormalisation: each frame subtracts the best kept rank from the scores and adds
 // it to an fp64 offset.  Limits (host errors beyond them): W <= 32, S <= 16, T' <= 8192, V <= 1025, H and JH <= 512 (multiples of 16).
 //
-// Word n-gram LM (template <bool LM>; gam_rnnt_beam_kernel<false> is the kernel without it, unchanged; tests/rnnt_lm_ref.py is the
-// float64 reference).  The word rules of gam_beam.h, applied to hypotheses: token classes from gam_set_lm (0 continues the current
+// Word n-gram LM (template <bool LM>; gam_rnnt_beam_kernel<false> is the kernel without it, unchanged; tests/rnnt_beam_ref.py with an
+// LMSpec is the float64 reference).  The word rules of gam_search.h, applied to hypotheses: token classes from gam_set_lm (0 continues the current
 // word, 1 starts a new word, 2 separates; blank is class 0 and never extends y).  A hypothesis carries the spelling hash of its
 // partial word (0 = empty), its last order - 1 completed word ids (<s> at the start) and lm, the LM term so far.
 //   rank = score + committed + acc + lm.
@@ -56,10 +56,10 @@
 //   With alpha = beta = 0 every lm and d is +0, so ids, frames, score and logp are bit-identical to the kernel without the LM.
 // Cost: one LM query per NEW hypothesis, not per candidate: d(a) and w's id depend on a alone, so wave 0 queries them for every entry
 // of A_{s+1} whose partial word is non-empty, right after its top-W selection, and the next joint phase only adds d to the
-// extensions by class-1/2 tokens (the split of gam_beam.h).  The LM state of the A lists and of B (36 B per entry) and the class
+// extensions by class-1/2 tokens (the split of gam_search.h).  The LM state of the A lists and of B (36 B per entry) and the class
 // table [V] i8 lie in LDS after the union region (gam_rb_lm_bytes): 22.4 KiB at W = 32, S = 16, V = 1025.
 #pragma once
-#include "gam_beam.h"
+#include "gam_search.h"
 
 #define GAM_RB_NT 256
 #define GAM_RB_MAX_S 16
@@ -79,9 +79,7 @@ struct GamRnntBeamArgs {
   const float* whh_x;    // [L-1][H][4H]
   const float* bias_x;   // [L-1][4H]
   int Tp, V, H, JH, L, W, K, S;
-  const int* hw;         // hotword trie (NULL: none)
-  int hw_nodes, hw_words, hw_lds;
-  float beta;
+  GamHwArgs hw;
   float* ws;             // [B][slots (S+1) W x SS | logits Wp x LGS] floats
   size_t ws_stride;      // floats per utterance
   int2* nodes;           // [B][Tp S W]
@@ -91,14 +89,11 @@ struct GamRnntBeamArgs {
   int* counts;           // [B]
   float* score;          // [B]
   float* logp;           // [B]
-  // the n-gram LM (gam_rnnt_beam_kernel<true> only; the fields and meanings of GamBeamArgs, read by gam_lm_query)
-  const int* lm_cls;     // [V] token classes
-  const uint4* lm_wt;    // word table slots
-  const uint4* lm_ng;    // n-gram table slots
-  int lm_wmask, lm_wprobe, lm_nmask, lm_nprobe;   // slots - 1, longest probe chain
-  int lm_m, lm_bos, lm_eos, lm_unk;               // order - 1, word ids
-  float lm_unk_logp, lm_alpha, lm_beta;
+  GamLmArgs lm;
 };
+// (the kernel argument layout the fields had before the two blocks were structs of their own)
+static_assert(sizeof(GamRnntBeamArgs) == 288 && offsetof(GamRnntBeamArgs, hw) == 120 && offsetof(GamRnntBeamArgs, ws) == 144 &&
+              offsetof(GamRnntBeamArgs, lm) == 216, "GamRnntBeamArgs layout");
 
 // LDS carve (host and device), in bytes, in this order: A lists [2][32] (hash u64; len, score, hotword node, acc, committed, prefix
 // node, slot, token, parent slot: i32 / f32), row blank log-probs [32], counters [16], B list [P] (hash u64; len, score, best
@@ -255,9 +250,9 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
     }
     return;
   }
-  const int* hw = a.hw;
-  if (hw != nullptr && a.hw_lds) {
-    for (int i = tid; i < a.hw_words; i += GAM_RB_NT) hw_sh[i] = a.hw[i];
+  const int* hw = a.hw.trie;
+  if (hw != nullptr && a.hw.lds) {
+    for (int i = tid; i < a.hw.words; i += GAM_RB_NT) hw_sh[i] = a.hw.trie[i];
     hw = hw_sh;
   }
   float* slots = a.ws + (size_t)b * a.ws_stride;
@@ -375,13 +370,13 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
 
   // ---- the empty hypothesis: predict(None, None) into slot 0
   if constexpr (LM)
-    for (int v = tid; v < V; v += GAM_RB_NT) cls_sh[v] = (signed char)a.lm_cls[v];
+    for (int v = tid; v < V; v += GAM_RB_NT) cls_sh[v] = (signed char)a.lm.lm_cls[v];
   if (tid == 0) {
     ah[0] = 0ull; alen[0] = 0; asc[0] = 0.f; ahn[0] = 0; aacc[0] = 0.f; acb[0] = 0.f; anode[0] = -1;
     aslot[0] = 0; atok[0] = V; apar[0] = -1;
     cnt[0] = 1;
     if constexpr (LM) {   // an empty partial word, the state <s>, lm 0
-      mctx[0] = make_int4(a.lm_m > 0 ? a.lm_bos : -1, -1, -1, -1);
+      mctx[0] = make_int4(a.lm.lm_m > 0 ? a.lm.lm_bos : -1, -1, -1, -1);
       mwh[0] = 0ull; mlm[0] = 0.f; mdl[0] = 0.f; mcw[0] = -1;
     }
   }
@@ -478,7 +473,7 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
             const float sc = asc[o] + (gam_beam_unord((unsigned)(out >> 32)) - lse);
             int hn = ahn[o];
             float acc = aacc[o], cb = acb[o];
-            if (hw != nullptr) gam_beam_hw_step(hw, a.hw_nodes, a.beta, v, hn, acc, cb);
+            if (hw != nullptr) gam_beam_hw_step(hw, a.hw.nodes, a.hw.beta, v, hn, acc, cb);
             float rank = sc + (cb + acc);
             if constexpr (LM) {   // a's lm, plus d(a) when v completes a's partial word
               float lmv = mlm[o];
@@ -487,7 +482,7 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
             }
             const int q = r * K + lane;
             const int key = r * GAM_BEAM_KEY_STRIDE + v + 1;
-            ckey[q] = rank > -INFINITY ? (((unsigned long long)gam_beam_ord(rank) << 32) | ((unsigned)(0xffff - key) << 16) | (unsigned)q) : 0ull;
+            ckey[q] = rank > -INFINITY ? gam_beam_key(gam_beam_ord(rank), key, q) : 0ull;
             csc[q] = sc;
             cacc[q] = acc;
             ccb[q] = cb;
@@ -538,9 +533,7 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
 #pragma unroll
             for (int j = 0; j < GAM_BEAM_RPL; ++j) {
               const int i = lane + 64 * j;
-              k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(brank(i)) << 32) |
-                                           ((unsigned)(0xffff - bkey[i]) << 16) | (unsigned)i)
-                                        : 0ull;
+              k[j] = (j < nr && i < nB) ? gam_beam_key(gam_beam_ord(brank(i)), bkey[i], i) : 0ull;
             }
             unsigned long long sel;
             gam_beam_wave_topn(k, nr, W, lane, sel);
@@ -581,7 +574,7 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
                   cl == 0 ? wh * GAM_BEAM_HASH_P + (unsigned long long)(v + 1) : (cl == 1 ? (unsigned long long)(v + 1) : 0ull);
               int w = -1;
               float dl = 0.f;
-              if (nwh != 0ull) dl = a.lm_alpha * gam_lm_query(a, true, nwh, w, ncx) + a.lm_beta;
+              if (nwh != 0ull) dl = a.lm.lm_alpha * gam_lm_query(a.lm, true, nwh, w, ncx) + a.lm.lm_beta;
               mlm[d] = done ? mlm[o] + mdl[o] : mlm[o];
               mctx[d] = ncx; mwh[d] = nwh; mdl[d] = dl; mcw[d] = w;
             }
@@ -603,9 +596,7 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
 #pragma unroll
       for (int j = 0; j < GAM_BEAM_RPL; ++j) {
         const int i = lane + 64 * j;
-        k[j] = (j < nr && i < nB) ? (((unsigned long long)gam_beam_ord(brank(i)) << 32) |
-                                     ((unsigned)(0xffff - bkey[i]) << 16) | (unsigned)i)
-                                  : 0ull;
+        k[j] = (j < nr && i < nB) ? gam_beam_key(gam_beam_ord(brank(i)), bkey[i], i) : 0ull;
       }
       unsigned long long sel;
       const int nb = gam_beam_wave_topn(k, nr, W, lane, sel);
@@ -644,8 +635,8 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
           lmf += mdl[lane];
           cx = make_int4(mcw[lane], cx.x, cx.y, cx.z);
         }
-        int w = a.lm_eos;
-        lmf += a.lm_alpha * gam_lm_query(a, false, 0ull, w, cx);
+        int w = a.lm.lm_eos;
+        lmf += a.lm.lm_alpha * gam_lm_query(a.lm, false, 0ull, w, cx);
         val += lmf;
       }
     }

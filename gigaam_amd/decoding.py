@@ -72,28 +72,8 @@ def _ragged(dec, *rest) -> List[Tuple[List[int], List[int]]]:
     return rows
 
 
-class CTCGreedyDecoding:
-    def __init__(self, vocabulary: List[str], model_path: Optional[str] = None):
-        self.tokenizer = Tokenizer(vocabulary, model_path)
-        self.blank_id = len(self.tokenizer)
-
-    @torch.inference_mode()
-    def decode_device(self, head: CTCHead, encoded: Tensor, lengths: Tensor, overlap: bool = False):
-        """The device half of ``decode``: (ids, frames, counts) i32 tensors on the GPU, no host sync -- a driver
-        can launch the next batch before it looks at this one (``finish``).  ``overlap`` is accepted for signature symmetry
-        with the RNN-T decoder and ignored: the CTC decode is one 8 us kernel."""
-        c = head.num_classes
-        assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
-        return head.engine.ctc_greedy(encoded, lengths)
-
-    def finish(self, dec, *rest) -> List[Tuple[str, List[int], List[int]]]:
-        """``dec``: the object ``decode_device`` returned (pass it whole: it carries the range flag word and the decode's
-        completion event as explicit fields)."""
-        return [(self.tokenizer.decode(i), i, f) for i, f in _ragged(dec, *rest)]
-
-    @torch.inference_mode()
-    def decode(self, head: CTCHead, encoded: Tensor, lengths: Tensor) -> List[Tuple[str, List[int], List[int]]]:
-        return self.finish(self.decode_device(head, encoded, lengths))
+class _BeamInputs:
+    """Hotwords and the LM as the beam searches take them (per-object caches); mixed into the decoding classes that search by beam."""
 
     def hotword_ids(self, hotwords) -> List[List[int]]:
         """Hotwords (each a string in the vocabulary -- ``Tokenizer.encode`` -- or token ids) -> token-id lists, the strings'
@@ -121,6 +101,30 @@ class CTCGreedyDecoding:
         if key not in cache:
             cache[key] = NgramLM.open(key)
         return cache[key]
+
+
+class CTCGreedyDecoding(_BeamInputs):
+    def __init__(self, vocabulary: List[str], model_path: Optional[str] = None):
+        self.tokenizer = Tokenizer(vocabulary, model_path)
+        self.blank_id = len(self.tokenizer)
+
+    @torch.inference_mode()
+    def decode_device(self, head: CTCHead, encoded: Tensor, lengths: Tensor, overlap: bool = False):
+        """The device half of ``decode``: (ids, frames, counts) i32 tensors on the GPU, no host sync -- a driver
+        can launch the next batch before it looks at this one (``finish``).  ``overlap`` is accepted for signature symmetry
+        with the RNN-T decoder and ignored: the CTC decode is one 8 us kernel."""
+        c = head.num_classes
+        assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
+        return head.engine.ctc_greedy(encoded, lengths)
+
+    def finish(self, dec, *rest) -> List[Tuple[str, List[int], List[int]]]:
+        """``dec``: the object ``decode_device`` returned (pass it whole: it carries the range flag word and the decode's
+        completion event as explicit fields)."""
+        return [(self.tokenizer.decode(i), i, f) for i, f in _ragged(dec, *rest)]
+
+    @torch.inference_mode()
+    def decode(self, head: CTCHead, encoded: Tensor, lengths: Tensor) -> List[Tuple[str, List[int], List[int]]]:
+        return self.finish(self.decode_device(head, encoded, lengths))
 
     @torch.inference_mode()
     def decode_beam_device(self, head: CTCHead, encoded: Tensor, lengths: Tensor, beam_size: int = 8, hotwords=None,
@@ -197,7 +201,7 @@ class RNNTGreedyDecoding:
         return self.finish(self.decode_device(head, encoded, enc_len))
 
 
-class RNNTBeamDecoding(RNNTGreedyDecoding):
+class RNNTBeamDecoding(RNNTGreedyDecoding, _BeamInputs):
     """RNN-T beam search with hotword boosting and word n-gram LM fusion (gam_rnnt_beam; the contract is in
     gigaam_amd/csrc/gam_rnnt_beam.h).  A ``cfg.decoding`` target like the greedy one, so a config naming
     ``gigaam.decoding.RNNTBeamDecoding`` loads a model that decodes by beam, and ``GigaAMASR.set_decoding`` switches to it.
@@ -217,9 +221,6 @@ class RNNTBeamDecoding(RNNTGreedyDecoding):
         self.hotwords = list(hotwords) if hotwords else []
         self.hotword_boost = float(hotword_boost)
         self.set_lm(lm, lm_weight, word_bonus)
-
-    hotword_ids = CTCGreedyDecoding.hotword_ids
-    language_model = CTCGreedyDecoding.language_model
 
     def set_lm(self, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0) -> None:
         """The LM of every later search (None: none); a path is read here, once."""

@@ -532,10 +532,26 @@ class HipEngine:
 
     MAX_BEAM = 32     # include/gigaam_hip.h gam_ctc_beam
 
-    def _launch_beam(self, fn, first, enc_len: Tensor, b: int, tp: int, extra, beam_size: int, what: str) -> BeamDecoded:
+    MAX_SYMBOLS_BEAM = 16     # include/gigaam_hip.h gam_rnnt_beam
+
+    def _beam_out(self, b: int, cap: int, beam_size: int, max_symbols: Optional[int] = None) -> BeamDecoded:
+        """Check the width (and the RNN-T search's ``max_symbols``); the result buffers for ``cap`` tokens per utterance."""
         if not 1 <= int(beam_size) <= self.MAX_BEAM:
             raise GigaAMHipError(f"beam_size {beam_size} outside [1, {self.MAX_BEAM}]")
-        out = BeamDecoded(torch.empty((2 * b * tp + 3 * b + 1,), dtype=torch.int32, device=self.device), b, tp)
+        if max_symbols is not None and not 1 <= int(max_symbols) <= self.MAX_SYMBOLS_BEAM:
+            raise GigaAMHipError(f"max_symbols {max_symbols} outside [1, {self.MAX_SYMBOLS_BEAM}] for the RNN-T beam search")
+        return BeamDecoded(torch.empty((2 * b * cap + 3 * b + 1,), dtype=torch.int32, device=self.device), b, cap)
+
+    def _op_beam_done(self, out: BeamDecoded) -> BeamDecoded:
+        """An ``op_*`` search ran no encoder: zero the flag word, record the completion event."""
+        out.ext[-1:].zero_()
+        st = torch.cuda.current_stream(self.device)
+        out.event, out.stream = torch.cuda.Event(), st
+        out.event.record(st)
+        return out
+
+    def _launch_beam(self, fn, first, enc_len: Tensor, b: int, tp: int, extra, beam_size: int, what: str) -> BeamDecoded:
+        out = self._beam_out(b, tp, beam_size)
         rc = fn(self._h, _ptr(first), _ptr(enc_len), b, tp, *extra, int(beam_size), _ptr(out.ids), _ptr(out.frames), _ptr(out.counts),
                 _ptr(out.score), _ptr(out.logp), self._stream())
         self._check(rc, what)
@@ -558,22 +574,8 @@ class HipEngine:
         enc_len = self._dev(enc_len, torch.int32)
         b, tp, v = log_probs.shape
         with torch.cuda.device(self.device):
-            out = self._launch_beam(self.lib.gam_op_ctc_beam, log_probs, enc_len, b, tp, (v,), beam_size, "gam_op_ctc_beam")
-            out.ext[b:].zero_()
-            st = torch.cuda.current_stream(self.device)
-            out.event, out.stream = torch.cuda.Event(), st
-            out.event.record(st)
-        return out
-
-    MAX_SYMBOLS_BEAM = 16     # include/gigaam_hip.h gam_rnnt_beam
-
-    def _rnnt_beam_out(self, b: int, tp: int, beam_size: int, max_symbols: int) -> BeamDecoded:
-        if not 1 <= int(beam_size) <= self.MAX_BEAM:
-            raise GigaAMHipError(f"beam_size {beam_size} outside [1, {self.MAX_BEAM}]")
-        if not 1 <= int(max_symbols) <= self.MAX_SYMBOLS_BEAM:
-            raise GigaAMHipError(f"max_symbols {max_symbols} outside [1, {self.MAX_SYMBOLS_BEAM}] for the RNN-T beam search")
-        cap = tp * int(max_symbols)
-        return BeamDecoded(torch.empty((2 * b * cap + 3 * b + 1,), dtype=torch.int32, device=self.device), b, cap)
+            return self._op_beam_done(self._launch_beam(self.lib.gam_op_ctc_beam, log_probs, enc_len, b, tp, (v,), beam_size,
+                                                        "gam_op_ctc_beam"))
 
     def rnnt_beam(self, encoded: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int) -> BeamDecoded:
         """RNN-T beam search (gam_rnnt_beam): the encoder projection GEMM and the beam kernel, no host sync; the hotword set of
@@ -583,7 +585,7 @@ class HipEngine:
         enc_len = self._dev(enc_len, torch.int32)
         b, _, tp = encoded.shape
         with torch.cuda.device(self.device):
-            out = self._rnnt_beam_out(b, tp, beam_size, max_symbols)
+            out = self._beam_out(b, tp * int(max_symbols), beam_size, max_symbols)
             rc = self.lib.gam_rnnt_beam(self._h, _ptr(encoded), _ptr(enc_len), b, tp, int(beam_size), int(max_symbols), _ptr(out.ids),
                                         _ptr(out.frames), _ptr(out.counts), _ptr(out.score), _ptr(out.logp), self._stream())
             self._check(rc, "gam_rnnt_beam")
@@ -599,15 +601,11 @@ class HipEngine:
         if jh != self.cfg.joint_hidden:
             raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
         with torch.cuda.device(self.device):
-            out = self._rnnt_beam_out(b, tp, beam_size, max_symbols)
+            out = self._beam_out(b, tp * int(max_symbols), beam_size, max_symbols)
             rc = self.lib.gam_op_rnnt_beam(self._h, _ptr(encp), _ptr(enc_len), b, tp, int(beam_size), int(max_symbols), _ptr(out.ids),
                                            _ptr(out.frames), _ptr(out.counts), _ptr(out.score), _ptr(out.logp), self._stream())
             self._check(rc, "gam_op_rnnt_beam")
-            out.ext[b:].zero_()
-            st = torch.cuda.current_stream(self.device)
-            out.event, out.stream = torch.cuda.Event(), st
-            out.event.record(st)
-        return out
+            return self._op_beam_done(out)
 
     def set_hotwords(self, phrases, boost: float = 2.0) -> None:
         """Hotword phrases (token-id lists) for the beam search, each matched token worth ``boost`` (gam_set_hotwords); an empty

@@ -1,11 +1,11 @@
-"""Word-level n-gram language model for CTC beam search (gam_set_lm, gigaam_amd/csrc/gam_beam.h).
+"""Word-level n-gram language model for CTC beam search (gam_set_lm, gigaam_amd/csrc/gam_search.h).
 
 ``NgramLM.from_arpa`` reads a plain or gzipped ARPA file with no external dependency; ``save`` / ``load`` keep the parsed model in a
 ``.npz`` (parsing a large ARPA in Python is slow).  ``score_words`` is the float64 sentence score the beam kernel's LM term follows.
 ``device_tables`` builds what the kernel reads: the token classes of a tokenizer, a word table (spelling hash -> LM word id) and an
 n-gram table (key of a word-id tuple -> ln p, ln backoff), both open addressing with linear probing at load <= 0.5.
 
-Hashes (shared with gam_beam.h and tests/ctc_lm_ref.py; all arithmetic mod 2^64, P = 0x100000001b3):
+Hashes (shared with gam_search.h and tests/ctc_lm_ref.py; all arithmetic mod 2^64, P = 0x100000001b3):
   spelling   h = 0, then h = h * P + (token + 1) per token of the word
   n-gram     h = n, then h = h * P + (word id + 1) per word, oldest first
   table key  mix64(h) (the splitmix64 finaliser), 1 where that is 0; slot i of a probe: (key + i) & (slots - 1); key 0 marks a free

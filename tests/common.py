@@ -95,3 +95,13 @@ def split_ragged(flat_ids, flat_frames, counts):
 def ragged_from_device(ids, frames, counts):
     n = counts.cpu().tolist()
     return [(ids[i, :c].cpu().tolist(), frames[i, :c].cpu().tolist()) for i, c in enumerate(n)]
+
+
+def make_engine(cfg, state_dict, mode="f16x3", head=True):
+    """A HipEngine on cuda:0 in GEMM mode "f16x3" (the product's default) or "f32" (exact-fp32 MFMA)."""
+    from gigaam_amd.engine import HipEngine, build_config
+    eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg.get("head") if head else None), state_dict,
+                    torch.device("cuda:0"))
+    eng.set_gemm_mode(mode)
+    assert eng.gemm_mode == mode
+    return eng

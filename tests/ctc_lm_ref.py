@@ -1,8 +1,8 @@
-"""Float64 reference of CTC prefix beam search with hotwords AND a word n-gram LM (gigaam_amd/csrc/gam_beam.h, gam_ctc_beam_kernel<true>).
-numpy only; used by the CPU and the GPU tests.  Prefixes and partial words are real tuples here, the ARPA model a dict of word
-tuples; the kernel identifies them by 64-bit hashes (gigaam_amd/lm.py).
+"""The word n-gram LM of the float64 beam search references (the word rules of gigaam_amd/csrc/gam_search.h): ``LMSpec`` is what
+``ctc_beam_ref.beam_search`` and ``rnnt_beam_ref.beam_search`` take as ``lm``.  numpy only; used by the CPU and the GPU tests.
+Partial words are real tuples here, the ARPA model a dict of word tuples; the kernels identify them by 64-bit hashes (gigaam_amd/lm.py).
 
-The search is tests/ctc_beam_ref.py's (same candidates, merges, ties and frame rule) with one more per-prefix term:
+The searches are unchanged by it (same candidates, merges, ties and frame rule) but for one more per-prefix term:
   Words.  Every token has a class: 0 continues the current word, 1 starts a new word (the token belongs to it), 2 separates words
   (belongs to none).  A prefix's partial word is its tokens since the last class-1/2 token; its LM state the last order - 1
   completed words, ("<s>",) at the start.  Extending y by a class-1/2 token completes y's partial word w when it is non-empty:
@@ -16,8 +16,6 @@ The search is tests/ctc_beam_ref.py's (same candidates, merges, ties and frame r
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
-
-from ctc_beam_ref import NEG, Trie, _lse, topk_ids
 
 HASH_P = 0x100000001B3
 MASK64 = (1 << 64) - 1
@@ -108,65 +106,6 @@ class LMSpec:
     def final(self, st) -> float:
         _, ctx, acc = self.complete(st)
         return acc + self.alpha * self.lm.lnprob("</s>", ctx)
-
-
-def beam_search(lp: np.ndarray, W: Optional[int], T: Optional[int] = None, hotwords: Sequence[Sequence[int]] = (),
-                beta: float = 2.0, lm: Optional[LMSpec] = None) -> Dict[str, object]:
-    """As ctc_beam_ref.beam_search, with the LM term when ``lm`` is given (``lm=None`` is that function exactly)."""
-    lp = np.asarray(lp, dtype=np.float64)
-    V = lp.shape[1]
-    T = lp.shape[0] if T is None else T
-    blank = V - 1
-    K = V - 1 if W is None else min(W, V - 1)
-    trie = Trie(hotwords)
-    lm0 = lm.start() if lm is not None else ((), (), 0.0)
-    beam = [((), 0.0, NEG, (0, 0.0, 0.0), (), lm0)]
-    margins: List[float] = []
-    for t in range(T):
-        row = lp[t]
-        cand_ids = topk_ids(row, K)
-        cands: Dict[tuple, list] = {}
-
-        def add(y, pb, pnb, key, hw, frames, stay, ls):
-            e = cands.setdefault(y, [NEG, NEG, key, hw, None, None, NEG, NEG, ls])
-            e[0], e[1] = _lse(e[0], pb), _lse(e[1], pnb)
-            e[2] = min(e[2], key)
-            assert e[3] == hw and e[8] == ls, "hotword and LM state must depend on the prefix only"
-            e[4 if stay else 5] = frames
-            e[6 if stay else 7] = _lse(pb, pnb)
-
-        for i, (y, pb, pnb, hw, fr, ls) in enumerate(beam):
-            tot = _lse(pb, pnb)
-            add(y, tot + row[blank], (pnb + row[y[-1]]) if y else NEG, (i, -1), hw, fr, True, ls)
-            for c in cand_ids:
-                base = pb if (y and c == y[-1]) else tot
-                add(y + (c,), NEG, base + row[c], (i, c), trie.step(hw, c, beta), fr + (t,), False,
-                    lm.step(ls, c) if lm is not None else ls)
-        ranked = []
-        for y, (pb, pnb, key, hw, fs, fe, ms, me, ls) in cands.items():
-            r = _lse(pb, pnb) + hw[2] + hw[1] + ls[2]
-            fr = fe if me > ms else fs
-            if r > NEG:
-                ranked.append((-r, key, y, pb, pnb, hw, fr, abs(ms - me) if ms > NEG and me > NEG else np.inf, ls))
-        ranked.sort(key=lambda e: (e[0], e[1]))
-        if W is not None and len(ranked) > W:
-            cut = float(ranked[W][0] - ranked[W - 1][0])
-            ranked = ranked[:W]
-        else:
-            cut = np.inf
-        margins.append(min([cut] + [e[7] for e in ranked]))
-        beam = [(y, pb, pnb, hw, fr, ls) for _, _, y, pb, pnb, hw, fr, _, ls in ranked]
-    if T == 0:
-        return {"ids": [], "frames": [], "score": 0.0, "logp": 0.0, "lm": 0.0, "margins": [], "final_margin": np.inf}
-    finals = []
-    for i, (_, pb, pnb, hw, _, ls) in enumerate(beam):
-        lmf = lm.final(ls) if lm is not None else 0.0
-        finals.append((_lse(pb, pnb) + hw[2] + lmf, i, lmf))
-    finals.sort(key=lambda e: (-e[0], e[1]))
-    y, pb, pnb, hw, fr, _ = beam[finals[0][1]]
-    logp = _lse(pb, pnb)
-    return {"ids": list(y), "frames": list(fr), "score": logp + hw[2] + finals[0][2], "logp": logp, "lm": finals[0][2],
-            "margins": margins, "final_margin": float(finals[0][0] - finals[1][0]) if len(finals) > 1 else np.inf}
 
 
 def words_of(ids: Sequence[int], classes: Sequence[int]) -> List[tuple]:

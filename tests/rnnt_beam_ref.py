@@ -8,7 +8,10 @@ extension (a.y + v, a.score + lp[v], key (s, p, v + 1)) into C_s; when s = S, th
 theta = the W-th highest rank in B (-inf while |B| < W); A_{s+1} = top W of {c in C_s: rank > theta} (ties: smaller key); the frame
 ends when it is empty.  The new beam is the top W of B.  Merging in B log-add-exps the scores; the entry keeps the frames of the
 contributor with the higher score (ties: the earlier one) and the key of its first contributor.  rank = score + committed + acc.
-Final: best score + committed, ties to the lower beam position."""
+Final: best score + committed, ties to the lower beam position.
+With ``lm`` (a ctc_lm_ref.LMSpec, where the word rules are): an extension a.y + v takes ``lm.step(state, v)``; blank candidates and
+the forced advance keep the state; equal y means equal state (asserted at every merge); rank and the final pick add the LM term
+(final: ``lm.final(state)``, the last word and </s>).  score = log p + committed + that term; logp = log p."""
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -92,35 +95,43 @@ def topk_ids(lp: np.ndarray, k: int) -> List[int]:
 
 
 def beam_search(head, encp, W: int, S: int, T: Optional[int] = None, hotwords: Sequence[Sequence[int]] = (),
-                beta: float = 2.0, joint=None) -> Dict[str, object]:
+                beta: float = 2.0, joint=None, lm=None) -> Dict[str, object]:
     """encp [>= T, JH] (float64: W_enc f + b_enc), beam width W, max symbols per frame S.  ``joint(t, y) -> lp`` replaces the
-    network's joint when given (tests with hand-made log-probs).  Returns ids, frames, score (log p + committed bonus), logp,
-    beam (the final [(y, score)]), margins (every top-W cut, theta comparison and kept merge) and final_margin."""
-    encp = np.asarray(encp, dtype=np.float64)
+    network's joint when given (tests with hand-made log-probs).  ``lm``: a ctc_lm_ref.LMSpec or None (its term is then an exact
+    + 0.0).  Returns ids, frames, score (log p + committed bonus + LM term), logp, lm (the picked hypothesis's final LM term), beam
+    (the final [(y, score)]), states (the final beam's LM states), margins (every top-W cut, theta comparison and kept merge),
+    merges (how many merges in B the search made, each with equal LM states) and final_margin."""
+    encp = np.asarray(encp, dtype=np.float64) if encp is not None else None
     T = encp.shape[0] if T is None else T
     pred = Predictor(head) if head is not None else None
     if joint is None:
         joint = lambda t, y: joint_lp(head, encp[t], pred(y))     # noqa: E731
     trie = Trie(hotwords)
-    # a hypothesis: [y, score, hw state, frames]
-    beam = [((), 0.0, (0, 0.0, 0.0), ())]
+    step = (lambda st, v: lm.step(st, v)) if lm is not None else (lambda st, v: st)     # noqa: E731
+    lm0 = lm.start() if lm is not None else ((), (), 0.0)
+    # a hypothesis: [y, score, hw state, frames, LM state]
+    beam = [((), 0.0, (0, 0.0, 0.0), (), lm0)]
     margins: List[float] = []
-    V = None
+    merges = 0
+
+    def rank(sc, hw, ls):
+        return sc + hw[2] + hw[1] + ls[2]
+
     for t in range(T):
-        Bd: Dict[tuple, list] = {}      # y -> [score, best contributor score, key, hw, frames, merge gap]
+        Bd: Dict[tuple, list] = {}      # y -> [score, best contributor score, key, hw, frames, merge gap, LM state]
         A = beam
         for s in range(S + 1):
             C = []
-            for p, (y, sc, hw, fr) in enumerate(A):
+            for p, (y, sc, hw, fr, ls) in enumerate(A):
                 if s < S:
                     lp = joint(t, y)
-                    V = len(lp)
                     cands = [(sc + lp[-1], (s, p, 0))]
-                    K = min(W, V - 1)
+                    K = min(W, len(lp) - 1)
                     for v in topk_ids(lp, K):
                         hw2 = trie.step(hw, v, beta)
+                        ls2 = step(ls, v)
                         sc2 = sc + lp[v]
-                        C.append((sc2 + hw2[2] + hw2[1], (s, p, v + 1), y + (v,), sc2, hw2, fr + (t,)))
+                        C.append((rank(sc2, hw2, ls2), (s, p, v + 1), y + (v,), sc2, hw2, fr + (t,), ls2))
                 else:
                     cands = [(sc, (s, p, 0))]
                 for csc, key in cands:
@@ -128,38 +139,44 @@ def beam_search(head, encp, W: int, S: int, T: Optional[int] = None, hotwords: S
                         continue
                     e = Bd.get(y)
                     if e is None:
-                        Bd[y] = [csc, csc, key, hw, fr, np.inf]
+                        Bd[y] = [csc, csc, key, hw, fr, np.inf, ls]
                     else:
-                        assert e[3] == hw
+                        assert e[3] == hw and e[6] == ls, "hotword and LM state must depend on y only"
+                        merges += 1
                         e[0] = float(np.logaddexp(e[0], csc))
                         e[5] = min(e[5], abs(csc - e[1]))
                         if csc > e[1]:
                             e[1], e[4] = csc, fr
             if not C:
                 break
-            ranks = sorted((e[0] + e[3][2] + e[3][1] for e in Bd.values()), reverse=True)
+            ranks = sorted((rank(e[0], e[3], e[6]) for e in Bd.values()), reverse=True)
             theta = ranks[W - 1] if len(ranks) >= W else NEG
             if theta > NEG:
                 margins.append(min(abs(c[0] - theta) for c in C))
             Cf = sorted([c for c in C if c[0] > theta], key=lambda c: (-c[0], c[1]))
             if len(Cf) > W:
                 margins.append(Cf[W - 1][0] - Cf[W][0])
-            A = [(c[2], c[3], c[4], c[5]) for c in Cf[:W]]
+            A = [(c[2], c[3], c[4], c[5], c[6]) for c in Cf[:W]]
             if not A:
                 break
-        ranked = sorted(Bd.items(), key=lambda kv: (-(kv[1][0] + kv[1][3][2] + kv[1][3][1]), kv[1][2]))
+        ranked = sorted(Bd.items(), key=lambda kv: (-rank(kv[1][0], kv[1][3], kv[1][6]), kv[1][2]))
         if len(ranked) > W:
-            r = [kv[1][0] + kv[1][3][2] + kv[1][3][1] for kv in ranked]
+            r = [rank(e[0], e[3], e[6]) for _, e in ranked]
             margins.append(r[W - 1] - r[W])
             ranked = ranked[:W]
         for _, e in ranked:
             if e[5] < np.inf:
                 margins.append(e[5])
-        beam = [(y, e[0], e[3], e[4]) for y, e in ranked]
-    finals = sorted(((sc + hw[2], i) for i, (_, sc, hw, _) in enumerate(beam)), key=lambda e: (-e[0], e[1]))
-    y, sc, hw, fr = beam[finals[0][1]]
-    return {"ids": list(y), "frames": list(fr), "score": sc + hw[2], "logp": sc, "beam": [(b[0], b[1]) for b in beam],
-            "margins": margins, "final_margin": float(finals[0][0] - finals[1][0]) if len(finals) > 1 else np.inf}
+        beam = [(y, e[0], e[3], e[4], e[6]) for y, e in ranked]
+    finals = []
+    for i, (_, sc, hw, _, ls) in enumerate(beam):
+        lmf = lm.final(ls) if lm is not None else 0.0
+        finals.append((sc + hw[2] + lmf, i, lmf))
+    finals.sort(key=lambda e: (-e[0], e[1]))
+    y, sc, hw, fr, _ = beam[finals[0][1]]
+    return {"ids": list(y), "frames": list(fr), "score": sc + hw[2] + finals[0][2], "logp": sc, "lm": finals[0][2],
+            "beam": [(b[0], b[1]) for b in beam], "states": [b[4] for b in beam], "margins": margins, "merges": merges,
+            "final_margin": float(finals[0][0] - finals[1][0]) if len(finals) > 1 else np.inf}
 
 
 def min_margin(res: Dict[str, object]) -> float:

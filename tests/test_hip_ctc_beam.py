@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 import torch
 
-from common import load_case, report
+from beam_common import ctc_hotwords as _hotwords, ctc_op_engine, fullsize_ctc_model as _fullsize_model, log_probs as _log_probs
+from beam_common import bar as _bar, compare, run_ctc_op as _run_op, wav_file as _wav_file
+from common import load_case, make_engine as _make_engine, report
 
 import ctc_align_ref as A
 import ctc_beam_ref as R
@@ -25,52 +27,12 @@ MARGIN = 2e-5           # op level: T' <= 40 frames of O(1) relative ranks
 MARGIN_LONG = 1e-4      # model level: up to 500 frames
 
 
-def _bar(ref):
-    return 1e-3 * max(1.0, abs(ref))
-
-
-def _make_engine(cfg, state_dict, mode="f16x3", head=True):
-    from gigaam_amd.engine import HipEngine, build_config
-    eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg.get("head") if head else None), state_dict,
-                    torch.device("cuda:0"))
-    eng.set_gemm_mode(mode)
-    return eng
-
-
-_OP_ENGINE = []
-
-
 def _op_engine():
-    if not _OP_ENGINE:
-        from gigaam_amd import synth
-        _OP_ENGINE.append(_make_engine(synth.model_cfg("v2_ctc"), {}, head=False))
-    return _OP_ENGINE[0]
+    return ctc_op_engine(__name__)
 
 
-def _log_probs(rng, B, T, V, kind):
-    """Seeded log-probs [B, T, V] (float32, log_softmax units): "peaked" (one dominant class per frame) or "flat" (small logits)."""
-    x = rng.standard_normal((B, T, V)).astype(np.float32) * (0.3 if kind == "flat" else 1.0)
-    if kind == "peaked":
-        top = rng.integers(0, V, (B, T))
-        np.put_along_axis(x, top[..., None], 9.0, axis=2)
-    return torch.log_softmax(torch.from_numpy(x), dim=-1).numpy()
-
-
-def _hotwords(rng, lp, n):
-    """n phrases of 2-3 tokens, each token one of the two best non-blank ids of a frame of a run of frames: phrases the beam meets."""
-    B, T, _ = lp.shape
-    top2 = np.argsort(-lp[:, :, :-1], axis=2, kind="stable")[:, :, :2]
-    out = []
-    for _ in range(n):
-        b, L = int(rng.integers(0, B)), int(rng.integers(2, 4))
-        t = int(rng.integers(0, max(T - L, 1)))
-        out.append([int(top2[b, min(t + i, T - 1), rng.integers(0, 2)]) for i in range(L)])
-    return out
-
-
-def _run_op(eng, lp, enc_len, W):
-    out = eng.op_ctc_beam(torch.from_numpy(np.ascontiguousarray(lp)), torch.tensor(enc_len, dtype=torch.int32), W)
-    return out.host()
+def _compare(h, b, ref, errs, margin):
+    return compare(h, b, ref, errs, margin, R.min_margin)
 
 
 def _greedy(lp, T):
@@ -84,20 +46,6 @@ def _greedy(lp, T):
             frames.append(t)
         prev = v
     return ids, frames
-
-
-def _compare(h, b, ref, errs, margin):
-    """ids / frames exactly and score / logp within the bar if the utterance's margin allows; returns whether it qualified."""
-    got_ids, got_fr = h["rows"][b]
-    if R.min_margin(ref) <= margin:
-        return False
-    assert got_ids == ref["ids"], (b, got_ids, ref["ids"])
-    assert got_fr == ref["frames"], (b, got_fr, ref["frames"])
-    for k in ("score", "logp"):
-        e = abs(float(h[k][b]) - ref[k])
-        errs[k] = max(errs.get(k, 0.0), e / max(1.0, abs(ref[k])))
-        assert e <= _bar(ref[k]), (b, k, float(h[k][b]), ref[k])
-    return True
 
 
 def test_op_beam_is_exact_map_when_nothing_is_pruned():
@@ -256,12 +204,6 @@ def test_encoded_beam_on_golden_cases_matches_reference(name, mode):
     assert ok >= 0.5 * n, (ok, n)
 
 
-def _fullsize_model():
-    import gigaam_amd
-    from gigaam_amd import synth
-    return gigaam_amd.model_from_checkpoint(synth.make_checkpoint("v2_ctc", seed=0), "cuda:0")
-
-
 @pytest.mark.parametrize("mode", MODES)
 def test_fullsize32_transcribe_batch_beam_matches_reference(mode):
     """The 32 x 20 s, 16-layer batch: transcribe_batch(beam_size=8) against the reference beam run on HipEngine.ctc_head's
@@ -299,20 +241,6 @@ def test_fullsize32_transcribe_batch_beam_matches_reference(mode):
     torch.cuda.synchronize()
     report(f"ctc_beam_fullsize32_{mode}", qualified=f"{ok}/32", op_beam_w8_ms=e0.elapsed_time(e1) / 5)
     assert ok >= 16, ok
-
-
-def _wav_file(tmp_path, seconds, seed):
-    import wave
-    from gigaam_amd import synth
-    wav, _ = synth.synth_audio(1, seconds, seed=seed)
-    pcm = (wav[0].numpy() * 32768.0).round().clip(-32768, 32767).astype(np.int16)
-    p = str(tmp_path / f"clip{seed}.wav")
-    with wave.open(p, "wb") as wf:
-        wf.setnchannels(1)
-        wf.setsampwidth(2)
-        wf.setframerate(16000)
-        wf.writeframes(pcm.tobytes())
-    return p
 
 
 def test_model_hotword_makes_a_chosen_word_appear(tmp_path):

@@ -9,10 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from beam_common import arpa as _arpa, ctc_hotwords as _hotwords, ctc_op_engine, fullsize_ctc_model as _fullsize_model
+from beam_common import bar as _bar, compare, log_probs as _log_probs, run_ctc_op as _run, tokenizer as _tokenizer, wav_file as _wav_file
 from common import report
 
 import ctc_lm_ref as L
-from ctc_beam_ref import min_margin
+import ctc_beam_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -20,41 +22,17 @@ MARGIN = 2e-5
 MARGIN_LONG = 1e-4
 
 
-def _bar(ref):
-    return 1e-3 * max(1.0, abs(ref))
+def _op_engine():
+    return ctc_op_engine(__name__)
 
 
-_OP = []
+def _compare(h, b, ref, errs, margin):
+    return compare(h, b, ref, errs, margin, R.min_margin)
 
 
 def token_classes(tok):
     from gigaam_amd.lm import token_classes as tc
     return tc(tok)
-
-
-def _op_engine():
-    if not _OP:
-        from gigaam_amd import synth
-        from gigaam_amd.engine import HipEngine, build_config
-        cfg = synth.model_cfg("v2_ctc")
-        eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], None), {}, torch.device("cuda:0"))
-        eng.set_gemm_mode("f16x3")
-        _OP.append(eng)
-    return _OP[0]
-
-
-def _tokenizer(V):
-    from gigaam_amd import synth
-    from gigaam_amd.decoding import Tokenizer
-    return Tokenizer(synth.CHAR_VOCAB if V == 34 else synth._e2e_vocab(V - 1))
-
-
-def _log_probs(rng, B, T, V, kind):
-    x = rng.standard_normal((B, T, V)).astype(np.float32) * (0.3 if kind == "flat" else 1.0)
-    if kind == "peaked":
-        top = rng.integers(0, V, (B, T))
-        np.put_along_axis(x, top[..., None], 9.0, axis=2)
-    return torch.log_softmax(torch.from_numpy(x), dim=-1).numpy()
 
 
 def _word_ids(rng, lp, classes, n):
@@ -79,28 +57,6 @@ def _word_ids(rng, lp, classes, n):
     return sorted(out)
 
 
-def _arpa(rng, words, order, sentences=(), unk=True):
-    """ARPA text over ``words`` (strings): every unigram, random bigrams / trigrams plus those of ``sentences``."""
-    ng = {1: {w: (-rng.uniform(0.5, 3.0), -rng.uniform(0.0, 1.0)) for w in list(words) + ["<s>", "</s>"] + (["<unk>"] if unk else [])}}
-    ng[1]["</s>"] = (ng[1]["</s>"][0], 0.0)
-    voc = list(words)
-    for n in range(2, order + 1):
-        d = {}
-        for s in sentences:
-            ws = ["<s>"] + list(s) + ["</s>"]
-            for i in range(len(ws) - n + 1):
-                d[tuple(ws[i:i + n])] = None
-        for _ in range(3 * len(voc)):
-            d[tuple(["<s>"] * (rng.random() < 0.2) + [voc[rng.integers(0, len(voc))] for _ in range(n)])[:n]] = None
-        ng[n] = {k: (-rng.uniform(0.05, 1.5), -rng.uniform(0.0, 0.8) if n < order else 0.0) for k in d}
-    lines = ["\\data\\"] + [f"ngram {n}={len(ng[n])}" for n in range(1, order + 1)]
-    for n in range(1, order + 1):
-        lines += ["", f"\\{n}-grams:"]
-        for k, (p, b) in ng[n].items():
-            lines.append(f"{p:.4f}\t{' '.join(k if n > 1 else (k,))}" + (f"\t{b:.4f}" if n < order else ""))
-    return "\n".join(lines + ["", "\\end\\", ""])
-
-
 def _make_lm(tmp_path, rng, tok, word_ids, order, alpha, beta, sentences=(), unk=True, name="lm.arpa"):
     """(NgramLM, LMSpec) over words spelt by ``word_ids``; every spelling round-trips through lm.word_spelling."""
     from gigaam_amd import lm as LM
@@ -118,34 +74,6 @@ def _make_lm(tmp_path, rng, tok, word_ids, order, alpha, beta, sentences=(), unk
     p = tmp_path / name
     p.write_text(text, encoding="utf-8")
     return LM.NgramLM.from_arpa(str(p)), L.LMSpec(L.ArpaLM(text), classes, spell, alpha, beta)
-
-
-def _run(eng, lp, enc_len, W):
-    return eng.op_ctc_beam(torch.from_numpy(np.ascontiguousarray(lp)), torch.tensor(enc_len, dtype=torch.int32), W).host()
-
-
-def _compare(h, b, ref, errs, margin):
-    got_ids, got_fr = h["rows"][b]
-    if min_margin(ref) <= margin:
-        return False
-    assert got_ids == ref["ids"], (b, got_ids, ref["ids"])
-    assert got_fr == ref["frames"], (b, got_fr, ref["frames"])
-    for k in ("score", "logp"):
-        e = abs(float(h[k][b]) - ref[k])
-        errs[k] = max(errs.get(k, 0.0), e / max(1.0, abs(ref[k])))
-        assert e <= _bar(ref[k]), (b, k, float(h[k][b]), ref[k])
-    return True
-
-
-def _hotwords(rng, lp, n):
-    B, T, _ = lp.shape
-    top2 = np.argsort(-lp[:, :, :-1], axis=2, kind="stable")[:, :, :2]
-    out = []
-    for _ in range(n):
-        b, Lh = int(rng.integers(0, B)), int(rng.integers(2, 4))
-        t = int(rng.integers(0, max(T - Lh, 1)))
-        out.append([int(top2[b, min(t + i, T - 1), rng.integers(0, 2)]) for i in range(Lh)])
-    return out
 
 
 @pytest.mark.parametrize("V", [34, 257, 1025])
@@ -167,7 +95,7 @@ def test_op_beam_lm_matches_float64_reference(tmp_path, V, kind):
         eng.set_lm(lm, tok, 0.8, 0.6)
         h = _run(eng, lp, enc_len, W)
         for b in range(B):
-            ref = L.beam_search(lp[b], W, enc_len[b], phrases, 1.5, spec)
+            ref = R.beam_search(lp[b], W, enc_len[b], phrases, 1.5, spec)
             ok += _compare(h, b, ref, errs, MARGIN)
             n += 1
     eng.set_lm(None)
@@ -234,7 +162,7 @@ def test_lm_flips_a_near_tied_decision(tmp_path):
         assert tok.decode(h["rows"][0][0]) == f"{good} кот", (good, h["rows"][0])
         spec = L.LMSpec(L.ArpaLM(arpa(good, bad)), LM.token_classes(tok), {tuple(tok.encode(w)): w for w in ("да", "та", "кот")},
                         0.5, 1.0)
-        ref = L.beam_search(lp[0], 8, 7, lm=spec)
+        ref = R.beam_search(lp[0], 8, 7, lm=spec)
         assert ref["ids"] == h["rows"][0][0]
         assert abs(float(h["score"][0]) - ref["score"]) <= 1e-4 and abs(float(h["logp"][0]) - ref["logp"]) <= 1e-4
         assert float(h["score"][0]) != float(h["logp"][0])
@@ -290,12 +218,6 @@ def test_library_rejects_lm_beyond_the_limits():
     eng.op_ctc_beam(torch.zeros((1, 4, 7)), torch.tensor([4], dtype=torch.int32), 4).host()
 
 
-def _fullsize_model():
-    import gigaam_amd
-    from gigaam_amd import synth
-    return gigaam_amd.model_from_checkpoint(synth.make_checkpoint("v2_ctc", seed=0), "cuda:0")
-
-
 def test_fullsize32_transcribe_batch_lm_matches_reference(tmp_path):
     """The 32 x 20 s, 16-layer batch with an LM built from the batch's own greedy transcripts (so lookups hit every order) plus
     random words: transcribe_batch(lm=...) against the reference on the head's log-probs.  Also times the beam kernel alone."""
@@ -325,8 +247,8 @@ def test_fullsize32_transcribe_batch_lm_matches_reference(tmp_path):
     el = elen.cpu().tolist()
     ok = 0
     for b in range(32):
-        ref = L.beam_search(lp[b], 8, el[b], lm=spec)
-        if min_margin(ref) <= MARGIN_LONG:
+        ref = R.beam_search(lp[b], 8, el[b], lm=spec)
+        if R.min_margin(ref) <= MARGIN_LONG:
             continue
         ok += 1
         assert got[b][0] == tok.decode(ref["ids"]), b
@@ -340,20 +262,6 @@ def test_fullsize32_transcribe_batch_lm_matches_reference(tmp_path):
     torch.cuda.synchronize()
     report("ctc_beam_lm_fullsize32", qualified=f"{ok}/32", ngrams=lm.counts, op_beam_lm_w8_ms=e0.elapsed_time(e1) / 5)
     assert ok >= 16, ok
-
-
-def _wav_file(tmp_path, seconds, seed):
-    import wave
-    from gigaam_amd import synth
-    wav, _ = synth.synth_audio(1, seconds, seed=seed)
-    pcm = (wav[0].numpy() * 32768.0).round().clip(-32768, 32767).astype(np.int16)
-    p = str(tmp_path / f"clip{seed}.wav")
-    with wave.open(p, "wb") as wf:
-        wf.setnchannels(1)
-        wf.setsampwidth(2)
-        wf.setframerate(16000)
-        wf.writeframes(pcm.tobytes())
-    return p
 
 
 def test_model_lm_transcribe_batch_longform_and_greedy_default(tmp_path):
@@ -386,9 +294,9 @@ def test_model_lm_transcribe_batch_longform_and_greedy_default(tmp_path):
     el = elen.cpu().tolist()
     ok = 0
     for b in range(3):
-        ref = L.beam_search(lp[b], 8, el[b], lm=spec)
+        ref = R.beam_search(lp[b], 8, el[b], lm=spec)
         assert dec[b][0] == got[b][0]
-        if min_margin(ref) <= MARGIN_LONG:
+        if R.min_margin(ref) <= MARGIN_LONG:
             continue
         ok += 1
         assert got[b][0] == tok.decode(ref["ids"]), b

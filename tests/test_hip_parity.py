@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from common import make_engine as _make_engine
 from common import (CASES, TOL_ENC, TOL_FEAT, TOL_FEAT_WEAK, TOL_LOGP, frontend_fixture, golden_trace, load_case, logmel_err,
                     oracle_features, ragged_from_device, report, tol_pre, split_ragged, valid_mask)
 from oracle import gigaam_oracle as O
@@ -16,16 +17,6 @@ SUPPORTED = list(CASES)
 # Every arithmetic mode of the dense contractions must hold the same bars: "f16x3" = the product's default (three-term split on the
 # LDS-DMA kernels of gam_gemm_sp.h; the v3 conv1d stem and v1's rel-pos projection included), "f32" = exact-fp32 MFMA.
 MODES = ["f16x3", "f32"]
-
-
-def _make_engine(cfg, state_dict, mode, head=True):
-    """mode "f16x3": the product's default; "f32": exact-fp32 MFMA."""
-    from gigaam_amd.engine import HipEngine, build_config
-    eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg.get("head") if head else None), state_dict,
-                    torch.device("cuda:0"))
-    eng.set_gemm_mode(mode)
-    assert eng.gemm_mode == mode
-    return eng
 
 
 def _engine(ck, mode="f16x3"):

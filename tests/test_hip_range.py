@@ -9,8 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from common import TOL_ENC, load_case, oracle_features, report, valid_mask
-from test_hip_parity import _make_engine
+from common import TOL_ENC, load_case, make_engine as _make_engine, oracle_features, report, valid_mask
 
 pytestmark = pytest.mark.gpu
 

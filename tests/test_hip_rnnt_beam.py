@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from beam_common import bar as _bar, compare, encp as _encp, fullsize_rnnt_model, run_rnnt_op as _run_op, small_rnnt_model, wav_file as _wav_file
 from common import load_case, report
 
 import rnnt_beam_ref as R
@@ -25,11 +26,19 @@ MARGIN = 1e-4           # op level: <= 24 frames; fp32 LSTM and joint against fp
 MARGIN_LONG = 5e-4      # model level: up to 500 frames, the encoder projection in the engine's GEMM mode
 
 
-def _bar(ref):
-    return 1e-3 * max(1.0, abs(ref))
-
-
 _ENGINES = {}
+
+
+def _compare(h, b, ref, errs, margin):
+    return compare(h, b, ref, errs, margin, R.min_margin)
+
+
+def _fullsize_model():
+    return fullsize_rnnt_model()[0]
+
+
+def _small_rnnt_model():
+    return small_rnnt_model()[0]
 
 
 def _engine(V, L=1, blank_bias=None, out_scale=1.0):
@@ -50,10 +59,6 @@ def _engine(V, L=1, blank_bias=None, out_scale=1.0):
     return _ENGINES[key]
 
 
-def _encp(rng, B, T, JH, scale):
-    return (rng.standard_normal((B, T, JH)) * scale).astype(np.float32)
-
-
 def _hotwords(rng, res_ids, V, n):
     """n phrases of 1-3 tokens: runs of tokens the reference emitted (phrases the beam meets), padded with random ones."""
     out = []
@@ -65,23 +70,6 @@ def _hotwords(rng, res_ids, V, n):
         else:
             out.append([int(c) for c in rng.integers(0, V - 1, int(rng.integers(1, 3)))])
     return out
-
-
-def _run_op(eng, encp, enc_len, W, S):
-    return eng.op_rnnt_beam(torch.from_numpy(np.ascontiguousarray(encp)), torch.tensor(enc_len, dtype=torch.int32), W, S).host()
-
-
-def _compare(h, b, ref, errs, margin):
-    got_ids, got_fr = h["rows"][b]
-    if R.min_margin(ref) <= margin:
-        return False
-    assert got_ids == ref["ids"], (b, got_ids, ref["ids"])
-    assert got_fr == ref["frames"], (b, got_fr, ref["frames"])
-    for k in ("score", "logp"):
-        e = abs(float(h[k][b]) - ref[k])
-        errs[k] = max(errs.get(k, 0.0), e / max(1.0, abs(ref[k])))
-        assert e <= _bar(ref[k]), (b, k, float(h[k][b]), ref[k])
-    return True
 
 
 @pytest.mark.parametrize("L", [1, 2])
@@ -258,17 +246,6 @@ def test_encoded_beam_on_golden_cases_matches_reference(name, mode):
     assert 3 * ok >= n, (ok, n)      # (the emission-heavy *_dense cases hold many near-ties over 100 frames)
 
 
-def _fullsize_model():
-    import json
-    import os
-
-    import gigaam_amd
-    from common import ROOT
-    from gigaam_amd import synth
-    meta = json.load(open(os.path.join(ROOT, "tests", "golden", "fullsize_meta.json")))["fullsize_v2_rnnt"]
-    return gigaam_amd.model_from_checkpoint(synth.make_checkpoint("v2_rnnt", seed=0, rnnt_blank_bias=meta.get("blank_bias")), "cuda:0")
-
-
 def test_fullsize32_transcribe_batch_beam_matches_reference():
     """32 x 20 s v2_rnnt through the model at W = 4 (set_decoding) against the reference run on the GPU encoder's output; word
     timestamps come from the beam's token frames.  Also times the beam kernel alone (device events)."""
@@ -320,26 +297,6 @@ def model_state(model):
         meta = json.load(open(os.path.join(ROOT, "tests", "golden", "fullsize_meta.json")))["fullsize_v2_rnnt"]
         _STATE["v2_rnnt"] = synth.make_checkpoint("v2_rnnt", seed=0, rnnt_blank_bias=meta.get("blank_bias"))["state_dict"]
     return _STATE["v2_rnnt"]
-
-
-def _wav_file(tmp_path, seconds, seed):
-    import wave
-    from gigaam_amd import synth
-    wav, _ = synth.synth_audio(1, seconds, seed=seed)
-    pcm = (wav[0].numpy() * 32768.0).round().clip(-32768, 32767).astype(np.int16)
-    p = str(tmp_path / f"clip{seed}.wav")
-    with wave.open(p, "wb") as wf:
-        wf.setnchannels(1)
-        wf.setsampwidth(2)
-        wf.setframerate(16000)
-        wf.writeframes(pcm.tobytes())
-    return p
-
-
-def _small_rnnt_model():
-    import gigaam_amd
-    from gigaam_amd import synth
-    return gigaam_amd.model_from_checkpoint(synth.make_checkpoint("v2_rnnt", seed=1, n_layers=2, rnnt_blank_bias=12.0), "cuda:0")
 
 
 def test_model_set_decoding_paths_and_greedy_restore(tmp_path):

@@ -1,5 +1,5 @@
 """GPU: RNN-T beam search with a word n-gram LM (gam_set_lm; gam_rnnt_beam_kernel<true> of gigaam_amd/csrc/gam_rnnt_beam.h) against
-the float64 reference of tests/rnnt_lm_ref.py -- alone and with hotwords, at V 34 / 257 / 1025 and L 1 / 2 --, bit-identity with the
+the float64 reference of tests/rnnt_beam_ref.py -- alone and with hotwords, at V 34 / 257 / 1025 and L 1 / 2 --, bit-identity with the
 kernel without LM at alpha = beta = 0, an LM that flips a near-tied decision, streams, limits, the full-size 32 x 20 s batch and the
 model (set_decoding).
 
@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 import torch
 
+from beam_common import arpa as _arpa, bar as _bar, compare, encp as _encp, fullsize_rnnt_model as _fullsize_model
+from beam_common import run_rnnt_op as _run_op, small_rnnt_model as _small_rnnt_model, tokenizer as _tokenizer, wav_file as _wav_file
 from common import report
 
 import ctc_lm_ref as CL
 import rnnt_beam_ref as R
-import rnnt_lm_ref as RL
-from test_hip_ctc_beam_lm import _arpa
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +23,11 @@ MARGIN = 1e-4
 MARGIN_LONG = 5e-4
 
 
-def _bar(ref):
-    return 1e-3 * max(1.0, abs(ref))
-
-
 _ENGINES = {}
+
+
+def _compare(h, b, ref, errs, margin):
+    return compare(h, b, ref, errs, margin, R.min_margin)
 
 
 def _engine(V, L=1, H=320, blank_bias=None):
@@ -44,12 +44,6 @@ def _engine(V, L=1, H=320, blank_bias=None):
         eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg["head"]), sd, torch.device("cuda:0"))
         _ENGINES[key] = (eng, R.head_from_state_dict(sd, L), cfg, sd)
     return _ENGINES[key]
-
-
-def _tokenizer(V):
-    from gigaam_amd import synth
-    from gigaam_amd.decoding import Tokenizer
-    return Tokenizer(synth.CHAR_VOCAB if V == 34 else synth._e2e_vocab(V - 1))
 
 
 def _words(tok, classes, id_lists, rng, n_random):
@@ -83,27 +77,6 @@ def _make_lm(tmp_path, rng, tok, id_lists, order, alpha, beta, unk=True, name="l
     return LM.NgramLM.from_arpa(str(p)), CL.LMSpec(CL.ArpaLM(text), classes, spell, alpha, beta)
 
 
-def _encp(rng, B, T, JH, scale=1.0):
-    return (rng.standard_normal((B, T, JH)) * scale).astype(np.float32)
-
-
-def _run_op(eng, encp, enc_len, W, S):
-    return eng.op_rnnt_beam(torch.from_numpy(np.ascontiguousarray(encp)), torch.tensor(enc_len, dtype=torch.int32), W, S).host()
-
-
-def _compare(h, b, ref, errs, margin):
-    got_ids, got_fr = h["rows"][b]
-    if R.min_margin(ref) <= margin:
-        return False
-    assert got_ids == ref["ids"], (b, got_ids, ref["ids"])
-    assert got_fr == ref["frames"], (b, got_fr, ref["frames"])
-    for k in ("score", "logp"):
-        e = abs(float(h[k][b]) - ref[k])
-        errs[k] = max(errs.get(k, 0.0), e / max(1.0, abs(ref[k])))
-        assert e <= _bar(ref[k]), (b, k, float(h[k][b]), ref[k])
-    return True
-
-
 @pytest.mark.parametrize("L", [1, 2])
 @pytest.mark.parametrize("V", [34, 257, 1025])
 def test_op_beam_lm_matches_float64_reference(tmp_path, V, L):
@@ -127,7 +100,7 @@ def test_op_beam_lm_matches_float64_reference(tmp_path, V, L):
         eng.set_lm(lm, tok, 0.8, 0.6)
         h = _run_op(eng, encp, enc_len, W, S)
         for b in range(B):
-            ref = RL.beam_search(head, encp[b].astype(np.float64), W, S, enc_len[b], phrases, 1.5, lm=spec)
+            ref = R.beam_search(head, encp[b].astype(np.float64), W, S, enc_len[b], phrases, 1.5, lm=spec)
             ok += _compare(h, b, ref, errs, MARGIN)
             n += 1
     eng.set_lm(None)
@@ -213,7 +186,7 @@ def test_lm_flips_a_near_tied_decision(tmp_path):
         assert tok.decode(h["rows"][0][0]) == f"{good} кот", (good, h["rows"][0])
         spec = CL.LMSpec(CL.ArpaLM(arpa(good, bad)), LM.token_classes(tok), {tuple(tok.encode(w)): w for w in ("да", "та", "кот")},
                          0.5, 1.0)
-        ref = RL.beam_search(head, encp[0].astype(np.float64), 8, 1, 7, lm=spec)
+        ref = R.beam_search(head, encp[0].astype(np.float64), 8, 1, 7, lm=spec)
         assert ref["ids"] == h["rows"][0][0] and ref["frames"] == h["rows"][0][1]
         assert abs(float(h["score"][0]) - ref["score"]) <= 1e-4 and abs(float(h["logp"][0]) - ref["logp"]) <= 1e-4
         assert float(h["score"][0]) != float(h["logp"][0])
@@ -290,18 +263,6 @@ def test_every_width_and_max_symbols_is_accepted_at_the_head_shapes_with_lm_and_
     assert n == 512
 
 
-def _fullsize_model():
-    import json
-    import os
-
-    import gigaam_amd
-    from common import ROOT
-    from gigaam_amd import synth
-    meta = json.load(open(os.path.join(ROOT, "tests", "golden", "fullsize_meta.json")))["fullsize_v2_rnnt"]
-    ck = synth.make_checkpoint("v2_rnnt", seed=0, rnnt_blank_bias=meta.get("blank_bias"))
-    return gigaam_amd.model_from_checkpoint(ck, "cuda:0"), ck["state_dict"]
-
-
 def test_fullsize32_transcribe_batch_beam_lm_matches_reference(tmp_path):
     """32 x 20 s v2_rnnt at W = 4 with an LM built from the batch's own greedy transcripts plus random words (set_decoding(lm=...))
     against the reference on the GPU encoder's output.  Also times the beam kernel alone with and without the LM."""
@@ -331,7 +292,7 @@ def test_fullsize32_transcribe_batch_beam_lm_matches_reference(tmp_path):
     el = elen.cpu().tolist()
     ok = 0
     for b in range(32):
-        ref = RL.beam_search(head, R.encoder_projection(head, encd[b]), 4, 10, el[b], lm=spec)
+        ref = R.beam_search(head, R.encoder_projection(head, encd[b]), 4, 10, el[b], lm=spec)
         if R.min_margin(ref) <= MARGIN_LONG:
             continue
         ok += 1
@@ -350,29 +311,6 @@ def test_fullsize32_transcribe_batch_beam_lm_matches_reference(tmp_path):
         times[key] = e0.elapsed_time(e1) / 3
     report("rnnt_beam_lm_fullsize32", qualified=f"{ok}/32", ngrams=lm.counts, **times)
     assert ok >= 16, ok
-
-
-def _wav_file(tmp_path, seconds, seed):
-    import wave
-    from gigaam_amd import synth
-    wav, _ = synth.synth_audio(1, seconds, seed=seed)
-    pcm = (wav[0].numpy() * 32768.0).round().clip(-32768, 32767).astype(np.int16)
-    p = str(tmp_path / f"clip{seed}.wav")
-    with wave.open(p, "wb") as wf:
-        wf.setnchannels(1)
-        wf.setsampwidth(2)
-        wf.setframerate(16000)
-        wf.writeframes(pcm.tobytes())
-    return p
-
-
-def _small_rnnt_model(decoding=None):
-    import gigaam_amd
-    from gigaam_amd import synth
-    ck = synth.make_checkpoint("v2_rnnt", seed=1, n_layers=2, rnnt_blank_bias=12.0)
-    if decoding is not None:
-        ck["cfg"]["decoding"] = decoding
-    return gigaam_amd.model_from_checkpoint(ck, "cuda:0"), ck["state_dict"]
 
 
 def test_model_set_decoding_lm_paths_and_greedy_restore(tmp_path):
@@ -415,7 +353,7 @@ def test_model_set_decoding_lm_paths_and_greedy_restore(tmp_path):
     for b in range(3):
         assert dec[b][0] == batch[b][0]
         assert all(w.start <= w.end for w in batch[b][1])
-        ref = RL.beam_search(head, R.encoder_projection(head, encd[b]), 4, 10, el[b], lm=spec)
+        ref = R.beam_search(head, R.encoder_projection(head, encd[b]), 4, 10, el[b], lm=spec)
         if R.min_margin(ref) <= MARGIN_LONG:
             continue
         ok += 1

@@ -1,5 +1,5 @@
 """CPU: the word n-gram LM of the CTC beam search -- the ARPA parser and back-off scores of gigaam_amd/lm.py, its device tables
-queried by a host emulation of the kernel's probe (gam_beam.h), the spelling hashes against tests/ctc_lm_ref.py for char-wise,
+queried by a host emulation of the kernel's probe (gam_search.h), the spelling hashes against tests/ctc_lm_ref.py for char-wise,
 piece and SentencePiece vocabularies, and the float64 reference itself: alpha = beta = 0 is the search without an LM, and an
 unbounded beam is the brute-force MAP of log p + LM term."""
 import gzip
@@ -252,10 +252,9 @@ def test_reference_with_zero_weights_is_the_search_without_lm():
         W = [1, 2, 4, 8, None][trial % 5]
         hot = [[0, 1]] if trial % 3 == 0 else []
         a = R.beam_search(lp, W, hotwords=hot, beta=1.5)
-        b = L.beam_search(lp, W, hotwords=hot, beta=1.5, lm=_spec(0.0, 0.0))
-        c = L.beam_search(lp, W, hotwords=hot, beta=1.5)
+        b = R.beam_search(lp, W, hotwords=hot, beta=1.5, lm=_spec(0.0, 0.0))
         for k in ("ids", "frames", "score", "logp", "margins", "final_margin"):
-            assert a[k] == b[k] == c[k], (trial, k)
+            assert a[k] == b[k], (trial, k)
 
 
 def test_reference_lm_term_follows_the_word_rule():
@@ -293,7 +292,7 @@ def test_unbounded_beam_with_lm_is_exact_map():
         for T in (1, 2, 3, 4):
             for _ in range(3):
                 lp = np.log(rng.dirichlet(np.ones(5) * 0.5, size=T))
-                res = L.beam_search(lp, None, lm=spec)
+                res = R.beam_search(lp, None, lm=spec)
                 y, val, ll = _brute_map(lp, T, spec)
                 assert res["ids"] == y, (alpha, beta, T, res["ids"], y)
                 assert res["score"] == pytest.approx(val, abs=1e-9)

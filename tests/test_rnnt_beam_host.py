@@ -7,25 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from beam_common import small_sd as _small_sd
 from common import O
 
 import rnnt_beam_ref as R
 from ctc_beam_ref import Trie
-
-
-def _small_sd(rng, V, H=8, JH=8, D=6, L=1, out_gain=1.0, blank_bias=0.0):
-    """A small RNN-T head as a float32 state dict (checkpoint key names)."""
-    t = lambda *s, g=1.0: torch.from_numpy((rng.standard_normal(s) * g).astype(np.float32))     # noqa: E731
-    sd = {"head.decoder.embed.weight": t(V, H)}
-    sd["head.decoder.embed.weight"][V - 1] = 0.0
-    for l in range(L):
-        for k, s in (("weight_ih", (4 * H, H)), ("weight_hh", (4 * H, H)), ("bias_ih", (4 * H,)), ("bias_hh", (4 * H,))):
-            sd[f"head.decoder.lstm.{k}_l{l}"] = t(*s, g=0.5)
-    sd["head.joint.enc.weight"], sd["head.joint.enc.bias"] = t(JH, D, g=0.6), t(JH, g=0.2)
-    sd["head.joint.pred.weight"], sd["head.joint.pred.bias"] = t(JH, H, g=0.6), t(JH, g=0.2)
-    sd["head.joint.joint_net.1.weight"], sd["head.joint.joint_net.1.bias"] = t(V, JH, g=out_gain), t(V, g=0.3)
-    sd["head.joint.joint_net.1.bias"][V - 1] += blank_bias
-    return sd
 
 
 @pytest.mark.parametrize("hot", [False, True])

@@ -1,4 +1,4 @@
-"""CPU: the float64 reference of RNN-T beam search with a word n-gram LM (tests/rnnt_lm_ref.py) -- with zero weights it is
+"""CPU: the float64 reference of RNN-T beam search with a word n-gram LM (tests/rnnt_beam_ref.py) -- with zero weights it is
 tests/rnnt_beam_ref.py's search exactly, with nothing pruned its pick is the exact MAP of log P_S(y | x) + LM term, merged hypotheses
 agree on their LM state -- under char-wise and SentencePiece-style word classes, with and without an <unk> unigram, at orders 1-5;
 and the decoding object / set_decoding API with an LM, without a GPU."""
@@ -7,11 +7,11 @@ import itertools
 import numpy as np
 import pytest
 
+from beam_common import small_sd as _small_sd
+
 import ctc_lm_ref as CL
 import rnnt_beam_ref as R
-import rnnt_lm_ref as RL
 from ctc_beam_ref import Trie
-from test_rnnt_beam_host import _small_sd
 
 # token classes over V - 1 non-blank ids (+ blank, class 0): char-wise letters and a space separator, or SentencePiece-style pieces
 # (class 1 starts a word, as a piece beginning with U+2581 does)
@@ -68,11 +68,9 @@ def test_zero_weights_equal_the_search_without_lm(kind):
         spec = _spec(rng, CLASSES[kind][V], 3, 0.0, 0.0)
         hw = [[0, 1], [V - 2]] if hot else []
         a = R.beam_search(head, encp, W, S, hotwords=hw, beta=1.5)
-        b = RL.beam_search(head, encp, W, S, hotwords=hw, beta=1.5, lm=spec)
-        c = RL.beam_search(head, encp, W, S, hotwords=hw, beta=1.5)
-        for r in (b, c):
-            for k in ("ids", "frames", "score", "logp", "beam", "margins", "final_margin"):
-                assert r[k] == a[k], (seed, k)
+        b = R.beam_search(head, encp, W, S, hotwords=hw, beta=1.5, lm=spec)
+        for k in ("ids", "frames", "score", "logp", "beam", "margins", "final_margin"):
+            assert b[k] == a[k], (seed, k)
         n += 1
     assert n == 4
 
@@ -87,7 +85,7 @@ def test_unbounded_beam_with_lm_is_exact_map(order, kind, unk):
         rng, head, encp = _case(1000 * order + 10 * trial + (5 if unk else 0) + (2 if kind == "piece" else 0), V, out_gain=0.8, T=T)
         spec = _spec(rng, CLASSES[kind][V], order, 1.3, 0.7, unk)
         hw = [[0, 1]] if trial == 1 else []
-        res = RL.beam_search(head, encp, 10 ** 6, S, hotwords=hw, beta=1.0, lm=spec)
+        res = R.beam_search(head, encp, 10 ** 6, S, hotwords=hw, beta=1.0, lm=spec)
         pred = R.Predictor(head)
         joint = lambda t, y: R.joint_lp(head, encp[t], pred(y))     # noqa: E731
         for y, sc in res["beam"]:
@@ -114,7 +112,7 @@ def test_merged_hypotheses_agree_on_their_lm_state(kind):
     for seed in range(4):
         rng, head, encp = _case(50 + seed, 5, L=2, out_gain=1.2, blank_bias=3.0, T=10)
         spec = _spec(rng, CLASSES[kind][5], 3, 0.9, 0.4)
-        res = RL.beam_search(head, encp, 32, 3, lm=spec)
+        res = R.beam_search(head, encp, 32, 3, lm=spec)
         merges += res["merges"]
         for (y, _), st in zip(res["beam"], res["states"]):
             want = spec.start()
@@ -139,11 +137,11 @@ def test_lm_changes_the_pick_on_a_near_tie():
             p[V - 1] = 0.99
         return np.log(p / p.sum())
 
-    plain = RL.beam_search(None, None, 4, 1, T=3, joint=joint)
+    plain = R.beam_search(None, None, 4, 1, T=3, joint=joint)
     assert plain["ids"] == [0, 2]
     arpa = "\\data\\\nngram 1=5\n\n\\1-grams:\n-1.0\t<s>\n-1.0\t</s>\n-3.0\ta\n-0.5\tb\n-2.0\t<unk>\n\n\\end\\\n"
     spec = CL.LMSpec(CL.ArpaLM(arpa), classes, {(0,): "a", (1,): "b"}, 0.5, 0.0)
-    res = RL.beam_search(None, None, 4, 1, T=3, joint=joint, lm=spec)
+    res = R.beam_search(None, None, 4, 1, T=3, joint=joint, lm=spec)
     assert res["ids"] == [1, 2]
     assert res["score"] == pytest.approx(res["logp"] + CL.lm_term([1, 2], spec), abs=1e-12)
 
@@ -151,7 +149,7 @@ def test_lm_changes_the_pick_on_a_near_tie():
 def test_empty_utterance_with_lm():
     rng, head, _ = _case(0, 4)
     spec = _spec(rng, CLASSES["char"][4], 2, 0.5, 1.0)
-    res = RL.beam_search(head, np.zeros((3, 8)), 4, 2, T=0, lm=spec)
+    res = R.beam_search(head, np.zeros((3, 8)), 4, 2, T=0, lm=spec)
     assert res["ids"] == [] and res["logp"] == 0.0
     assert res["score"] == pytest.approx(0.5 * spec.lm.lnprob("</s>", ["<s>"]), abs=1e-12)
 
