@@ -61,6 +61,10 @@ SIGNATURES = {
     "gam_rnnt_greedy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
     "gam_rnnt_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_rnnt_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gam_rnnt_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "gam_op_rnnt_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gam_op_rnnt_lattice_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "gam_set_rnnt_align_workspace": (C.c_int, [_P, C.c_int64]),
     "gam_emo_probs": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P]),
     "gam_rnnt_predict": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "gam_rnnt_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),

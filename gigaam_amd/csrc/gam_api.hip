@@ -23,6 +23,7 @@
 #include "gam_common.h"
 #include "gam_convmod.h"
 #include "gam_decode.h"
+#include "gam_rnnt_align.h"
 #include "gam_decode_cluster.h"
 #include "gam_frontend.h"
 #include "gam_gemm.h"
@@ -132,6 +133,9 @@ struct gam_handle {
   DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
   DevBuf beam_nodes;                    // CTC beam search prefix-trie nodes, B x T' x W (gam_beam.h)
   DevBuf rb_ws, rb_nodes;               // RNN-T beam search: predictor-state slots + logit rows, prefix-trie nodes (gam_rnnt_beam.h)
+  DevBuf ra_g, ra_pp, ra_lat, ra_bp;    // transducer alignment (gam_rnnt_align.h): predictor outputs, their projection, the (lb, le)
+                                        // lattice of one slice, backpointers that do not fit the sweep kernel's LDS
+  size_t ra_ws_limit = GAM_RA_WS_DEFAULT;   // bytes of lattice per slice (gam_set_rnnt_align_workspace; GAM_RNNT_ALIGN_WS at gam_create)
   int* hw_trie = nullptr;               // hotword trie of gam_set_hotwords (CSR, gam_search.h): offsets | edges; NULL = no hotwords
   size_t hw_cap = 0;                    // ints allocated at hw_trie
   int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
@@ -511,6 +515,7 @@ int gam_create(const gam_config* cfg, int device_id, gam_handle** out) {
   if (const char* e = getenv("GAM_GRAPH")) h->use_graph = atoi(e);
   if (const char* e = getenv("GAM_GRAPH_MAX_ROWS")) h->graph_max_rows = atoi(e);
   if (const char* e = getenv("GAM_RNNT_CLUSTER")) h->rnnt_cluster = std::max(-1, std::min(8, atoi(e)));   // (the range gam_set_rnnt_cluster accepts)
+  if (const char* e = getenv("GAM_RNNT_ALIGN_WS")) h->ra_ws_limit = (size_t)std::max(1ll, atoll(e));
   if (const char* e = getenv("GAM_RNNT_EXCLUSIVE")) h->rnnt_exclusive = atoi(e);
   if (const char* e = getenv("GAM_RNNT_COOP")) h->rnnt_coop = atoi(e);
   if (const char* e = getenv("GAM_RNNT_FORCE_TIMEOUT")) h->rnnt_force_timeout = atoi(e);
@@ -561,6 +566,8 @@ void gam_destroy(gam_handle* h) {
   if (h->beam_nodes.p) hipFree(h->beam_nodes.p);
   if (h->rb_ws.p) hipFree(h->rb_ws.p);
   if (h->rb_nodes.p) hipFree(h->rb_nodes.p);
+  for (DevBuf* b : {&h->ra_g, &h->ra_pp, &h->ra_lat, &h->ra_bp})
+    if (b->p) hipFree(b->p);
   if (h->hw_trie) hipFree(h->hw_trie);
   if (h->lm_cls) hipFree(h->lm_cls);
   if (h->lm_wt) hipFree(h->lm_wt);
@@ -1940,6 +1947,150 @@ int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, i
   HIPCHK(h, hipSetDevice(h->device));
   DecodeScope ds(h, s);
   return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s);
+}
+
+// ---- transducer forced alignment (gam_rnnt_align.h).  Decode class (the caller holds a DecodeScope): every buffer is the handle's.
+// The lattice sweep over (lb, le) float2 [B, Tp, Umax + 1]: one workgroup per utterance.
+static int rnnt_lattice_dp_launch(gam_handle* h, const float2* lat, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
+                                  const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
+                                  hipStream_t s) {
+  const int u1 = Umax + 1;
+  const int nt = std::min(GAM_RA_MAX_NT, std::max(64, (u1 + 63) / 64 * 64));
+  const int spt = (u1 + nt - 1) / nt;
+  const int nchunk = (u1 + 63) / 64;
+  const bool bp_lds = gam_ra_dp_lds_bytes(true, (int)Tp, Umax, nchunk, spt, nt) <= GAM_RA_LDS_MAX;
+  const size_t sm = gam_ra_dp_lds_bytes(bp_lds, (int)Tp, Umax, nchunk, spt, nt);
+  GamRnntDpArgs a;
+  a.lat = lat; a.enc_len = enc_len; a.targets = targets; a.target_len = target_len;
+  a.Tp = (int)Tp; a.Umax = Umax; a.V = V; a.nchunk = nchunk; a.bp_glob = nullptr;
+  a.tok_frame = tok_frame; a.score = score; a.loglik = loglik; a.status = status;
+  if (!bp_lds) {
+    if (int r = ensure(h, h->ra_bp, (size_t)B * (Tp + Umax) * nchunk * 2 + 64)) return r;
+    a.bp_glob = reinterpret_cast<unsigned long long*>(h->ra_bp.p);
+  }
+  static std::atomic<unsigned long long> lds_set[4];
+  const int which = (bp_lds ? 2 : 0) + (spt - 1);
+  void (*const kerns[4])(GamRnntDpArgs) = {gam_rnnt_lattice_dp_kernel<false, 1>, gam_rnnt_lattice_dp_kernel<false, 2>,
+                                           gam_rnnt_lattice_dp_kernel<true, 1>, gam_rnnt_lattice_dp_kernel<true, 2>};
+  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds((const void*)kerns[which], GAM_RA_LDS_MAX, lds_set[which]));
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * u1 * 8.0);
+  hipLaunchKernelGGL(kerns[which], dim3(B), dim3(nt), sm, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+static int rnnt_align_shape_check(gam_handle* h, int B, int64_t Tp, int Umax, int V, bool null_buf) {
+  if (B <= 0 || Tp <= 0 || V < 2) return fail(h, -1, "RNN-T alignment: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
+  if (Tp > GAM_RA_MAX_T) return fail(h, -1, "RNN-T alignment: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_RA_MAX_T);
+  if (Umax < 0 || Umax > GAM_RA_MAX_U) return fail(h, -1, "RNN-T alignment: Umax=%d tokens outside [0, %d]", Umax, GAM_RA_MAX_U);
+  if (V > GAM_BEAM_MAX_V) return fail(h, -1, "RNN-T alignment: V=%d outside [2, %d]", V, GAM_BEAM_MAX_V);
+  if (null_buf) return fail(h, -1, "RNN-T alignment: NULL buffer");
+  return 0;
+}
+
+// The whole alignment from the encoder projection encp [B, Tp, JH]: predictor, its projection, then per slice of utterances the fused
+// lattice kernel and the sweep.  lattice_out (may be NULL): a copy of the (lb, le) lattice, [B, Tp, Umax + 1] float2.
+static int rnnt_align_launch(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                             const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
+                             float* lattice_out, hipStream_t s) {
+  const gam_config& c = h->cfg;
+  const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden, L = c.pred_rnn_layers;
+  if (int r = rnnt_align_shape_check(h, B, Tp, Umax, V,
+                                     !encp || !enc_len || !target_len || !score || !loglik || !status || (Umax > 0 && (!targets || !tok_frame))))
+    return r;
+  if (H > GAM_RA_MAX_H || JH > GAM_RA_MAX_H || H % 16 != 0 || JH % 16 != 0 || L < 1 || L > 4)
+    return fail(h, -1, "RNN-T alignment: H=%d / JH=%d must be multiples of 16 up to %d, 1..4 predictor layers (L=%d)", H, JH, GAM_RA_MAX_H, L);
+  const int u1 = Umax + 1;
+  const size_t per = (size_t)Tp * u1 * sizeof(float2);      // lattice bytes of one utterance
+  if (per > h->ra_ws_limit)
+    return fail(h, -1, "RNN-T alignment: the lattice of one utterance (T'=%lld x %d nodes) takes %zu bytes, the workspace limit is %zu bytes",
+                (long long)Tp, u1, per, h->ra_ws_limit);
+  const int nb = (int)std::min<size_t>((size_t)B, h->ra_ws_limit / per);
+  if (int r = ensure(h, h->ra_g, (size_t)B * u1 * H + 64)) return r;
+  if (int r = ensure(h, h->ra_pp, (size_t)B * u1 * JH + 64)) return r;
+  if (int r = ensure(h, h->ra_lat, (size_t)nb * Tp * u1 * 2 + 64)) return r;
+  {
+    GamRnntTfArgs a;
+    a.targets = targets; a.target_len = target_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x;
+    a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x; a.g = h->ra_g.p; a.Umax = Umax; a.V = V; a.H = H; a.L = L;
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)B * u1 * L * 8.0 * H * H * 4.0);
+    const size_t sm = gam_ra_tf_lds_bytes(H, L);
+    if (4 * H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<5>, dim3(B), dim3(256), sm, s, a);
+    else hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<8>, dim3(B), dim3(256), sm, s, a);
+    HIPCHK(h, hipGetLastError());
+  }
+  GamGemmArgs gp = gemm_args(h->ra_g.p, H, h->jn_pred_w, h->jn_pred_b, h->ra_pp.p, JH, B * u1, JH, H);
+  if (int r = gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  static std::atomic<unsigned long long> lds_set;
+  const size_t sml = gam_ra_lat_lds_bytes(JH);
+  if (sml > 64 * 1024) HIPCHK(h, gam_set_max_lds((const void*)gam_rnnt_lattice_kernel, GAM_RA_LDS_MAX, lds_set));
+  for (int b0 = 0; b0 < B; b0 += nb) {
+    const int n = std::min(nb, B - b0);
+    GamRnntLatArgs a;
+    a.encp = encp + (size_t)b0 * Tp * JH; a.predp = h->ra_pp.p + (size_t)b0 * u1 * JH; a.enc_len = enc_len + b0;
+    a.targets = targets ? targets + (size_t)b0 * Umax : nullptr; a.target_len = target_len + b0; a.wout = h->jn_out_w; a.bout = h->jn_out_b;
+    a.lat = reinterpret_cast<float2*>(h->ra_lat.p); a.Tp = (int)Tp; a.Umax = Umax; a.V = V; a.JH = JH;
+    {
+      ProfScope ps(h, s, GAM_PF_DECODE, (double)n * Tp * u1 * ((double)V * JH * 2.0));
+      hipLaunchKernelGGL(gam_rnnt_lattice_kernel, dim3(gam_cdiv(Tp, GAM_RA_TF), gam_cdiv(u1, 16), n), dim3(256), sml, s, a);
+      HIPCHK(h, hipGetLastError());
+    }
+    if (lattice_out)
+      HIPCHK(h, hipMemcpyAsync(lattice_out + (size_t)b0 * Tp * u1 * 2, h->ra_lat.p, (size_t)n * per, hipMemcpyDeviceToDevice, s));
+    if (int r = rnnt_lattice_dp_launch(h, a.lat, a.enc_len, n, Tp, V, a.targets, a.target_len, Umax,
+                                       tok_frame ? tok_frame + (size_t)b0 * Umax : nullptr, score + b0, loglik + b0, status + b0, s))
+      return r;
+  }
+  return 0;
+}
+
+int gam_rnnt_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                   const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status, void* stream) {
+  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
+  DecodeScope ds(h, s);
+  if (int r = rnnt_align_shape_check(h, B, Tp, Umax, h->cfg.num_classes, !encoded)) return r;
+  const gam_config& c = h->cfg;
+  const int D = c.d_model, JH = c.joint_hidden;
+  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
+  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
+  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
+  if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  return rnnt_align_launch(h, h->encp.p, enc_len, B, Tp, targets, target_len, Umax, tok_frame, score, loglik, status, nullptr, s);
+}
+
+int gam_op_rnnt_align(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                      const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
+                      float* lattice_out, void* stream) {
+  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return rnnt_align_launch(h, encp, enc_len, B, Tp, targets, target_len, Umax, tok_frame, score, loglik, status, lattice_out, s);
+}
+
+int gam_op_rnnt_lattice_align(gam_handle* h, const float* lattice, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
+                              const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
+                              void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  if (int r = rnnt_align_shape_check(h, B, Tp, Umax, V,
+                                     !lattice || !enc_len || !target_len || !score || !loglik || !status || (Umax > 0 && !tok_frame)))
+    return r;
+  return rnnt_lattice_dp_launch(h, reinterpret_cast<const float2*>(lattice), enc_len, B, Tp, V, targets, target_len, Umax, tok_frame, score,
+                                loglik, status, s);
+}
+
+int gam_set_rnnt_align_workspace(gam_handle* h, int64_t bytes) {
+  if (!h) return -1;
+  if (bytes < 0) return fail(h, -1, "RNN-T alignment: workspace limit %lld bytes is negative", (long long)bytes);
+  h->ra_ws_limit = bytes == 0 ? GAM_RA_WS_DEFAULT : (size_t)bytes;
+  return 0;
 }
 
 int gam_rnnt_predict(gam_handle* h, const int32_t* labels, const float* h_in, const float* c_in, int B, float* g_out,

@@ -45,6 +45,15 @@ __device__ __forceinline__ float gam_sigmoid(float x) {
 }
 __device__ __forceinline__ float gam_silu(float x) { return x * gam_sigmoid(x); }
 __device__ __forceinline__ float gam_sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
+// The LSTM cell on the four gate pre-activations (nn.LSTM order i, f, g, o): (c, gates) -> (c', h'), the arithmetic of the cells in
+// gam_decode.h and gam_rnnt_beam.h as a function (gam_rnnt_align.h calls it).  Those kernels keep their inlined form: calling this
+// from them reordered their instruction streams (per-symbol disassembly against the parent).
+__device__ __forceinline__ void gam_lstm_cell(float gi, float gf, float gg_, float go, float c0, float& c2, float& h2) {
+  const float ig = gam_sigmoid_exact(gi), fg = gam_sigmoid_exact(gf);
+  const float gg = tanhf(gg_), og = gam_sigmoid_exact(go);
+  c2 = fg * c0 + ig * gg;
+  h2 = og * tanhf(c2);
+}
 
 typedef _Float16 gam_half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 gam_half8 __attribute__((ext_vector_type(8)));

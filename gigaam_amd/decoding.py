@@ -200,6 +200,29 @@ class RNNTGreedyDecoding:
     def decode(self, head: RNNTHead, encoded: Tensor, enc_len: Tensor) -> List[Tuple[str, List[int], List[int]]]:
         return self.finish(self.decode_device(head, encoded, enc_len))
 
+    MAX_ALIGN_TOKENS = 1024     # include/gigaam_hip.h gam_rnnt_align
+
+    @torch.inference_mode()
+    def align(self, head: RNNTHead, encoded: Tensor, enc_len: Tensor, targets: List[List[int]]):
+        """Transducer forced alignment of known token ids (one list per utterance) on the device (gam_rnnt_align), ONE D2H for the
+        result.  Returns per utterance ``(ids, frames, score, loglik, feasible)``: the frame at which each token is emitted on the
+        best path (the meaning ``decode``'s frames have), that path's log-prob, log p(ids | audio) over all alignments (=
+        -rnnt_loss) and whether any path exists (if not: an empty frame list, -inf scores).  The lattice is the loss's:
+        ``max_symbols_per_step`` does not bound it, and neither hotwords nor the LM are read.  Raises ``RangeOverflow`` like
+        ``finish``."""
+        targets = [[int(t) for t in ids] for ids in targets]
+        too_long = [len(t) for t in targets if len(t) > self.MAX_ALIGN_TOKENS]
+        if too_long:
+            raise ValueError(f"forced alignment takes at most {self.MAX_ALIGN_TOKENS} tokens per utterance (got {max(too_long)})")
+        h = head.engine.rnnt_align(encoded, enc_len, targets).host()
+        if h["flag"]:
+            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        out = []
+        for i, ids in enumerate(targets):
+            ok = bool(h["status"][i])
+            out.append((ids, h["tok_frame"][i, :len(ids)].tolist() if ok else [], float(h["score"][i]), float(h["loglik"][i]), ok))
+        return out
+
 
 class RNNTBeamDecoding(RNNTGreedyDecoding, _BeamInputs):
     """RNN-T beam search with hotword boosting and word n-gram LM fusion (gam_rnnt_beam; the contract is in

@@ -160,6 +160,39 @@ class Aligned:
         return out
 
 
+class RnntAligned:
+    """What ``rnnt_align`` / ``op_rnnt_align`` / ``op_rnnt_lattice_align`` return: every output of the transducer alignment as a view of
+    ONE i32 device buffer (``whole``) that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: tok_frame [B, Umax] |
+    status [B] | score [B] (f32 bits) | loglik [B] (f32 bits) | range flag word.  ``lattice`` (``op_rnnt_align(want_lattice=True)``):
+    the (log P(blank), log P(next token)) lattice f32 [B, T', Umax + 1, 2] on the device."""
+
+    def __init__(self, whole: Tensor, b: int, umax: int, event=None, stream=None):
+        self.whole, self.b, self.umax, self.event, self.stream = whole, b, umax, event, stream
+        self.lattice: Optional[Tensor] = None
+        self.tok_frame = whole[: b * umax].view(b, umax)
+        o = b * umax
+        self.status = whole[o: o + b]
+        self.score = whole[o + b: o + 2 * b].view(torch.float32)
+        self.loglik = whole[o + 2 * b: o + 3 * b].view(torch.float32)
+        self.ext = whole[o + 3 * b: o + 3 * b + 1]
+
+    def host(self) -> Dict[str, Any]:
+        """One blocking D2H of the whole result, on the collect stream behind the alignment's own completion event -> numpy arrays
+        (``tok_frame``, ``status``, ``score``, ``loglik``) and ``flag`` (the split-fp16 range flag, as ``Aligned.host``)."""
+        side = HipEngine._collect_stream(self.whole.device)
+        with torch.cuda.stream(side):
+            if self.event is not None:
+                side.wait_event(self.event)
+            else:
+                side.wait_stream(torch.cuda.current_stream(self.whole.device))
+            arr = self.whole.cpu().numpy()
+        self.whole.record_stream(side)
+        b, um = self.b, self.umax
+        o = b * um
+        return {"tok_frame": arr[:o].reshape(b, um), "status": arr[o: o + b], "score": arr[o + b: o + 2 * b].view(np.float32),
+                "loglik": arr[o + 2 * b: o + 3 * b].view(np.float32), "flag": HipEngine._flag_of(int(arr[o + 3 * b]))}
+
+
 class BeamDecoded(Decoded):
     """What ``ctc_beam`` / ``op_ctc_beam`` / ``rnnt_beam`` / ``op_rnnt_beam`` return: a ``Decoded`` (ids, frames, counts + range flag word: ``collect``, ``finish`` and the
     word builder take it as they take a greedy decode) whose buffer goes on with ``score`` and ``logp`` f32 [B] (``buf``: ids [B, cap] |
@@ -529,6 +562,78 @@ class HipEngine:
             out.event, out.stream = torch.cuda.Event(), st
             out.event.record(st)
         return out
+
+    def _rnnt_align_buffers(self, b: int, targets, target_len):
+        """As ``_align_buffers``: device targets / lengths and the ``RnntAligned`` result buffer."""
+        tgt, tlen, _ = self._align_buffers(b, 0, targets, target_len)
+        um = tgt.shape[1]
+        return tgt, tlen, RnntAligned(torch.empty((b * um + 3 * b + 1,), dtype=torch.int32, device=self.device), b, um)
+
+    def _op_align_done(self, out: "RnntAligned") -> "RnntAligned":
+        out.ext.zero_()
+        st = torch.cuda.current_stream(self.device)
+        out.event, out.stream = torch.cuda.Event(), st
+        out.event.record(st)
+        return out
+
+    def rnnt_align(self, encoded: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None) -> "RnntAligned":
+        """Transducer forced alignment of known targets (gam_rnnt_align): the encoder projection, the teacher-forced predictor, the
+        fused joint lattice and its sweep, no host sync.  ``targets``: i32 [B, Umax] (entries past ``target_len[b]`` are ignored) or
+        a list of B token-id lists.  ``max_symbols_per_step`` does not bound the lattice; hotwords and the LM are not read.  The
+        split-fp16 range flag is CONSUMED as ``rnnt_greedy`` does: it lands in the result's last word."""
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        tgt, tlen, out = self._rnnt_align_buffers(b, targets, target_len)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_rnnt_align(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(tgt), _ptr(tlen), out.umax, _ptr(out.tok_frame),
+                                         _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
+            self._check(rc, "gam_rnnt_align")
+            out.event, out.stream = self._fetch_flag(out.ext)
+        return out
+
+    def op_rnnt_align(self, encp: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None,
+                      want_lattice: bool = False) -> "RnntAligned":
+        """gam_op_rnnt_align: the same from a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with this engine's
+        predictor and joint weights.  ``want_lattice``: also keep the (log P(blank), log P(next token)) lattice the call swept
+        (``RnntAligned.lattice``, f32 [B, T', Umax + 1, 2] on the device).  The flag word is 0."""
+        encp = self._dev(encp, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, jh = encp.shape
+        if jh != self.cfg.joint_hidden:
+            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        tgt, tlen, out = self._rnnt_align_buffers(b, targets, target_len)
+        with torch.cuda.device(self.device):
+            if want_lattice:
+                out.lattice = torch.empty((b, tp, out.umax + 1, 2), dtype=torch.float32, device=self.device)
+            rc = self.lib.gam_op_rnnt_align(self._h, _ptr(encp), _ptr(enc_len), b, tp, _ptr(tgt), _ptr(tlen), out.umax,
+                                            _ptr(out.tok_frame), _ptr(out.score), _ptr(out.loglik), _ptr(out.status),
+                                            _ptr(out.lattice), self._stream())
+            self._check(rc, "gam_op_rnnt_align")
+            return self._op_align_done(out)
+
+    def op_rnnt_lattice_align(self, lattice: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None,
+                              num_classes: Optional[int] = None) -> "RnntAligned":
+        """gam_op_rnnt_lattice_align: the lattice sweep alone on a caller-supplied lattice f32 [B, T', Umax + 1, 2] of
+        (log P(blank), log P(next token)), read as it is.  ``num_classes`` (default: large enough for every id >= 0) only serves
+        the id check of the status.  The flag word is 0."""
+        lattice = self._dev(lattice, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, u1, two = lattice.shape
+        tgt, tlen, out = self._rnnt_align_buffers(b, targets, target_len)
+        if two != 2 or u1 != out.umax + 1:
+            raise GigaAMHipError(f"lattice must be [B, T', Umax + 1 = {out.umax + 1}, 2], got {tuple(lattice.shape)}")
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_rnnt_lattice_align(self._h, _ptr(lattice), _ptr(enc_len), b, tp, int(num_classes or 1025), _ptr(tgt),
+                                                    _ptr(tlen), out.umax, _ptr(out.tok_frame), _ptr(out.score), _ptr(out.loglik),
+                                                    _ptr(out.status), self._stream())
+            self._check(rc, "gam_op_rnnt_lattice_align")
+            return self._op_align_done(out)
+
+    def set_rnnt_align_workspace(self, nbytes: int = 0) -> None:
+        """Bytes of lattice one slice of ``rnnt_align`` / ``op_rnnt_align`` may take (gam_set_rnnt_align_workspace; 0: the default,
+        1 GiB).  A batch above it is processed in slices of utterances; one utterance above it is an error."""
+        self._check(self.lib.gam_set_rnnt_align_workspace(self._h, int(nbytes)), "gam_set_rnnt_align_workspace")
 
     MAX_BEAM = 32     # include/gigaam_hip.h gam_ctc_beam
 

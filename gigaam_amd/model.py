@@ -404,6 +404,54 @@ class GigaAMASR(GigaAM):
                                        log_likelihood=loglik, feasible=ok))
         return out
 
+    # ---- transducer forced alignment: the same for RNN-T heads (gam_rnnt_align)
+    def _require_rnnt(self) -> None:
+        if not isinstance(self.decoding, _decoding.RNNTGreedyDecoding):
+            raise TypeError("transducer alignment needs an RNN-T head")
+
+    @torch.inference_mode()
+    def rnnt_align(self, wav_file: str, text: Union[str, List[int]]) -> AlignmentResult:
+        """``align`` for RNN-T heads: place ``text`` (a string in the model's vocabulary, or token ids) on a clip of at most 25 s by
+        transducer forced alignment.  ``token_frames`` are the frames at which the tokens are emitted on the best path, words are
+        built from them as ``transcribe(word_timestamps=True)`` builds them; ``log_likelihood`` is log p(text | audio) over all
+        alignments (= -rnnt_loss).  ``max_symbols_per_step`` does not bound the lattice, and the result does not depend on
+        ``set_decoding``.  Raises ``ValueError`` for a longer clip, for characters outside the vocabulary, for more than 1024
+        tokens, or for a text that no alignment can fit into the clip; ``TypeError`` on a CTC model."""
+        self._require_rnnt()
+        wav, length = self._prepare_wav_f32(wav_file)
+        if length.item() > LONGFORM_THRESHOLD:
+            raise ValueError("Too long wav file for forced alignment (at most 25 s).")
+        res = self.rnnt_align_batch(wav, length, [text])[0]
+        if not res.feasible:
+            raise ValueError(f"the text ({len(res.token_ids)} tokens) cannot be aligned to this audio")
+        return res
+
+    @torch.inference_mode()
+    def rnnt_align_batch(self, wav: Tensor, lengths: Tensor, texts: Sequence[Union[str, List[int]]]) -> List[AlignmentResult]:
+        """Batched ``rnnt_align`` on a collated batch (wav [B,L] zero padded, len [B]); ``texts`` holds a ``str`` or token ids per
+        utterance.  An utterance no alignment fits gets ``feasible=False`` (empty words, -inf scores) instead of an error."""
+        self._require_rnnt()
+        if len(texts) != wav.shape[0]:
+            raise ValueError(f"{len(texts)} texts for a batch of {wav.shape[0]}")
+        tok = self.decoding.tokenizer
+        targets = [tok.encode(t) if isinstance(t, str) else [int(i) for i in t] for t in texts]
+
+        def run():
+            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
+            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            return self.decoding.align(self.head, encoded, encoded_len, targets), encoded_len
+
+        rows, encoded_len = self._with_f32_fallback(run, "this batch was")
+        from .timestamps_utils import compute_frame_shift, frames_to_words
+
+        wl, el = lengths.tolist(), encoded_len.tolist()
+        out: List[AlignmentResult] = []
+        for i, (ids, frames, score, loglik, ok) in enumerate(rows):
+            words = frames_to_words(tok, ids, frames, compute_frame_shift(int(wl[i]), int(el[i]))) if ok else []
+            out.append(AlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_frames=frames, score=score,
+                                       log_likelihood=loglik, feasible=ok))
+        return out
+
     @torch.inference_mode()
     def transcribe_longform(self, wav_file: str, word_timestamps: bool = False, fr_batch_size: int = 16,
                             fr_num_workers: int = 0, *, beam_size: Optional[int] = None,

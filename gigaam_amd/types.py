@@ -27,7 +27,9 @@ class AlignmentResult:
     """``GigaAMASR.align``: a known transcript placed on the audio by CTC forced alignment.  ``token_frames``: the first encoder
     frame of each token on the best path; ``score``: that path's log-prob; ``log_likelihood``: log p(text | audio) over all paths
     (= -CTC loss); ``feasible``: False when no path exists (the text is too long for the audio) -- then ``words`` and
-    ``token_frames`` are empty and both scores are -inf."""
+    ``token_frames`` are empty and both scores are -inf.
+    ``GigaAMASR.rnnt_align`` returns the same for RNN-T heads (transducer forced alignment): ``token_frames`` are then the frames at
+    which the tokens are emitted on the best path, ``log_likelihood`` is -RNN-T loss, and every clip with a frame is feasible."""
     text: str
     words: List[Word]
     token_ids: List[int]

@@ -207,6 +207,42 @@ int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, i
 int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
                      int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
 
+/* Transducer forced alignment and transcript scoring (gigaam_amd/csrc/gam_rnnt_align.h holds the contract): the standard RNN-T
+ * lattice, the one the transducer loss sums over.  For utterance b, T = enc_len[b], targets i32 [B, Umax] hold U = target_len[b]
+ * token ids in [0, V - 2] (entries past U are never read), blank = V - 1.
+ *   tok_frame i32 [B, Umax]: the frame at which each token is emitted on the best (Viterbi) path -- the meaning the `frames` of
+ *   gam_rnnt_greedy / gam_rnnt_beam have; -1 past target_len[b].  score f32 [B]: that path's log-prob.  loglik f32 [B]:
+ *   log p(targets | audio) over ALL alignments = -rnnt_loss.  (gam_rnnt_beam's logp is a lower bound of the DECODERS' capped model,
+ *   where a frame advances for free after max_symbols tokens; it bounds loglik only where that cap does not bind, and can exceed it
+ *   by many nats where it does.)
+ *   status i32 [B]: 1 aligned (T = 0 with U = 0 included: score = loglik = 0); 0 when T = 0 with U > 0, a target id is outside
+ *   [0, V - 2], target_len is outside [0, Umax] or no path has a finite score -- then score = loglik = -inf, token frames -1.
+ * max_symbols_per_step does NOT bound the lattice: it is the loss's definition, not the decode's cap -- a best path may emit any
+ * number of tokens in one frame and the likelihood includes such paths.  Ties: the blank predecessor wins.  Hotwords and the LM are
+ * not read.  Runs the encoder projection GEMM of gam_rnnt_greedy, the teacher-forced predictor (one launch), its projection GEMM,
+ * a fused joint kernel that stores only (log P(blank), log P(next token)) per lattice node, and the lattice sweep with its backtrack.
+ * The lattice workspace is B x T' x (Umax + 1) x 8 bytes; above the handle's limit (gam_set_rnnt_align_workspace) the batch is
+ * processed in slices of utterances with the same results; ONE utterance above the limit is an error that names the bytes.
+ * Limits: Umax <= 1024, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512 (an error beyond them).  Decode class, like
+ * gam_rnnt_greedy; no host synchronisation. */
+int gam_rnnt_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                   const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status, void* stream);
+/* The same from a caller-supplied encoder projection encp f32 [B, T', joint_hidden] (W_enc f + b_enc), with the handle's predictor
+ * and joint weights (gam_op_rnnt_beam's counterpart).  lattice_out (may be NULL): f32 [B, T', Umax + 1, 2], a copy of the lattice
+ * (log P(blank), log P(next token)) the call swept; nodes with t >= enc_len[b] or u > target_len[b] carry no defined value. */
+int gam_op_rnnt_align(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                      const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
+                      float* lattice_out, void* stream);
+/* The lattice sweep alone on a caller-supplied lattice f32 [B, T', Umax + 1, 2] (read as it is; the second value at u = target_len[b]
+ * is never used) for callers that bring their own joint: no model weights are needed.  targets (may be NULL: ids not checked) and V
+ * only serve the id check of the status. */
+int gam_op_rnnt_lattice_align(gam_handle* h, const float* lattice, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
+                              const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
+                              void* stream);
+/* Bytes of lattice workspace one slice of gam_rnnt_align / gam_op_rnnt_align may take (0: the default, 1 GiB; environment
+ * GAM_RNNT_ALIGN_WS sets the initial value). */
+int gam_set_rnnt_align_workspace(gam_handle* h, int64_t bytes);
+
 /* Workgroups per utterance of the cluster decode kernel behind gam_rnnt_greedy: -1 = as many as the device holds at once
  * (the default: the decode has the GPU to itself), 0 = the one-workgroup-per-utterance kernel, 1..8 = at most that many.
  * A caller that runs the decode of batch n on a side stream BESIDE the encoder of batch n+1 (the product's RNN-T
