@@ -65,6 +65,10 @@ SIGNATURES = {
     "gam_op_rnnt_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_rnnt_lattice_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "gam_set_rnnt_align_workspace": (C.c_int, [_P, C.c_int64]),
+    "gam_ctc_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gam_op_ctc_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gam_rnnt_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "gam_op_rnnt_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "gam_emo_probs": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P]),
     "gam_rnnt_predict": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "gam_rnnt_joint": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),

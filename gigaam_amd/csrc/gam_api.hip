@@ -24,6 +24,7 @@
 #include "gam_convmod.h"
 #include "gam_decode.h"
 #include "gam_rnnt_align.h"
+#include "gam_confidence.h"
 #include "gam_decode_cluster.h"
 #include "gam_frontend.h"
 #include "gam_gemm.h"
@@ -135,6 +136,7 @@ struct gam_handle {
   DevBuf rb_ws, rb_nodes;               // RNN-T beam search: predictor-state slots + logit rows, prefix-trie nodes (gam_rnnt_beam.h)
   DevBuf ra_g, ra_pp, ra_lat, ra_bp;    // transducer alignment (gam_rnnt_align.h): predictor outputs, their projection, the (lb, le)
                                         // lattice of one slice, backpointers that do not fit the sweep kernel's LDS
+  DevBuf cf_stats;                      // token confidence (gam_confidence.h): the CTC pass's per-frame (argmax, measure), B x T' x 8 bytes
   size_t ra_ws_limit = GAM_RA_WS_DEFAULT;   // bytes of lattice per slice (gam_set_rnnt_align_workspace; GAM_RNNT_ALIGN_WS at gam_create)
   int* hw_trie = nullptr;               // hotword trie of gam_set_hotwords (CSR, gam_search.h): offsets | edges; NULL = no hotwords
   size_t hw_cap = 0;                    // ints allocated at hw_trie
@@ -566,7 +568,7 @@ void gam_destroy(gam_handle* h) {
   if (h->beam_nodes.p) hipFree(h->beam_nodes.p);
   if (h->rb_ws.p) hipFree(h->rb_ws.p);
   if (h->rb_nodes.p) hipFree(h->rb_nodes.p);
-  for (DevBuf* b : {&h->ra_g, &h->ra_pp, &h->ra_lat, &h->ra_bp})
+  for (DevBuf* b : {&h->ra_g, &h->ra_pp, &h->ra_lat, &h->ra_bp, &h->cf_stats})
     if (b->p) hipFree(b->p);
   if (h->hw_trie) hipFree(h->hw_trie);
   if (h->lm_cls) hipFree(h->lm_cls);
@@ -2091,6 +2093,148 @@ int gam_set_rnnt_align_workspace(gam_handle* h, int64_t bytes) {
   if (bytes < 0) return fail(h, -1, "RNN-T alignment: workspace limit %lld bytes is negative", (long long)bytes);
   h->ra_ws_limit = bytes == 0 ? GAM_RA_WS_DEFAULT : (size_t)bytes;
   return 0;
+}
+
+// ---- token confidence of a finished decode (gam_confidence.h).  Decode class (the caller holds a DecodeScope): every buffer is the handle's.
+static int conf_shape_check(gam_handle* h, const char* what, int B, int64_t Tp, int V, int cap, int cap_max, int measure, int agg, bool null_buf) {
+  if (B <= 0 || Tp <= 0 || V < 2) return fail(h, -1, "%s confidence: bad shape B=%d T'=%lld V=%d", what, B, (long long)Tp, V);
+  if (Tp > GAM_CF_MAX_T) return fail(h, -1, "%s confidence: T'=%lld frames exceed the limit %d", what, (long long)Tp, GAM_CF_MAX_T);
+  if (V > GAM_CF_MAX_V) return fail(h, -1, "%s confidence: V=%d outside [2, %d]", what, V, GAM_CF_MAX_V);
+  if (cap < 0 || cap > cap_max) return fail(h, -1, "%s confidence: cap=%d tokens outside [0, %d]", what, cap, cap_max);
+  if (measure != GAM_CF_PROB && measure != GAM_CF_ENTROPY) return fail(h, -1, "%s confidence: unknown measure %d (0 prob, 1 entropy)", what, measure);
+  if (agg < GAM_CF_MEAN || agg > GAM_CF_PROD) return fail(h, -1, "%s confidence: unknown aggregation %d (0 mean, 1 min, 2 prod)", what, agg);
+  if (null_buf) return fail(h, -1, "%s confidence: NULL buffer", what);
+  return 0;
+}
+
+static int ctc_conf_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* ids,
+                           const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
+                           int32_t* status, hipStream_t s) {
+  if (int r = conf_shape_check(h, "CTC", B, Tp, V, cap, 1 << 24, measure, agg,
+                               !lp || !enc_len || !counts || !status || (cap > 0 && (!ids || !frames || !conf || !span))))
+    return r;
+  const long rows = (long)B * Tp;
+  if (int r = ensure(h, h->cf_stats, (size_t)rows * 2 + 64)) return r;
+  const float inv_lnv = (float)(1.0 / std::log((double)V));
+  {
+    GamConfStatArgs a;
+    a.lp = lp; a.enc_len = enc_len; a.stats = reinterpret_cast<int2*>(h->cf_stats.p); a.rows = (int)rows; a.Tp = (int)Tp; a.V = V;
+    a.measure = measure; a.inv_lnv = inv_lnv;
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 4.0);
+    if (V <= 64) hipLaunchKernelGGL(gam_ctc_conf_stats_kernel<16>, dim3(gam_cdiv(rows, 16)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gam_ctc_conf_stats_kernel<64>, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, a);
+    HIPCHK(h, hipGetLastError());
+  }
+  GamConfAggArgs a;
+  a.lp = lp; a.stats = reinterpret_cast<const int2*>(h->cf_stats.p); a.enc_len = enc_len; a.ids = ids; a.frames = frames; a.counts = counts;
+  a.Tp = (int)Tp; a.V = V; a.cap = cap; a.measure = measure; a.agg = agg; a.conf = conf; a.span = span; a.status = status;
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * 8.0);
+  hipLaunchKernelGGL(gam_ctc_conf_agg_kernel, dim3(B), dim3(256), 0, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_ctc_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
+                       const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
+                       int32_t* status, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  if (!h->finalized) return fail(h, -1, "CTC head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_CTC || !h->has_head) return fail(h, -1, "model has no CTC head");
+  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
+  DecodeScope ds(h, s);
+  const int V = h->cfg.num_classes;
+  if (int r = conf_shape_check(h, "CTC", B, Tp, V, cap, 1 << 24, measure, agg, !encoded)) return r;
+  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
+  const int rows = (int)(B * Tp);
+  {
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
+    // in place: each row is read whole by its wave before that wave writes it (as gam_ctc_align)
+    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
+    HIPCHK(h, hipGetLastError());
+  }
+  return ctc_conf_launch(h, h->logits.p, enc_len, B, Tp, V, ids, frames, counts, cap, measure, agg, conf, span, status, s);
+}
+
+int gam_op_ctc_confidence(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* ids,
+                          const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
+                          int32_t* status, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return ctc_conf_launch(h, log_probs, enc_len, B, Tp, V, ids, frames, counts, cap, measure, agg, conf, span, status, s);
+}
+
+// From the encoder projection encp [B, Tp, JH]: the rows are checked, then the teacher-forced predictor and its projection exactly as
+// rnnt_align_launch runs them (the decoded ids as targets), then the joint at the listed nodes.
+static int rnnt_conf_launch(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
+                            const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, hipStream_t s) {
+  const gam_config& c = h->cfg;
+  const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden, L = c.pred_rnn_layers;
+  if (int r = conf_shape_check(h, "RNN-T", B, Tp, V, cap, GAM_RA_MAX_U, measure, GAM_CF_MEAN,
+                               !encp || !enc_len || !counts || !status || (cap > 0 && (!ids || !frames || !conf))))
+    return r;
+  if (H > GAM_RA_MAX_H || JH > GAM_RA_MAX_H || H % 16 != 0 || JH % 16 != 0 || L < 1 || L > 4)
+    return fail(h, -1, "RNN-T confidence: H=%d / JH=%d must be multiples of 16 up to %d, 1..4 predictor layers (L=%d)", H, JH, GAM_RA_MAX_H, L);
+  {
+    GamRnntConfPrepArgs a;
+    a.enc_len = enc_len; a.ids = ids; a.frames = frames; a.counts = counts; a.Tp = (int)Tp; a.V = V; a.cap = cap; a.conf = conf; a.status = status;
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)B * cap * 12.0);
+    hipLaunchKernelGGL(gam_rnnt_conf_prep_kernel, dim3(B), dim3(256), 0, s, a);
+    HIPCHK(h, hipGetLastError());
+  }
+  if (cap == 0) return 0;
+  const int u1 = cap + 1;
+  if (int r = ensure(h, h->ra_g, (size_t)B * u1 * H + 64)) return r;
+  if (int r = ensure(h, h->ra_pp, (size_t)B * u1 * JH + 64)) return r;
+  {
+    GamRnntTfArgs a;
+    a.targets = ids; a.target_len = counts; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x;
+    a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x; a.g = h->ra_g.p; a.Umax = cap; a.V = V; a.H = H; a.L = L;
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)B * u1 * L * 8.0 * H * H * 4.0);
+    const size_t sm = gam_ra_tf_lds_bytes(H, L);
+    if (4 * H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<5>, dim3(B), dim3(256), sm, s, a);
+    else hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<8>, dim3(B), dim3(256), sm, s, a);
+    HIPCHK(h, hipGetLastError());
+  }
+  GamGemmArgs gp = gemm_args(h->ra_g.p, H, h->jn_pred_w, h->jn_pred_b, h->ra_pp.p, JH, B * u1, JH, H);
+  if (int r = gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  GamRnntConfArgs a;
+  a.encp = encp; a.predp = h->ra_pp.p; a.ids = ids; a.frames = frames; a.counts = counts; a.status = status; a.wout = h->jn_out_w;
+  a.bout = h->jn_out_b; a.conf = conf; a.Tp = (int)Tp; a.cap = cap; a.V = V; a.JH = JH; a.measure = measure;
+  a.inv_lnv = (float)(1.0 / std::log((double)V));
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * cap * ((double)V * JH * 2.0));
+  hipLaunchKernelGGL(gam_rnnt_conf_nodes_kernel, dim3(gam_cdiv(cap, 16), B), dim3(64), gam_cf_nodes_lds_bytes(JH), s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_rnnt_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
+                        const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream) {
+  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
+  DecodeScope ds(h, s);
+  const gam_config& c = h->cfg;
+  if (int r = conf_shape_check(h, "RNN-T", B, Tp, c.num_classes, cap, GAM_RA_MAX_U, measure, GAM_CF_MEAN, !encoded)) return r;
+  const int D = c.d_model, JH = c.joint_hidden;
+  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
+  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
+  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
+  if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  return rnnt_conf_launch(h, h->encp.p, enc_len, B, Tp, ids, frames, counts, cap, measure, conf, status, s);
+}
+
+int gam_op_rnnt_confidence(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
+                           const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream) {
+  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return rnnt_conf_launch(h, encp, enc_len, B, Tp, ids, frames, counts, cap, measure, conf, status, s);
 }
 
 int gam_rnnt_predict(gam_handle* h, const int32_t* labels, const float* h_in, const float* c_in, int B, float* g_out,

@@ -193,6 +193,38 @@ class RnntAligned:
                 "loglik": arr[o + 2 * b: o + 3 * b].view(np.float32), "flag": HipEngine._flag_of(int(arr[o + 3 * b]))}
 
 
+class Confidence:
+    """What ``ctc_confidence`` / ``op_ctc_confidence`` / ``rnnt_confidence`` / ``op_rnnt_confidence`` return: the token confidences of a
+    finished decode as views of ONE i32 device buffer (``whole``) that reaches the host in ONE copy (``host``), like ``Aligned``.
+    Layout: conf [B, cap] (f32 bits) | span [B, cap] (CTC only) | status [B] | range flag word."""
+
+    def __init__(self, whole: Tensor, b: int, cap: int, has_span: bool, event=None, stream=None):
+        self.whole, self.b, self.cap, self.has_span, self.event, self.stream = whole, b, cap, has_span, event, stream
+        n = b * cap
+        self.conf = whole[:n].view(torch.float32).view(b, cap)
+        self.span = whole[n: 2 * n].view(b, cap) if has_span else None
+        o = 2 * n if has_span else n
+        self.status = whole[o: o + b]
+        self.ext = whole[o + b: o + b + 1]
+
+    def host(self) -> Dict[str, Any]:
+        """One blocking D2H of the whole result, on the collect stream behind the pass's own completion event -> numpy arrays
+        (``conf`` f32 [B, cap], ``span`` i32 [B, cap] or None, ``status`` i32 [B]) and ``flag`` (the split-fp16 range flag, as
+        ``Aligned.host``)."""
+        side = HipEngine._collect_stream(self.whole.device)
+        with torch.cuda.stream(side):
+            if self.event is not None:
+                side.wait_event(self.event)
+            else:
+                side.wait_stream(torch.cuda.current_stream(self.whole.device))
+            arr = self.whole.cpu().numpy()
+        self.whole.record_stream(side)
+        b, n = self.b, self.b * self.cap
+        o = 2 * n if self.has_span else n
+        return {"conf": arr[:n].view(np.float32).reshape(b, self.cap), "span": arr[n: 2 * n].reshape(b, self.cap) if self.has_span else None,
+                "status": arr[o: o + b], "flag": HipEngine._flag_of(int(arr[o + b]))}
+
+
 class BeamDecoded(Decoded):
     """What ``ctc_beam`` / ``op_ctc_beam`` / ``rnnt_beam`` / ``op_rnnt_beam`` return: a ``Decoded`` (ids, frames, counts + range flag word: ``collect``, ``finish`` and the
     word builder take it as they take a greedy decode) whose buffer goes on with ``score`` and ``logp`` f32 [B] (``buf``: ids [B, cap] |
@@ -634,6 +666,131 @@ class HipEngine:
         """Bytes of lattice one slice of ``rnnt_align`` / ``op_rnnt_align`` may take (gam_set_rnnt_align_workspace; 0: the default,
         1 GiB).  A batch above it is processed in slices of utterances; one utterance above it is an error."""
         self._check(self.lib.gam_set_rnnt_align_workspace(self._h, int(nbytes)), "gam_set_rnnt_align_workspace")
+
+    # ---- token confidence of a finished decode (gam_confidence.h)
+    MEASURES = {"prob": 0, "entropy": 1}
+    AGGREGATIONS = {"mean": 0, "min": 1, "prod": 2}
+    MAX_RNNT_CONFIDENCE_TOKENS = 1024     # include/gigaam_hip.h gam_rnnt_confidence
+
+    @classmethod
+    def _confidence_codes(cls, measure: str, aggregation: str) -> Tuple[int, int]:
+        if measure not in cls.MEASURES:
+            raise ValueError(f"unknown confidence measure {measure!r} (one of {', '.join(cls.MEASURES)})")
+        if aggregation not in cls.AGGREGATIONS:
+            raise ValueError(f"unknown confidence aggregation {aggregation!r} (one of {', '.join(cls.AGGREGATIONS)})")
+        return cls.MEASURES[measure], cls.AGGREGATIONS[aggregation]
+
+    def _confidence_tokens(self, b: int, decoded, frames, counts, cap_max: Optional[int] = None):
+        """``decoded``: a ``Decoded`` / ``BeamDecoded`` (its ids, frames and counts are used where they are), or ids as an i32
+        [B, cap] tensor or B int lists with ``frames`` alike (``counts`` None: the rows' lengths / the full width) -> device i32
+        ids, frames [B, cap], counts [B].  ``cap_max``: a wider buffer is narrowed to it (a row that holds more gets status 0)."""
+        if isinstance(decoded, Decoded):
+            ids, frames, counts = decoded[0], decoded[1], decoded[2]
+        elif isinstance(decoded, Tensor):
+            if frames is None:
+                raise GigaAMHipError("token confidence: ids without frames")
+            ids = decoded.reshape(b, -1)
+            frames = torch.as_tensor(frames).reshape(b, -1)
+            if counts is None:
+                counts = torch.full((b,), ids.shape[1], dtype=torch.int32)
+        else:
+            if frames is None or len(decoded) != b or len(frames) != b or any(len(i) != len(f) for i, f in zip(decoded, frames)):
+                raise GigaAMHipError(f"token confidence: ids and frames must hold {b} rows of equal lengths")
+            cap = max([len(r) for r in decoded] + [0])
+            host = torch.zeros((2, b, cap), dtype=torch.int32)
+            for i, (r, f) in enumerate(zip(decoded, frames)):
+                if len(r):
+                    host[0, i, : len(r)] = torch.as_tensor(list(r), dtype=torch.int32)
+                    host[1, i, : len(r)] = torch.as_tensor(list(f), dtype=torch.int32)
+            ids, frames = host[0], host[1]
+            if counts is None:
+                counts = torch.tensor([len(r) for r in decoded], dtype=torch.int32)
+        if tuple(ids.shape) != tuple(frames.shape) or ids.shape[0] != b:
+            raise GigaAMHipError(f"token confidence: ids {tuple(ids.shape)} and frames {tuple(frames.shape)} must both be [{b}, cap]")
+        if cap_max is not None and ids.shape[1] > cap_max:
+            ids, frames = ids[:, :cap_max], frames[:, :cap_max]
+        return self._dev(ids, torch.int32), self._dev(frames, torch.int32), self._dev(torch.as_tensor(counts), torch.int32)
+
+    def _confidence_out(self, b: int, cap: int, has_span: bool) -> "Confidence":
+        return Confidence(torch.empty(((2 if has_span else 1) * b * cap + b + 1,), dtype=torch.int32, device=self.device), b, cap, has_span)
+
+    def _confidence_done(self, out: "Confidence", consumed_flag: bool) -> "Confidence":
+        if consumed_flag:
+            out.event, out.stream = self._fetch_flag(out.ext)
+        else:
+            out.ext.zero_()
+            st = torch.cuda.current_stream(self.device)
+            out.event, out.stream = torch.cuda.Event(), st
+            out.event.record(st)
+        return out
+
+    def ctc_confidence(self, encoded: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob",
+                       aggregation: str = "mean") -> "Confidence":
+        """Token confidences of a finished CTC decode (gam_ctc_confidence): the CTC head, its log-softmax, one pass over the log-probs
+        and the span walk, no host sync.  ``decoded``: what ``ctc_greedy`` / ``ctc_beam`` returned, or ids with ``frames`` (and
+        ``counts``) as tensors or lists -- e.g. a transcript's ids at ``ctc_align``'s first frames.  ``measure``: "prob" | "entropy";
+        ``aggregation`` over a token's span: "mean" | "min" | "prod".  The split-fp16 range flag is CONSUMED as ``ctc_greedy`` does."""
+        m, a = self._confidence_codes(measure, aggregation)
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts)
+        out = self._confidence_out(b, ids.shape[1], True)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_ctc_confidence(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap, m, a,
+                                             _ptr(out.conf), _ptr(out.span), _ptr(out.status), self._stream())
+            self._check(rc, "gam_ctc_confidence")
+            return self._confidence_done(out, True)
+
+    def op_ctc_confidence(self, log_probs: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob",
+                          aggregation: str = "mean") -> "Confidence":
+        """gam_op_ctc_confidence: the same on caller-supplied log-probs [B, T', V] (used as they are).  The flag word is 0."""
+        m, a = self._confidence_codes(measure, aggregation)
+        log_probs = self._dev(log_probs, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, v = log_probs.shape
+        ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts)
+        out = self._confidence_out(b, ids.shape[1], True)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_ctc_confidence(self._h, _ptr(log_probs), _ptr(enc_len), b, tp, v, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap,
+                                                m, a, _ptr(out.conf), _ptr(out.span), _ptr(out.status), self._stream())
+            self._check(rc, "gam_op_ctc_confidence")
+            return self._confidence_done(out, False)
+
+    def rnnt_confidence(self, encoded: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob") -> "Confidence":
+        """Token confidences of a finished RNN-T decode (gam_rnnt_confidence): the encoder projection, the teacher-forced predictor
+        over the decoded ids and the joint at the nodes (frames[u], ids[:u]) the tokens were emitted from, no host sync.  ``decoded``:
+        what ``rnnt_greedy`` / ``rnnt_beam`` returned, or ids with ``frames`` (and ``counts``) -- e.g. a transcript's ids at
+        ``rnnt_align``'s frames.  At most 1024 tokens per utterance: a wider decode buffer is read up to there, and an utterance
+        that holds more gets status 0.  The split-fp16 range flag is CONSUMED as ``rnnt_greedy`` does."""
+        m, _ = self._confidence_codes(measure, "mean")
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts, self.MAX_RNNT_CONFIDENCE_TOKENS)
+        out = self._confidence_out(b, ids.shape[1], False)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_rnnt_confidence(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap, m,
+                                              _ptr(out.conf), _ptr(out.status), self._stream())
+            self._check(rc, "gam_rnnt_confidence")
+            return self._confidence_done(out, True)
+
+    def op_rnnt_confidence(self, encp: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob") -> "Confidence":
+        """gam_op_rnnt_confidence: the same from a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with this engine's
+        predictor and joint weights.  The flag word is 0."""
+        m, _ = self._confidence_codes(measure, "mean")
+        encp = self._dev(encp, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, jh = encp.shape
+        if jh != self.cfg.joint_hidden:
+            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts, self.MAX_RNNT_CONFIDENCE_TOKENS)
+        out = self._confidence_out(b, ids.shape[1], False)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_rnnt_confidence(self._h, _ptr(encp), _ptr(enc_len), b, tp, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap, m,
+                                                 _ptr(out.conf), _ptr(out.status), self._stream())
+            self._check(rc, "gam_op_rnnt_confidence")
+            return self._confidence_done(out, False)
 
     MAX_BEAM = 32     # include/gigaam_hip.h gam_ctc_beam
 

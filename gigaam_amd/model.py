@@ -16,9 +16,10 @@ from . import decoder as _decoder
 from . import decoding as _decoding
 from . import encoder as _encoder
 from . import preprocess as _preprocess
+from ._lib import GigaAMHipError
 from .engine import HipEngine, build_config
 from .preprocess import SAMPLE_RATE, load_audio
-from .types import AlignmentResult, LongformTranscriptionResult, Segment, TranscriptionResult, Word
+from .types import AlignmentResult, ConfidenceResult, LongformTranscriptionResult, ScoredWord, Segment, TranscriptionResult, Word
 
 LONGFORM_THRESHOLD = 25 * SAMPLE_RATE
 
@@ -450,6 +451,96 @@ class GigaAMASR(GigaAM):
             words = frames_to_words(tok, ids, frames, compute_frame_shift(int(wl[i]), int(el[i]))) if ok else []
             out.append(AlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_frames=frames, score=score,
                                        log_likelihood=loglik, feasible=ok))
+        return out
+
+    # ---- token / word / utterance confidence: a post-pass over a finished decode or alignment (gam_ctc_confidence / gam_rnnt_confidence)
+    @torch.inference_mode()
+    def confidence(self, wav_file: str, text: Optional[Union[str, List[int]]] = None, *, measure: str = "prob", aggregation: str = "mean",
+                   beam_size: Optional[int] = None, hotwords: Optional[Sequence[Union[str, List[int]]]] = None,
+                   hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0) -> ConfidenceResult:
+        """How sure the model is of each token and word of a clip of at most 25 s.  Without ``text`` the clip is decoded as
+        ``transcribe`` decodes it (CTC: greedy, or beam search from the per-call options; RNN-T: what ``set_decoding`` selected --
+        the per-call beam options are a ``TypeError`` there) and the decode is scored on the same encoder output.  With ``text`` (a
+        string in the vocabulary, or token ids) the transcript is first placed by forced alignment (``align`` / ``rnnt_align``) and its
+        tokens are scored at the aligned frames: the confidence of a KNOWN transcript (``ValueError`` if it cannot be aligned).
+        ``measure``: "prob" -- p(token) under the distribution it was emitted from -- or "entropy" -- 1 - H / ln V;
+        ``aggregation``: "mean" | "min" | "prod", over the frames of a CTC token's run, over the tokens of a word and over the
+        utterance.  Every number lies in [0, 1]; none is calibrated."""
+        HipEngine._confidence_codes(measure, aggregation)
+        self._beam_width(beam_size, hotwords, lm)
+        wav, length = self._prepare_wav_f32(wav_file)
+        if length.item() > LONGFORM_THRESHOLD:
+            raise ValueError("Too long wav file for confidence scoring (at most 25 s).")
+        res = self.confidence_batch(wav, length, None if text is None else [text], measure=measure, aggregation=aggregation,
+                                    beam_size=beam_size, hotwords=hotwords, hotword_boost=hotword_boost, lm=lm, lm_weight=lm_weight,
+                                    word_bonus=word_bonus)[0]
+        if not res.feasible:
+            raise ValueError(f"the text ({len(res.token_ids)} tokens) cannot be aligned to this audio")
+        return res
+
+    @torch.inference_mode()
+    def confidence_batch(self, wav: Tensor, lengths: Tensor, texts: Optional[Sequence[Union[str, List[int]]]] = None, *,
+                         measure: str = "prob", aggregation: str = "mean", beam_size: Optional[int] = None,
+                         hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
+                         lm_weight: float = 0.5, word_bonus: float = 1.0) -> List[ConfidenceResult]:
+        """Batched ``confidence`` on a collated batch (wav [B,L] zero padded, len [B]).  Text, token ids, token frames and word times
+        are those of ``transcribe_batch(word_timestamps=True)`` (without ``texts``) or of ``align_batch`` / ``rnnt_align_batch`` (with
+        ``texts``: a ``str`` or token ids per utterance; one that cannot be aligned gets ``feasible=False``).  ONE encoder run: the
+        decode or the alignment and the confidence pass read the same encoder output."""
+        m_code, a_code = HipEngine._confidence_codes(measure, aggregation)
+        width = self._beam_width(beam_size, hotwords, lm)
+        is_ctc = isinstance(self.decoding, _decoding.CTCGreedyDecoding)
+        tok = self.decoding.tokenizer
+        targets = None
+        if texts is not None:
+            if width is not None:
+                raise ValueError("beam search options select a decode; they cannot be combined with a given text")
+            if len(texts) != wav.shape[0]:
+                raise ValueError(f"{len(texts)} texts for a batch of {wav.shape[0]}")
+            targets = [tok.encode(t) if isinstance(t, str) else [int(i) for i in t] for t in texts]
+
+        def run():
+            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
+            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            if targets is not None:
+                rows = [(tok.decode(r[0]), r[0], r[1], r[-1]) for r in self.decoding.align(self.head, encoded, encoded_len, targets)]
+            elif width is not None:
+                dev_out = self.decoding.decode_beam_device(self.head, encoded, encoded_len, width, hotwords, hotword_boost, lm, lm_weight,
+                                                           word_bonus)
+                rows = [(t, i, f, True) for t, i, f in self.decoding.finish(dev_out)]
+            else:
+                rows = [(t, i, f, True) for t, i, f in self.decoding.finish(self.decoding.decode_device(self.head, encoded, encoded_len))]
+            ids = [i if ok else [] for _, i, _, ok in rows]
+            frames = [f if ok else [] for _, _, f, ok in rows]
+            eng = self.head.engine
+            if is_ctc:
+                h = eng.ctc_confidence(encoded, encoded_len, ids, frames, measure=measure, aggregation=aggregation).host()
+            else:
+                h = eng.rnnt_confidence(encoded, encoded_len, ids, frames, measure=measure).host()
+            if h["flag"]:
+                raise _decoding.RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+            return rows, h, encoded_len
+
+        rows, h, encoded_len = self._with_f32_fallback(run, "this batch was")
+        from .timestamps_utils import aggregate_confidence, compute_frame_shift, frames_to_words, word_token_groups
+
+        wl, el = lengths.tolist(), encoded_len.tolist()
+        out: List[ConfidenceResult] = []
+        for i, (text, ids, frames, ok) in enumerate(rows):
+            if not ok:
+                out.append(ConfidenceResult(text=text, words=[], token_ids=ids, token_frames=[], token_confidence=[], confidence=None,
+                                            feasible=False))
+                continue
+            if not int(h["status"][i]):
+                raise GigaAMHipError(f"confidence pass rejected the tokens of utterance {i}")
+            conf = [float(c) for c in h["conf"][i, :len(ids)]]
+            words = frames_to_words(tok, ids, frames, compute_frame_shift(int(wl[i]), int(el[i])))
+            groups = word_token_groups(tok, ids)
+            assert len(groups) == len(words)
+            scored = [ScoredWord(text=w.text, start=w.start, end=w.end, confidence=aggregate_confidence([conf[k] for k in g], aggregation))
+                      for w, g in zip(words, groups)]
+            out.append(ConfidenceResult(text=text, words=scored, token_ids=ids, token_frames=frames, token_confidence=conf,
+                                        confidence=aggregate_confidence(conf, aggregation), feasible=True))
         return out
 
     @torch.inference_mode()

@@ -43,6 +43,35 @@ class AlignmentResult:
 
 
 @dataclass
+class ScoredWord:
+    """A ``Word`` with its confidence: the aggregation of its tokens' confidences."""
+    text: str
+    start: float
+    end: float
+    confidence: float
+
+
+@dataclass
+class ConfidenceResult:
+    """``GigaAMASR.confidence``: a transcript -- the model's own decode, or a known text placed by forced alignment -- with a
+    confidence in [0, 1] per token, per word and for the utterance.  ``token_confidence``: the measure ("prob": p(token) under the
+    distribution it was emitted from; "entropy": 1 - H / ln V) per token, for CTC heads aggregated over the frames of the token's
+    run; ``words``: the words of ``transcribe(word_timestamps=True)``, each with the aggregation ("mean" / "min" / "prod") of its
+    tokens; ``confidence``: the same aggregation over all tokens, None for an empty transcript.  ``feasible``: False when a given
+    text cannot be aligned to the audio -- then ``words``, ``token_frames`` and ``token_confidence`` are empty."""
+    text: str
+    words: List[ScoredWord]
+    token_ids: List[int]
+    token_frames: List[int]
+    token_confidence: List[float]
+    confidence: Optional[float]
+    feasible: bool
+
+    def __str__(self) -> str:
+        return self.text
+
+
+@dataclass
 class Segment:
     text: str
     start: float

@@ -243,6 +243,36 @@ int gam_op_rnnt_lattice_align(gam_handle* h, const float* lattice, const int32_t
  * GAM_RNNT_ALIGN_WS sets the initial value). */
 int gam_set_rnnt_align_workspace(gam_handle* h, int64_t bytes);
 
+/* Token confidence of a finished decode (gigaam_amd/csrc/gam_confidence.h holds the contract): a post-pass over what the greedy
+ * decodes, the beam searches or the alignments returned.  ids / frames i32 [B, cap] hold counts[b] tokens per utterance (their
+ * decoders' meaning), blank = V - 1.  measure: 0 prob -- p(decoded token) under the step distribution it was emitted from; 1 entropy --
+ * 1 - H(p) / ln V over all V classes.  Both lie in [0, 1].
+ *   CTC: the step distributions are the frames of the token's span -- frames[u] and the following frames before frames[u + 1] (before
+ *   enc_len[b] for the last token) whose argmax over all V classes (ties to the lower id) is ids[u]; agg combines them: 0 mean, 1 min,
+ *   2 prod.  span i32 [B, cap]: the span lengths.  RNN-T: one step per token, the joint at (frames[u], ids[:u]); no span, no agg.
+ *   conf f32 [B, cap]; entries past counts[b] are -1 (span 0).
+ *   status i32 [B]: 1 scored (enc_len[b] = 0 with counts[b] = 0 included); 0 when an id is outside [0, V - 2], a frame is outside
+ *   [0, enc_len[b]), CTC frames are not strictly increasing, RNN-T frames decrease, or counts[b] is outside [0, cap] -- then every
+ *   conf is -1 and every span 0, and no entry is used as an address.
+ * gam_ctc_confidence runs the CTC head, its log-softmax, ONE pass over the log-probs that keeps 8 bytes per frame (argmax, measure) in
+ * a workspace of the handle, and a span walk per token.  gam_rnnt_confidence runs the encoder projection GEMM, the teacher-forced
+ * predictor and its projection GEMM as gam_rnnt_align does (the decoded ids as targets), then a fused joint at the listed nodes that
+ * stores one float per token; the logits never reach memory.
+ * Limits (an error beyond them): V <= 1025, T' <= 8192; RNN-T: cap <= 1024, pred_hidden and joint_hidden <= 512.  Calling a function of
+ * the other head family is an error.  Decode class; no host synchronisation. */
+int gam_ctc_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
+                       const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
+                       int32_t* status, void* stream);
+/* The same from caller-supplied log-probs f32 [B, T', V] (read as they are: no normalisation); needs no head. */
+int gam_op_ctc_confidence(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* ids,
+                          const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
+                          int32_t* status, void* stream);
+int gam_rnnt_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
+                        const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream);
+/* The same from a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with the handle's predictor and joint weights. */
+int gam_op_rnnt_confidence(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
+                           const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream);
+
 /* Workgroups per utterance of the cluster decode kernel behind gam_rnnt_greedy: -1 = as many as the device holds at once
  * (the default: the decode has the GPU to itself), 0 = the one-workgroup-per-utterance kernel, 1..8 = at most that many.
  * A caller that runs the decode of batch n on a side stream BESIDE the encoder of batch n+1 (the product's RNN-T
