@@ -1529,6 +1529,12 @@ static int beam_check(gam_handle* h, const char* name, int W, int V, bool null_b
   if (h->lm_ng && h->lm_V != V) return fail(h, -1, lm_fmt, h->lm_V, V);
   return 0;
 }
+// The N-best calls' own check (n_hyp != NULL marks an N-best call): 1 <= N <= W <= 32.
+static int nbest_check(gam_handle* h, const char* name, int W, int N, const int32_t* n_hyp) {
+  if (N < 1 || N > W || N > GAM_BEAM_MAX_W) return fail(h, -1, "%s: N=%d hypotheses outside [1, min(W, %d)] for W=%d", name, N, GAM_BEAM_MAX_W, W);
+  if (!n_hyp) return fail(h, -1, "%s: NULL buffer", name);
+  return 0;
+}
 // Launch one instantiation of a beam kernel; its LDS limit is raised once (`once`: one word per instantiation) when it needs > 64 KiB.
 static int beam_launch(gam_handle* h, const void* kern, std::atomic<unsigned long long>& once, size_t max_lds, int B, int nt, size_t sm,
                        hipStream_t s, void* args) {
@@ -1538,14 +1544,18 @@ static int beam_launch(gam_handle* h, const void* kern, std::atomic<unsigned lon
 }
 
 // CTC prefix beam search over log-probs [B, Tp, V] (gam_beam.h): one workgroup per utterance.  Decode class (the caller holds a
-// DecodeScope): the prefix-trie nodes are the handle's.
+// DecodeScope): the prefix-trie nodes are the handle's.  nbest: the <.., true> kernels, ids / frames [B, N, Tp] and counts / score / logp
+// [B, N]; else N and n_hyp are not read.
 static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
-                           int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s) {
+                           int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s, bool nbest = false, int N = 0,
+                           int32_t* n_hyp = nullptr) {
   if (B <= 0 || Tp <= 0 || V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "CTC beam search: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
   if (Tp > GAM_ALIGN_MAX_T) return fail(h, -1, "CTC beam search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_ALIGN_MAX_T);
   if (int r = beam_check(h, "CTC beam search", W, V, !lp || !enc_len || !ids || !frames || !counts || !score || !logp,
                          "CTC beam search: the LM's token classes are for V=%d, the log-probs have V=%d"))
     return r;
+  if (nbest)
+    if (int r = nbest_check(h, "CTC beam search", W, N, n_hyp)) return r;
   const int K = std::min(W, V - 1);
   const bool lm = h->lm_ng != nullptr;
   const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
@@ -1557,20 +1567,26 @@ static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_le
   a.lm = lm_args(h);
   a.nodes = reinterpret_cast<int2*>(h->beam_nodes.p);
   a.ids = ids; a.frames = frames; a.counts = counts; a.score = score; a.logp = logp;
-  static std::atomic<unsigned long long> lds_set[2];
+  a.nb.n_hyp = nbest ? n_hyp : nullptr; a.nb.n = nbest ? N : 0; a.nb.pad = 0;
+  static std::atomic<unsigned long long> lds_set[4];
+  static const void* const kern[4] = {(const void*)gam_ctc_beam_kernel<false, false>, (const void*)gam_ctc_beam_kernel<true, false>,
+                                      (const void*)gam_ctc_beam_kernel<false, true>, (const void*)gam_ctc_beam_kernel<true, true>};
+  const int ki = (lm ? 1 : 0) + (nbest ? 2 : 0);
   ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * W * (K + 1) * 4.0);
-  return beam_launch(h, lm ? (const void*)gam_ctc_beam_kernel<true> : (const void*)gam_ctc_beam_kernel<false>, lds_set[lm], sm, B,
-                     GAM_BEAM_NT, sm, s, &a);
+  return beam_launch(h, kern[ki], lds_set[ki], sm, B, GAM_BEAM_NT, sm, s, &a);
 }
 
-int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
-                 int32_t* counts, float* score, float* logp, void* stream) {
+// gam_ctc_beam / gam_ctc_beam_nbest: the CTC head, its log-softmax in place, the beam kernel.
+static int ctc_beam_run(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
+                        int32_t* counts, float* score, float* logp, void* stream, bool nbest, int N, int32_t* n_hyp) {
   hipStream_t s = (hipStream_t)stream;
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
   DecodeScope ds(h, s);
   if (Tp > GAM_ALIGN_MAX_T || W < 1 || W > GAM_BEAM_MAX_W)
     return fail(h, -1, "CTC beam search: T'=%lld / W=%d beyond the limits (%d / [1, %d])", (long long)Tp, W, GAM_ALIGN_MAX_T, GAM_BEAM_MAX_W);
+  if (nbest)
+    if (int r = nbest_check(h, "CTC beam search", W, N, n_hyp)) return r;
   if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
   const int V = h->cfg.num_classes, rows = (int)(B * Tp);
   {
@@ -1579,7 +1595,26 @@ int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, in
     hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
     HIPCHK(h, hipGetLastError());
   }
-  return ctc_beam_launch(h, h->logits.p, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s);
+  return ctc_beam_launch(h, h->logits.p, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s, nbest, N, n_hyp);
+}
+
+int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
+                 int32_t* counts, float* score, float* logp, void* stream) {
+  return ctc_beam_run(h, encoded, enc_len, B, Tp, W, ids, frames, counts, score, logp, stream, false, 0, nullptr);
+}
+
+int gam_ctc_beam_nbest(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int N, int32_t* ids,
+                       int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream) {
+  return ctc_beam_run(h, encoded, enc_len, B, Tp, W, ids, frames, counts, score, logp, stream, true, N, n_hyp);
+}
+
+int gam_op_ctc_beam_nbest(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int N,
+                          int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return ctc_beam_launch(h, log_probs, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s, true, N, n_hyp);
 }
 
 int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
@@ -1880,9 +1915,11 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
 
 // RNN-T beam search over the encoder projection encp [B, Tp, JH] (gam_rnnt_beam.h): one workgroup per utterance; with the handle's LM
 // (gam_set_lm) gam_rnnt_beam_kernel<true>.  Decode class (the caller holds a DecodeScope): the state slots, logit rows and prefix-trie
-// nodes are the handle's.
+// nodes are the handle's.  nbest: the <.., true> kernels, ids / frames [B, N, cap] and counts / score / logp [B, N]; else N and n_hyp
+// are not read.
 static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols,
-                            int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s) {
+                            int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, hipStream_t s, bool nbest = false,
+                            int N = 0, int32_t* n_hyp = nullptr) {
   const gam_config& c = h->cfg;
   const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden, L = c.pred_rnn_layers;
   if (B <= 0 || Tp <= 0) return fail(h, -1, "RNN-T beam search: bad shape B=%d T'=%lld", B, (long long)Tp);
@@ -1895,6 +1932,8 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
   if (int r = beam_check(h, "RNN-T beam search", W, V, !encp || !enc_len || !ids || !frames || !counts || !score || !logp,
                          "RNN-T beam search: the LM's token classes are for V=%d, the model has V=%d"))
     return r;
+  if (nbest)
+    if (int r = nbest_check(h, "RNN-T beam search", W, N, n_hyp)) return r;
   const bool lm = h->lm_ng != nullptr;
   const int K = std::min(W, V - 1);
   const size_t base = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, 0, lm ? V : 0);
@@ -1916,14 +1955,19 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
   a.ws = h->rb_ws.p; a.ws_stride = per;
   a.nodes = reinterpret_cast<int2*>(h->rb_nodes.p);
   a.ids = ids; a.frames = frames; a.cap = (int)Tp * max_symbols; a.counts = counts; a.score = score; a.logp = logp;
-  static std::atomic<unsigned long long> lds_set[2];
+  a.nb.n_hyp = nbest ? n_hyp : nullptr; a.nb.n = nbest ? N : 0;
+  static std::atomic<unsigned long long> lds_set[4];
+  static const void* const kern[4] = {(const void*)gam_rnnt_beam_kernel<false, false>, (const void*)gam_rnnt_beam_kernel<true, false>,
+                                      (const void*)gam_rnnt_beam_kernel<false, true>, (const void*)gam_rnnt_beam_kernel<true, true>};
+  const int ki = (lm ? 1 : 0) + (nbest ? 2 : 0);
   ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * ((double)V * JH + 4.0 * H * H) * 4.0);
-  return beam_launch(h, lm ? (const void*)gam_rnnt_beam_kernel<true> : (const void*)gam_rnnt_beam_kernel<false>, lds_set[lm], 160 * 1024, B,
-                     GAM_RB_NT, sm, s, &a);
+  return beam_launch(h, kern[ki], lds_set[ki], 160 * 1024, B, GAM_RB_NT, sm, s, &a);
 }
 
-int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
-                  int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
+// gam_rnnt_beam / gam_rnnt_beam_nbest: the encoder projection GEMM, the beam kernel.
+static int rnnt_beam_run(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols,
+                         int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, void* stream, bool nbest, int N,
+                         int32_t* n_hyp) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
   hipStream_t s = (hipStream_t)stream;
@@ -1932,13 +1976,35 @@ int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, i
   if (B <= 0 || Tp <= 0 || Tp > GAM_RB_MAX_T || W < 1 || W > GAM_BEAM_MAX_W || max_symbols < 1 || max_symbols > GAM_RB_MAX_S)
     return fail(h, -1, "RNN-T beam search: B=%d T'=%lld / W=%d / S=%d beyond the limits (%d / [1, %d] / [1, %d])", B, (long long)Tp, W,
                 max_symbols, GAM_RB_MAX_T, GAM_BEAM_MAX_W, GAM_RB_MAX_S);
+  if (nbest)
+    if (int r = nbest_check(h, "RNN-T beam search", W, N, n_hyp)) return r;
   const gam_config& c = h->cfg;
   const int D = c.d_model, JH = c.joint_hidden;
   if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
   if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
   GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
   if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
-  return rnnt_beam_launch(h, h->encp.p, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s);
+  return rnnt_beam_launch(h, h->encp.p, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s, nbest, N, n_hyp);
+}
+
+int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
+                  int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
+  return rnnt_beam_run(h, encoded, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, stream, false, 0, nullptr);
+}
+
+int gam_rnnt_beam_nbest(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int N,
+                        int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream) {
+  return rnnt_beam_run(h, encoded, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, stream, true, N, n_hyp);
+}
+
+int gam_op_rnnt_beam_nbest(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int N,
+                           int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream) {
+  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s, true, N, n_hyp);
 }
 
 int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,

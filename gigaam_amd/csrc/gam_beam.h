@@ -33,6 +33,9 @@
 // B x T' x W nodes (at most W per frame).  The backtrack runs in the same kernel and writes ids / frames / count / score / logp.
 // Limits (host errors beyond them): those of gam_search.h and T' <= GAM_ALIGN_MAX_T.
 //
+// N-best (template <bool NBEST>; gam_ctc_beam_nbest): the final pick becomes gam_search.h's emission of the n best entries of the
+// final beam; everything before it is the same code.
+//
 // Word n-gram LM (template <bool LM>; gam_ctc_beam_kernel<false> is the kernel without it, unchanged; tests/ctc_beam_ref.py with an
 // LMSpec is the float64 reference).  The word rules, the cost split and the tables of gam_search.h, applied to prefixes:
 // rank = (p_b (+) p_nb) + bonus + lm.  Final pick: best (p_b (+) p_nb) + committed + lm with the last word and </s> added.
@@ -56,10 +59,11 @@ struct GamBeamArgs {
   float* score;          // [B]
   float* logp;           // [B]
   GamLmArgs lm;
+  GamNbestArgs nb;       // the <.., true> kernels only: ids / frames are then [B, n, Tp], counts / score / logp [B, n]
 };
-// (the kernel argument layout the fields had before the two blocks were structs of their own)
-static_assert(sizeof(GamBeamArgs) == 176 && offsetof(GamBeamArgs, hw) == 32 && offsetof(GamBeamArgs, nodes) == 56 &&
-              offsetof(GamBeamArgs, lm) == 104, "GamBeamArgs layout");
+// (the kernel argument layout the fields had before the two blocks were structs of their own; the N-best block is appended)
+static_assert(sizeof(GamBeamArgs) == 192 && offsetof(GamBeamArgs, hw) == 32 && offsetof(GamBeamArgs, nodes) == 56 &&
+              offsetof(GamBeamArgs, lm) == 104 && offsetof(GamBeamArgs, nb) == 176, "GamBeamArgs layout");
 
 // LDS carve (host and device): beam state [2][32] (hash, parent hash: u64; p_b, p_nb, acc, committed: f32; len, last, prefix node,
 // hotword node, parent, child mask: i32), top-K ids / values [2][32], beam sizes, candidate keys u64 [NC], candidate p_b, p_nb, acc,
@@ -76,7 +80,7 @@ static inline size_t gam_beam_lds_bytes(int W, int K, int V, int hw_lds_words, b
   return ((base + 15) & ~(size_t)15) + 2 * 32 * (8 + 16 + 3 * 4) + 2 * 32 * 4 + (((size_t)V + 3) & ~(size_t)3);
 }
 
-template <bool LM>
+template <bool LM, bool NBEST = false>
 __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a) {
   extern __shared__ uint4 gam_smem_beam[];
   unsigned char* p = reinterpret_cast<unsigned char*>(gam_smem_beam);
@@ -129,7 +133,8 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
   int T = a.enc_len[b];
   T = T < 0 ? 0 : (T > Tp ? Tp : T);
   if (T == 0) {
-    if (tid == 0) {
+    if constexpr (NBEST) gam_beam_emit_empty(a.nb, b, a.counts, a.score, a.logp, tid);
+    else if (tid == 0) {
       a.counts[b] = 0;
       a.score[b] = 0.f;
       a.logp[b] = 0.f;
@@ -365,6 +370,13 @@ __global__ __launch_bounds__(GAM_BEAM_NT) void gam_ctc_beam_kernel(GamBeamArgs a
         lmf += a.lm.lm_alpha * gam_lm_query(a.lm, false, 0ull, w, cx);
         val += lmf;
       }
+    }
+    if constexpr (NBEST) {   // the nb.n best entries instead of the best one (gam_search.h): the same value, key and arithmetic
+      const double lp_ = (double)lse + off;
+      const float sc = lane < nb ? (LM ? (float)(lp_ + (double)bcb[d] + (double)lmf) : (float)(lp_ + (double)bcb[d])) : -INFINITY;
+      gam_beam_emit_nbest(a.nb, b, Tp, lane < nb, val, sc, (float)lp_, lane < nb ? blen[d] : 0, lane < nb ? bnode[d] : -1, nodes, a.ids,
+                          a.frames, a.counts, a.score, a.logp, lane);
+      return;
     }
     const unsigned long long key = lane < nb ? (((unsigned long long)gam_beam_ord(val) << 32) | (unsigned)(0xffff - lane)) : 0ull;
     const unsigned long long m = gam_beam_wave_max(key);

@@ -41,6 +41,9 @@
 // one y always gets bit-identical predictor outputs.  Renormalisation: each frame subtracts the best kept rank from the scores and adds
 // it to an fp64 offset.  Limits (host errors beyond them): W <= 32, S <= 16, T' <= 8192, V <= 1025, H and JH <= 512 (multiples of 16).
 //
+// N-best (template <bool NBEST>; gam_rnnt_beam_nbest): the final pick becomes gam_search.h's emission of the n best entries of the
+// final beam; everything before it is the same code.
+//
 // Word n-gram LM (template <bool LM>; gam_rnnt_beam_kernel<false> is the kernel without it, unchanged; tests/rnnt_beam_ref.py with an
 // LMSpec is the float64 reference).  The word rules of gam_search.h, applied to hypotheses: token classes from gam_set_lm (0 continues the current
 // word, 1 starts a new word, 2 separates; blank is class 0 and never extends y).  A hypothesis carries the spelling hash of its
@@ -90,10 +93,11 @@ struct GamRnntBeamArgs {
   float* score;          // [B]
   float* logp;           // [B]
   GamLmArgs lm;
+  GamNbestArgs nb;       // the <.., true> kernels only: ids / frames are then [B, n, cap], counts / score / logp [B, n]
 };
-// (the kernel argument layout the fields had before the two blocks were structs of their own)
-static_assert(sizeof(GamRnntBeamArgs) == 288 && offsetof(GamRnntBeamArgs, hw) == 120 && offsetof(GamRnntBeamArgs, ws) == 144 &&
-              offsetof(GamRnntBeamArgs, lm) == 216, "GamRnntBeamArgs layout");
+// (the kernel argument layout the fields had before the two blocks were structs of their own; the N-best block is appended)
+static_assert(sizeof(GamRnntBeamArgs) == 304 && offsetof(GamRnntBeamArgs, hw) == 120 && offsetof(GamRnntBeamArgs, ws) == 144 &&
+              offsetof(GamRnntBeamArgs, lm) == 216 && offsetof(GamRnntBeamArgs, nb) == 288, "GamRnntBeamArgs layout");
 
 // LDS carve (host and device), in bytes, in this order: A lists [2][32] (hash u64; len, score, hotword node, acc, committed, prefix
 // node, slot, token, parent slot: i32 / f32), row blank log-probs [32], counters [16], B list [P] (hash u64; len, score, best
@@ -162,16 +166,16 @@ __device__ __forceinline__ void gam_rb_gates_mm(f32x4 (&acc)[4][2], const float*
   }
 }
 
-template <int RT, bool LM>
+template <int RT, bool LM, bool NBEST>
 __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a);
 
-template <bool LM>
+template <bool LM, bool NBEST = false>
 __global__ __launch_bounds__(GAM_RB_NT) void gam_rnnt_beam_kernel(GamRnntBeamArgs a) {
-  if (a.W > 16) gam_rb_body<2, LM>(a);
-  else gam_rb_body<1, LM>(a);
+  if (a.W > 16) gam_rb_body<2, LM, NBEST>(a);
+  else gam_rb_body<1, LM, NBEST>(a);
 }
 
-template <int RT, bool LM>
+template <int RT, bool LM, bool NBEST>
 __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
   extern __shared__ uint4 gam_smem_rbeam[];
   unsigned char* p = reinterpret_cast<unsigned char*>(gam_smem_rbeam);
@@ -243,7 +247,8 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
   int T = a.enc_len[b];
   T = T < 0 ? 0 : (T > Tp ? Tp : T);
   if (T == 0) {
-    if (tid == 0) {
+    if constexpr (NBEST) gam_beam_emit_empty(a.nb, b, a.counts, a.score, a.logp, tid);
+    else if (tid == 0) {
       a.counts[b] = 0;
       a.score[b] = 0.f;
       a.logp[b] = 0.f;
@@ -639,6 +644,13 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
         lmf += a.lm.lm_alpha * gam_lm_query(a.lm, false, 0ull, w, cx);
         val += lmf;
       }
+    }
+    if constexpr (NBEST) {   // the nb.n best entries instead of the best one (gam_search.h): the same value, key and arithmetic
+      const double lp_ = (double)(lane < nb ? asc[lane] : -INFINITY) + off;
+      const float sc = lane < nb ? (LM ? (float)(lp_ + (double)acb[lane] + (double)lmf) : (float)(lp_ + (double)acb[lane])) : -INFINITY;
+      gam_beam_emit_nbest(a.nb, b, a.cap, lane < nb, val, sc, (float)lp_, lane < nb ? alen[lane] : 0, lane < nb ? anode[lane] : -1, nodes,
+                          a.ids, a.frames, a.counts, a.score, a.logp, lane);
+      return;
     }
     const unsigned long long key = lane < nb ? (((unsigned long long)gam_beam_ord(val) << 32) | (unsigned)(0xffff - lane)) : 0ull;
     const unsigned long long m = gam_beam_wave_max(key);

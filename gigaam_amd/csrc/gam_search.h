@@ -1,5 +1,5 @@
 // gam_search.h -- what the CTC prefix beam search (gam_beam.h) and the RNN-T beam search (gam_rnnt_beam.h) share: limits, the
-// hotword and LM argument blocks, log-add-exp, orderable selection keys, the wave top-n, the hotword trie walk and the n-gram LM query.
+// hotword and LM argument blocks, log-add-exp, orderable selection keys, the wave top-n, the hotword trie walk, the n-gram LM query and the N-best emission.
 // Every function is __forceinline__: left to the inliner, a body became a call that copied the argument struct to scratch
 // (DESIGN.md 4.12).
 //
@@ -248,4 +248,66 @@ __device__ __forceinline__ float gam_lm_query(const GamLmArgs& a, bool word, uns
     if (!got && k >= 1 && ((fA >> k) & 1)) bo += __uint_as_float(vA[k]);
   }
   return lp;
+}
+
+// ---- N-best emission (gam_ctc_beam_nbest / gam_rnnt_beam_nbest): what the <.., true> kernels run in place of the 1-best pick.
+// The kernels' ids / frames are then [B, n, cap] and counts / score / logp [B, n]; rows r >= n_hyp[b] get counts 0 and score =
+// logp = -inf (their ids / frames are not written).
+struct GamNbestArgs {
+  int* n_hyp;            // [B] hypotheses written (NULL in the 1-best calls)
+  int n, pad;            // hypotheses asked for, 1 <= n <= W
+};
+static_assert(sizeof(GamNbestArgs) == 16, "N-best argument block");
+
+// Wave 0 after the last frame.  Lane i holds entry i of the final beam: `live`, its ranking value `val` (what the 1-best pick ranks
+// by), its rounded score and logp, its token count and prefix-trie node.  The nb.n best by (val descending, position ascending) --
+// the 1-best pick's key -- are written in that order: lane r fetches hypothesis r from its lane and backtracks it, the lanes in
+// parallel.  Row 0 is therefore the 1-best result bit for bit.
+__device__ __forceinline__ void gam_beam_emit_nbest(const GamNbestArgs& nb, int b, int cap, bool live, float val, float score, float logp,
+                                                    int len, int node, const int2* nodes, int* ids, int* frames, int* counts, float* oscore,
+                                                    float* ologp, int lane) {
+  unsigned long long k[GAM_BEAM_RPL];
+#pragma unroll
+  for (int r = 0; r < GAM_BEAM_RPL; ++r) k[r] = 0ull;
+  k[0] = live ? (((unsigned long long)gam_beam_ord(val) << 32) | (unsigned)(0xffff - lane)) : 0ull;
+  unsigned long long sel;
+  const int nh = gam_beam_wave_topn(k, 1, nb.n, lane, sel);
+  const int src = lane < nh ? 0xffff - (int)(sel & 0xffff) : lane;
+  score = __shfl(score, src);
+  logp = __shfl(logp, src);
+  len = __shfl(len, src);
+  node = __shfl(node, src);
+  if (lane == 0) nb.n_hyp[b] = nh;
+  if (lane >= nb.n) return;
+  const size_t row = (size_t)b * nb.n + lane;
+  if (lane >= nh) {
+    counts[row] = 0;
+    oscore[row] = -INFINITY;
+    ologp[row] = -INFINITY;
+    return;
+  }
+  const int n = len < cap ? len : cap;
+  counts[row] = n;
+  oscore[row] = score;
+  ologp[row] = logp;
+  int* oi = ids + row * cap;
+  int* of = frames + row * cap;
+  for (int i = len - 1; i >= 0; --i) {
+    const int2 e = nodes[node];
+    if (i < n) {
+      oi[i] = e.y >> 13;
+      of[i] = e.y & 8191;
+    }
+    node = e.x;
+  }
+}
+// enc_len[b] = 0: one empty hypothesis with score = logp = 0 (threads tid < nb.n of the workgroup).
+__device__ __forceinline__ void gam_beam_emit_empty(const GamNbestArgs& nb, int b, int* counts, float* score, float* logp, int tid) {
+  if (tid == 0) nb.n_hyp[b] = 1;
+  if (tid < nb.n) {
+    const size_t row = (size_t)b * nb.n + tid;
+    counts[row] = 0;
+    score[row] = tid == 0 ? 0.f : -INFINITY;
+    logp[row] = tid == 0 ? 0.f : -INFINITY;
+  }
 }

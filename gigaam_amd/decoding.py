@@ -75,6 +75,15 @@ def _ragged(dec, *rest) -> List[Tuple[List[int], List[int]]]:
 class _BeamInputs:
     """Hotwords and the LM as the beam searches take them (per-object caches); mixed into the decoding classes that search by beam."""
 
+    def finish_nbest(self, dec) -> List[List[Tuple[str, List[int], List[int], float, float]]]:
+        """An ``engine.NBestDecoded`` -> per utterance its hypotheses ``(text, ids, frames, score, logp)``, best first (at most two
+        D2H copies: ``NBestDecoded.host``); raises ``RangeOverflow`` like ``finish``."""
+        h = dec.host()
+        if h["flag"]:
+            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        return [[(self.tokenizer.decode(i), i, f, float(h["score"][b][r]), float(h["logp"][b][r])) for r, (i, f) in enumerate(rows)]
+                for b, rows in enumerate(h["rows"])]
+
     def hotword_ids(self, hotwords) -> List[List[int]]:
         """Hotwords (each a string in the vocabulary -- ``Tokenizer.encode`` -- or token ids) -> token-id lists, the strings'
         encodings cached."""
@@ -150,6 +159,26 @@ class CTCGreedyDecoding(_BeamInputs):
         if h["flag"]:
             raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
         return [(self.tokenizer.decode(i), i, f, float(h["score"][k]), float(h["logp"][k])) for k, (i, f) in enumerate(h["rows"])]
+
+    @torch.inference_mode()
+    def decode_nbest_device(self, head: CTCHead, encoded: Tensor, lengths: Tensor, n_best: int, beam_size: int = 8, hotwords=None,
+                            hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0):
+        """The device half of ``decode_nbest`` (gam_ctc_beam_nbest), no host sync: an ``engine.NBestDecoded``."""
+        c = head.num_classes
+        assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
+        head.engine.set_hotwords(self.hotword_ids(hotwords), hotword_boost)
+        head.engine.set_lm(self.language_model(lm), self.tokenizer, lm_weight, word_bonus)
+        return head.engine.ctc_beam_nbest(encoded, lengths, beam_size, n_best)
+
+    @torch.inference_mode()
+    def decode_nbest(self, head: CTCHead, encoded: Tensor, lengths: Tensor, n_best: int, beam_size: int = 8, hotwords=None,
+                     hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5,
+                     word_bonus: float = 1.0) -> List[List[Tuple[str, List[int], List[int], float, float]]]:
+        """``decode_beam`` returning the ``n_best`` (<= ``beam_size``) best prefixes of the final beam: per utterance a list of
+        ``(text, ids, frames, score, logp)``, best first by ``score`` (ties: the beam's order); entry 0 is ``decode_beam``'s result
+        bit for bit.  A short utterance can have fewer than ``n_best``.  Raises ``RangeOverflow`` like ``finish``."""
+        return self.finish_nbest(self.decode_nbest_device(head, encoded, lengths, n_best, beam_size, hotwords, hotword_boost, lm,
+                                                          lm_weight, word_bonus))
 
     MAX_ALIGN_TOKENS = 1024     # include/gigaam_hip.h gam_ctc_align
 
@@ -276,3 +305,22 @@ class RNNTBeamDecoding(RNNTGreedyDecoding, _BeamInputs):
         if h["flag"]:
             raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
         return [(self.tokenizer.decode(i), i, f, float(h["score"][k]), float(h["logp"][k])) for k, (i, f) in enumerate(h["rows"])]
+
+    @torch.inference_mode()
+    def decode_nbest_device(self, head: RNNTHead, encoded: Tensor, enc_len: Tensor, n_best: int, beam_size: Optional[int] = None,
+                            hotwords=None, hotword_boost: Optional[float] = None):
+        """The device half of ``decode_nbest`` (gam_rnnt_beam_nbest), no host sync: an ``engine.NBestDecoded``.  The per-call
+        overrides are ``decode_device``'s."""
+        hw = self.hotwords if hotwords is None else hotwords
+        boost = self.hotword_boost if hotword_boost is None else hotword_boost
+        head.engine.set_hotwords(self.hotword_ids(hw), boost)
+        head.engine.set_lm(self.lm, self.tokenizer, self.lm_weight, self.word_bonus)
+        return head.engine.rnnt_beam_nbest(encoded, enc_len, self.beam_size if beam_size is None else beam_size, self.max_symbols, n_best)
+
+    @torch.inference_mode()
+    def decode_nbest(self, head: RNNTHead, encoded: Tensor, enc_len: Tensor, n_best: int, beam_size: Optional[int] = None,
+                     hotwords=None, hotword_boost: Optional[float] = None) -> List[List[Tuple[str, List[int], List[int], float, float]]]:
+        """``decode_beam`` returning the ``n_best`` (<= the beam width) best hypotheses of the final beam: per utterance a list of
+        ``(text, ids, frames, score, logp)``, best first by ``score`` (ties: the beam's order); entry 0 is ``decode_beam``'s result
+        bit for bit.  Raises ``RangeOverflow`` like ``finish``."""
+        return self.finish_nbest(self.decode_nbest_device(head, encoded, enc_len, n_best, beam_size, hotwords, hotword_boost))

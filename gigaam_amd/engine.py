@@ -260,6 +260,57 @@ class BeamDecoded(Decoded):
                 "flag": HipEngine._flag_of(int(arr[n0 - 1]))}
 
 
+class NBestDecoded:
+    """What ``ctc_beam_nbest`` / ``op_ctc_beam_nbest`` / ``rnnt_beam_nbest`` / ``op_rnnt_beam_nbest`` return: the ``n`` best hypotheses
+    of each final beam, on the device.  ``ids`` / ``frames`` i32 [B, n, cap]; the small block ``small`` is ONE i32 buffer: n_hyp [B] |
+    counts [B, n] | score bits [B, n] | logp bits [B, n] | range flag word.  Row 0 of every utterance is the 1-best search's result."""
+
+    def __init__(self, tok: Tensor, small: Tensor, event=None, stream=None):
+        # (tok: i32 [2, B, n, cap], ids | frames)
+        _, b, n, cap = tok.shape
+        self.tok, self.ids, self.frames, self.small, self.b, self.n, self.cap = tok, tok[0], tok[1], small, b, n, cap
+        self.event, self.stream = event, stream
+        bn = b * n
+        self.n_hyp = small[:b]
+        self.counts = small[b: b + bn].view(b, n)
+        self.score = small[b + bn: b + 2 * bn].view(torch.float32).view(b, n)
+        self.logp = small[b + 2 * bn: b + 3 * bn].view(torch.float32).view(b, n)
+        self.ext = small[b + 3 * bn: b + 3 * bn + 1]
+        self.copied_bytes = 0     # what the last ``host()`` brought over
+
+    def flag_word(self) -> Tensor:
+        return self.ext
+
+    def host(self) -> Dict[str, Any]:
+        """At most TWO blocking D2H copies, on the collect stream behind the search's own completion event: the small block, then
+        columns [0, longest hypothesis) of ids | frames ([B, n, cap] can be tens of MB for RNN-T and is never copied whole) ->
+        ``rows`` [b][r] = (ids, frames) host lists for r < n_hyp[b], ``score`` / ``logp`` numpy f32 [B, n] (-inf past n_hyp),
+        ``n_hyp`` numpy i32 [B] and ``flag`` (the split-fp16 range flag, as ``collect``)."""
+        side = HipEngine._collect_stream(self.small.device)
+        b, n, bn = self.b, self.n, self.b * self.n
+        with torch.cuda.stream(side):
+            if self.event is not None:
+                side.wait_event(self.event)
+            else:
+                side.wait_stream(torch.cuda.current_stream(self.small.device))
+            arr = self.small.cpu().numpy()
+            self.copied_bytes = arr.nbytes
+            n_hyp = arr[:b].copy()
+            counts = arr[b: b + bn].reshape(b, n)
+            m = int(counts.max()) if bn else 0
+            tok = None
+            if m > 0:
+                tok = self.tok[..., :m].contiguous().cpu().numpy()
+                self.copied_bytes += tok.nbytes
+        for t in (self.small, self.tok):
+            t.record_stream(side)
+        rows = [[(tok[0, i, r, :counts[i, r]].tolist(), tok[1, i, r, :counts[i, r]].tolist()) if counts[i, r] else ([], [])
+                 for r in range(int(n_hyp[i]))] for i in range(b)]
+        return {"rows": rows, "score": arr[b + bn: b + 2 * bn].view(np.float32).reshape(b, n).copy(),
+                "logp": arr[b + 2 * bn: b + 3 * bn].view(np.float32).reshape(b, n).copy(), "n_hyp": n_hyp,
+                "flag": HipEngine._flag_of(int(arr[b + 3 * bn]))}
+
+
 def _ptr(t: Optional[Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -868,6 +919,76 @@ class HipEngine:
                                            _ptr(out.frames), _ptr(out.counts), _ptr(out.score), _ptr(out.logp), self._stream())
             self._check(rc, "gam_op_rnnt_beam")
             return self._op_beam_done(out)
+
+    def _nbest_out(self, b: int, cap: int, beam_size: int, n_best: int, max_symbols: Optional[int] = None) -> NBestDecoded:
+        """Check the width, ``n_best`` (and the RNN-T search's ``max_symbols``); the result buffers for ``n_best`` hypotheses of ``cap``
+        tokens per utterance."""
+        if not 1 <= int(beam_size) <= self.MAX_BEAM:
+            raise GigaAMHipError(f"beam_size {beam_size} outside [1, {self.MAX_BEAM}]")
+        if not 1 <= int(n_best) <= int(beam_size):
+            raise GigaAMHipError(f"n_best {n_best} outside [1, beam_size = {beam_size}]")
+        if max_symbols is not None and not 1 <= int(max_symbols) <= self.MAX_SYMBOLS_BEAM:
+            raise GigaAMHipError(f"max_symbols {max_symbols} outside [1, {self.MAX_SYMBOLS_BEAM}] for the RNN-T beam search")
+        n = int(n_best)
+        return NBestDecoded(torch.empty((2, b, n, cap), dtype=torch.int32, device=self.device),
+                            torch.empty((b + 3 * b * n + 1,), dtype=torch.int32, device=self.device))
+
+    def _launch_nbest(self, fn, what: str, first: Tensor, enc_len: Tensor, b: int, tp: int, extra, out: NBestDecoded, op: bool) -> NBestDecoded:
+        rc = fn(self._h, _ptr(first), _ptr(enc_len), b, tp, *extra, out.n, _ptr(out.ids), _ptr(out.frames), _ptr(out.counts),
+                _ptr(out.score), _ptr(out.logp), _ptr(out.n_hyp), self._stream())
+        self._check(rc, what)
+        if op:      # no encoder ran: zero the flag word, record the completion event
+            out.ext.zero_()
+            st = torch.cuda.current_stream(self.device)
+            out.event, out.stream = torch.cuda.Event(), st
+            out.event.record(st)
+        else:
+            out.event, out.stream = self._fetch_flag(out.ext)
+        return out
+
+    def ctc_beam_nbest(self, encoded: Tensor, enc_len: Tensor, beam_size: int, n_best: int) -> NBestDecoded:
+        """``ctc_beam`` returning the ``n_best`` (<= ``beam_size``) best prefixes of each final beam (gam_ctc_beam_nbest), no host
+        sync; hypothesis 0 is ``ctc_beam``'s result bit for bit.  The range flag lands in the flag word, as in ``ctc_beam``."""
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        with torch.cuda.device(self.device):
+            out = self._nbest_out(b, tp, beam_size, n_best)
+            return self._launch_nbest(self.lib.gam_ctc_beam_nbest, "gam_ctc_beam_nbest", encoded, enc_len, b, tp, (int(beam_size),), out, False)
+
+    def op_ctc_beam_nbest(self, log_probs: Tensor, enc_len: Tensor, beam_size: int, n_best: int) -> NBestDecoded:
+        """gam_op_ctc_beam_nbest: the N-best beam kernel alone on caller-supplied log-probs [B, T', V].  The flag word is 0."""
+        log_probs = self._dev(log_probs, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, v = log_probs.shape
+        with torch.cuda.device(self.device):
+            out = self._nbest_out(b, tp, beam_size, n_best)
+            return self._launch_nbest(self.lib.gam_op_ctc_beam_nbest, "gam_op_ctc_beam_nbest", log_probs, enc_len, b, tp,
+                                      (v, int(beam_size)), out, True)
+
+    def rnnt_beam_nbest(self, encoded: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int, n_best: int) -> NBestDecoded:
+        """``rnnt_beam`` returning the ``n_best`` (<= ``beam_size``) best hypotheses of each final beam (gam_rnnt_beam_nbest), no host
+        sync; hypothesis 0 is ``rnnt_beam``'s result bit for bit.  ids / frames are [B, n_best, T' * max_symbols]."""
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        with torch.cuda.device(self.device):
+            out = self._nbest_out(b, tp * int(max_symbols), beam_size, n_best, max_symbols)
+            return self._launch_nbest(self.lib.gam_rnnt_beam_nbest, "gam_rnnt_beam_nbest", encoded, enc_len, b, tp,
+                                      (int(beam_size), int(max_symbols)), out, False)
+
+    def op_rnnt_beam_nbest(self, encp: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int, n_best: int) -> NBestDecoded:
+        """gam_op_rnnt_beam_nbest: the N-best beam kernel alone on a caller-supplied encoder projection encp f32 [B, T', joint_hidden],
+        as ``op_rnnt_beam``.  The flag word is 0."""
+        encp = self._dev(encp, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, jh = encp.shape
+        if jh != self.cfg.joint_hidden:
+            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        with torch.cuda.device(self.device):
+            out = self._nbest_out(b, tp * int(max_symbols), beam_size, n_best, max_symbols)
+            return self._launch_nbest(self.lib.gam_op_rnnt_beam_nbest, "gam_op_rnnt_beam_nbest", encp, enc_len, b, tp,
+                                      (int(beam_size), int(max_symbols)), out, True)
 
     def set_hotwords(self, phrases, boost: float = 2.0) -> None:
         """Hotword phrases (token-id lists) for the beam search, each matched token worth ``boost`` (gam_set_hotwords); an empty

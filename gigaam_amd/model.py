@@ -19,7 +19,8 @@ from . import preprocess as _preprocess
 from ._lib import GigaAMHipError
 from .engine import HipEngine, build_config
 from .preprocess import SAMPLE_RATE, load_audio
-from .types import AlignmentResult, ConfidenceResult, LongformTranscriptionResult, ScoredWord, Segment, TranscriptionResult, Word
+from .types import (AlignmentResult, ConfidenceResult, Hypothesis, LongformTranscriptionResult, NBestResult, ScoredWord, Segment,
+                    TranscriptionResult, Word, nbest_posteriors)
 
 LONGFORM_THRESHOLD = 25 * SAMPLE_RATE
 
@@ -358,6 +359,78 @@ class GigaAMASR(GigaAM):
             return self._with_f32_fallback(lambda: self.collect_batch(self.launch_batch(wav, lengths), word_timestamps), "this batch was")
         kw = dict(beam_size=beam_size, hotwords=hotwords, hotword_boost=hotword_boost, lm=lm, lm_weight=lm_weight, word_bonus=word_bonus)
         return self._with_f32_fallback(lambda: self.collect_batch(self.launch_batch(wav, lengths, **kw), word_timestamps), "this batch was")
+
+    # ---- N-best: the best hypotheses of the final beam instead of the best one (gam_ctc_beam_nbest / gam_rnnt_beam_nbest)
+    def _nbest_width(self, n_best: int, beam_size: Optional[int], hotwords, lm) -> int:
+        """Check ``n_best`` against the search a ``transcribe_nbest`` call runs; its beam width.  Needs no device."""
+        n_best = int(n_best)
+        if not 1 <= n_best <= 32:
+            raise ValueError(f"n_best {n_best} outside [1, 32]")
+        dec = self.decoding
+        if isinstance(dec, _decoding.CTCGreedyDecoding):
+            width = max(8, n_best) if beam_size is None else int(beam_size)
+            if not 1 <= width <= 32:
+                raise ValueError(f"beam_size {width} outside [1, 32]")
+            if n_best > width:
+                raise ValueError(f"n_best {n_best} exceeds beam_size {width}")
+            return width
+        if beam_size is not None or hotwords is not None or lm is not None:
+            raise TypeError("beam search needs a CTC head")       # (as transcribe: RNN-T heads take them through set_decoding)
+        if not isinstance(dec, _decoding.RNNTBeamDecoding):
+            raise ValueError("N-best needs a beam search: select one with set_decoding(beam_size=...)")
+        if n_best > dec.beam_size:
+            raise ValueError(f"n_best {n_best} exceeds the beam width {dec.beam_size} that set_decoding(beam_size=...) configured")
+        return dec.beam_size
+
+    @torch.inference_mode()
+    def transcribe_nbest(self, wav_file: str, n_best: int = 5, word_timestamps: bool = False, *, beam_size: Optional[int] = None,
+                         hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
+                         lm_weight: float = 0.5, word_bonus: float = 1.0) -> NBestResult:
+        """The ``n_best`` (1..32) best hypotheses of the beam search's final beam for a clip of at most 25 s, best first.  CTC heads:
+        the options of ``transcribe``; ``beam_size`` defaults to max(8, ``n_best``) and must not be below ``n_best``.  RNN-T heads:
+        the search ``set_decoding`` selected (a beam at least ``n_best`` wide; per-call options are a TypeError as in ``transcribe``).
+        ``.best`` is what ``transcribe`` returns under the same options; the list can be shorter than ``n_best`` when the final beam
+        holds fewer hypotheses."""
+        self._nbest_width(n_best, beam_size, hotwords, lm)
+        wav, length = self._prepare_wav_f32(wav_file)
+        if length.item() > LONGFORM_THRESHOLD:
+            raise ValueError("Too long wav file for transcribe_nbest (at most 25 s).")
+        return self.transcribe_nbest_batch(wav, length, n_best, word_timestamps, beam_size=beam_size, hotwords=hotwords,
+                                           hotword_boost=hotword_boost, lm=lm, lm_weight=lm_weight, word_bonus=word_bonus)[0]
+
+    @torch.inference_mode()
+    def transcribe_nbest_batch(self, wav: Tensor, lengths: Tensor, n_best: int = 5, word_timestamps: bool = False, *,
+                               beam_size: Optional[int] = None, hotwords: Optional[Sequence[Union[str, List[int]]]] = None,
+                               hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, word_bonus: float = 1.0) -> List[NBestResult]:
+        """Batched twin of ``transcribe_nbest`` on an already collated batch (wav [B,L] zero padded, len [B])."""
+        width = self._nbest_width(n_best, beam_size, hotwords, lm)
+        ctc = isinstance(self.decoding, _decoding.CTCGreedyDecoding)
+
+        def run():
+            # as launch_batch: sample counts on the host give a ragged batch packed rows
+            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
+            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            if ctc:
+                dev = self.decoding.decode_nbest_device(self.head, encoded, encoded_len, int(n_best), width, hotwords, hotword_boost, lm,
+                                                        lm_weight, word_bonus)
+            else:
+                dev = self.decoding.decode_nbest_device(self.head, encoded, encoded_len, int(n_best))
+            return self.decoding.finish_nbest(dev), encoded_len
+
+        rows, encoded_len = self._with_f32_fallback(run, "this batch was")
+        out: List[NBestResult] = []
+        shifts = None
+        if word_timestamps:     # the frames_to_words call of _with_words, per hypothesis
+            from .timestamps_utils import compute_frame_shift, frames_to_words
+            wl, el = lengths.tolist(), encoded_len.tolist()
+            shifts = [compute_frame_shift(int(w), int(e)) for w, e in zip(wl, el)]
+        tok = self.decoding.tokenizer
+        for b, hyps in enumerate(rows):
+            post = nbest_posteriors([h[3] for h in hyps])
+            out.append(NBestResult([Hypothesis(text=t, token_ids=i, token_frames=f, score=sc, logp=lp, posterior=post[r],
+                                               words=frames_to_words(tok, i, f, shifts[b]) if word_timestamps else None)
+                                    for r, (t, i, f, sc, lp) in enumerate(hyps)]))
+        return out
 
     # ---- CTC forced alignment: a KNOWN transcript placed on the audio, and its log-likelihood (gam_ctc_align)
     def _require_ctc(self) -> None:

@@ -2,8 +2,9 @@
 behaviour as the reference's gigaam/types.py:18-68 (boundary types)."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
-from typing import Iterator, List, Optional
+from typing import Iterator, List, Optional, Sequence
 
 
 @dataclass
@@ -69,6 +70,60 @@ class ConfidenceResult:
 
     def __str__(self) -> str:
         return self.text
+
+
+@dataclass
+class Hypothesis:
+    """One entry of an ``NBestResult``.  ``token_frames``: the frames the search's ``frames`` are; ``score``: log p + committed hotword
+    bonus + LM term, the value the list is ordered by; ``logp``: that log p alone (over the paths / alignments the beam kept);
+    ``posterior``: the softmax of ``score`` over the hypotheses RETURNED -- the usual N-best posterior: it sums to 1 over the list
+    whatever its length and is not a calibrated probability; ``words``: with ``word_timestamps=True``."""
+    text: str
+    token_ids: List[int]
+    token_frames: List[int]
+    score: float
+    logp: float
+    posterior: float
+    words: Optional[List[Word]] = None
+
+    def __str__(self) -> str:
+        return self.text
+
+
+def nbest_posteriors(scores: Sequence[float]) -> List[float]:
+    """Softmax of the scores in float64 (empty -> empty)."""
+    if not scores:
+        return []
+    m = max(scores)
+    if m == -math.inf:
+        return [1.0 / len(scores)] * len(scores)
+    e = [math.exp(float(s) - m) for s in scores]
+    z = math.fsum(e)
+    return [x / z for x in e]
+
+
+@dataclass
+class NBestResult:
+    """``GigaAMASR.transcribe_nbest``: the hypotheses of the final beam, best first (score descending).  ``best`` is what ``transcribe``
+    returns under the same options."""
+    hypotheses: List[Hypothesis]
+
+    @property
+    def best(self) -> Hypothesis:
+        return self.hypotheses[0]
+
+    @property
+    def text(self) -> str:
+        return self.hypotheses[0].text if self.hypotheses else ""
+
+    def __str__(self) -> str:
+        return self.text
+
+    def __iter__(self) -> Iterator[Hypothesis]:
+        return iter(self.hypotheses)
+
+    def __len__(self) -> int:
+        return len(self.hypotheses)
 
 
 @dataclass

@@ -13,9 +13,11 @@
  *   gam_ctc_greedy   <- CTCGreedyDecoding.decode          gigaam/decoding.py:56-96
  *   gam_ctc_align    (no reference counterpart: CTC forced alignment + log-likelihood of a given transcript)
  *   gam_ctc_beam     (no reference counterpart: CTC prefix beam search with hotword boosting and n-gram LM fusion)
+ *   gam_ctc_beam_nbest   (no reference counterpart: the N best prefixes of that search's final beam)
  *   gam_rnnt_greedy  <- RNNTGreedyDecoding.decode         gigaam/decoding.py:128-207
  *   gam_rnnt_beam    (no reference counterpart: RNN-T beam search with hotword boosting and n-gram LM fusion)
  *                        (+ RNNTDecoder.predict decoder.py:85-102, RNNTJoint.joint :41-47)
+ *   gam_rnnt_beam_nbest  (no reference counterpart: the N best hypotheses of that search's final beam)
  *   gam_emo_probs    <- GigaAMEmo.get_probs (pool+head)    gigaam/model.py:272-285
  *   gam_set_weight   <- nn.Module.load_state_dict         gigaam/__init__.py:185
  *   gam_create       <- hydra.utils.instantiate(cfg.*)    gigaam/model.py:24-25,93-94
@@ -158,6 +160,22 @@ int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, in
 /* The same from caller-supplied log-probs f32 [B, T', V] (read as they are), 2 <= V <= 1025. */
 int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
                     int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
+/* N-best of the CTC prefix beam search: the same search (same kernel up to its last frame, same hotwords and LM, same limits), then
+ * the N best entries of its final beam instead of the best one, 1 <= N <= W <= 32 (an error otherwise, without a launch).  An entry's
+ * value is what gam_ctc_beam's final pick ranks by: log p + committed hotword bonus + LM term with the last word and </s> (a pending
+ * partial hotword match does not count); order: value descending, ties to the lower beam position.
+ *   ids / frames i32 [B, N, T'], counts i32 [B, N], score / logp f32 [B, N]: hypothesis r of utterance b, with gam_ctc_beam's meaning
+ *   and arithmetic -- row 0 is gam_ctc_beam's result bit for bit.
+ *   n_hyp i32 [B] = min(N, entries of the final beam) (prefixes of probability 0 never enter a beam, so a short utterance can have
+ *   fewer than N).  Rows r >= n_hyp[b]: counts = 0, score = logp = -inf, ids / frames not written.
+ *   enc_len[b] = 0 gives n_hyp = 1: one empty hypothesis with score = logp = 0.
+ * The scores are the search's own (paths and alignments the beam kept), comparable within one call; gam_ctc_align scores any of the
+ * hypotheses exactly.  Decode class; no host synchronisation. */
+int gam_ctc_beam_nbest(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int N, int32_t* ids,
+                       int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream);
+/* The same from caller-supplied log-probs f32 [B, T', V], as gam_op_ctc_beam. */
+int gam_op_ctc_beam_nbest(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int N,
+                          int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream);
 /* Hotword phrases for the beam search: phrase i is tokens[offsets[i] .. offsets[i + 1]) (host arrays; offsets has n_phrases + 1
  * entries, offsets[0] = 0), every matched token worth `boost` in the ranking; a partial match is rolled back when the prefix leaves
  * the phrase, and only complete phrases count in the final score.  Ids outside [0, V - 2], empty phrases, more than 1024 phrases or
@@ -206,6 +224,21 @@ int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, i
  * predictor and joint weights, hotwords and LM. */
 int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
                      int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
+
+/* N-best of the RNN-T beam search: the same search (same kernel up to its last frame, same hotwords and LM, same limits), then the N
+ * best entries of its final beam instead of the best one, 1 <= N <= W <= 32 (an error otherwise, without a launch).  An entry's value
+ * is what gam_rnnt_beam's final pick ranks by: score + committed hotword bonus + LM term with the last word and </s>; order: value
+ * descending, ties to the lower beam position.
+ *   ids / frames i32 [B, N, T' * max_symbols], counts i32 [B, N], score / logp f32 [B, N]: hypothesis r of utterance b, with
+ *   gam_rnnt_beam's meaning and arithmetic -- row 0 is gam_rnnt_beam's result bit for bit.
+ *   n_hyp i32 [B] = min(N, entries of the final beam).  Rows r >= n_hyp[b]: counts = 0, score = logp = -inf, ids / frames not written.
+ *   enc_len[b] = 0 gives n_hyp = 1: one empty hypothesis with score = logp = 0.
+ * gam_rnnt_align scores any of the hypotheses exactly.  Decode class; no host synchronisation. */
+int gam_rnnt_beam_nbest(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int N,
+                        int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream);
+/* The same on a caller-supplied encoder projection, as gam_op_rnnt_beam. */
+int gam_op_rnnt_beam_nbest(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int N,
+                           int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream);
 
 /* Transducer forced alignment and transcript scoring (gigaam_amd/csrc/gam_rnnt_align.h holds the contract): the standard RNN-T
  * lattice, the one the transducer loss sums over.  For utterance b, T = enc_len[b], targets i32 [B, Umax] hold U = target_len[b]
