@@ -21,7 +21,7 @@ NORM_BATCH, NORM_LAYER = 0, 1
 HEAD_NONE, HEAD_CTC, HEAD_RNNT, HEAD_EMO = 0, 1, 2, 3
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_F64, DTYPE_I64 = 0, 1, 2, 3, 4
 GEMM_F32, GEMM_F16X3, GEMM_F16 = 0, 1, 2
-PF_CLASSES = ["gemm", "conv2", "attn", "norm", "convmod", "stem", "frontend", "decode", "misc"]
+PF_CLASSES = ["gemm", "conv2", "attn", "norm", "convmod", "stem", "frontend", "decode", "misc", "align_bt", "align_out"]
 
 
 class GamConfig(C.Structure):
@@ -53,6 +53,9 @@ SIGNATURES = {
     "gam_ctc_greedy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P]),
     "gam_ctc_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gam_op_ctc_align_long": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gam_set_ctc_align_workspace": (C.c_int, [_P, C.c_int64]),
+    "gam_tune_ctc_align_long": (C.c_int, [C.c_int, C.c_int]),
     "gam_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_set_hotwords": (C.c_int, [_P, _P, _P, C.c_int, C.c_float]),

@@ -15,6 +15,7 @@
 
 #include "../../include/gigaam_hip.h"
 #include "gam_align.h"
+#include "gam_align_long.h"
 #include "gam_attn.h"
 #include "gam_beam.h"
 #include "gam_rnnt_beam.h"
@@ -132,6 +133,8 @@ struct gam_handle {
   DevBuf wavp, spec, img, c2, xin, y1, x, y, yr, hbuf, qkv, ctx, ubuf, zbuf, tok, logits, encp, pbuf, aplanes;
   DevBuf op_planes, op_sp, splitk_ws;   // gam_op_gemm operand planes; split-K partial sums
   DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
+  DevBuf align_long_ws;                 // long-utterance CTC alignment (gam_align_long.h): backpointers | edges | rows | offsets | path | ctrl
+  size_t al_ws_limit = GAM_AL_WS_DEFAULT;   // bytes that workspace may take (gam_set_ctc_align_workspace; GAM_CTC_ALIGN_WS at gam_create)
   DevBuf beam_nodes;                    // CTC beam search prefix-trie nodes, B x T' x W (gam_beam.h)
   DevBuf rb_ws, rb_nodes;               // RNN-T beam search: predictor-state slots + logit rows, prefix-trie nodes (gam_rnnt_beam.h)
   DevBuf ra_g, ra_pp, ra_lat, ra_bp;    // transducer alignment (gam_rnnt_align.h): predictor outputs, their projection, the (lb, le)
@@ -518,6 +521,7 @@ int gam_create(const gam_config* cfg, int device_id, gam_handle** out) {
   if (const char* e = getenv("GAM_GRAPH_MAX_ROWS")) h->graph_max_rows = atoi(e);
   if (const char* e = getenv("GAM_RNNT_CLUSTER")) h->rnnt_cluster = std::max(-1, std::min(8, atoi(e)));   // (the range gam_set_rnnt_cluster accepts)
   if (const char* e = getenv("GAM_RNNT_ALIGN_WS")) h->ra_ws_limit = (size_t)std::max(1ll, atoll(e));
+  if (const char* e = getenv("GAM_CTC_ALIGN_WS")) h->al_ws_limit = (size_t)std::max(1ll, atoll(e));
   if (const char* e = getenv("GAM_RNNT_EXCLUSIVE")) h->rnnt_exclusive = atoi(e);
   if (const char* e = getenv("GAM_RNNT_COOP")) h->rnnt_coop = atoi(e);
   if (const char* e = getenv("GAM_RNNT_FORCE_TIMEOUT")) h->rnnt_force_timeout = atoi(e);
@@ -1501,6 +1505,87 @@ int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_l
   DecodeScope ds(h, s);
   return ctc_align_launch(h, log_probs, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score, loglik,
                           status, s);
+}
+
+// CTC forced alignment of ONE long utterance (gam_align_long.h): the anti-diagonal sweep launches, the backtrack and the outputs kernel on
+// one stream.  Decode class: the workspace is the handle's.
+int gam_op_ctc_align_long(gam_handle* h, const float* log_probs, int64_t T, int V, const int32_t* targets, int U, int32_t* frame_labels,
+                          int32_t* tok_first, int32_t* tok_last, double* score, double* loglik, int32_t* status, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  if (T < 0 || T > 2147483647ll || V < 2 || U < 0 || U > (1 << 30) - 1)
+    return fail(h, -1, "long CTC alignment: bad shape T=%lld V=%d U=%d", (long long)T, V, U);
+  if (!score || !loglik || !status || (T > 0 && (!log_probs || !frame_labels)) || (U > 0 && (!targets || !tok_first || !tok_last)))
+    return fail(h, -1, "long CTC alignment: NULL buffer");
+  const GamAlignLongForce& frc = gam_align_long_force();
+  const int fsb = frc.sb.load(), ftt = frc.tt.load();
+  GamAlignLongArgs a;
+  a.lp = log_probs; a.targets = targets; a.T = (int)T; a.V = V; a.U = U;
+  a.sb = fsb ? fsb : GAM_AL_SB_DEFAULT;
+  a.tt = ftt ? ftt : GAM_AL_TT_DEFAULT;
+  const int64_t S = 2 * (int64_t)U + 1;
+  a.nS = (int)((S + a.sb - 1) / a.sb);
+  a.nT = (int)((T + a.tt - 1) / a.tt);
+  a.nchunk = (int)((S + 63) / 64);
+  a.frame_labels = frame_labels; a.tok_first = tok_first; a.tok_last = tok_last; a.score = score; a.loglik = loglik; a.status = status;
+  // workspace, every part 256-byte aligned: backpointers | edges | rows d, a | offsets | path | ctrl
+  auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+  const size_t n_bp = up((size_t)T * a.nchunk * 16), n_edge = up((size_t)a.nS * T * 16), n_row = up((size_t)a.nS * a.sb * 4);
+  const size_t n_off = up((size_t)a.nS * 16), n_path = up((size_t)T * 4), n_ctrl = 256;
+  const size_t need = n_bp + n_edge + 2 * n_row + n_off + n_path + n_ctrl;
+  if (need > h->al_ws_limit)
+    return fail(h, -1, "long CTC alignment: T=%lld x U=%d needs %zu bytes of workspace, the limit is %zu bytes (gam_set_ctc_align_workspace / "
+                "GAM_CTC_ALIGN_WS)", (long long)T, U, need, h->al_ws_limit);
+  if (int r = ensure(h, h->align_long_ws, need / 4)) return r;
+  unsigned char* w = reinterpret_cast<unsigned char*>(h->align_long_ws.p);
+  a.bp = reinterpret_cast<uint4*>(w); w += n_bp;
+  a.edge = reinterpret_cast<double2*>(w); w += n_edge;
+  a.rowD = reinterpret_cast<float*>(w); w += n_row;
+  a.rowA = reinterpret_cast<float*>(w); w += n_row;
+  a.off = reinterpret_cast<double2*>(w); w += n_off;
+  a.path = reinterpret_cast<int*>(w); w += n_path;
+  a.ctrl = reinterpret_cast<int*>(w);
+  int nt = 0, spt = 0;
+  gam_align_long_shape(a.sb, &nt, &spt);
+  const size_t sm = gam_align_long_lds_bytes(spt, nt);
+  HIPCHK(h, hipMemsetAsync(a.ctrl, 0, 16, s));
+  if (U > 0) hipLaunchKernelGGL(gam_ctc_align_long_prep_kernel, dim3(gam_cdiv(U, 256)), dim3(256), 0, s, a);
+  if (T > 0 && T >= U) {      // (T < U is infeasible whatever the ids are: the outputs kernel alone reports it)
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)T * (double)S * 4.0);
+    for (int d = 0; d < a.nT + a.nS - 1; ++d) {
+      const int jlo = std::max(0, d - (a.nT - 1)), jhi = std::min(a.nS - 1, d);
+      if (spt == 1) hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<1>, dim3(jhi - jlo + 1), dim3(nt), sm, s, a, d);
+      else if (spt == 2) hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<2>, dim3(jhi - jlo + 1), dim3(nt), sm, s, a, d);
+      else hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<3>, dim3(jhi - jlo + 1), dim3(nt), sm, s, a, d);
+    }
+  }
+  if (T > 0 && T >= U) {
+    ProfScope ps(h, s, GAM_PF_ALIGN_BT, (double)T * 16.0);
+    hipLaunchKernelGGL(gam_ctc_align_long_backtrack_kernel, dim3(1), dim3(64), 0, s, a);
+  }
+  const int64_t n_out = std::max<int64_t>(std::max<int64_t>(T, U), 1);
+  ProfScope ps(h, s, GAM_PF_ALIGN_OUT, (double)T * 8.0 + (double)U * 8.0);
+  hipLaunchKernelGGL(gam_ctc_align_long_outputs_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_set_ctc_align_workspace(gam_handle* h, int64_t bytes) {
+  if (!h) return -1;
+  if (bytes < 0) return fail(h, -1, "long CTC alignment: workspace limit %lld bytes is negative", (long long)bytes);
+  h->al_ws_limit = bytes == 0 ? GAM_AL_WS_DEFAULT : (size_t)bytes;
+  return 0;
+}
+
+int gam_tune_ctc_align_long(int sb, int tt) {
+  // (multiples of 64 only: whole backpointer chunks, and EVEN -- the one-edge-state scheme of gam_align_long.h rests on it)
+  if (sb != 0 && (sb < 64 || sb > GAM_AL_SB_MAX || sb % 64 != 0)) return -1;
+  if (tt < 0) return -1;
+  GamAlignLongForce& f = gam_align_long_force();
+  f.sb = sb; f.tt = tt;
+  return 0;
 }
 
 // ---- what the two beam searches share (gam_search.h): the handle's hotwords and LM as kernel arguments, the common checks, the launch

@@ -160,6 +160,39 @@ class Aligned:
         return out
 
 
+class AlignedLong:
+    """What ``op_ctc_align_long`` returns: every output of the long-utterance alignment as a view of ONE i32 device buffer (``whole``)
+    that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: score (f64 bits, 2 words) | loglik (f64 bits, 2 words) |
+    status | range flag word | frame_labels [T] | tok_first [U] | tok_last [U]."""
+
+    def __init__(self, whole: Tensor, t: int, u: int, event=None, stream=None):
+        self.whole, self.t, self.u, self.event, self.stream = whole, t, u, event, stream
+        self.score = whole[0:2].view(torch.float64)
+        self.loglik = whole[2:4].view(torch.float64)
+        self.status = whole[4:5]
+        self.ext = whole[5:6]
+        self.frame_labels = whole[6: 6 + t]
+        self.tok_first = whole[6 + t: 6 + t + u]
+        self.tok_last = whole[6 + t + u: 6 + t + 2 * u]
+
+    def host(self) -> Dict[str, Any]:
+        """One blocking D2H of the whole result, on the collect stream behind the alignment's own completion event -> ``frame_labels``,
+        ``tok_first``, ``tok_last`` (numpy i32), ``status`` (int), ``score`` / ``loglik`` (Python floats from the float64 outputs) and
+        ``flag`` (as ``Aligned.host``)."""
+        side = HipEngine._collect_stream(self.whole.device)
+        with torch.cuda.stream(side):
+            if self.event is not None:
+                side.wait_event(self.event)
+            else:
+                side.wait_stream(torch.cuda.current_stream(self.whole.device))
+            arr = self.whole.cpu().numpy()
+        self.whole.record_stream(side)
+        t, u = self.t, self.u
+        return {"score": float(arr[0:2].view(np.float64)[0]), "loglik": float(arr[2:4].view(np.float64)[0]), "status": int(arr[4]),
+                "flag": HipEngine._flag_of(int(arr[5])), "frame_labels": arr[6: 6 + t], "tok_first": arr[6 + t: 6 + t + u],
+                "tok_last": arr[6 + t + u: 6 + t + 2 * u]}
+
+
 class RnntAligned:
     """What ``rnnt_align`` / ``op_rnnt_align`` / ``op_rnnt_lattice_align`` return: every output of the transducer alignment as a view of
     ONE i32 device buffer (``whole``) that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: tok_frame [B, Umax] |
@@ -645,6 +678,42 @@ class HipEngine:
             out.event, out.stream = torch.cuda.Event(), st
             out.event.record(st)
         return out
+
+    def op_ctc_align_long(self, log_probs: Tensor, targets, consume_flag: bool = False) -> AlignedLong:
+        """gam_op_ctc_align_long: CTC forced alignment of ONE long utterance, log-probs f32 [T, V] (used as they are) against ``targets``
+        (token ids: a list or an i32 tensor [U]), tiled over the whole GPU (gam_align_long.h); no host sync.  ``consume_flag``: move
+        the split-fp16 range flag of the encoder runs that produced the log-probs into the result's flag word (as ``ctc_align`` does);
+        otherwise the word is 0."""
+        log_probs = self._dev(log_probs, torch.float32)
+        t, v = log_probs.shape
+        tgt = self._dev(targets if isinstance(targets, Tensor) else torch.tensor([int(i) for i in targets], dtype=torch.int32),
+                        torch.int32).reshape(-1)
+        u = tgt.numel()
+        out = AlignedLong(torch.empty((6 + t + 2 * u,), dtype=torch.int32, device=self.device), t, u)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_ctc_align_long(self._h, _ptr(log_probs), t, v, _ptr(tgt), u, _ptr(out.frame_labels), _ptr(out.tok_first),
+                                                _ptr(out.tok_last), _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
+            self._check(rc, "gam_op_ctc_align_long")
+            if consume_flag:
+                # (the flag word sits inside ``whole``, not at its end: hand _fetch_flag a view that ends there)
+                out.event, out.stream = self._fetch_flag(out.whole[:6])
+            else:
+                out.ext.zero_()
+                st = torch.cuda.current_stream(self.device)
+                out.event, out.stream = torch.cuda.Event(), st
+                out.event.record(st)
+        return out
+
+    def set_ctc_align_workspace(self, nbytes: int = 0) -> None:
+        """Bytes of workspace ``op_ctc_align_long`` may take (gam_set_ctc_align_workspace; 0: the default, 3 GiB).  A call that needs
+        more is an error that names the needed and the allowed bytes."""
+        self._check(self.lib.gam_set_ctc_align_workspace(self._h, int(nbytes)), "gam_set_ctc_align_workspace")
+
+    def tune_ctc_align_long(self, sb: int = 0, tt: int = 0) -> None:
+        """Force the tiling of ``op_ctc_align_long`` (gam_tune_ctc_align_long): ``sb`` states per block (a multiple of 64 in
+        [64, 3072]), ``tt`` frames per tile (>= 1); 0 = planned.  Process-wide, like ``gam_tune_sp``."""
+        if self.lib.gam_tune_ctc_align_long(int(sb), int(tt)) != 0:
+            raise GigaAMHipError(f"gam_tune_ctc_align_long: sb={sb} must be 0 or a multiple of 64 in [64, 3072], tt={tt} must be >= 0")
 
     def _rnnt_align_buffers(self, b: int, targets, target_len):
         """As ``_align_buffers``: device targets / lengths and the ``RnntAligned`` result buffer."""

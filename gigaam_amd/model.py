@@ -19,8 +19,8 @@ from . import preprocess as _preprocess
 from ._lib import GigaAMHipError
 from .engine import HipEngine, build_config
 from .preprocess import SAMPLE_RATE, load_audio
-from .types import (AlignmentResult, ConfidenceResult, Hypothesis, LongformTranscriptionResult, NBestResult, ScoredWord, Segment,
-                    TranscriptionResult, Word, nbest_posteriors)
+from .types import (AlignmentResult, ConfidenceResult, Hypothesis, LongformAlignmentResult, LongformTranscriptionResult, NBestResult,
+                    ScoredWord, Segment, TranscriptionResult, Word, nbest_posteriors)
 
 LONGFORM_THRESHOLD = 25 * SAMPLE_RATE
 
@@ -616,6 +616,26 @@ class GigaAMASR(GigaAM):
                                         confidence=aggregate_confidence(conf, aggregation), feasible=True))
         return out
 
+    def _default_vad(self, kwargs: Dict[str, Any], what: str) -> None:
+        """The segmentation keywords of the longform calls: ``vad="energy"`` becomes the EnergyVAD stand-in; with neither ``vad`` nor
+        ``speech_regions`` the reference's pyannote pipeline is used when importable, else the stand-in, with a warning."""
+        from .vad_utils import EnergyVAD
+
+        if kwargs.get("vad") == "energy":   # stand-in detector on the HIP frontend (NOT pyannote)
+            kwargs["vad"] = EnergyVAD(self.preprocessor)
+        elif kwargs.get("vad") is None and kwargs.get("speech_regions") is None:
+            # reference default: pyannote (model.py:212-216 -> vad_utils.py:100-101).  Without that optional
+            # third-party package the call still works, on the labelled stand-in, and says so.
+            try:
+                import pyannote.audio  # noqa: F401
+            except ImportError:
+                import warnings
+                warnings.warn(f"pyannote.audio is not installed: {what}() segments with gigaam_amd's "
+                              "EnergyVAD stand-in instead of the reference's pyannote/segmentation-3.0 pipeline "
+                              "(chunk boundaries will differ); pass speech_regions= or vad= to control segmentation",
+                              RuntimeWarning, stacklevel=3)
+                kwargs["vad"] = EnergyVAD(self.preprocessor)
+
     @torch.inference_mode()
     def transcribe_longform(self, wav_file: str, word_timestamps: bool = False, fr_batch_size: int = 16,
                             fr_num_workers: int = 0, *, beam_size: Optional[int] = None,
@@ -634,26 +654,13 @@ class GigaAMASR(GigaAM):
 
         ``beam_size`` / ``hotwords`` / ``hotword_boost`` / ``lm`` / ``lm_weight`` / ``word_bonus``: as for ``transcribe`` (CTC prefix
         beam search on every chunk; each chunk starts its own LM history at <s>)."""
-        from .vad_utils import EnergyVAD, segment_audio_file
+        from .vad_utils import segment_audio_file
 
         beam_kw = {} if self._beam_width(beam_size, hotwords, lm) is None else dict(beam_size=beam_size, hotwords=hotwords,
                                                                                      hotword_boost=hotword_boost, lm=lm,
                                                                                      lm_weight=lm_weight, word_bonus=word_bonus)
 
-        if kwargs.get("vad") == "energy":   # stand-in detector on the HIP frontend (NOT pyannote)
-            kwargs["vad"] = EnergyVAD(self.preprocessor)
-        elif kwargs.get("vad") is None and kwargs.get("speech_regions") is None:
-            # reference default: pyannote (model.py:212-216 -> vad_utils.py:100-101).  Without that optional
-            # third-party package the call still works, on the labelled stand-in, and says so.
-            try:
-                import pyannote.audio  # noqa: F401
-            except ImportError:
-                import warnings
-                warnings.warn("pyannote.audio is not installed: transcribe_longform() segments with gigaam_amd's "
-                              "EnergyVAD stand-in instead of the reference's pyannote/segmentation-3.0 pipeline "
-                              "(chunk boundaries will differ); pass speech_regions= or vad= to control segmentation",
-                              RuntimeWarning, stacklevel=2)
-                kwargs["vad"] = EnergyVAD(self.preprocessor)
+        self._default_vad(kwargs, "transcribe_longform")
         segments, boundaries = segment_audio_file(wav_file, SAMPLE_RATE, device=self._device, **kwargs)
         if not segments:
             return LongformTranscriptionResult(segments=[])
@@ -693,3 +700,71 @@ class GigaAMASR(GigaAM):
         if eng is not None and eng.gemm_mode != "f32":
             eng.range_flag()     # a flag left behind by earlier direct engine use must not cost this file an fp32 rerun
         return LongformTranscriptionResult(segments=self._with_f32_fallback(run, "the file was"))
+
+    @torch.inference_mode()
+    def align_longform(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int = 16, **kwargs: Any) -> LongformAlignmentResult:
+        """Align ``text`` (a string in the model's vocabulary, or token ids) to a recording of any length: forced alignment of the
+        WHOLE text against the WHOLE recording (``align`` stops at 25 s and 1024 tokens).  Segmentation keywords as for
+        ``transcribe_longform`` (``speech_regions=``, ``vad=``, the pack_regions keywords; the same pyannote / EnergyVAD default).
+
+        The speech regions are encoded in batches of ``fr_batch_size``; the CTC log-probs of every region's valid frames are
+        concatenated on the device into one [T_total, V] utterance, which gam_op_ctc_align_long aligns in one go.  So: the
+        concatenated speech frames are ONE CTC utterance -- where the text splits between the regions is found by the alignment,
+        not given; a token's run may continue across a region boundary; nothing can be placed in non-speech.  A token's time is
+        its region's start + its frame inside the region x that region's frame shift; words follow the rule of
+        ``transcribe(word_timestamps=True)`` on those file times.
+
+        Raises ``ValueError`` for characters outside the vocabulary, for a text that no alignment fits into the speech found, for a
+        non-empty text when no speech was found, and for a lattice beyond the workspace cap (the message carries the needed and
+        the allowed bytes; ``HipEngine.set_ctc_align_workspace`` / GAM_CTC_ALIGN_WS raise it); ``TypeError`` on RNN-T models."""
+        from .decoding import RangeOverflow
+        from .feeder import BatchFeeder
+        from .timestamps_utils import compute_frame_shift, concat_frames_to_segments, longform_words
+        from .vad_utils import segment_audio_file
+
+        self._require_ctc()
+        tok = self.decoding.tokenizer
+        ids = tok.encode(text) if isinstance(text, str) else [int(i) for i in text]
+        self._default_vad(kwargs, "align_longform")
+        segments, boundaries = segment_audio_file(wav_file, SAMPLE_RATE, device=self._device, **kwargs)
+        if not segments:
+            if ids:
+                raise ValueError(f"no speech found in the recording: the text ({len(ids)} tokens) cannot be aligned to it")
+            return LongformAlignmentResult(text=tok.decode(ids), words=[], token_ids=ids, token_segments=[], token_frames=[], token_times=[],
+                                           score=0.0, log_likelihood=0.0, segments=[], feasible=True)
+        eng = self.head.engine
+
+        def run():
+            rows: List[Tensor] = []
+            seg_frames: List[Tensor] = []
+            feeder = BatchFeeder(segments, fr_batch_size, self._device)
+            for wav, lens in feeder:
+                encoded, encoded_len = self._encode(wav, lens, getattr(feeder, "host_lengths", None))
+                lp = eng.ctc_head(encoded)                                         # [B, T', V] log-probs, on the device
+                valid = torch.arange(lp.shape[1], device=lp.device)[None, :] < encoded_len[:, None]
+                rows.append(lp[valid])                                             # each utterance's valid rows, utterance after utterance
+                seg_frames.append(encoded_len)
+            out = eng.op_ctc_align_long(torch.cat(rows, dim=0), ids, consume_flag=True)
+            h = out.host()
+            if h["flag"]:
+                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+            return h, torch.cat(seg_frames).tolist()
+
+        if eng.gemm_mode != "f32":
+            eng.range_flag()     # (as transcribe_longform: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
+        try:
+            h, seg_frames = self._with_f32_fallback(run, "the file was")
+        except GigaAMHipError as e:
+            if "gam_set_ctc_align_workspace" in str(e):
+                raise ValueError(f"the alignment lattice does not fit the workspace cap: {e}") from e
+            raise
+        if not h["status"]:
+            raise ValueError(f"the text ({len(ids)} tokens) cannot be aligned to this audio: too long for the speech found "
+                             f"({sum(seg_frames)} frames)")
+        shifts = [compute_frame_shift(int(seg.shape[0]), int(n)) if n else 0.0 for seg, n in zip(segments, seg_frames)]
+        token_segments, token_frames, token_times = concat_frames_to_segments(h["tok_first"].tolist(), seg_frames,
+                                                                              [b[0] for b in boundaries], shifts)
+        words, segs = longform_words(tok, ids, token_segments, token_frames, boundaries, shifts)
+        return LongformAlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_segments=token_segments,
+                                       token_frames=token_frames, token_times=token_times, score=h["score"],
+                                       log_likelihood=h["loglik"], segments=segs, feasible=True)

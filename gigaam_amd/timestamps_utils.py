@@ -2,11 +2,11 @@
 Pure host-side string work over the exact ``frames`` the HIP decoders emit."""
 from __future__ import annotations
 
-from typing import List
+from typing import List, Sequence, Tuple
 
 from .decoding import Tokenizer
 from .preprocess import SAMPLE_RATE
-from .types import Word
+from .types import Segment, Word
 
 
 def compute_frame_shift(audio_length_samples: int, seq_len: int) -> float:
@@ -83,3 +83,46 @@ def aggregate_confidence(values: List[float], aggregation: str):
     for v in values:
         out *= float(v)
     return out
+
+
+def concat_frames_to_segments(frames: Sequence[int], seg_frames: Sequence[int], seg_starts: Sequence[float],
+                              seg_shifts: Sequence[float]) -> Tuple[List[int], List[int], List[float]]:
+    """Frames of the concatenation of several segments' encoder frames (segment i contributes ``seg_frames[i]`` of them, starts at
+    ``seg_starts[i]`` seconds in the file and has a frame shift of ``seg_shifts[i]`` seconds) -> per frame (segment, frame inside the
+    segment, time in the file = start + local frame x shift).  Segments without frames are skipped over."""
+    bounds, total = [], 0
+    for n in seg_frames:
+        total += int(n)
+        bounds.append(total)
+    segs, local, times = [], [], []
+    from bisect import bisect_right
+    for f in frames:
+        f = int(f)
+        if f < 0 or f >= total:
+            raise ValueError(f"frame {f} outside the {total} concatenated frames")
+        i = bisect_right(bounds, f)
+        loc = f - (bounds[i - 1] if i else 0)
+        segs.append(i)
+        local.append(loc)
+        times.append(seg_starts[i] + loc * seg_shifts[i])
+    return segs, local, times
+
+
+def longform_words(tokenizer: Tokenizer, token_ids: Sequence[int], token_segments: Sequence[int], token_frames: Sequence[int],
+                   boundaries: Sequence[Tuple[float, float]], seg_shifts: Sequence[float]) -> Tuple[List[Word], List[Segment]]:
+    """Words of a transcript aligned to concatenated segments, by the rule of ``frames_to_words`` applied to file times: a word
+    starts at its first token's first frame and ends one frame after its last token's first frame, each taken in the segment the
+    token fell in (so a word whose tokens straddle two regions starts in the first and ends in the second).  Returns the words and
+    one ``Segment(text, start, end, words)`` per entry of ``boundaries`` holding the words whose first token fell in it."""
+    words: List[Word] = []
+    per_seg: List[List[Word]] = [[] for _ in boundaries]
+    for group in word_token_groups(tokenizer, list(token_ids)):
+        a, b = group[0], group[-1]
+        sa, sb = token_segments[a], token_segments[b]
+        text = "".join(tokenizer.id_to_str(token_ids[i]) for i in group).replace("▁", "").strip()
+        w = Word(text=text, start=round(boundaries[sa][0] + token_frames[a] * seg_shifts[sa], 3),
+                 end=round(boundaries[sb][0] + (token_frames[b] + 1) * seg_shifts[sb], 3))
+        words.append(w)
+        per_seg[sa].append(w)
+    segments = [Segment(text=" ".join(w.text for w in ws), start=s, end=e, words=ws) for (s, e), ws in zip(boundaries, per_seg)]
+    return words, segments

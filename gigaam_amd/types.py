@@ -158,3 +158,32 @@ class LongformTranscriptionResult:
 
     def __len__(self) -> int:
         return len(self.segments)
+
+
+@dataclass
+class LongformAlignmentResult:
+    """``GigaAMASR.align_longform``: a known transcript placed on a long recording by CTC forced alignment of the whole text against
+    the concatenated speech regions.  ``words``: file times; ``token_segments`` / ``token_frames`` / ``token_times``: per token the
+    speech region its first frame fell in, that frame counted inside the region, and its time in the file; ``score`` /
+    ``log_likelihood``: the best path's log-prob and log p(text | audio) = -CTC loss over the concatenated frames; ``segments``: one
+    ``Segment(text, start, end, words)`` per speech region, holding the words whose first token fell in it; ``feasible``: always
+    True on a returned result (an infeasible text is a ``ValueError``)."""
+    text: str
+    words: List[Word]
+    token_ids: List[int]
+    token_segments: List[int]
+    token_frames: List[int]
+    token_times: List[float]
+    score: float
+    log_likelihood: float
+    segments: List[Segment]
+    feasible: bool
+
+    def __str__(self) -> str:
+        return self.text
+
+    def __iter__(self) -> Iterator[Segment]:
+        return iter(self.segments)
+
+    def __len__(self) -> int:
+        return len(self.segments)

@@ -144,6 +144,24 @@ int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_l
                      const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
                      float* loglik, int32_t* status, void* stream);
 
+/* CTC forced alignment of ONE long utterance (gigaam_amd/csrc/gam_align_long.h): the recurrences, tie rule, feasibility rule and
+ * statuses of gam_op_ctc_align, tiled over states and frames so that the whole GPU works on it -- blocks of SB states x tiles of
+ * TT frames, run as nT + nS - 1 plain launches (one per anti-diagonal) on the given stream, then a backtrack and an outputs kernel.
+ *   log_probs f32 [T, V] (read as they are), targets i32 [U]; blank = V - 1.  All pointers are device pointers.
+ *   frame_labels i32 [T], tok_first / tok_last i32 [U], score / loglik f64 [1] (|score| reaches 1e4-1e5 at these lengths: fp32
+ *   would cost 1e-2 nats), status i32 [1]: as gam_op_ctc_align (infeasible: -inf scores, -1 everywhere; T = 0 with U = 0 scores 0).
+ * Limits: T < 2^31; U whatever the workspace allows.  The workspace is the handle's: T x ceil((2U + 1) / 64) x 16 bytes of
+ * backpointers + ceil((2U + 1) / SB) x T x 16 bytes of block edges + T x 4 bytes of path (+ a block row each); a call that needs
+ * more than the cap fails.  Decode class; no host synchronisation (workspace growth aside). */
+int gam_op_ctc_align_long(gam_handle* h, const float* log_probs, int64_t T, int V, const int32_t* targets, int U, int32_t* frame_labels,
+                          int32_t* tok_first, int32_t* tok_last, double* score, double* loglik, int32_t* status, void* stream);
+/* Bytes of workspace gam_op_ctc_align_long may take (0: the default, 3 GiB -- a one-hour recording, T = 9e4 frames, with a
+ * char-level transcript of 5e4 tokens needs 2.25 GB of backpointers + 0.14 GB of edges; environment GAM_CTC_ALIGN_WS at gam_create). */
+int gam_set_ctc_align_workspace(gam_handle* h, int64_t bytes);
+/* Tuning hook of gam_op_ctc_align_long, modelled on gam_tune_sp: force the states per block (sb: a multiple of 64 in [64, 3072]) and
+ * the frames per tile (tt >= 1) of every following call in this process; 0 = planned (1024 x 256).  Returns -1 for other values. */
+int gam_tune_ctc_align_long(int sb, int tt);
+
 /* CTC prefix beam search with hotword boosting (gigaam_amd/csrc/gam_beam.h).  Runs the CTC head, its log-softmax and ONE beam
  * kernel (a workgroup per utterance, t the sequential loop, backtrack in the same kernel).  Beam width 1 <= W <= 32; per frame the
  * top min(W, V - 1) non-blank ids are the candidate tokens; blank = V - 1.  Ties follow a fixed rule (gam_beam.h), so the result is
@@ -420,7 +438,9 @@ int gam_tune_sp_stages(int stages);
  * returns, for class `cls`, the summed milliseconds, launch count and algorithmic work
  * (FLOP for GEMM/attention classes, bytes for the HBM-bound classes); it then resets. */
 enum { GAM_PF_GEMM = 0, GAM_PF_CONV2 = 1, GAM_PF_ATTN = 2, GAM_PF_NORM = 3, GAM_PF_CONVMOD = 4,
-       GAM_PF_STEM = 5, GAM_PF_FRONTEND = 6, GAM_PF_DECODE = 7, GAM_PF_MISC = 8, GAM_PF_NCLASS = 9 };
+       GAM_PF_STEM = 5, GAM_PF_FRONTEND = 6, GAM_PF_DECODE = 7, GAM_PF_MISC = 8,
+       GAM_PF_ALIGN_BT = 9, GAM_PF_ALIGN_OUT = 10,   /* gam_op_ctc_align_long: its backtrack and its outputs kernel (its sweep is DECODE) */
+       GAM_PF_NCLASS = 11 };
 int gam_profile_enable(gam_handle* h, int on);
 int gam_profile_read(gam_handle* h, int cls, double* ms, int64_t* launches, double* work);
 /* Switch the collection level (0 / 1 / 2) WITHOUT resetting what was collected: bench.py samples every 4th timed step (an
