@@ -17,9 +17,9 @@ import torch
 from .lm import NgramLM
 from .model import GigaAM, GigaAMASR, GigaAMEmo
 from .preprocess import load_audio
-from .types import ConfidenceResult, LongformAlignmentResult, ScoredWord
+from .types import ConfidenceResult, KeywordHit, KeywordSearchResult, LongformAlignmentResult, ScoredWord
 
-__all__ = ["GigaAM", "GigaAMASR", "GigaAMEmo", "NgramLM", "ConfidenceResult", "LongformAlignmentResult", "ScoredWord", "load_audio", "format_time", "load_model", "model_from_checkpoint"]
+__all__ = ["GigaAM", "GigaAMASR", "GigaAMEmo", "NgramLM", "ConfidenceResult", "KeywordHit", "KeywordSearchResult", "LongformAlignmentResult", "ScoredWord", "load_audio", "format_time", "load_model", "model_from_checkpoint"]
 
 _CACHE_DIR = os.path.expanduser("~/.cache/gigaam")
 # md5 of the reference's published checkpoints (gigaam/__init__.py:28-41)

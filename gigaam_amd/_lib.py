@@ -56,6 +56,9 @@ SIGNATURES = {
     "gam_op_ctc_align_long": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_set_ctc_align_workspace": (C.c_int, [_P, C.c_int64]),
     "gam_tune_ctc_align_long": (C.c_int, [C.c_int, C.c_int]),
+    "gam_ctc_kws": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gam_op_ctc_kws": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gam_set_keywords": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "gam_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_set_hotwords": (C.c_int, [_P, _P, _P, C.c_int, C.c_float]),

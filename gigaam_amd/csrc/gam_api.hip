@@ -16,6 +16,7 @@
 #include "../../include/gigaam_hip.h"
 #include "gam_align.h"
 #include "gam_align_long.h"
+#include "gam_kws.h"
 #include "gam_attn.h"
 #include "gam_beam.h"
 #include "gam_rnnt_beam.h"
@@ -145,6 +146,11 @@ struct gam_handle {
   size_t hw_cap = 0;                    // ints allocated at hw_trie
   int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
   float hw_boost = 0.f;
+  // the keyword set of gam_set_keywords (gam_kws.h): offsets [K + 1] | tokens | min_score [K] (f32 bits) in one buffer; NULL = no set
+  int* kw_dev = nullptr;
+  size_t kw_cap = 0;                    // ints allocated at kw_dev
+  int kw_K = 0, kw_ntok = 0, kw_max_tok = -1;
+  DevBuf kws_mb;                        // keyword search: per row {maximum, blank's emission}, B x T' x 8 bytes
   // the n-gram LM of gam_set_lm (gam_search.h): token classes [lm_V], word / n-gram table slots; lm_ng NULL = no LM
   int* lm_cls = nullptr;
   void *lm_wt = nullptr, *lm_ng = nullptr;
@@ -575,6 +581,8 @@ void gam_destroy(gam_handle* h) {
   for (DevBuf* b : {&h->ra_g, &h->ra_pp, &h->ra_lat, &h->ra_bp, &h->cf_stats})
     if (b->p) hipFree(b->p);
   if (h->hw_trie) hipFree(h->hw_trie);
+  if (h->kw_dev) hipFree(h->kw_dev);
+  if (h->kws_mb.p) hipFree(h->kws_mb.p);
   if (h->lm_cls) hipFree(h->lm_cls);
   if (h->lm_wt) hipFree(h->lm_wt);
   if (h->lm_ng) hipFree(h->lm_ng);
@@ -1586,6 +1594,131 @@ int gam_tune_ctc_align_long(int sb, int tt) {
   GamAlignLongForce& f = gam_align_long_force();
   f.sb = sb; f.tt = tt;
   return 0;
+}
+
+// ---- keyword search (gam_kws.h).  Decode class (the caller holds a DecodeScope): the row-maximum workspace is the handle's.
+int gam_set_keywords(gam_handle* h, const int32_t* tokens, const int32_t* offsets, int n_keywords, const float* min_score) {
+  if (!h) return -1;
+  if (n_keywords < 0 || n_keywords > GAM_KWS_MAX_K)
+    return fail(h, -1, "keywords: %d keywords outside [0, %d]", n_keywords, GAM_KWS_MAX_K);
+  if (n_keywords > 0 && (!tokens || !offsets || !min_score)) return fail(h, -1, "keywords: NULL buffer");
+  int max_tok = -1, ntok = 0;
+  if (n_keywords > 0) {
+    if (offsets[0] != 0) return fail(h, -1, "keywords: offsets[0] = %d, expected 0", offsets[0]);
+    // (a handle without a CTC head learns V with the log-probs: gam_op_ctc_kws checks the ids then)
+    const int hi = h->cfg.head_type == GAM_HEAD_CTC && h->cfg.num_classes >= 2 ? h->cfg.num_classes - 2 : 0x3fffffff;
+    for (int i = 0; i < n_keywords; ++i) {
+      const int a = offsets[i], e = offsets[i + 1];
+      if (e <= a) return fail(h, -1, "keywords: keyword %d is empty or its offsets decrease", i);
+      if (e - a > GAM_KWS_MAX_U) return fail(h, -1, "keywords: keyword %d has %d tokens, the limit is %d", i, e - a, GAM_KWS_MAX_U);
+      if (!std::isfinite(min_score[i]) || min_score[i] > 0.f)
+        return fail(h, -1, "keywords: min_score[%d] = %g must be finite and <= 0", i, (double)min_score[i]);
+      for (int k = a; k < e; ++k) {
+        const int c = tokens[k];
+        if (c < 0 || c > hi) return fail(h, -1, "keywords: token id %d of keyword %d outside [0, %d]", c, i, hi);
+        max_tok = std::max(max_tok, c);
+      }
+    }
+    ntok = offsets[n_keywords];
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  // a decode-class kernel still in flight may read the current set
+  if (h->dec_evt != nullptr && h->dec_evt_set) HIPCHK(h, hipEventSynchronize(h->dec_evt));
+  if (n_keywords == 0) {
+    h->kw_K = h->kw_ntok = 0;
+    h->kw_max_tok = -1;
+    if (h->kw_dev) HIPCHK(h, hipFree(h->kw_dev));
+    h->kw_dev = nullptr;
+    h->kw_cap = 0;
+    return 0;
+  }
+  std::vector<int> flat((size_t)n_keywords + 1 + ntok + n_keywords);
+  memcpy(flat.data(), offsets, ((size_t)n_keywords + 1) * sizeof(int));
+  memcpy(flat.data() + n_keywords + 1, tokens, (size_t)ntok * sizeof(int));
+  memcpy(flat.data() + n_keywords + 1 + ntok, min_score, (size_t)n_keywords * sizeof(float));
+  if (flat.size() > h->kw_cap) {
+    if (h->kw_dev) HIPCHK(h, hipFree(h->kw_dev));
+    h->kw_dev = nullptr;
+    h->kw_cap = 0;
+    HIPCHK(h, hipMalloc(&h->kw_dev, flat.size() * sizeof(int)));
+    h->kw_cap = flat.size();
+  }
+  HIPCHK(h, hipMemcpy(h->kw_dev, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+  h->kw_K = n_keywords;
+  h->kw_ntok = ntok;
+  h->kw_max_tok = max_tok;
+  return 0;
+}
+
+// Everything the two entry points check before a launch (shape, limits, the keyword set against V).
+static int ctc_kws_check(gam_handle* h, int B, int64_t Tp, int V, int max_hits, bool null_buf) {
+  if (B <= 0 || Tp <= 0 || V < 2) return fail(h, -1, "keyword search: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
+  if (Tp > GAM_KWS_MAX_T) return fail(h, -1, "keyword search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_KWS_MAX_T);
+  if (max_hits < 1 || max_hits > GAM_KWS_MAX_HITS)
+    return fail(h, -1, "keyword search: max_hits=%d outside [1, %d]", max_hits, GAM_KWS_MAX_HITS);
+  if (!h->kw_dev || h->kw_K <= 0) return fail(h, -1, "keyword search: no keyword set (gam_set_keywords)");
+  if (h->kw_max_tok > V - 2) return fail(h, -1, "keyword search: keyword token id %d outside [0, %d] for V=%d", h->kw_max_tok, V - 2, V);
+  if ((int64_t)B * ((h->kw_K + GAM_KWS_WAVES - 1) / GAM_KWS_WAVES) > 2147483647ll)
+    return fail(h, -1, "keyword search: B=%d x %d keywords exceed the grid", B, h->kw_K);
+  if (null_buf) return fail(h, -1, "keyword search: NULL buffer");
+  return 0;
+}
+
+// The row-maximum pre-pass and the search kernel over log-probs [B, Tp, V] (the checks are the caller's).
+static int ctc_kws_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, int max_hits,
+                          int32_t* hit_frames, float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start,
+                          hipStream_t s) {
+  const long rows = (long)B * Tp;
+  if (int r = ensure(h, h->kws_mb, (size_t)rows * 2 + 64)) return r;
+  {
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 4.0);
+    hipLaunchKernelGGL(gam_kws_rowmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, lp, enc_len, (int)Tp, V, rows,
+                       reinterpret_cast<float2*>(h->kws_mb.p));
+    HIPCHK(h, hipGetLastError());
+  }
+  const int K = h->kw_K;
+  GamKwsArgs a;
+  a.lp = lp; a.enc_len = enc_len; a.mb = reinterpret_cast<const float2*>(h->kws_mb.p);
+  a.kw_off = h->kw_dev; a.kw_tok = h->kw_dev + K + 1; a.kw_min = reinterpret_cast<const float*>(h->kw_dev + K + 1 + h->kw_ntok);
+  a.B = B; a.Tp = (int)Tp; a.V = V; a.K = K; a.max_hits = max_hits;
+  a.hit_frames = hit_frames; a.hit_score = hit_score; a.n_hits = n_hits; a.dense_score = dense_score; a.dense_start = dense_start;
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * K * 64.0 * 4.0);
+  const dim3 grid(B * gam_cdiv(K, GAM_KWS_WAVES)), block(64 * GAM_KWS_WAVES);
+  if (dense_score || dense_start) hipLaunchKernelGGL(gam_ctc_kws_kernel<true>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(gam_ctc_kws_kernel<false>, grid, block, 0, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_ctc_kws(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int max_hits, int32_t* hit_frames,
+                float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
+  DecodeScope ds(h, s);
+  if (!h->finalized) return fail(h, -1, "CTC head before gam_finalize");
+  if (h->cfg.head_type != GAM_HEAD_CTC || !h->has_head) return fail(h, -1, "model has no CTC head");
+  const int V = h->cfg.num_classes;
+  if (int r = ctc_kws_check(h, B, Tp, V, max_hits, !encoded || !enc_len || !hit_frames || !hit_score || !n_hits)) return r;
+  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
+  const int rows = (int)(B * Tp);
+  {
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
+    // in place: each row is read whole by its wave before that wave writes it (as gam_ctc_align)
+    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
+    HIPCHK(h, hipGetLastError());
+  }
+  return ctc_kws_launch(h, h->logits.p, enc_len, B, Tp, V, max_hits, hit_frames, hit_score, n_hits, dense_score, dense_start, s);
+}
+
+int gam_op_ctc_kws(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int max_hits,
+                   int32_t* hit_frames, float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!h) return -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  DecodeScope ds(h, s);
+  if (int r = ctc_kws_check(h, B, Tp, V, max_hits, !log_probs || !enc_len || !hit_frames || !hit_score || !n_hits)) return r;
+  return ctc_kws_launch(h, log_probs, enc_len, B, Tp, V, max_hits, hit_frames, hit_score, n_hits, dense_score, dense_start, s);
 }
 
 // ---- what the two beam searches share (gam_search.h): the handle's hotwords and LM as kernel arguments, the common checks, the launch

@@ -72,6 +72,48 @@ def _ragged(dec, *rest) -> List[Tuple[List[int], List[int]]]:
     return rows
 
 
+def keyword_min_scores(token_counts, threshold) -> "np.ndarray":
+    """Per keyword the lowest score that still counts: ``U_k * ln(threshold_k)`` in float32 -- ``threshold`` (one value, or one per
+    keyword) is the geometric-mean likelihood ratio per token a hit must reach, in (0, 1]."""
+    import numpy as np
+    n = len(token_counts)
+    thr = np.asarray(threshold, dtype=np.float64)
+    if thr.ndim > 1 or (thr.ndim == 1 and thr.shape[0] != n):
+        raise ValueError(f"threshold: one value or one per keyword ({n}) expected, got shape {thr.shape}")
+    thr = np.broadcast_to(thr, (n,))
+    if not np.all(np.isfinite(thr) & (thr > 0.0) & (thr <= 1.0)):
+        raise ValueError(f"threshold must lie in (0, 1], got {threshold!r}")
+    return (np.asarray(token_counts, dtype=np.float64) * np.log(thr)).astype(np.float32)
+
+
+def keyword_hits(h, b: int, keywords, texts, frame_shift: float, offset: float = 0.0, segment=None):
+    """Row ``b`` of a ``KeywordHits.host()`` dict -> (``KeywordHit`` list in keyword order, indices of the truncated keywords):
+    ``start`` = start_frame x frame_shift, ``end`` = (end_frame + 1) x frame_shift (frames_to_words' convention); with ``segment``
+    (a longform speech region) both are shifted by ``offset``, the region's start in the file."""
+    import math
+    from .types import KeywordHit
+    hits, truncated = [], []
+    mh = h["hit_frames"].shape[2]
+    for k, ids in enumerate(keywords):
+        n = int(h["n_hits"][b, k])
+        if n > mh:
+            truncated.append(k)
+        for r in range(min(n, mh)):
+            s, e = int(h["hit_frames"][b, k, r, 0]), int(h["hit_frames"][b, k, r, 1])
+            sc = float(h["hit_score"][b, k, r])
+            t0, t1 = s * frame_shift, (e + 1) * frame_shift
+            if segment is not None:     # file times, rounded as transcribe_longform rounds its shifted word times
+                t0, t1 = round(t0 + offset, 3), round(t1 + offset, 3)
+            hits.append(KeywordHit(keyword=texts[k], keyword_index=k, start=t0, end=t1, score=sc, confidence=math.exp(sc / len(ids)),
+                                   start_frame=s, end_frame=e, segment=segment))
+    return hits, truncated
+
+
+def sort_keyword_hits(hits):
+    """By start time, then keyword index (then end time)."""
+    return sorted(hits, key=lambda x: (x.start, x.keyword_index, x.end))
+
+
 class _BeamInputs:
     """Hotwords and the LM as the beam searches take them (per-object caches); mixed into the decoding classes that search by beam."""
 
@@ -179,6 +221,50 @@ class CTCGreedyDecoding(_BeamInputs):
         bit for bit.  A short utterance can have fewer than ``n_best``.  Raises ``RangeOverflow`` like ``finish``."""
         return self.finish_nbest(self.decode_nbest_device(head, encoded, lengths, n_best, beam_size, hotwords, hotword_boost, lm,
                                                           lm_weight, word_bonus))
+
+    MAX_KEYWORD_TOKENS, MAX_KEYWORDS = 64, 4096     # include/gigaam_hip.h gam_set_keywords
+
+    def keyword_ids(self, keywords) -> List[List[int]]:
+        """Keywords (each a string in the vocabulary -- ``Tokenizer.encode``, nothing is normalised -- or token ids) -> token-id
+        lists.  ``ValueError`` for characters outside the vocabulary, an empty keyword or list, more than 64 tokens in a keyword,
+        more than 4096 keywords, an id outside the vocabulary."""
+        if isinstance(keywords, str):
+            raise ValueError("keywords: a list of keywords is expected, not one string")
+        out = []
+        for w in keywords:
+            ids = self.tokenizer.encode(w) if isinstance(w, str) else [int(i) for i in w]
+            if not ids:
+                raise ValueError(f"keyword {len(out)} is empty")
+            if len(ids) > self.MAX_KEYWORD_TOKENS:
+                raise ValueError(f"keyword {len(out)} has {len(ids)} tokens, at most {self.MAX_KEYWORD_TOKENS} are searched")
+            bad = [i for i in ids if not 0 <= i < self.blank_id]
+            if bad:
+                raise ValueError(f"keyword {len(out)}: token id {bad[0]} outside [0, {self.blank_id - 1}]")
+            out.append(ids)
+        if not out:
+            raise ValueError("keywords: the list is empty")
+        if len(out) > self.MAX_KEYWORDS:
+            raise ValueError(f"{len(out)} keywords, at most {self.MAX_KEYWORDS} are searched at once")
+        return out
+
+    @torch.inference_mode()
+    def find_keywords_device(self, head: CTCHead, encoded: Tensor, lengths: Tensor, keywords: List[List[int]], min_score,
+                             max_hits: int = 8):
+        """The device half of ``find_keywords`` (gam_ctc_kws), no host sync: an ``engine.KeywordHits``.  The keyword set is uploaded
+        only when it differs from the one the engine holds."""
+        c = head.num_classes
+        assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
+        if not 1 <= int(max_hits) <= 64:
+            raise ValueError(f"max_hits={max_hits} outside [1, 64]")
+        head.engine.set_keywords(keywords, min_score)
+        return head.engine.ctc_kws(encoded, lengths, max_hits)
+
+    def finish_keywords(self, dec) -> dict:
+        """An ``engine.KeywordHits`` -> its host arrays (ONE D2H copy); raises ``RangeOverflow`` like ``finish``."""
+        h = dec.host()
+        if h["flag"]:
+            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        return h
 
     MAX_ALIGN_TOKENS = 1024     # include/gigaam_hip.h gam_ctc_align
 

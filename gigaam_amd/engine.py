@@ -160,6 +160,49 @@ class Aligned:
         return out
 
 
+class KeywordHits:
+    """What ``ctc_kws`` / ``op_ctc_kws`` return: the hits of every (utterance, keyword) pair as views of ONE i32 device buffer
+    (``whole``) that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: n_hits [B, K] | hit_frames [B, K, H, 2]
+    (start, end) | hit_score [B, K, H] (f32 bits) | range flag word.  ``dense_score`` f32 / ``dense_start`` i32 [B, K, T'] (the
+    per-frame E_t / S_t of gam_kws.h) are tensors of their own, present only when they were asked for."""
+
+    def __init__(self, whole: Tensor, b: int, k: int, max_hits: int, dense_score: Optional[Tensor] = None,
+                 dense_start: Optional[Tensor] = None, event=None, stream=None):
+        self.whole, self.b, self.k, self.max_hits, self.event, self.stream = whole, b, k, max_hits, event, stream
+        self.dense_score, self.dense_start = dense_score, dense_start
+        n = b * k
+        self.n_hits = whole[:n].view(b, k)
+        mh = max(max_hits, 0)
+        self.hit_frames = whole[n: n + 2 * n * mh].view(b, k, mh, 2)
+        self.hit_score = whole[n + 2 * n * mh: n + 3 * n * mh].view(torch.float32).view(b, k, mh)
+        self.ext = whole[n + 3 * n * mh:]
+
+    def host(self) -> Dict[str, Any]:
+        """One blocking D2H of the hits, on the collect stream behind the search's own completion event -> numpy arrays ``n_hits``
+        [B, K], ``hit_frames`` [B, K, H, 2], ``hit_score`` [B, K, H] and ``flag`` (the split-fp16 range flag of the encoder run that
+        produced the log-probs: True = repeat under GAM_GEMM_F32).  With dense outputs: ``dense_score`` / ``dense_start`` too (a
+        copy each).  Never the log-probs."""
+        side = HipEngine._collect_stream(self.whole.device)
+        with torch.cuda.stream(side):
+            if self.event is not None:
+                side.wait_event(self.event)
+            else:
+                side.wait_stream(torch.cuda.current_stream(self.whole.device))
+            arr = self.whole.cpu().numpy()
+            dense = [None if t is None else t.cpu().numpy() for t in (self.dense_score, self.dense_start)]
+        for t in (self.whole, self.dense_score, self.dense_start):
+            if t is not None:
+                t.record_stream(side)
+        b, k, mh = self.b, self.k, self.max_hits
+        n = b * k
+        out = {"n_hits": arr[:n].reshape(b, k), "hit_frames": arr[n: n + 2 * n * mh].reshape(b, k, mh, 2),
+               "hit_score": arr[n + 2 * n * mh: n + 3 * n * mh].view(np.float32).reshape(b, k, mh)}
+        if dense[0] is not None:
+            out["dense_score"], out["dense_start"] = dense
+        out["flag"] = HipEngine._flag_of(int(arr[-1]))
+        return out
+
+
 class AlignedLong:
     """What ``op_ctc_align_long`` returns: every output of the long-utterance alignment as a view of ONE i32 device buffer (``whole``)
     that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: score (f64 bits, 2 words) | loglik (f64 bits, 2 words) |
@@ -1074,6 +1117,71 @@ class HipEngine:
         off = (C.c_int32 * len(offs))(*offs)
         self._check(self.lib.gam_set_hotwords(self._h, tok, off, len(key[0]), C.c_float(key[1])), "gam_set_hotwords")
         self._hotwords_key = key
+
+    # ---- keyword search (gam_kws.h)
+    MAX_KEYWORD_TOKENS, MAX_KEYWORDS, MAX_KEYWORD_HITS = 64, 4096, 64     # include/gigaam_hip.h gam_set_keywords / gam_ctc_kws
+
+    def set_keywords(self, keywords, min_score) -> None:
+        """The keyword set of ``ctc_kws`` / ``op_ctc_kws`` (gam_set_keywords): token-id lists and, per keyword, the lowest score a
+        frame may have to count as the end of an occurrence (finite, <= 0; one float for all keywords is accepted).  An empty list
+        clears the set.  Re-uploads only when the set or the scores changed; a setup call that waits for in-flight decodes."""
+        kws = tuple(tuple(int(c) for c in p) for p in keywords)
+        ms = np.broadcast_to(np.asarray(min_score, dtype=np.float32), (len(kws),)) if kws else np.zeros((0,), np.float32)
+        key = (kws, ms.tobytes())
+        prev = getattr(self, "_keywords_key", None)
+        if key == prev or (not kws and (prev is None or not prev[0])):     # (no set and none uploaded: nothing to clear)
+            return
+        flat = [c for p in kws for c in p]
+        offs = [0]
+        for p in kws:
+            offs.append(offs[-1] + len(p))
+        tok = (C.c_int32 * max(len(flat), 1))(*flat)
+        off = (C.c_int32 * len(offs))(*offs)
+        msc = (C.c_float * max(len(kws), 1))(*ms.tolist())
+        self._check(self.lib.gam_set_keywords(self._h, tok, off, len(kws), msc), "gam_set_keywords")
+        self._keywords_key = key
+
+    def _kws_out(self, b: int, tp: int, max_hits: int, dense: bool) -> KeywordHits:
+        key = getattr(self, "_keywords_key", None)
+        k = len(key[0]) if key else 0
+        max_hits = int(max_hits)          # (no set, or max_hits outside [1, 64]: the library's errors; the buffers only must not be negative)
+        whole = torch.empty((b * k * (1 + 3 * max(max_hits, 0)) + 1,), dtype=torch.int32, device=self.device)
+        ds = torch.empty((b, k, tp), dtype=torch.float32, device=self.device) if dense else None
+        dst = torch.empty((b, k, tp), dtype=torch.int32, device=self.device) if dense else None
+        return KeywordHits(whole, b, k, max_hits, ds, dst)
+
+    def ctc_kws(self, encoded: Tensor, enc_len: Tensor, max_hits: int = 8, dense: bool = False) -> KeywordHits:
+        """Keyword search on the encoder output (gam_ctc_kws): the CTC head, its log-softmax and the search kernels, no host sync;
+        the set of ``set_keywords`` is searched in every utterance.  ``dense``: also return the per-frame scores and starts.  The
+        split-fp16 range flag is CONSUMED as ``ctc_align`` does: it lands in the result's last word (``KeywordHits.host()['flag']``)."""
+        encoded = self._dev(encoded, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, _, tp = encoded.shape
+        out = self._kws_out(b, tp, max_hits, dense)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_ctc_kws(self._h, _ptr(encoded), _ptr(enc_len), b, tp, out.max_hits, _ptr(out.hit_frames), _ptr(out.hit_score),
+                                      _ptr(out.n_hits), _ptr(out.dense_score), _ptr(out.dense_start), self._stream())
+            self._check(rc, "gam_ctc_kws")
+            out.event, out.stream = self._fetch_flag(out.ext)
+        return out
+
+    def op_ctc_kws(self, log_probs: Tensor, enc_len: Tensor, max_hits: int = 8, dense: bool = False) -> KeywordHits:
+        """gam_op_ctc_kws: the search kernels alone on caller-supplied log-probs [B, T', V] (used as they are).  The result's flag word
+        is 0 (no encoder ran)."""
+        log_probs = self._dev(log_probs, torch.float32)
+        enc_len = self._dev(enc_len, torch.int32)
+        b, tp, v = log_probs.shape
+        out = self._kws_out(b, tp, max_hits, dense)
+        with torch.cuda.device(self.device):
+            out.ext.zero_()
+            rc = self.lib.gam_op_ctc_kws(self._h, _ptr(log_probs), _ptr(enc_len), b, tp, v, out.max_hits, _ptr(out.hit_frames),
+                                         _ptr(out.hit_score), _ptr(out.n_hits), _ptr(out.dense_score), _ptr(out.dense_start),
+                                         self._stream())
+            self._check(rc, "gam_op_ctc_kws")
+            st = torch.cuda.current_stream(self.device)
+            out.event, out.stream = torch.cuda.Event(), st
+            out.event.record(st)
+        return out
 
     def set_lm(self, lm=None, tokenizer=None, weight: float = 0.5, word_bonus: float = 1.0) -> None:
         """An n-gram LM (``lm.NgramLM``) for the beam search, its words spelt by ``tokenizer`` (gam_set_lm); None clears it.

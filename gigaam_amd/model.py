@@ -19,7 +19,7 @@ from . import preprocess as _preprocess
 from ._lib import GigaAMHipError
 from .engine import HipEngine, build_config
 from .preprocess import SAMPLE_RATE, load_audio
-from .types import (AlignmentResult, ConfidenceResult, Hypothesis, LongformAlignmentResult, LongformTranscriptionResult, NBestResult,
+from .types import (AlignmentResult, ConfidenceResult, Hypothesis, KeywordSearchResult, LongformAlignmentResult, LongformTranscriptionResult, NBestResult,
                     ScoredWord, Segment, TranscriptionResult, Word, nbest_posteriors)
 
 LONGFORM_THRESHOLD = 25 * SAMPLE_RATE
@@ -477,6 +477,115 @@ class GigaAMASR(GigaAM):
             out.append(AlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_frames=first, score=score,
                                        log_likelihood=loglik, feasible=ok))
         return out
+
+    # ---- keyword search: does a phrase occur, where, and how sure (gam_ctc_kws)
+    def _keyword_setup(self, keywords, threshold, max_hits: int):
+        """(token-id lists, their text, min_score f32 [K]) of a keyword search; every error that needs no audio is raised here."""
+        if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
+            raise TypeError("keyword search needs a CTC head")
+        ids = self.decoding.keyword_ids(keywords)
+        if not 1 <= int(max_hits) <= 64:
+            raise ValueError(f"max_hits={max_hits} outside [1, 64]")
+        tok = self.decoding.tokenizer
+        texts = [w if isinstance(w, str) else tok.decode(i) for w, i in zip(keywords, ids)]
+        return ids, texts, _decoding.keyword_min_scores([len(i) for i in ids], threshold)
+
+    @torch.inference_mode()
+    def find_keywords(self, wav_file: str, keywords: Sequence[Union[str, List[int]]], threshold=0.5, max_hits: int = 8) -> KeywordSearchResult:
+        """Find every occurrence of each keyword in a clip of at most 25 s.  A keyword is a string in the model's vocabulary
+        (``Tokenizer.encode``; nothing is normalised) or token ids, of at most 64 tokens; at most 4096 keywords per call.  An
+        occurrence is a stretch of frames on which the keyword's tokens, with optional blanks and repeats, are at most a factor
+        away from the greedy path: ``score`` is its log-likelihood ratio against that path (0 where the greedy path spells the
+        keyword) and ``confidence`` = exp(score / tokens).  ``threshold`` in (0, 1] (one value or one per keyword) is the lowest
+        confidence reported; the default 0.5 is a convention, not a measurement, and the confidence is uncalibrated.  At most
+        ``max_hits`` (1..64) occurrences per keyword are returned, the earliest ones; ``truncated`` names the keywords that had more.
+
+        In a char-wise vocabulary a keyword also matches INSIDE longer words; a space in the keyword is the vocabulary's " " token
+        and enforces a word boundary there ("кот " does not match "котик").
+
+        Raises ``ValueError`` for a longer clip, characters outside the vocabulary, an empty keyword or list, more than 64 tokens,
+        more than 4096 keywords, a threshold outside (0, 1]; ``TypeError`` on RNN-T models."""
+        self._keyword_setup(keywords, threshold, max_hits)
+        wav, length = self._prepare_wav_f32(wav_file)
+        if length.item() > LONGFORM_THRESHOLD:
+            raise ValueError("Too long wav file for find_keywords (at most 25 s), use 'find_keywords_longform' method.")
+        return self.find_keywords_batch(wav, length, keywords, threshold, max_hits)[0]
+
+    @torch.inference_mode()
+    def find_keywords_batch(self, wav: Tensor, lengths: Tensor, keywords: Sequence[Union[str, List[int]]], threshold=0.5,
+                            max_hits: int = 8) -> List[KeywordSearchResult]:
+        """Batched ``find_keywords`` on a collated batch (wav [B,L] zero padded, len [B]): every keyword is searched in every
+        utterance, one result per utterance."""
+        ids, texts, min_score = self._keyword_setup(keywords, threshold, max_hits)
+
+        def run():
+            # as launch_batch: sample counts on the host give a ragged batch packed rows
+            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
+            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            dec = self.decoding.find_keywords_device(self.head, encoded, encoded_len, ids, min_score, max_hits)
+            return self.decoding.finish_keywords(dec), encoded_len
+
+        h, encoded_len = self._with_f32_fallback(run, "this batch was")
+        from .timestamps_utils import compute_frame_shift
+
+        wl, el = lengths.tolist(), encoded_len.tolist()
+        out: List[KeywordSearchResult] = []
+        for b in range(wav.shape[0]):
+            shift = compute_frame_shift(int(wl[b]), int(el[b])) if el[b] else 0.0
+            hits, truncated = _decoding.keyword_hits(h, b, ids, texts, shift)
+            out.append(KeywordSearchResult(hits=_decoding.sort_keyword_hits(hits), truncated=truncated, keywords=list(texts)))
+        return out
+
+    @torch.inference_mode()
+    def find_keywords_longform(self, wav_file: str, keywords: Sequence[Union[str, List[int]]], threshold=0.5, max_hits: int = 8,
+                               fr_batch_size: int = 16, **kwargs: Any) -> KeywordSearchResult:
+        """``find_keywords`` on a recording of any length.  Segmentation keywords as for ``transcribe_longform`` (``speech_regions=``,
+        ``vad=``, the pack_regions keywords; the same pyannote / EnergyVAD default and warnings).  Every speech region's chunk is
+        searched as one batch entry; hits come in file time (region start + frame x that region's frame shift) with the region's
+        index in ``segment`` and the frames counted inside it; ``max_hits`` and ``truncated`` apply per region.  An occurrence that
+        straddles two regions is NOT found: the regions are searched independently and nothing is stitched."""
+        from .feeder import BatchFeeder
+        from .timestamps_utils import compute_frame_shift
+        from .vad_utils import segment_audio_file
+
+        ids, texts, min_score = self._keyword_setup(keywords, threshold, max_hits)
+        self._default_vad(kwargs, "find_keywords_longform")
+        segments, boundaries = segment_audio_file(wav_file, SAMPLE_RATE, device=self._device, **kwargs)
+        if not segments:
+            return KeywordSearchResult(hits=[], truncated=[], keywords=list(texts))
+
+        # the one-batch pipeline of transcribe_longform: batch n is launched before batch n - 1 is brought to the host
+        def run():
+            hits, truncated, seg = [], set(), 0
+
+            def emit(pending) -> None:
+                nonlocal seg
+                dec, encoded_len, lens = pending
+                h = self.decoding.finish_keywords(dec)
+                for b, (n_wav, n_enc) in enumerate(zip(lens.tolist(), encoded_len.tolist())):
+                    shift = compute_frame_shift(int(n_wav), int(n_enc)) if n_enc else 0.0
+                    got, trunc = _decoding.keyword_hits(h, b, ids, texts, shift, boundaries[seg][0], seg)
+                    hits.extend(got)
+                    truncated.update(trunc)
+                    seg += 1
+
+            pending = None
+            feeder = BatchFeeder(segments, fr_batch_size, self._device)
+            for wav, lens in feeder:
+                encoded, encoded_len = self._encode(wav, lens, getattr(feeder, "host_lengths", None))
+                dec = self.decoding.find_keywords_device(self.head, encoded, encoded_len, ids, min_score, max_hits)
+                if pending is not None:
+                    emit(pending)
+                pending = (dec, encoded_len, lens)
+            if pending is not None:
+                emit(pending)
+            return _decoding.sort_keyword_hits(hits), sorted(truncated)
+
+        eng = self.head.engine
+        if eng.gemm_mode != "f32":
+            eng.range_flag()     # (as transcribe_longform: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
+        hits, truncated = self._with_f32_fallback(run, "the file was")
+        return KeywordSearchResult(hits=hits, truncated=truncated, keywords=list(texts))
 
     # ---- transducer forced alignment: the same for RNN-T heads (gam_rnnt_align)
     def _require_rnnt(self) -> None:

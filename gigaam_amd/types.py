@@ -187,3 +187,37 @@ class LongformAlignmentResult:
 
     def __len__(self) -> int:
         return len(self.segments)
+
+
+@dataclass
+class KeywordHit:
+    """One occurrence of a keyword (``GigaAMASR.find_keywords``).  ``start`` / ``end``: seconds, ``start_frame`` x frame shift and
+    (``end_frame`` + 1) x frame shift -- the convention of ``transcribe(word_timestamps=True)``; in a longform result they are file
+    times and the frames count inside speech region ``segment``.  ``score``: the occurrence's log-likelihood ratio against the
+    greedy path (<= 0; 0 where the greedy path spells the keyword); ``confidence`` = exp(score / tokens), the geometric mean of
+    that ratio per token, in (0, 1] -- UNCALIBRATED: a ranking value, not a probability of being right."""
+    keyword: str
+    keyword_index: int
+    start: float
+    end: float
+    score: float
+    confidence: float
+    start_frame: int
+    end_frame: int
+    segment: Optional[int] = None
+
+
+@dataclass
+class KeywordSearchResult:
+    """``GigaAMASR.find_keywords``: ``hits`` sorted by start time, then keyword index; ``truncated``: the indices of the keywords that
+    had more than ``max_hits`` occurrences (in one utterance / speech region) -- only the first ``max_hits`` of those are listed;
+    ``keywords``: the keywords as text."""
+    hits: List[KeywordHit]
+    truncated: List[int]
+    keywords: List[str]
+
+    def __iter__(self) -> Iterator[KeywordHit]:
+        return iter(self.hits)
+
+    def __len__(self) -> int:
+        return len(self.hits)

@@ -12,6 +12,7 @@
  *   gam_ctc_head     <- CTCHead.forward                   gigaam/decoder.py:18-21
  *   gam_ctc_greedy   <- CTCGreedyDecoding.decode          gigaam/decoding.py:56-96
  *   gam_ctc_align    (no reference counterpart: CTC forced alignment + log-likelihood of a given transcript)
+ *   gam_ctc_kws      (no reference counterpart: keyword search -- where each phrase of a set occurs, with a score)
  *   gam_ctc_beam     (no reference counterpart: CTC prefix beam search with hotword boosting and n-gram LM fusion)
  *   gam_ctc_beam_nbest   (no reference counterpart: the N best prefixes of that search's final beam)
  *   gam_rnnt_greedy  <- RNNTGreedyDecoding.decode         gigaam/decoding.py:128-207
@@ -161,6 +162,33 @@ int gam_set_ctc_align_workspace(gam_handle* h, int64_t bytes);
 /* Tuning hook of gam_op_ctc_align_long, modelled on gam_tune_sp: force the states per block (sb: a multiple of 64 in [64, 3072]) and
  * the frames per tile (tt >= 1) of every following call in this process; 0 = planned (1024 x 256).  Returns -1 for other values. */
 int gam_tune_ctc_align_long(int sb, int tt);
+
+/* Keyword search over the CTC posteriors (gigaam_amd/csrc/gam_kws.h holds the contract): for every (utterance, keyword) pair, where
+ * the keyword occurs and how well it scores.  Runs the CTC head, its log-softmax, a row-maximum pre-pass and ONE search kernel (a
+ * wave per pair: a CTC Viterbi over the keyword's tokens with a free start and a free end, blank = V - 1).  Emissions are
+ * log-likelihood ratios against the greedy path, c_t(v) = lp[t, v] - max_w lp[t, w] <= 0, so a score is 0 where the greedy path
+ * spells the keyword and falls with every frame on which it does not.  Per frame t the kernel knows E_t, the best score of an
+ * occurrence that ends at t, and S_t, where that occurrence starts; frames with E_t >= min_score[k] are merged into hits in one
+ * streaming pass (overlapping ones keep the better, later one; gam_kws.h).  Ties follow a fixed rule: a hit starts at the earliest
+ * frame and ends at the last frame of its last token's run.  Uses the set of gam_set_keywords (an error when there is none).
+ *   hit_frames i32 [B, K, max_hits, 2]: (start, end) frames, end inclusive; hit_score f32 [B, K, max_hits]; in time order.
+ *   n_hits i32 [B, K]: hits found; n_hits > max_hits means the list is truncated to the first max_hits.  Slots past
+ *   min(n_hits, max_hits) hold -1 / -inf.  enc_len[b] = 0 gives n_hits = 0.
+ *   dense_score f32 [B, K, T'] and dense_start i32 [B, K, T'] (each may be NULL): E_t and S_t; -inf / -1 where no occurrence ends
+ *   and at t >= enc_len[b].
+ * Limits: 1 <= max_hits <= 64, T' <= 8192 (an error beyond them, without a launch).  Decode class, like gam_ctc_greedy; no host
+ * synchronisation.  Consumers of the range flag fetch it behind this call. */
+int gam_ctc_kws(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int max_hits, int32_t* hit_frames,
+                float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream);
+/* The same from caller-supplied log-probs f32 [B, T', V] (read as they are: no normalisation). */
+int gam_op_ctc_kws(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int max_hits,
+                   int32_t* hit_frames, float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream);
+/* The keyword set of gam_ctc_kws: keyword i is tokens[offsets[i] .. offsets[i + 1]) (host arrays; offsets has n_keywords + 1 entries,
+ * offsets[0] = 0) and reports the frames whose score reaches min_score[i] (f32 [n_keywords], finite and <= 0; U x ln(p) asks for a
+ * geometric-mean likelihood ratio of p per token).  Ids outside [0, V - 2], empty keywords, more than 64 tokens in a keyword, more
+ * than 4096 keywords, a non-finite or positive min_score are errors; n_keywords = 0 clears the set.  A setup call, like
+ * gam_set_hotwords: it waits for the handle's in-flight decode-class work before it replaces the set. */
+int gam_set_keywords(gam_handle* h, const int32_t* tokens, const int32_t* offsets, int n_keywords, const float* min_score);
 
 /* CTC prefix beam search with hotword boosting (gigaam_amd/csrc/gam_beam.h).  Runs the CTC head, its log-softmax and ONE beam
  * kernel (a workgroup per utterance, t the sequential loop, backtrack in the same kernel).  Beam width 1 <= W <= 32; per frame the
