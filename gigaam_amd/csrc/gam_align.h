@@ -6,28 +6,22 @@
 //   forward  a_t(s) = the same recursion with log-sum-exp instead of max
 // with score = max(d_{T-1}(S-1), d_{T-1}(S-2)) and log-likelihood = logsumexp(a_{T-1}(S-1), a_{T-1}(S-2)) (= -ctc_loss).
 //
-// Shape: one workgroup per utterance, states across the lanes (state s = i * blockDim + tid, i < spt <= 3), t the sequential
+// Shape: one workgroup per utterance, states across the lanes (state s = i * blockDim + tid, i < SPT <= 3), t the sequential
 // loop with ONE barrier per step (d / a double-buffered in LDS).  The emission row of frame t + GAM_ALIGN_PF is loaded while
-// frame t is computed.  Precision: every step subtracts the previous step's maximum (of d and of a separately, read from the
-// per-wave maxima of that step) and carries the offsets in fp64, so the stored values stay O(one frame's log-prob) and their
-// fp32 ulp far below the top-1 / top-2 margins of real frames.  Backpointers: 2 bits per (t, s) as two 64-bit ballots per
-// 64-state chunk; in LDS when T' x chunks x 16 B fit beside the rest of the workgroup's LDS (BP_LDS), else in a global scratch
-// buffer the handle owns.  The backtrack runs in the same kernel (one lane walks the 2-bit pointers, then every lane writes).
+// frame t is computed.  The frame step, its renormalisation (fp64 offsets), the tie rule, the backpointer encoding, the end rule
+// and the feasibility rule are gam_trellis.h's, shared with gam_align_long.h.  Backpointers sit in LDS when T' x chunks x 16 B
+// fit beside the rest of the workgroup's LDS (BP_LDS), else in a global scratch buffer the handle owns.  The backtrack runs in
+// the same kernel (one lane walks the 2-bit pointers, then every lane writes).
 //
-// Tie rule (deterministic, shared with tests/ctc_align_ref.py): among equal predecessors prefer s over s-1 over s-2; at the
-// end prefer S-1 over S-2.
 // Limits: U <= GAM_ALIGN_MAX_U (S <= 2049) tokens, T' <= GAM_ALIGN_MAX_T frames (the host entry points fail beyond them).
 // Infeasible utterances -- T < U + #{i : y_i == y_{i-1}}, a target id outside [0, V-2], target_len outside [0, Umax], or no
 // path of finite score -- get status 0, score = loglik = -inf, frame labels and token frames -1; target entries past
 // target_len[b] are never read.  U = 0 is the all-blank path; T = 0 with U = 0 scores 0.
 #pragma once
-#include "gam_common.h"
+#include "gam_trellis.h"
 
 #define GAM_ALIGN_MAX_U 1024
 #define GAM_ALIGN_MAX_T 8192
-#define GAM_ALIGN_MAX_NT 1024
-#define GAM_ALIGN_MAX_SPT 3
-#define GAM_ALIGN_PF 4          // emission rows in flight ahead of the step that uses them
 #define GAM_ALIGN_LDS_MAX (160 * 1024)
 
 struct GamAlignArgs {
@@ -36,7 +30,6 @@ struct GamAlignArgs {
   const int* targets;        // [B, Umax] (may be NULL when Umax == 0)
   const int* target_len;     // [B]
   int Tp, V, Umax;
-  int spt;                   // states per thread: S_max <= spt * blockDim
   int nchunk;                // 64-state backpointer chunks per frame: ceil(S_max / 64)
   uint4* bp_glob;            // !BP_LDS: [B, Tp, nchunk] chunks of {bit0 lo, bit0 hi, bit1 lo, bit1 hi}
   int* frame_labels;         // [B, Tp]
@@ -50,45 +43,23 @@ struct GamAlignArgs {
 // LDS bytes of one workgroup (host and device carve it the same way)
 static inline size_t gam_align_lds_bytes(bool bp_lds, int Tp, int nchunk, int spt, int nt) {
   const size_t sp = (size_t)spt * nt + 2;
-  return (bp_lds ? (size_t)Tp * nchunk * 16 : 0) + 16 * sp + 64 * sizeof(float) + 64 + (((size_t)Tp * 2 + 15) & ~(size_t)15);
+  return (bp_lds ? (size_t)Tp * nchunk * 16 : 0) + 16 * sp + GAM_TRELLIS_WM * sizeof(float) + 64 + (((size_t)Tp * 2 + 15) & ~(size_t)15);
 }
 
-// The forward recursion's log-sum-exp on the hardware transcendentals (v_exp_f32 / v_log_f32, ~1 ulp): arguments of exp are <= 0,
-// the sum of the three terms lies in [1, 3], so each step adds an absolute error of ~1e-7 (measured loglik errors: DESIGN.md section 4.8).
-__device__ __forceinline__ float gam_align_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
-__device__ __forceinline__ float gam_align_log(float x) { return __builtin_amdgcn_logf(x) * 0.693147180559945309f; }
-
-// Wave maximum by DPP (row quad-perms and mirrors, then the two GFX9 row broadcasts): the per-step renormalisation needs two of
-// these on the sequential path, where the ds_bpermute chain of gam_wave_max costs six LDS round trips each.  Result in lane 63.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float gam_align_dpp_max(float v) {
-  const int o = __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
-  return fmaxf(v, __int_as_float(o));
-}
-__device__ __forceinline__ float gam_align_wave_max(float v) {
-  v = gam_align_dpp_max<0xb1, 0xf>(v);    // quad_perm [1,0,3,2]
-  v = gam_align_dpp_max<0x4e, 0xf>(v);    // quad_perm [2,3,0,1]
-  v = gam_align_dpp_max<0x141, 0xf>(v);   // row_half_mirror
-  v = gam_align_dpp_max<0x140, 0xf>(v);   // row_mirror: every lane holds its row's maximum
-  v = gam_align_dpp_max<0x142, 0xa>(v);   // row_bcast:15 -> rows 1, 3
-  v = gam_align_dpp_max<0x143, 0xc>(v);   // row_bcast:31 -> rows 2, 3
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-template <bool BP_LDS>
+template <bool BP_LDS, int SPT>   // SPT states per thread: S_max <= SPT * blockDim
 __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlignArgs a) {
   extern __shared__ uint4 gam_smem_align[];
   unsigned char* smem = reinterpret_cast<unsigned char*>(gam_smem_align);
   const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
   const int b = blockIdx.x;
   const int Tp = a.Tp, V = a.V, blank = V - 1;
-  const int sp = a.spt * nt + 2;                 // floats per state buffer: two -inf sentinels (s - 1, s - 2 of s = 0), then states
+  const int sp = SPT * nt + 2;                   // floats per state buffer: two -inf sentinels (s - 1, s - 2 of s = 0), then states
   size_t off = BP_LDS ? (size_t)Tp * a.nchunk * 16 : 0;
   uint4* bpl = gam_smem_align;
   float* D = reinterpret_cast<float*>(smem + off);     // D[buf][2 + s], buf = t & 1
   float* A = D + 2 * sp;
-  float* wm = A + 2 * sp;                              // per-wave maxima of the step: wm[(buf * 2 + {0: d, 1: a}) * 16 + wave]
-  int* misc = reinterpret_cast<int*>(wm + 64);         // repeats, bad id, path found
+  float* wm = A + 2 * sp;                              // per-wave maxima of the step (gam_trellis.h)
+  int* misc = reinterpret_cast<int*>(wm + GAM_TRELLIS_WM);   // repeats, bad id, path found
   // the six output pointers, parked in LDS across the sweep: held in SGPRs through it they made the kernel spill SGPRs
   void** outp = reinterpret_cast<void**>(misc + 4);
   unsigned short* path = reinterpret_cast<unsigned short*>(misc + 16);
@@ -119,7 +90,7 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
   int* fl = a.frame_labels + (size_t)b * Tp;
   int* tf = a.tok_first + (size_t)b * a.Umax;
   int* tl = a.tok_last + (size_t)b * a.Umax;
-  const bool feasible = ulen_ok && misc[1] == 0 && T >= U + misc[0];
+  const bool feasible = ulen_ok && gam_ctc_feasible(T, U, misc[0], misc[1]);
   if (!feasible || T == 0) {      // (T == 0 and feasible: U == 0, the empty path)
     for (int t = tid; t < Tp; t += nt) fl[t] = -1;
     for (int u = tid; u < a.Umax; u += nt) tf[u] = tl[u] = -1;
@@ -132,22 +103,15 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
   }
 
   // this thread's states: label, whether the s-2 skip is allowed
-  int lab[GAM_ALIGN_MAX_SPT];
-  bool act[GAM_ALIGN_MAX_SPT], skip[GAM_ALIGN_MAX_SPT];
-#pragma unroll
-  for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) {
-    const int s = i * nt + tid;
-    act[i] = i < a.spt && s < S;
-    const bool tok = act[i] && (s & 1);
-    lab[i] = tok ? y[(s - 1) >> 1] : blank;
-    skip[i] = tok && s >= 3 && y[(s - 1) >> 1] != y[(s - 3) >> 1];
-  }
+  int lab[SPT];
+  bool act[SPT], skip[SPT];
+  gam_ctc_lanes<SPT>(y, blank, S, 0, S, nt, tid, lab, act, skip);
   // t = -1: a virtual start that only state 0 holds (then d_0(0) = lp[0, blank], d_0(1) = lp[0, y0], the rest -inf)
   for (int k = tid; k < 2 * sp; k += nt) {
     D[k] = -INFINITY;
     A[k] = -INFINITY;
   }
-  if (tid < 64) wm[tid] = -INFINITY;
+  gam_trellis_wm_init(wm, tid);
   __syncthreads();
   if (tid == 0) {
     D[sp + 2] = 0.f;
@@ -158,11 +122,11 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
   // Emission loads are unconditional (a row index clamped to T - 1, inactive states read the blank column): a load under a branch makes
   // hipcc wait for every load in flight at its first use, which would serialise the prefetch.
   const float* lpb = a.lp + (size_t)b * Tp * V;
-  float e[GAM_ALIGN_PF][GAM_ALIGN_MAX_SPT];
+  float e[GAM_ALIGN_PF][SPT];
 #pragma unroll
   for (int k = 0; k < GAM_ALIGN_PF; ++k)
 #pragma unroll
-    for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) e[k][i] = lpb[(size_t)(k < T ? k : T - 1) * V + lab[i]];
+    for (int i = 0; i < SPT; ++i) e[k][i] = lpb[(size_t)(k < T ? k : T - 1) * V + lab[i]];
 
   double offD = 0.0, offA = 0.0;   // what the renormalisations subtracted so far
   for (int t0 = 0; t0 < T; t0 += GAM_ALIGN_PF) {
@@ -175,61 +139,27 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
       const float* Ap = A + prv * sp + 2;
       float* Dc = D + cur * sp + 2;
       float* Ac = A + cur * sp + 2;
-      float mD = -INFINITY, mA = -INFINITY;
-#pragma unroll
-      for (int w = 0; w < 16; w += 4) {   // (all 16 slots: those of absent waves hold -inf)
-        const float4 xd = *reinterpret_cast<const float4*>(wm + (prv * 2) * 16 + w);
-        const float4 xa = *reinterpret_cast<const float4*>(wm + (prv * 2 + 1) * 16 + w);
-        mD = fmaxf(mD, fmaxf(fmaxf(xd.x, xd.y), fmaxf(xd.z, xd.w)));
-        mA = fmaxf(mA, fmaxf(fmaxf(xa.x, xa.y), fmaxf(xa.z, xa.w)));
-      }
-      if (mD == -INFINITY) mD = 0.f;
-      if (mA == -INFINITY) mA = 0.f;
+      float mD, mA;
+      gam_trellis_wm_read(wm, prv, mD, mA);
       offD += (double)mD;
       offA += (double)mA;
       float lmD = -INFINITY, lmA = -INFINITY;
-      unsigned bpv[GAM_ALIGN_MAX_SPT];
+      unsigned bpv[SPT];
 #pragma unroll
-      for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) {
-        const int s = i * nt + tid;
-        unsigned bp = 0;
-        if (act[i]) {
-          const float d0 = Dp[s], d1 = Dp[s - 1], d2 = skip[i] ? Dp[s - 2] : -INFINITY;
-          float best = d0;
-          if (d1 > best) { best = d1; bp = 1; }
-          if (d2 > best) { best = d2; bp = 2; }
-          const float nd = (best - mD) + e[k][i];
-          const float a0 = Ap[s], a1 = Ap[s - 1], a2 = skip[i] ? Ap[s - 2] : -INFINITY;
-          const float M = fmaxf(fmaxf(a0, a1), a2);
-          float na = -INFINITY;
-          if (M > -INFINITY) na = ((M - mA) + gam_align_log(gam_align_exp(a0 - M) + gam_align_exp(a1 - M) + gam_align_exp(a2 - M))) + e[k][i];
-          Dc[s] = nd;
-          Ac[s] = na;
-          lmD = fmaxf(lmD, nd);
-          lmA = fmaxf(lmA, na);
-        }
-        bpv[i] = bp;
+      for (int i = 0; i < SPT; ++i) {
+        float nd, na;
+        bpv[i] = gam_ctc_step(Dp, Ap, Dc, Ac, i * nt + tid, act[i], skip[i], e[k][i], mD, mA, lmD, lmA, nd, na);
       }
       // the row t + PF replaces the one just used (its load is in flight during the next PF - 1 steps)
       const int tn = t + GAM_ALIGN_PF < T ? t + GAM_ALIGN_PF : T - 1;
 #pragma unroll
-      for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) e[k][i] = lpb[(size_t)tn * V + lab[i]];
-      lmD = gam_align_wave_max(lmD);
-      lmA = gam_align_wave_max(lmA);
+      for (int i = 0; i < SPT; ++i) e[k][i] = lpb[(size_t)tn * V + lab[i]];
+      gam_trellis_wm_publish(wm, cur, lane, wave, lmD, lmA);
 #pragma unroll
-      for (int i = 0; i < GAM_ALIGN_MAX_SPT; ++i) {
-        if (i >= a.spt) break;
-        const unsigned long long m1 = __ballot(bpv[i] & 1u), m2 = __ballot(bpv[i] >> 1);
+      for (int i = 0; i < SPT; ++i) {
         const int c = i * nw + wave;
-        if (lane == 0 && c < a.nchunk) {
-          const uint4 w = make_uint4((unsigned)m1, (unsigned)(m1 >> 32), (unsigned)m2, (unsigned)(m2 >> 32));
-          if (BP_LDS) bpl[(size_t)t * a.nchunk + c] = w;
-          else a.bp_glob[((size_t)b * Tp + t) * a.nchunk + c] = w;
-        }
-      }
-      if (lane == 0) {
-        wm[(cur * 2) * 16 + wave] = lmD;
-        wm[(cur * 2 + 1) * 16 + wave] = lmA;
+        if (BP_LDS) gam_ctc_bp_pack(bpv[i], lane == 0 && c < a.nchunk, bpl + ((size_t)t * a.nchunk + c));
+        else gam_ctc_bp_pack(bpv[i], lane == 0 && c < a.nchunk, a.bp_glob + (((size_t)b * Tp + t) * a.nchunk + c));
       }
       __syncthreads();
     }
@@ -245,14 +175,11 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
     const int fb = (T - 1) & 1;
     const float* Df = D + fb * sp + 2;
     const float* Af = A + fb * sp + 2;
-    int s = S - 1;
-    float best = Df[S - 1];
-    if (S >= 2 && Df[S - 2] > best) { best = Df[S - 2]; s = S - 2; }
-    const float a1 = Af[S - 1], a2 = S >= 2 ? Af[S - 2] : -INFINITY;
-    const float M = fmaxf(a1, a2);
-    const bool found = best > -INFINITY;
+    int s;
+    float best, ll;
+    const bool found = gam_ctc_end<float>(S, Df[S - 1], S >= 2 ? Df[S - 2] : -INFINITY, Af[S - 1], S >= 2 ? Af[S - 2] : -INFINITY, s, best, ll);
     score[b] = found ? (float)((double)best + offD) : -INFINITY;
-    loglik[b] = found && M > -INFINITY ? (float)((double)(M + logf(expf(a1 - M) + expf(a2 - M))) + offA) : -INFINITY;
+    loglik[b] = ll > -INFINITY ? (float)((double)ll + offA) : -INFINITY;
     status[b] = found ? 1 : 0;
     misc[2] = found ? 1 : 0;
     if (found) {
@@ -260,9 +187,7 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
         path[t] = (unsigned short)s;
         if (t == 0) break;
         const uint4 w = BP_LDS ? bpl[(size_t)t * a.nchunk + (s >> 6)] : a.bp_glob[((size_t)b * Tp + t) * a.nchunk + (s >> 6)];
-        const int sh = s & 31;
-        const unsigned lo = (s & 32) ? w.y : w.x, hi = (s & 32) ? w.w : w.z;
-        s -= (int)(((lo >> sh) & 1u) | (((hi >> sh) & 1u) << 1));
+        s -= gam_ctc_bp_step(w, s);
       }
     }
   }
@@ -272,18 +197,6 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
     for (int u = tid; u < a.Umax; u += nt) tf[u] = tl[u] = -1;
     return;
   }
-  for (int t = tid; t < Tp; t += nt) {
-    int out = -1;
-    if (t < T) {
-      const int s = path[t];
-      out = (s & 1) ? y[(s - 1) >> 1] : blank;
-      if (s & 1) {
-        const int u = (s - 1) >> 1;
-        if (t == 0 || path[t - 1] != s) tf[u] = t;
-        if (t == T - 1 || path[t + 1] != s) tl[u] = t;
-      }
-    }
-    fl[t] = out;
-  }
+  for (int t = tid; t < Tp; t += nt) fl[t] = t < T ? gam_ctc_frame_out(path, t, T, y, blank, tf, tl) : -1;
   for (int u = U + tid; u < a.Umax; u += nt) tf[u] = tl[u] = -1;
 }

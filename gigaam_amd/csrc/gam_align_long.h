@@ -1,7 +1,8 @@
 // gam_align_long.h -- CTC forced alignment of ONE long utterance (gam_op_ctc_align_long), tiled over states and frames.
 //
-// The recurrences, the tie rule, the feasibility rule and the statuses are those of gam_align.h (read its header first); what
-// differs is the shape.  gam_align.h keeps the whole state row of an utterance in one workgroup's LDS (S <= 2049, T' <= 8192).
+// The recurrences and the statuses are those of gam_align.h; the frame step, the tie rule, the backpointer encoding, the end rule and
+// the feasibility rule are the same code, gam_trellis.h (read its header first).  What differs is the shape.  gam_align.h keeps
+// the whole state row of an utterance in one workgroup's LDS (S <= 2049, T' <= 8192).
 // Here the S = 2U + 1 states are cut into nS blocks of SB states (a multiple of 64) and the T frames into nT tiles of TT frames.
 // Tile (j, k) = block j over time tile k needs
 //   (a) block j's own state row at the end of tile k - 1, and
@@ -12,13 +13,13 @@
 // by launch d - 1 and (b) by launches d - 1 and d - 2.  STREAM ORDER IS THE ONLY DEPENDENCY: nT + nS - 1 plain launches, no flag, no
 // spin, no grid sync, no graph -- no workgroup ever waits for a value a running workgroup produces.
 //
-// Precision: per block the scheme of gam_align.h -- each step subtracts the block's previous-step maximum (of d and of a), the
+// Precision: per block the scheme of gam_trellis.h -- each step subtracts the block's previous-step maximum (of d and of a), the
 // offsets are carried in fp64 -- with the block's offsets and its last row kept in the workspace between tiles.  A block publishes
 // its edge state per frame in ABSOLUTE terms as fp64 {d, a}; the reader subtracts its own fp64 offset and rounds to fp32 (one
 // extra rounding of an O(frame log-prob) number per block edge and frame; -inf stays -inf).  A block whose states are all
-// unreachable keeps offset 0 (the mD == -inf rule of gam_align.h).
+// unreachable keeps offset 0 (the -inf -> 0 rule of gam_trellis.h).
 //
-// Backpointers: 2 bits per (t, s) as two 64-bit ballots per 64-state chunk, in a global workspace of T x ceil(S / 64) x 16 bytes.
+// Backpointers: gam_trellis.h's chunk words, in a global workspace of T x ceil(S / 64) x 16 bytes.
 // The whole workspace (backpointers + edges nS x T x 16 B + rows nS x SB x 8 B + path T x 4 B) is the handle's and is capped by
 // gam_set_ctc_align_workspace / GAM_CTC_ALIGN_WS; the default cap GAM_AL_WS_DEFAULT = 3 GiB holds a one-hour recording with a
 // char-level transcript (T = 9e4, U = 5e4: 2.25 GB of backpointers + 0.14 GB of edges).
@@ -30,7 +31,7 @@
 // Scores leave the device as float64.  Limits: T < 2^31, U whatever the workspace cap allows (state indices are 32-bit ints: the host
 // entry point refuses U >= 2^30, far beyond what any cap that fits a GPU admits).
 #pragma once
-#include "gam_align.h"
+#include "gam_trellis.h"
 
 #define GAM_AL_SB_DEFAULT 1024   // states per block: one state per thread of a 1024-thread workgroup
 #define GAM_AL_TT_DEFAULT 256    // frames per tile
@@ -67,13 +68,13 @@ static inline void gam_align_long_shape(int sb, int* nt, int* spt) {
   *spt = (m + 15) / 16;
   *nt = 64 * ((m + *spt - 1) / *spt);
 }
-static inline size_t gam_align_long_lds_bytes(int spt, int nt) { return 16 * ((size_t)spt * nt + 2) + 64 * sizeof(float); }
+static inline size_t gam_align_long_lds_bytes(int spt, int nt) { return 16 * ((size_t)spt * nt + 2) + GAM_TRELLIS_WM * sizeof(float); }
 // tuning hook (gam_tune_ctc_align_long): 0 = the defaults above.  Process-wide like gam_tune_sp; the fields are atomics.
 struct GamAlignLongForce { std::atomic<int> sb{0}, tt{0}; };
 static inline GamAlignLongForce& gam_align_long_force() { static GamAlignLongForce f; return f; }
 
 __device__ __forceinline__ bool gam_align_long_feasible(const GamAlignLongArgs& a) {
-  return a.ctrl[1] == 0 && (long long)a.T >= (long long)a.U + a.ctrl[0];
+  return gam_ctc_feasible(a.T, a.U, a.ctrl[0], a.ctrl[1]);
 }
 
 // repeats and bad ids of the target (U > 0)
@@ -104,25 +105,17 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_ker
   const int sp = SPT * nt + 2;                   // floats per state buffer: the neighbour's edge at [1] ([0] unused), then the states
   float* D = reinterpret_cast<float*>(gam_smem_align_long);   // D[buf][2 + local state], buf = t & 1
   float* A = D + 2 * sp;
-  float* wm = A + 2 * sp;                        // per-wave maxima of the step: wm[(buf * 2 + {0: d, 1: a}) * 16 + wave]
-  const int* y = a.targets;
+  float* wm = A + 2 * sp;                        // per-wave maxima of the step (gam_trellis.h)
 
   // this thread's states: label, whether the s-2 skip is allowed
   int lab[SPT];
   bool act[SPT], skip[SPT];
-#pragma unroll
-  for (int i = 0; i < SPT; ++i) {
-    const int sl = i * nt + tid, s = j * sb + sl;
-    act[i] = sl < sb && s < S;
-    const bool tok = act[i] && (s & 1);
-    lab[i] = tok ? y[(s - 1) >> 1] : blank;
-    skip[i] = tok && s >= 3 && y[(s - 1) >> 1] != y[(s - 3) >> 1];
-  }
+  gam_ctc_lanes<SPT>(a.targets, blank, S, j * sb, sb, nt, tid, lab, act, skip);
   for (int q = tid; q < 2 * sp; q += nt) {
     D[q] = -INFINITY;
     A[q] = -INFINITY;
   }
-  if (tid < 64) wm[tid] = -INFINITY;
+  gam_trellis_wm_init(wm, tid);
   __syncthreads();
 
   // the row this tile starts from, in buffer prv of its first step: t = -1 is a virtual start that only state 0 holds
@@ -152,12 +145,7 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_ker
         lmA = fmaxf(lmA, va);
       }
     }
-    lmD = gam_align_wave_max(lmD);
-    lmA = gam_align_wave_max(lmA);
-    if (lane == 0) {
-      wm[(pb * 2) * 16 + wave] = lmD;
-      wm[(pb * 2 + 1) * 16 + wave] = lmA;
-    }
+    gam_trellis_wm_publish(wm, pb, lane, wave, lmD, lmA);
     if (tid == 0 && j > 0) {                     // the neighbour's last state at t0 - 1, in this block's frame of reference
       const double2 e = eg[t0 - 1];
       D[pb * sp + 1] = (float)(e.x - offD);
@@ -188,41 +176,17 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_ker
       const float* Ap = A + prv * sp + 2;
       float* Dc = D + cur * sp + 2;
       float* Ac = A + cur * sp + 2;
-      float mD = -INFINITY, mA = -INFINITY;
-#pragma unroll
-      for (int w = 0; w < 16; w += 4) {   // (all 16 slots: those of absent waves hold -inf)
-        const float4 xd = *reinterpret_cast<const float4*>(wm + (prv * 2) * 16 + w);
-        const float4 xa = *reinterpret_cast<const float4*>(wm + (prv * 2 + 1) * 16 + w);
-        mD = fmaxf(mD, fmaxf(fmaxf(xd.x, xd.y), fmaxf(xd.z, xd.w)));
-        mA = fmaxf(mA, fmaxf(fmaxf(xa.x, xa.y), fmaxf(xa.z, xa.w)));
-      }
-      if (mD == -INFINITY) mD = 0.f;
-      if (mA == -INFINITY) mA = 0.f;
+      float mD, mA;
+      gam_trellis_wm_read(wm, prv, mD, mA);
       offD += (double)mD;
       offA += (double)mA;
       float lmD = -INFINITY, lmA = -INFINITY;
       unsigned bpv[SPT];
 #pragma unroll
       for (int i = 0; i < SPT; ++i) {
-        const int sl = i * nt + tid;
-        unsigned bp = 0;
-        float nd = -INFINITY, na = -INFINITY;
-        if (act[i]) {
-          const float d0 = Dp[sl], d1 = Dp[sl - 1], d2 = skip[i] ? Dp[sl - 2] : -INFINITY;
-          float best = d0;
-          if (d1 > best) { best = d1; bp = 1; }
-          if (d2 > best) { best = d2; bp = 2; }
-          nd = (best - mD) + e[q][i];
-          const float a0 = Ap[sl], a1 = Ap[sl - 1], a2 = skip[i] ? Ap[sl - 2] : -INFINITY;
-          const float M = fmaxf(fmaxf(a0, a1), a2);
-          if (M > -INFINITY) na = ((M - mA) + gam_align_log(gam_align_exp(a0 - M) + gam_align_exp(a1 - M) + gam_align_exp(a2 - M))) + e[q][i];
-          Dc[sl] = nd;
-          Ac[sl] = na;
-          lmD = fmaxf(lmD, nd);
-          lmA = fmaxf(lmA, na);
-        }
+        float nd, na;
+        bpv[i] = gam_ctc_step(Dp, Ap, Dc, Ac, i * nt + tid, act[i], skip[i], e[q][i], mD, mA, lmD, lmA, nd, na);
         if (i == ie && tid == te) a.edge[(size_t)j * T + t] = make_double2((double)nd + offD, (double)na + offA);
-        bpv[i] = bp;
       }
       // the neighbour's last state at t, for the step t + 1, relative to this block's offsets after this step
       if (tid == 0) {
@@ -234,18 +198,11 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_ker
 #pragma unroll
       for (int i = 0; i < SPT; ++i) e[q][i] = a.lp[(size_t)tn * V + lab[i]];
       ne[q] = eg[tn];
-      lmD = gam_align_wave_max(lmD);
-      lmA = gam_align_wave_max(lmA);
+      gam_trellis_wm_publish(wm, cur, lane, wave, lmD, lmA);
 #pragma unroll
       for (int i = 0; i < SPT; ++i) {
-        const unsigned long long m1 = __ballot(bpv[i] & 1u), m2 = __ballot(bpv[i] >> 1);
         const int cl = i * nw + wave, c = j * (sb >> 6) + cl;
-        if (lane == 0 && cl < (sb >> 6) && c < a.nchunk)
-          a.bp[(size_t)t * a.nchunk + c] = make_uint4((unsigned)m1, (unsigned)(m1 >> 32), (unsigned)m2, (unsigned)(m2 >> 32));
-      }
-      if (lane == 0) {
-        wm[(cur * 2) * 16 + wave] = lmD;
-        wm[(cur * 2 + 1) * 16 + wave] = lmA;
+        gam_ctc_bp_pack(bpv[i], lane == 0 && cl < (sb >> 6) && c < a.nchunk, a.bp + ((size_t)t * a.nchunk + c));
       }
       __syncthreads();
     }
@@ -286,13 +243,11 @@ __global__ __launch_bounds__(64) void gam_ctc_align_long_backtrack_kernel(GamAli
         a2 = e.y;
       }
     }
-    int s = S - 1;
-    double best = d1;
-    if (d2 > best) { best = d2; s = S - 2; }
-    const double M = fmax(a1, a2);
-    const bool found = best > -INFINITY;
+    int s;
+    double best, ll;
+    const bool found = gam_ctc_end<double>(S, d1, d2, a1, a2, s, best, ll);
     *a.score = found ? best : -INFINITY;
-    *a.loglik = found && M > -INFINITY ? M + log(exp(a1 - M) + exp(a2 - M)) : -INFINITY;
+    *a.loglik = ll;
     *a.status = found ? 1 : 0;
     a.ctrl[2] = found ? 1 : 0;
     start[0] = s;
@@ -315,9 +270,7 @@ __global__ __launch_bounds__(64) void gam_ctc_align_long_backtrack_kernel(GamAli
       if (lane == i) mine = s;
       if (tb - i == 0) break;
       const uint4 w = bpl[i * 3 + (c0 - (s >> 6))];
-      const int sh = s & 31;
-      const unsigned lo = (s & 32) ? w.y : w.x, hi = (s & 32) ? w.w : w.z;
-      s -= (int)(((lo >> sh) & 1u) | (((hi >> sh) & 1u) << 1));
+      s -= gam_ctc_bp_step(w, s);
     }
     if (lane < n) a.path[t] = mine;
     __syncthreads();
@@ -340,11 +293,5 @@ __global__ __launch_bounds__(256) void gam_ctc_align_long_outputs_kernel(GamAlig
     return;
   }
   if (idx >= T) return;
-  const int t = (int)idx, s = a.path[t];
-  a.frame_labels[t] = (s & 1) ? a.targets[(s - 1) >> 1] : a.V - 1;
-  if (s & 1) {
-    const int u = (s - 1) >> 1;
-    if (t == 0 || a.path[t - 1] != s) a.tok_first[u] = t;
-    if (t == T - 1 || a.path[t + 1] != s) a.tok_last[u] = t;
-  }
+  a.frame_labels[idx] = gam_ctc_frame_out(a.path, (int)idx, T, a.targets, a.V - 1, a.tok_first, a.tok_last);
 }

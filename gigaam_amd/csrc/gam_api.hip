@@ -1467,18 +1467,19 @@ static int ctc_align_launch(gam_handle* h, const float* lp, const int32_t* enc_l
   if (sm > GAM_ALIGN_LDS_MAX) return fail(h, -1, "CTC alignment: T'=%lld x Umax=%d needs %zu bytes of LDS", (long long)Tp, Umax, sm);
   GamAlignArgs a;
   a.lp = lp; a.enc_len = enc_len; a.targets = targets; a.target_len = target_len;
-  a.Tp = (int)Tp; a.V = V; a.Umax = Umax; a.spt = spt; a.nchunk = nchunk; a.bp_glob = nullptr;
+  a.Tp = (int)Tp; a.V = V; a.Umax = Umax; a.nchunk = nchunk; a.bp_glob = nullptr;
   a.frame_labels = frame_labels; a.tok_first = tok_first; a.tok_last = tok_last; a.score = score; a.loglik = loglik; a.status = status;
   if (!bp_lds) {
     if (int r = ensure(h, h->align_bp, (size_t)B * Tp * nchunk * 4 + 64)) return r;
     a.bp_glob = reinterpret_cast<uint4*>(h->align_bp.p);
   }
-  static std::atomic<unsigned long long> lds_set[2];
-  const void* kern = bp_lds ? (const void*)gam_ctc_align_kernel<true> : (const void*)gam_ctc_align_kernel<false>;
-  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds(kern, GAM_ALIGN_LDS_MAX, lds_set[bp_lds ? 1 : 0]));
+  static std::atomic<unsigned long long> lds_set[6];
+  const int which = (bp_lds ? 3 : 0) + (spt - 1);
+  void (*const kerns[6])(GamAlignArgs) = {gam_ctc_align_kernel<false, 1>, gam_ctc_align_kernel<false, 2>, gam_ctc_align_kernel<false, 3>,
+                                          gam_ctc_align_kernel<true, 1>, gam_ctc_align_kernel<true, 2>, gam_ctc_align_kernel<true, 3>};
+  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds((const void*)kerns[which], GAM_ALIGN_LDS_MAX, lds_set[which]));
   ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * smax * 4.0);
-  if (bp_lds) hipLaunchKernelGGL(gam_ctc_align_kernel<true>, dim3(B), dim3(nt), sm, s, a);
-  else hipLaunchKernelGGL(gam_ctc_align_kernel<false>, dim3(B), dim3(nt), sm, s, a);
+  hipLaunchKernelGGL(kerns[which], dim3(B), dim3(nt), sm, s, a);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

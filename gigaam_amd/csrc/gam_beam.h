@@ -28,7 +28,7 @@
 //                            itself into LDS (blank and repeat terms); the row of frame t + 2 is loaded meanwhile.  -- barrier B
 // Prefix identity: (length, 64-bit hash), gam_search.h.
 // Precision: every frame subtracts the best kept rank from p_b / p_nb and adds it to an fp64 offset, so the stored values stay
-// O(one frame's log-probs); the log-add-exp runs on the hardware transcendentals (gam_align_exp / gam_align_log, ~1 ulp).
+// O(one frame's log-probs); the log-add-exp runs on the hardware transcendentals (gam_fast_exp / gam_fast_log, ~1 ulp).
 // Prefix trie: only surviving extensions (and re-entries) create a node {parent, token << 13 | frame}, in a grow-only handle workspace of
 // B x T' x W nodes (at most W per frame).  The backtrack runs in the same kernel and writes ids / frames / count / score / logp.
 // Limits (host errors beyond them): those of gam_search.h and T' <= GAM_ALIGN_MAX_T.

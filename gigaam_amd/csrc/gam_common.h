@@ -37,6 +37,28 @@ __device__ __forceinline__ float gam_wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// Log-domain exp / log on the hardware transcendentals (v_exp_f32 / v_log_f32, ~1 ulp).  In a forward recursion's log-sum-exp the
+// arguments of exp are <= 0 and the sum of the terms lies in [1, 3], so each step adds an absolute error of ~1e-7 (measured loglik
+// errors: DESIGN.md section 4.8).
+__device__ __forceinline__ float gam_fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
+__device__ __forceinline__ float gam_fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.693147180559945309f; }
+
+// Wave maximum by DPP (row quad-perms and mirrors, then the two GFX9 row broadcasts): a per-step renormalisation needs two of
+// these on the sequential path, where the ds_bpermute chain of gam_wave_max costs six LDS round trips each.  Result in lane 63.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float gam_dpp_max(float v) {
+  const int o = __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
+  return fmaxf(v, __int_as_float(o));
+}
+__device__ __forceinline__ float gam_dpp_wave_max(float v) {
+  v = gam_dpp_max<0xb1, 0xf>(v);    // quad_perm [1,0,3,2]
+  v = gam_dpp_max<0x4e, 0xf>(v);    // quad_perm [2,3,0,1]
+  v = gam_dpp_max<0x141, 0xf>(v);   // row_half_mirror
+  v = gam_dpp_max<0x140, 0xf>(v);   // row_mirror: every lane holds its row's maximum
+  v = gam_dpp_max<0x142, 0xa>(v);   // row_bcast:15 -> rows 1, 3
+  v = gam_dpp_max<0x143, 0xc>(v);   // row_bcast:31 -> rows 2, 3
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
 // sigmoid / SiLU on the hardware transcendentals (v_exp_f32 = 2^x, v_rcp_f32; ~1 ulp each):
 // 4 VALU instructions instead of ~40 for expf + IEEE divide -- the SiLU epilogue of the
 // FFN-up GEMM was costing as much as its main loop.

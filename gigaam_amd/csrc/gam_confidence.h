@@ -40,7 +40,7 @@
 #define GAM_CF_MAX_V 1025
 #define GAM_CF_NV 4             // class tiles of the node kernel in flight
 
-// Sums by DPP, the pattern of gam_align_wave_max.  Lanes a step does not write receive 0 (not their own value: that would double it).
+// Sums by DPP, the pattern of gam_dpp_wave_max.  Lanes a step does not write receive 0 (not their own value: that would double it).
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float gam_conf_dpp_add(float v) {
   return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
@@ -58,10 +58,10 @@ __device__ __forceinline__ float gam_conf_wave_sum(float v) {    // uniform: the
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 __device__ __forceinline__ float gam_conf_row_max(float v) {     // every lane: the maximum of its 16-lane row
-  v = gam_align_dpp_max<0xb1, 0xf>(v);
-  v = gam_align_dpp_max<0x4e, 0xf>(v);
-  v = gam_align_dpp_max<0x141, 0xf>(v);
-  return gam_align_dpp_max<0x140, 0xf>(v);
+  v = gam_dpp_max<0xb1, 0xf>(v);
+  v = gam_dpp_max<0x4e, 0xf>(v);
+  v = gam_dpp_max<0x141, 0xf>(v);
+  return gam_dpp_max<0x140, 0xf>(v);
 }
 __device__ __forceinline__ unsigned long long gam_conf_row_max(unsigned long long v) {
   v = gam_beam_dpp_max<0xb1, 0xf>(v);
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void gam_ctc_conf_stats_kernel(GamConfStatArgs
     const unsigned long long k = ((unsigned long long)gam_beam_ord(x) << 32) | (unsigned)(0xffffffffu - (unsigned)v);
     key = k > key ? k : key;          // equal values: the lower id holds the larger key
     if (a.measure == GAM_CF_ENTROPY) {
-      const float p = gam_align_exp(x);
+      const float p = gam_fast_exp(x);
       sum += p > 0.f ? p * x : 0.f;
     }
   }
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void gam_ctc_conf_stats_kernel(GamConfStatArgs
   }
   if (active && li == 0) {
     const int am = (int)(0xffffffffu - (unsigned)key);
-    const float st = a.measure == GAM_CF_ENTROPY ? 1.0f + sum * a.inv_lnv : gam_align_exp(gam_beam_unord((unsigned)(key >> 32)));
+    const float st = a.measure == GAM_CF_ENTROPY ? 1.0f + sum * a.inv_lnv : gam_fast_exp(gam_beam_unord((unsigned)(key >> 32)));
     a.stats[row] = make_int2(am, __float_as_int(gam_conf_clamp01(st)));
   }
 }
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void gam_ctc_conf_agg_kernel(GamConfAggArgs a)
       continue;
     }
     const int id = y[u], f0 = fr[u], lim = u + 1 < U ? fr[u + 1] : T;
-    float acc = a.measure == GAM_CF_PROB ? gam_conf_clamp01(gam_align_exp(a.lp[((size_t)b * a.Tp + f0) * a.V + id]))
+    float acc = a.measure == GAM_CF_PROB ? gam_conf_clamp01(gam_fast_exp(a.lp[((size_t)b * a.Tp + f0) * a.V + id]))
                                          : __int_as_float(st[f0].y);
     int n = 1;
     for (int f = f0 + 1; f < lim; ++f, ++n) {
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(64) void gam_rnnt_conf_nodes_kernel(GamRnntConfArgs
         for (int r = 0; r < 4; ++r) {
           const float x = acc[j][r] + bo;
           const float nm = fmaxf(m[r], x);
-          const float sc = gam_align_exp(m[r] - nm), e = gam_align_exp(x - nm);
+          const float sc = gam_fast_exp(m[r] - nm), e = gam_fast_exp(x - nm);
           s[r] = s[r] * sc + e;
           ax[r] = ax[r] * sc + e * x;
           m[r] = nm;
@@ -315,14 +315,14 @@ __global__ __launch_bounds__(64) void gam_rnnt_conf_nodes_kernel(GamRnntConfArgs
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float M = gam_conf_row_max(m[r]);
-    const float sc = m[r] > -INFINITY ? gam_align_exp(m[r] - M) : 0.f;
+    const float sc = m[r] > -INFINITY ? gam_fast_exp(m[r] - M) : 0.f;
     const float S = gam_conf_row_sum(s[r] * sc);
     const float A = gam_conf_row_sum(ax[r] * sc);
     const float X = gam_conf_row_max(xt[r]);
-    const float lns = gam_align_log(S);
+    const float lns = gam_fast_log(S);
     const int u = u0 + 4 * lg4 + r;
     if (li == 0 && u < U) {
-      const float c = a.measure == GAM_CF_ENTROPY ? 1.0f - (M + lns - A / S) * a.inv_lnv : gam_align_exp(X - M - lns);
+      const float c = a.measure == GAM_CF_ENTROPY ? 1.0f - (M + lns - A / S) * a.inv_lnv : gam_fast_exp(X - M - lns);
       a.conf[(size_t)b * a.cap + u] = gam_conf_clamp01(c);
     }
   }

@@ -33,7 +33,7 @@
 //  3. gam_rnnt_lattice_dp_kernel -- one workgroup per utterance sweeps the anti-diagonals d = t + u with ONE barrier per step;
 //     thread u owns column u: its blank predecessor is its own value of the step before (a register), its emission predecessor
 //     comes from thread u - 1 through LDS (double-buffered).  Viterbi max and forward log-sum-exp in the same sweep; every step
-//     subtracts the previous diagonal's maximum (of each separately) into an fp64 offset, as gam_align.h does.  Backpointers: 1 bit
+//     subtracts the previous diagonal's maximum (of each separately) into an fp64 offset: gam_trellis.h's frame.  Backpointers: 1 bit
 //     per node as one 64-bit ballot per (diagonal, 64 columns); in LDS while (T' + Umax) x ceil((Umax + 1) / 64) x 8 B fit beside
 //     the rest (BP_LDS), else in a global scratch buffer the handle owns.  The lattice values of diagonal d + GAM_RA_PF are loaded
 //     while diagonal d is computed.  The backtrack runs in the same kernel (the thread that owns column U walks the bits).
@@ -44,6 +44,7 @@
 #pragma once
 #include "gam_search.h"
 #include "gam_decode.h"
+#include "gam_trellis.h"
 
 #define GAM_RA_MAX_U 1024
 #define GAM_RA_MAX_T 8192
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(256) void gam_rnnt_lattice_kernel(GamRnntLatArgs a)
         for (int r = 0; r < 4; ++r) {
           const float x = acc[rt][r] + bo;
           const float nm = fmaxf(m[rt][r], x);
-          s[rt][r] = s[rt][r] * gam_align_exp(m[rt][r] - nm) + gam_align_exp(x - nm);
+          s[rt][r] = s[rt][r] * gam_fast_exp(m[rt][r] - nm) + gam_fast_exp(x - nm);
           m[rt][r] = nm;
           if (v == V - 1) xb[rt][r] = x;
           if (v == yv[r]) xe[rt][r] = x;
@@ -241,10 +242,10 @@ __global__ __launch_bounds__(256) void gam_rnnt_lattice_kernel(GamRnntLatArgs a)
       float M = m[rt][r];
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
-      float S = m[rt][r] > -INFINITY ? s[rt][r] * gam_align_exp(m[rt][r] - M) : 0.f;
+      float S = m[rt][r] > -INFINITY ? s[rt][r] * gam_fast_exp(m[rt][r] - M) : 0.f;
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) S += __shfl_xor(S, o, 64);
-      const float lse = M + gam_align_log(S);
+      const float lse = M + gam_fast_log(S);
       const int u = u0 + 4 * lg4 + r;
       if (t < T && u <= U) {
         const size_t o2 = (((size_t)b * a.Tp + t) * U1 + u) * 2;
@@ -273,7 +274,7 @@ struct GamRnntDpArgs {
 // LDS bytes of one workgroup (host and device carve it the same way)
 static inline size_t gam_ra_dp_lds_bytes(bool bp_lds, int Tp, int Umax, int nchunk, int spt, int nt) {
   const size_t sp = ((size_t)spt * nt + 1 + 3) & ~(size_t)3;
-  return (bp_lds ? (((size_t)(Tp + Umax) * nchunk * 8 + 15) & ~(size_t)15) : 0) + 16 * sp + 64 * sizeof(float) + 64;
+  return (bp_lds ? (((size_t)(Tp + Umax) * nchunk * 8 + 15) & ~(size_t)15) : 0) + 16 * sp + GAM_TRELLIS_WM * sizeof(float) + 64;
 }
 
 template <bool BP_LDS, int SPT>   // SPT columns per thread: Umax + 1 <= SPT * blockDim
@@ -287,8 +288,8 @@ __global__ __launch_bounds__(GAM_RA_MAX_NT) void gam_rnnt_lattice_dp_kernel(GamR
   unsigned long long* bpl = reinterpret_cast<unsigned long long*>(smem);
   float* XD = reinterpret_cast<float*>(smem + (BP_LDS ? (((size_t)(Tp + a.Umax) * a.nchunk * 8 + 15) & ~(size_t)15) : 0));   // XD[buf][1 + u]: node + le
   float* XA = XD + 2 * sp;
-  float* wm = XA + 2 * sp;                       // per-wave maxima of the step: wm[(buf * 2 + {0: d, 1: a}) * 16 + wave]
-  int* misc = reinterpret_cast<int*>(wm + 64);   // [1] bad id, [2] path found
+  float* wm = XA + 2 * sp;                       // per-wave maxima of the step (gam_trellis.h)
+  int* misc = reinterpret_cast<int*>(wm + GAM_TRELLIS_WM);   // [1] bad id, [2] path found
 
   int T = a.enc_len[b];
   T = T < 0 ? 0 : (T > Tp ? Tp : T);
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(GAM_RA_MAX_NT) void gam_rnnt_lattice_dp_kernel(GamR
     XD[k] = -INFINITY;
     XA[k] = -INFINITY;
   }
-  if (tid < 64) wm[tid] = -INFINITY;
+  gam_trellis_wm_init(wm, tid);
   __syncthreads();
 
   // Lattice loads are unconditional (indices clamped into the utterance): a load under a branch would serialise the prefetch
@@ -359,16 +360,8 @@ __global__ __launch_bounds__(GAM_RA_MAX_NT) void gam_rnnt_lattice_dp_kernel(GamR
       const float* XAp = XA + prv * sp;
       float* XDc = XD + cur * sp + 1;
       float* XAc = XA + cur * sp + 1;
-      float mD = -INFINITY, mA = -INFINITY;
-#pragma unroll
-      for (int w = 0; w < 16; w += 4) {   // (all 16 slots: those of absent waves hold -inf)
-        const float4 xd = *reinterpret_cast<const float4*>(wm + (prv * 2) * 16 + w);
-        const float4 xa = *reinterpret_cast<const float4*>(wm + (prv * 2 + 1) * 16 + w);
-        mD = fmaxf(mD, fmaxf(fmaxf(xd.x, xd.y), fmaxf(xd.z, xd.w)));
-        mA = fmaxf(mA, fmaxf(fmaxf(xa.x, xa.y), fmaxf(xa.z, xa.w)));
-      }
-      if (mD == -INFINITY) mD = 0.f;
-      if (mA == -INFINITY) mA = 0.f;
+      float mD, mA;
+      gam_trellis_wm_read(wm, prv, mD, mA);
       offD += (double)mD;
       offA += (double)mA;
       float lmD = -INFINITY, lmA = -INFINITY;
@@ -390,7 +383,7 @@ __global__ __launch_bounds__(GAM_RA_MAX_NT) void gam_rnnt_lattice_dp_kernel(GamR
               nd = (bp ? pe : pb) - mD;
               const float a0 = bA[i], a1 = XAp[u];
               const float M = fmaxf(a0, a1);
-              if (M > -INFINITY) na = (M - mA) + gam_align_log(gam_align_exp(a0 - M) + gam_align_exp(a1 - M));
+              if (M > -INFINITY) na = (M - mA) + gam_fast_log(gam_fast_exp(a0 - M) + gam_fast_exp(a1 - M));
             }
             lmD = fmaxf(lmD, nd);
             lmA = fmaxf(lmA, na);
@@ -406,8 +399,7 @@ __global__ __launch_bounds__(GAM_RA_MAX_NT) void gam_rnnt_lattice_dp_kernel(GamR
       // the diagonal d + PF replaces the one just used (its load is in flight during the next PF - 1 steps)
 #pragma unroll
       for (int i = 0; i < SPT; ++i) e[k][i] = node(d + GAM_RA_PF, i);
-      lmD = gam_align_wave_max(lmD);
-      lmA = gam_align_wave_max(lmA);
+      gam_trellis_wm_publish(wm, cur, lane, wave, lmD, lmA);
 #pragma unroll
       for (int i = 0; i < SPT; ++i) {
         const unsigned long long mk = __ballot(bpv[i]);
@@ -416,10 +408,6 @@ __global__ __launch_bounds__(GAM_RA_MAX_NT) void gam_rnnt_lattice_dp_kernel(GamR
           if (BP_LDS) bpl[(size_t)d * a.nchunk + c] = mk;
           else a.bp_glob[((size_t)b * (Tp + a.Umax) + d) * a.nchunk + c] = mk;
         }
-      }
-      if (lane == 0) {
-        wm[(cur * 2) * 16 + wave] = lmD;
-        wm[(cur * 2 + 1) * 16 + wave] = lmA;
       }
       __syncthreads();
     }

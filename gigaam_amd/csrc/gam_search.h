@@ -36,7 +36,7 @@
 // are compared: a collision is accepted (2^-64 per compare), as for hypotheses.  Limits: order <= 5.
 #pragma once
 #include <stddef.h>
-#include "gam_align.h"
+#include "gam_common.h"
 
 #define GAM_BEAM_MAX_W 32
 #define GAM_BEAM_MAX_V 1025
@@ -68,7 +68,7 @@ static_assert(sizeof(GamHwArgs) == 24 && offsetof(GamHwArgs, beta) == 20 && size
 __device__ __forceinline__ float gam_beam_lse(float a, float b) {
   const float m = fmaxf(a, b);
   if (m == -INFINITY) return -INFINITY;
-  return m + gam_align_log(1.0f + gam_align_exp(fminf(a, b) - m));
+  return m + gam_fast_log(1.0f + gam_fast_exp(fminf(a, b) - m));
 }
 __device__ __forceinline__ unsigned gam_beam_ord(float f) {     // float -> unsigned, order preserving
   const unsigned u = __float_as_uint(f);
@@ -82,7 +82,7 @@ __device__ __forceinline__ unsigned long long gam_beam_key(unsigned rank_ord, in
   return ((unsigned long long)rank_ord << 32) | ((unsigned)(0xffff - key) << 16) | (unsigned)q;
 }
 
-// Wave maximum of a 64-bit key by DPP (the pattern of gam_align_wave_max on both halves), read from lane 63: uniform.
+// Wave maximum of a 64-bit key by DPP (the pattern of gam_dpp_wave_max on both halves), read from lane 63: uniform.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ unsigned long long gam_beam_dpp_max(unsigned long long v) {
   const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);

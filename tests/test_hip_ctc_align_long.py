@@ -159,17 +159,21 @@ def test_planted_path_beyond_the_one_workgroup_limits(V):
 
 
 # ---- inside the limits of the one-workgroup kernel: every check of its own test, and no larger an error
-@pytest.mark.parametrize("V,Tp", [(34, 160), (257, 400)])
-@pytest.mark.parametrize("kind", ["peaked", "flat"])
-def test_long_op_matches_float64_reference_and_the_one_workgroup_kernel(V, Tp, kind):
-    eng = _op_engine()
+def _plan_case(V, Tp, kind):
+    """The plan of test_op_align_matches_float64_reference -- (U, repeats, T), None = exactly minimal T -- as (lp, enc_len, targets)."""
     rng = np.random.default_rng(V * 7 + Tp + (1 if kind == "flat" else 0))
-    # the plan of test_op_align_matches_float64_reference: (U, repeats, T), None = exactly minimal T
     plan = [(0, 0, Tp), (1, 0, Tp // 3), (12, 4, Tp), (40, 10, None), (Tp // 4, 3, Tp - 7), (Tp // 2, 0, Tp),
             (0, 0, 0), (30, 5, Tp // 2)]
     targets = [_target(rng, U, V, r) for U, r, _ in plan]
     enc_len = [T if T is not None else len(y) + sum(y[i] == y[i - 1] for i in range(1, len(y))) for (_, _, T), y in zip(plan, targets)]
-    lp = _log_probs(rng, len(plan), Tp, V, kind)
+    return _log_probs(rng, len(plan), Tp, V, kind), enc_len, targets
+
+
+@pytest.mark.parametrize("V,Tp", [(34, 160), (257, 400)])
+@pytest.mark.parametrize("kind", ["peaked", "flat"])
+def test_long_op_matches_float64_reference_and_the_one_workgroup_kernel(V, Tp, kind):
+    eng = _op_engine()
+    lp, enc_len, targets = _plan_case(V, Tp, kind)
     old = _run_op(eng, lp, enc_len, targets)
     errs, worst = {}, {"long_score": 0.0, "long_loglik": 0.0, "old_score": 0.0, "old_loglik": 0.0}
     with _tiling(eng, 64, 16):
@@ -188,6 +192,34 @@ def test_long_op_matches_float64_reference_and_the_one_workgroup_kernel(V, Tp, k
     print(f"V{V} T{Tp} {kind}", worst)
     for k in ("score", "loglik"):
         assert worst[f"long_{k}"] <= MARGIN * worst[f"old_{k}"] + MARGIN_FLOOR, (k, worst)
+
+
+@pytest.mark.parametrize("kind", ["peaked", "flat"])
+def test_single_tile_long_op_is_the_one_workgroup_kernel(kind):
+    """One block and one tile (sb = 192 >= the largest S = 161, tt = 400 >= T): no edge conversion happens, and the two kernels run
+    the same frame step (gam_trellis.h) on the same numbers.  So paths and statuses are equal, the Viterbi score rounded to fp32 is
+    the one-workgroup kernel's bit for bit, and loglik differs only by the final two-term log-sum-exp (float there, double here) on
+    running values of O(10): within MARGIN_FLOOR plus one rounding of the total to fp32."""
+    eng = _op_engine()
+    lp, enc_len, targets = _plan_case(34, 160, kind)
+    old = _run_op(eng, lp, enc_len, targets)
+    worst = 0.0
+    with _tiling(eng, 192, 400):
+        for b, y in enumerate(targets):
+            T, U = enc_len[b], len(y)
+            h = _run_long(eng, lp[b][:T], y)
+            assert int(h["status"][0]) == int(old["status"][b]), b
+            assert np.array_equal(h["frame_labels"][0][:T], old["frame_labels"][b][:T]), b
+            assert np.array_equal(h["tok_first"][0][:U], old["tok_first"][b][:U]), b
+            assert np.array_equal(h["tok_last"][0][:U], old["tok_last"][b][:U]), b
+            if int(old["status"][b]) != 1 or T == 0:
+                continue
+            assert np.float32(h["score"][0]).tobytes() == np.float32(old["score"][b]).tobytes(), (b, h["score"][0], old["score"][b])
+            ll = np.float32(old["loglik"][b])
+            d = abs(float(np.float32(h["loglik"][0])) - float(ll))
+            worst = max(worst, d)
+            assert d <= MARGIN_FLOOR + float(np.spacing(np.float32(abs(ll)))), (b, h["loglik"][0], ll)
+    print(f"single tile {kind}: largest loglik difference {worst:.3g}")
 
 
 def test_long_op_exact_ties_follow_the_tie_rule():
