@@ -505,6 +505,14 @@ struct DecodeScope {
   }
 };
 
+// The preamble of a decode-class entry point: the stream `s`, the null-handle check, the handle's device made current (before the scope:
+// its event belongs to that device) and the DecodeScope.  Checks an entry point makes BEFORE the scope stand in front of it.
+#define GAM_DECODE_ENTRY(h, stream)      \
+  hipStream_t s = (hipStream_t)(stream); \
+  if (!(h)) return -1;                   \
+  HIPCHK(h, hipSetDevice((h)->device));  \
+  DecodeScope ds(h, s)
+
 }  // namespace
 
 // ===================================================================================
@@ -1418,25 +1426,34 @@ static int ctc_logits(gam_handle* h, const float* encoded, int B, int64_t Tp, hi
   return gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE);
 }
 
-int gam_ctc_head(gam_handle* h, const float* encoded, int B, int64_t Tp, float* log_probs, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+// The encoder half of the RNN-T joint for a whole batch: encoded [B, D, Tp] -> h->encp [B * Tp, JH] = W_enc f + b_enc.
+static int rnnt_encp(gam_handle* h, const float* encoded, int B, int64_t Tp, hipStream_t s) {
+  const int D = h->cfg.d_model, JH = h->cfg.joint_hidden;
+  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
+  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
+  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
+  return gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE);
+}
+
+// The CTC head's log-probs [B * Tp, V]: the logits GEMM into h->logits, then the log-softmax into `out` -- NULL: in place on h->logits
+// (each row is read whole by its wave before that wave writes it).
+static int ctc_log_probs(gam_handle* h, const float* encoded, int B, int64_t Tp, float* out, hipStream_t s) {
   if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
   const int V = h->cfg.num_classes, rows = (int)(B * Tp);
   ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
-  hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, log_probs, rows, V);
+  hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, out ? out : h->logits.p, rows, V);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
+int gam_ctc_head(gam_handle* h, const float* encoded, int B, int64_t Tp, float* log_probs, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  return ctc_log_probs(h, encoded, B, Tp, log_probs, s);
+}
+
 int gam_ctc_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int32_t* ids,
                    int32_t* frames, int32_t* counts, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
   const int V = h->cfg.num_classes;
   const size_t sm = ((size_t)Tp + GAM_CTC_NT / 64 + 8) * sizeof(int);
@@ -1487,20 +1504,11 @@ static int ctc_align_launch(gam_handle* h, const float* lp, const int32_t* enc_l
 int gam_ctc_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
                   const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
                   float* loglik, int32_t* status, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (Tp > GAM_ALIGN_MAX_T || Umax < 0 || Umax > GAM_ALIGN_MAX_U)
     return fail(h, -1, "CTC alignment: T'=%lld / Umax=%d beyond the limits (%d / %d)", (long long)Tp, Umax, GAM_ALIGN_MAX_T, GAM_ALIGN_MAX_U);
-  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
-  const int V = h->cfg.num_classes, rows = (int)(B * Tp);
-  {
-    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
-    // in place: each row is read whole by its wave before that wave writes it
-    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (int r = ctc_log_probs(h, encoded, B, Tp, nullptr, s)) return r;
+  const int V = h->cfg.num_classes;
   return ctc_align_launch(h, h->logits.p, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score,
                           loglik, status, s);
 }
@@ -1508,10 +1516,7 @@ int gam_ctc_align(gam_handle* h, const float* encoded, const int32_t* enc_len, i
 int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
                      const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
                      float* loglik, int32_t* status, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return ctc_align_launch(h, log_probs, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score, loglik,
                           status, s);
 }
@@ -1520,10 +1525,7 @@ int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_l
 // one stream.  Decode class: the workspace is the handle's.
 int gam_op_ctc_align_long(gam_handle* h, const float* log_probs, int64_t T, int V, const int32_t* targets, int U, int32_t* frame_labels,
                           int32_t* tok_first, int32_t* tok_last, double* score, double* loglik, int32_t* status, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (T < 0 || T > 2147483647ll || V < 2 || U < 0 || U > (1 << 30) - 1)
     return fail(h, -1, "long CTC alignment: bad shape T=%lld V=%d U=%d", (long long)T, V, U);
   if (!score || !loglik || !status || (T > 0 && (!log_probs || !frame_labels)) || (U > 0 && (!targets || !tok_first || !tok_last)))
@@ -1693,31 +1695,18 @@ static int ctc_kws_launch(gam_handle* h, const float* lp, const int32_t* enc_len
 
 int gam_ctc_kws(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int max_hits, int32_t* hit_frames,
                 float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (!h->finalized) return fail(h, -1, "CTC head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_CTC || !h->has_head) return fail(h, -1, "model has no CTC head");
   const int V = h->cfg.num_classes;
   if (int r = ctc_kws_check(h, B, Tp, V, max_hits, !encoded || !enc_len || !hit_frames || !hit_score || !n_hits)) return r;
-  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
-  const int rows = (int)(B * Tp);
-  {
-    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
-    // in place: each row is read whole by its wave before that wave writes it (as gam_ctc_align)
-    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (int r = ctc_log_probs(h, encoded, B, Tp, nullptr, s)) return r;
   return ctc_kws_launch(h, h->logits.p, enc_len, B, Tp, V, max_hits, hit_frames, hit_score, n_hits, dense_score, dense_start, s);
 }
 
 int gam_op_ctc_kws(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int max_hits,
                    int32_t* hit_frames, float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (int r = ctc_kws_check(h, B, Tp, V, max_hits, !log_probs || !enc_len || !hit_frames || !hit_score || !n_hits)) return r;
   return ctc_kws_launch(h, log_probs, enc_len, B, Tp, V, max_hits, hit_frames, hit_score, n_hits, dense_score, dense_start, s);
 }
@@ -1798,22 +1787,13 @@ static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_le
 // gam_ctc_beam / gam_ctc_beam_nbest: the CTC head, its log-softmax in place, the beam kernel.
 static int ctc_beam_run(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
                         int32_t* counts, float* score, float* logp, void* stream, bool nbest, int N, int32_t* n_hyp) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (Tp > GAM_ALIGN_MAX_T || W < 1 || W > GAM_BEAM_MAX_W)
     return fail(h, -1, "CTC beam search: T'=%lld / W=%d beyond the limits (%d / [1, %d])", (long long)Tp, W, GAM_ALIGN_MAX_T, GAM_BEAM_MAX_W);
   if (nbest)
     if (int r = nbest_check(h, "CTC beam search", W, N, n_hyp)) return r;
-  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
-  const int V = h->cfg.num_classes, rows = (int)(B * Tp);
-  {
-    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
-    // in place: each row is read whole by its wave before that wave writes it
-    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (int r = ctc_log_probs(h, encoded, B, Tp, nullptr, s)) return r;
+  const int V = h->cfg.num_classes;
   return ctc_beam_launch(h, h->logits.p, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s, nbest, N, n_hyp);
 }
 
@@ -1829,19 +1809,13 @@ int gam_ctc_beam_nbest(gam_handle* h, const float* encoded, const int32_t* enc_l
 
 int gam_op_ctc_beam_nbest(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int N,
                           int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return ctc_beam_launch(h, log_probs, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s, true, N, n_hyp);
 }
 
 int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
                     int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return ctc_beam_launch(h, log_probs, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s);
 }
 
@@ -2007,15 +1981,10 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
   if (B <= 0 || Tp <= 0 || max_symbols <= 0) return fail(h, -1, "bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   const gam_config& c = h->cfg;
-  const int D = c.d_model, JH = c.joint_hidden;
-  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
-  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
-  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
-  if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  const int JH = c.joint_hidden;
+  if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
   GamRnntArgs a;
   memset(&a, 0, sizeof a);
   a.encp = h->encp.p; a.enc_len = enc_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wpred_t = h->jn_pred_t;
@@ -2189,20 +2158,13 @@ static int rnnt_beam_run(gam_handle* h, const float* encoded, const int32_t* enc
                          int32_t* n_hyp) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (B <= 0 || Tp <= 0 || Tp > GAM_RB_MAX_T || W < 1 || W > GAM_BEAM_MAX_W || max_symbols < 1 || max_symbols > GAM_RB_MAX_S)
     return fail(h, -1, "RNN-T beam search: B=%d T'=%lld / W=%d / S=%d beyond the limits (%d / [1, %d] / [1, %d])", B, (long long)Tp, W,
                 max_symbols, GAM_RB_MAX_T, GAM_BEAM_MAX_W, GAM_RB_MAX_S);
   if (nbest)
     if (int r = nbest_check(h, "RNN-T beam search", W, N, n_hyp)) return r;
-  const gam_config& c = h->cfg;
-  const int D = c.d_model, JH = c.joint_hidden;
-  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
-  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
-  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
-  if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
   return rnnt_beam_launch(h, h->encp.p, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s, nbest, N, n_hyp);
 }
 
@@ -2220,9 +2182,7 @@ int gam_op_rnnt_beam_nbest(gam_handle* h, const float* encp, const int32_t* enc_
                            int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s, true, N, n_hyp);
 }
 
@@ -2230,9 +2190,7 @@ int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, i
                      int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s);
 }
 
@@ -2266,6 +2224,27 @@ static int rnnt_lattice_dp_launch(gam_handle* h, const float2* lat, const int32_
   return 0;
 }
 
+// The predictor half of the joint for given label sequences: the teacher-forced predictor g = h->ra_g [B, Umax + 1, H] (gam_rnnt_align.h),
+// then pp = W_pred g + b_pred = h->ra_pp [B, Umax + 1, JH].  The caller has checked H, JH and L against the kernel's limits.
+static int rnnt_tf_pp(gam_handle* h, const int32_t* targets, const int32_t* target_len, int B, int Umax, hipStream_t s) {
+  const gam_config& c = h->cfg;
+  const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden, L = c.pred_rnn_layers, u1 = Umax + 1;
+  if (int r = ensure(h, h->ra_g, (size_t)B * u1 * H + 64)) return r;
+  if (int r = ensure(h, h->ra_pp, (size_t)B * u1 * JH + 64)) return r;
+  {
+    GamRnntTfArgs a;
+    a.targets = targets; a.target_len = target_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x;
+    a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x; a.g = h->ra_g.p; a.Umax = Umax; a.V = V; a.H = H; a.L = L;
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)B * u1 * L * 8.0 * H * H * 4.0);
+    const size_t sm = gam_ra_tf_lds_bytes(H, L);
+    if (4 * H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<5>, dim3(B), dim3(256), sm, s, a);
+    else hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<8>, dim3(B), dim3(256), sm, s, a);
+    HIPCHK(h, hipGetLastError());
+  }
+  GamGemmArgs gp = gemm_args(h->ra_g.p, H, h->jn_pred_w, h->jn_pred_b, h->ra_pp.p, JH, B * u1, JH, H);
+  return gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_DECODE);
+}
+
 static int rnnt_align_shape_check(gam_handle* h, int B, int64_t Tp, int Umax, int V, bool null_buf) {
   if (B <= 0 || Tp <= 0 || V < 2) return fail(h, -1, "RNN-T alignment: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
   if (Tp > GAM_RA_MAX_T) return fail(h, -1, "RNN-T alignment: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_RA_MAX_T);
@@ -2293,21 +2272,8 @@ static int rnnt_align_launch(gam_handle* h, const float* encp, const int32_t* en
     return fail(h, -1, "RNN-T alignment: the lattice of one utterance (T'=%lld x %d nodes) takes %zu bytes, the workspace limit is %zu bytes",
                 (long long)Tp, u1, per, h->ra_ws_limit);
   const int nb = (int)std::min<size_t>((size_t)B, h->ra_ws_limit / per);
-  if (int r = ensure(h, h->ra_g, (size_t)B * u1 * H + 64)) return r;
-  if (int r = ensure(h, h->ra_pp, (size_t)B * u1 * JH + 64)) return r;
+  if (int r = rnnt_tf_pp(h, targets, target_len, B, Umax, s)) return r;
   if (int r = ensure(h, h->ra_lat, (size_t)nb * Tp * u1 * 2 + 64)) return r;
-  {
-    GamRnntTfArgs a;
-    a.targets = targets; a.target_len = target_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x;
-    a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x; a.g = h->ra_g.p; a.Umax = Umax; a.V = V; a.H = H; a.L = L;
-    ProfScope ps(h, s, GAM_PF_DECODE, (double)B * u1 * L * 8.0 * H * H * 4.0);
-    const size_t sm = gam_ra_tf_lds_bytes(H, L);
-    if (4 * H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<5>, dim3(B), dim3(256), sm, s, a);
-    else hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<8>, dim3(B), dim3(256), sm, s, a);
-    HIPCHK(h, hipGetLastError());
-  }
-  GamGemmArgs gp = gemm_args(h->ra_g.p, H, h->jn_pred_w, h->jn_pred_b, h->ra_pp.p, JH, B * u1, JH, H);
-  if (int r = gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
   static std::atomic<unsigned long long> lds_set;
   const size_t sml = gam_ra_lat_lds_bytes(JH);
   if (sml > 64 * 1024) HIPCHK(h, gam_set_max_lds((const void*)gam_rnnt_lattice_kernel, GAM_RA_LDS_MAX, lds_set));
@@ -2335,16 +2301,9 @@ int gam_rnnt_align(gam_handle* h, const float* encoded, const int32_t* enc_len, 
                    const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status, void* stream) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (int r = rnnt_align_shape_check(h, B, Tp, Umax, h->cfg.num_classes, !encoded)) return r;
-  const gam_config& c = h->cfg;
-  const int D = c.d_model, JH = c.joint_hidden;
-  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
-  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
-  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
-  if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
   return rnnt_align_launch(h, h->encp.p, enc_len, B, Tp, targets, target_len, Umax, tok_frame, score, loglik, status, nullptr, s);
 }
 
@@ -2353,19 +2312,14 @@ int gam_op_rnnt_align(gam_handle* h, const float* encp, const int32_t* enc_len, 
                       float* lattice_out, void* stream) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return rnnt_align_launch(h, encp, enc_len, B, Tp, targets, target_len, Umax, tok_frame, score, loglik, status, lattice_out, s);
 }
 
 int gam_op_rnnt_lattice_align(gam_handle* h, const float* lattice, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
                               const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
                               void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   if (int r = rnnt_align_shape_check(h, B, Tp, Umax, V,
                                      !lattice || !enc_len || !target_len || !score || !loglik || !status || (Umax > 0 && !tok_frame)))
     return r;
@@ -2422,37 +2376,25 @@ static int ctc_conf_launch(gam_handle* h, const float* lp, const int32_t* enc_le
 int gam_ctc_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                        const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
                        int32_t* status, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   if (!h) return -1;
   if (!h->finalized) return fail(h, -1, "CTC head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_CTC || !h->has_head) return fail(h, -1, "model has no CTC head");
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   const int V = h->cfg.num_classes;
   if (int r = conf_shape_check(h, "CTC", B, Tp, V, cap, 1 << 24, measure, agg, !encoded)) return r;
-  if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
-  const int rows = (int)(B * Tp);
-  {
-    ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 8.0);
-    // in place: each row is read whole by its wave before that wave writes it (as gam_ctc_align)
-    hipLaunchKernelGGL(gam_log_softmax_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, h->logits.p, h->logits.p, rows, V);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (int r = ctc_log_probs(h, encoded, B, Tp, nullptr, s)) return r;
   return ctc_conf_launch(h, h->logits.p, enc_len, B, Tp, V, ids, frames, counts, cap, measure, agg, conf, span, status, s);
 }
 
 int gam_op_ctc_confidence(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* ids,
                           const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
                           int32_t* status, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) return -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return ctc_conf_launch(h, log_probs, enc_len, B, Tp, V, ids, frames, counts, cap, measure, agg, conf, span, status, s);
 }
 
-// From the encoder projection encp [B, Tp, JH]: the rows are checked, then the teacher-forced predictor and its projection exactly as
-// rnnt_align_launch runs them (the decoded ids as targets), then the joint at the listed nodes.
+// From the encoder projection encp [B, Tp, JH]: the rows are checked, then the teacher-forced predictor and its projection (rnnt_tf_pp,
+// the decoded ids as targets), then the joint at the listed nodes.
 static int rnnt_conf_launch(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                             const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, hipStream_t s) {
   const gam_config& c = h->cfg;
@@ -2470,21 +2412,7 @@ static int rnnt_conf_launch(gam_handle* h, const float* encp, const int32_t* enc
     HIPCHK(h, hipGetLastError());
   }
   if (cap == 0) return 0;
-  const int u1 = cap + 1;
-  if (int r = ensure(h, h->ra_g, (size_t)B * u1 * H + 64)) return r;
-  if (int r = ensure(h, h->ra_pp, (size_t)B * u1 * JH + 64)) return r;
-  {
-    GamRnntTfArgs a;
-    a.targets = ids; a.target_len = counts; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x;
-    a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x; a.g = h->ra_g.p; a.Umax = cap; a.V = V; a.H = H; a.L = L;
-    ProfScope ps(h, s, GAM_PF_DECODE, (double)B * u1 * L * 8.0 * H * H * 4.0);
-    const size_t sm = gam_ra_tf_lds_bytes(H, L);
-    if (4 * H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<5>, dim3(B), dim3(256), sm, s, a);
-    else hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<8>, dim3(B), dim3(256), sm, s, a);
-    HIPCHK(h, hipGetLastError());
-  }
-  GamGemmArgs gp = gemm_args(h->ra_g.p, H, h->jn_pred_w, h->jn_pred_b, h->ra_pp.p, JH, B * u1, JH, H);
-  if (int r = gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  if (int r = rnnt_tf_pp(h, ids, counts, B, cap, s)) return r;
   GamRnntConfArgs a;
   a.encp = encp; a.predp = h->ra_pp.p; a.ids = ids; a.frames = frames; a.counts = counts; a.status = status; a.wout = h->jn_out_w;
   a.bout = h->jn_out_b; a.conf = conf; a.Tp = (int)Tp; a.cap = cap; a.V = V; a.JH = JH; a.measure = measure;
@@ -2499,16 +2427,9 @@ int gam_rnnt_confidence(gam_handle* h, const float* encoded, const int32_t* enc_
                         const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));     // (before the scope: its event belongs to the handle's device)
-  DecodeScope ds(h, s);
-  const gam_config& c = h->cfg;
-  if (int r = conf_shape_check(h, "RNN-T", B, Tp, c.num_classes, cap, GAM_RA_MAX_U, measure, GAM_CF_MEAN, !encoded)) return r;
-  const int D = c.d_model, JH = c.joint_hidden;
-  if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
-  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
-  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
-  if (int r = gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE)) return r;
+  GAM_DECODE_ENTRY(h, stream);
+  if (int r = conf_shape_check(h, "RNN-T", B, Tp, h->cfg.num_classes, cap, GAM_RA_MAX_U, measure, GAM_CF_MEAN, !encoded)) return r;
+  if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
   return rnnt_conf_launch(h, h->encp.p, enc_len, B, Tp, ids, frames, counts, cap, measure, conf, status, s);
 }
 
@@ -2516,9 +2437,7 @@ int gam_op_rnnt_confidence(gam_handle* h, const float* encp, const int32_t* enc_
                            const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream) {
   if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
   if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(h, hipSetDevice(h->device));
-  DecodeScope ds(h, s);
+  GAM_DECODE_ENTRY(h, stream);
   return rnnt_conf_launch(h, encp, enc_len, B, Tp, ids, frames, counts, cap, measure, conf, status, s);
 }
 

@@ -67,15 +67,58 @@ __device__ __forceinline__ float gam_sigmoid(float x) {
 }
 __device__ __forceinline__ float gam_silu(float x) { return x * gam_sigmoid(x); }
 __device__ __forceinline__ float gam_sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
-// The LSTM cell on the four gate pre-activations (nn.LSTM order i, f, g, o): (c, gates) -> (c', h'), the arithmetic of the cells in
-// gam_decode.h and gam_rnnt_beam.h as a function (gam_rnnt_align.h calls it).  Those kernels keep their inlined form: calling this
-// from them reordered their instruction streams (per-symbol disassembly against the parent).
+// The LSTM cell on the four gate pre-activations (nn.LSTM order i, f, g, o): (c, gates) -> (c', h').  Every predictor of the RNN-T
+// head calls it: gam_decode.h, gam_decode_cluster.h, gam_rnnt_beam.h, gam_rnnt_align.h.
+// c' = f c + i g is one product and one fused multiply-add, and WHICH product is fused is part of the result's last bit.  hipcc used
+// to choose by the order in which the inlined text happened to load c, so the kernels differ: the greedy decode, the cluster decode
+// and the per-step predictor fuse i g (FUSE_IG), the beam search and the teacher-forced predictor fuse f c.  Written out here so that
+// each keeps its bits whatever the compiler would pick.
+template <bool FUSE_IG>
 __device__ __forceinline__ void gam_lstm_cell(float gi, float gf, float gg_, float go, float c0, float& c2, float& h2) {
   const float ig = gam_sigmoid_exact(gi), fg = gam_sigmoid_exact(gf);
   const float gg = tanhf(gg_), og = gam_sigmoid_exact(go);
-  c2 = fg * c0 + ig * gg;
+  c2 = FUSE_IG ? fmaf(ig, gg, fg * c0) : fmaf(fg, c0, ig * gg);
   h2 = og * tanhf(c2);
 }
+
+// One k-group of the fp32 matrix core: the four v_mfma_f32_16x16x4_f32 of a 16-byte A fragment and a 16-byte B fragment into ONE
+// accumulator, in x, y, z, w order (the order is the sum's order: it is part of every result's bits).  Either operand may come as
+// four scalars (a fragment formed in registers, a weight column gathered element by element).
+__device__ __forceinline__ f32x4 gam_mfma4(f32x4 acc, f32x4 a, f32x4 b) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+  return acc;
+}
+__device__ __forceinline__ f32x4 gam_mfma4(f32x4 acc, float a0, float a1, float a2, float a3, f32x4 b) {
+  return gam_mfma4(acc, (f32x4){a0, a1, a2, a3}, b);
+}
+__device__ __forceinline__ f32x4 gam_mfma4(f32x4 acc, f32x4 a, const float (&b)[4]) {
+  return gam_mfma4(acc, a, (f32x4){b[0], b[1], b[2], b[3]});
+}
+
+// Argmax across WIDTH adjacent lanes (xor butterfly) with torch's tie rule: of equal maxima the smallest index wins.  In: each lane's
+// own (best, bi); out: every lane of the group holds the group's.
+template <int WIDTH>
+__device__ __forceinline__ void gam_first_max(float& best, int& bi) {
+#pragma unroll
+  for (int o = WIDTH / 2; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+}
+
+// 16-byte loads with the address space stated (the decode kernels hold no FLAT instruction: every pointer that may be LDS or global
+// gets two instantiations of its loop)
+__device__ __forceinline__ f32x4 gam_rc_lds4(const float* p) {
+  return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>((__attribute__((address_space(3))) const void*)(p));
+}
+__device__ __forceinline__ f32x4 gam_rc_glb4(const float* p) {
+  return *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>((__attribute__((address_space(1))) const void*)(p));
+}
+__device__ __forceinline__ float gam_rc_glb1(const float* p) { return *p; }
 
 typedef _Float16 gam_half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 gam_half8 __attribute__((ext_vector_type(8)));

@@ -285,10 +285,7 @@ __global__ __launch_bounds__(64) void gam_rnnt_conf_nodes_kernel(GamRnntConfArgs
       const f32x4 zf = gam_rc_lds4(zl + k0);
 #pragma unroll
       for (int j = 0; j < GAM_CF_NV; ++j) {
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.x, wf[j].x, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.y, wf[j].y, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.z, wf[j].z, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.w, wf[j].w, acc[j], 0, 0, 0);
+        acc[j] = gam_mfma4(acc[j], zf, wf[j]);
       }
 #pragma unroll
       for (int j = 0; j < GAM_CF_NV; ++j) wf[j] = wn[j];

@@ -69,12 +69,7 @@ __global__ __launch_bounds__(GAM_CTC_NT) void gam_ctc_greedy_kernel(const float*
         const float x = xr[v];
         if (x > best || (x == best && v < bi)) { best = x; bi = v; }
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-      }
+      gam_first_max<64>(best, bi);
       if (lane == 0) lab[t] = bi;
     }
   }
@@ -152,14 +147,54 @@ struct GamRnntArgs {
 #define GAM_RNNT_MAXV 2048
 #define GAM_RNNT_WIN 16
 
-// 16-byte loads with the address space stated (the decode kernels hold no FLAT instruction: every pointer that may be LDS or global gets two instantiations of its loop)
-__device__ __forceinline__ f32x4 gam_rc_lds4(const float* p) {
-  return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>((__attribute__((address_space(3))) const void*)(p));
+// One predictor layer step of a 256-thread workgroup (vectors in LDS, weights k-major [H][4H] in L2), nn.LSTM gate order i, f, g, o:
+//   gates = init + W_ih x + W_hh h;  (h2, c2) = cell(gates, c)
+// init is the row's start: the layer's gate_tab row (W_ih embed + b_ih + b_hh, layer 0: wih_t = null) or its summed bias.  h2 / c2
+// is the candidate state, apart from h / c.  Thread tid owns gate rows tid + 256 j, j < NR (4H <= 256 NR).
+// 16 k x NR rows of a weight matrix are in flight per thread: the step is L2-latency-bound, so the number of independent loads per
+// wait is what sets its duration.  Every load is unconditional (row index clamped): a per-element "load or 0" select makes hipcc
+// branch around each load and wait for it (cdna_hip_programming.md §5 trap c).  Each row's sum is ONE ascending-k fmaf chain, the
+// W_ih term before the W_hh term: the order is part of every decode's bits.  Ends on a barrier: h2 / c2 are visible to all threads.
+template <int NR>
+__device__ __forceinline__ void gam_rnnt_layer_step(const float* init, const float* wih_t, const float* x, const float* whh_t, const float* h,
+                                                    const float* c, float* h2, float* c2, float* gates, int H, int tid) {
+  float acc[NR];
+  int roff[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    roff[j] = tid + 256 * j < 4 * H ? tid + 256 * j : 4 * H - 1;
+    acc[j] = init[roff[j]];
+  }
+  // acc[row] += sum_k Wt[k][row] vec[k]
+  auto matvec = [&](const float* __restrict__ wt, const float* vec) {
+    for (int k0 = 0; k0 < H; k0 += 16) {          // H % 16 == 0 (checked at gam_create)
+      float w[16][NR];
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+        for (int j = 0; j < NR; ++j) w[kk][j] = wt[(size_t)(k0 + kk) * 4 * H + roff[j]];
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk) {
+        const float hk = vec[k0 + kk];
+#pragma unroll
+        for (int j = 0; j < NR; ++j) acc[j] = fmaf(w[kk][j], hk, acc[j]);
+      }
+    }
+  };
+  if (wih_t != nullptr) matvec(wih_t, x);
+  matvec(whh_t, h);
+#pragma unroll
+  for (int j = 0; j < NR; ++j)
+    if (tid + 256 * j < 4 * H) gates[tid + 256 * j] = acc[j];
+  __syncthreads();
+  for (int i = tid; i < H; i += 256) {
+    float cn, hn;
+    gam_lstm_cell<true>(gates[i], gates[H + i], gates[2 * H + i], gates[3 * H + i], c[i], cn, hn);
+    c2[i] = cn;
+    h2[i] = hn;
+  }
+  __syncthreads();
 }
-__device__ __forceinline__ f32x4 gam_rc_glb4(const float* p) {
-  return *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>((__attribute__((address_space(1))) const void*)(p));
-}
-__device__ __forceinline__ float gam_rc_glb1(const float* p) { return *p; }
 
 static inline size_t gam_rnnt_smem(int H, int JH, int V, int wout_in_lds, int L = 1) {
   const int vp = (V + 15) / 16 * 16;
@@ -220,61 +255,14 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
 
   while (t < len) {
     if (need_pred) {
-      // ---- LSTM cell: gates = tab[label] + W_hh.h  (gate order i,f,g,o); thread = gate row(s),
-      //      W_hh^T rows are contiguous over the gate index (coalesced), 8 k in flight ----
-      {
-        // 16 k x NR rows of W_hh^T in flight per thread: the step is L2-latency-bound, so the
-        // number of independent loads per wait is what sets its duration.  Every load is
-        // unconditional (row index clamped): a per-element "load or 0" select makes hipcc
-        // branch around each load and wait for it (cdna_hip_programming.md §5 trap c).
-        float acc[NR];
-        int roff[NR];
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-          roff[j] = tid + 256 * j < 4 * H ? tid + 256 * j : 4 * H - 1;
-          acc[j] = a.gate_tab[(size_t)label * 4 * H + roff[j]];
-        }
-        // acc[row] += sum_k Wt[k][row] vec[k]
-        auto matvec = [&](const float* __restrict__ wt, const float* vec) {
-          for (int k0 = 0; k0 < H; k0 += 16) {          // H % 16 == 0 (checked at gam_create)
-            float w[16][NR];
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-              for (int j = 0; j < NR; ++j) w[kk][j] = wt[(size_t)(k0 + kk) * 4 * H + roff[j]];
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) {
-              const float hk = vec[k0 + kk];
-#pragma unroll
-              for (int j = 0; j < NR; ++j) acc[j] = fmaf(w[kk][j], hk, acc[j]);
-            }
-          }
-        };
-        auto cell = [&](const float* c_old, float* h_new, float* c_new) {   // gates (i, f, g, o) -> (h', c')
-#pragma unroll
-          for (int j = 0; j < NR; ++j)
-            if (tid + 256 * j < 4 * H) gates[tid + 256 * j] = acc[j];
-          __syncthreads();
-          for (int i = tid; i < H; i += 256) {
-            const float ig = gam_sigmoid_exact(gates[i]), fg = gam_sigmoid_exact(gates[H + i]);
-            const float gg = tanhf(gates[2 * H + i]), og = gam_sigmoid_exact(gates[3 * H + i]);
-            const float cn = fg * c_old[i] + ig * gg;
-            c_new[i] = cn;
-            h_new[i] = og * tanhf(cn);
-          }
-          __syncthreads();
-        };
-        matvec(a.whh_t, h_s);
-        cell(c_s, hn_s, cn_s);
-        for (int l = 1; l < L; ++l) {     // layers above the first: input = the NEW hidden state of the layer below
-          float* st = xs + (size_t)(l - 1) * 4 * H;
-          const float* below = l == 1 ? hn_s : xs + (size_t)(l - 2) * 4 * H + 2 * H;
-#pragma unroll
-          for (int j = 0; j < NR; ++j) acc[j] = a.bias_x[(size_t)(l - 1) * 4 * H + roff[j]];
-          matvec(a.wih_x + (size_t)(l - 1) * H * 4 * H, below);
-          matvec(a.whh_x + (size_t)(l - 1) * H * 4 * H, st);
-          cell(st + H, st + 2 * H, st + 3 * H);
-        }
+      // ---- predictor: the candidate (h', c') of every layer from the committed state; layer 0's input term is gate_tab[label],
+      //      a layer above takes the NEW hidden state of the layer below ----
+      gam_rnnt_layer_step<NR>(a.gate_tab + (size_t)label * 4 * H, nullptr, nullptr, a.whh_t, h_s, c_s, hn_s, cn_s, gates, H, tid);
+      for (int l = 1; l < L; ++l) {
+        float* st = xs + (size_t)(l - 1) * 4 * H;
+        const float* below = l == 1 ? hn_s : xs + (size_t)(l - 2) * 4 * H + 2 * H;
+        gam_rnnt_layer_step<NR>(a.bias_x + (size_t)(l - 1) * 4 * H, a.wih_x + (size_t)(l - 1) * H * 4 * H, below,
+                                a.whh_x + (size_t)(l - 1) * H * 4 * H, st, st + H, st + 2 * H, st + 3 * H, gates, H, tid);
       }
       const float* gtop = L > 1 ? xs + (size_t)(L - 2) * 4 * H + 2 * H : hn_s;   // g = the top layer's new hidden state
       {
@@ -336,22 +324,9 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) wf[u] = load4(wr + k0 + 16 * u);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const f32x4 zf = gam_rc_lds4(zr + k0 + 16 * u);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.x, wf[u].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.y, wf[u].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.z, wf[u].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.w, wf[u].w, acc, 0, 0, 0);
-          }
+          for (int u = 0; u < 4; ++u) acc = gam_mfma4(acc, gam_rc_lds4(zr + k0 + 16 * u), wf[u]);
         }
-        for (int k0 = JH / 64 * 64; k0 + 16 <= JH; k0 += 16) {
-          const f32x4 zf = gam_rc_lds4(zr + k0);
-          const f32x4 wf = load4(wr + k0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.x, wf.x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.y, wf.y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.z, wf.z, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.w, wf.w, acc, 0, 0, 0);
-        }
+        for (int k0 = JH / 64 * 64; k0 + 16 <= JH; k0 += 16) acc = gam_mfma4(acc, gam_rc_lds4(zr + k0), load4(wr + k0));
       };
       if (wout_l != nullptr) tile([](const float* p) { return gam_rc_lds4(p); }, wout_l + (size_t)vc * WLD + 4 * lg4);
       else tile([](const float* p) { return gam_rc_glb4(p); }, a.wout + (size_t)vc * JH + 4 * lg4);
@@ -372,12 +347,7 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
         const float x = lr[v];
         if (x > best || (x == best && v < bi)) { best = x; bi = v; }
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-      }
+      gam_first_max<64>(best, bi);
       float se = 0.f;
       if (a.dump != nullptr) {
         for (int v = lane; v < V; v += 64) se += expf(lr[v] - best);
@@ -520,11 +490,8 @@ __global__ __launch_bounds__(256) void gam_rnnt_predict_kernel(GamPredictArgs a)
     }
     __syncthreads();
     for (int k = tid; k < a.PH; k += 256) {   // gate order i, f, g, o (nn.LSTM)
-      const float ig = gam_sigmoid_exact(gs[k]), fg = gam_sigmoid_exact(gs[a.PH + k]);
-      const float gg = tanhf(gs[2 * a.PH + k]), og = gam_sigmoid_exact(gs[3 * a.PH + k]);
-      const float c0 = a.c_in != nullptr ? a.c_in[so + k] : 0.f;
-      const float c2 = fg * c0 + ig * gg;
-      const float h2 = og * tanhf(c2);
+      float c2, h2;
+      gam_lstm_cell<true>(gs[k], gs[a.PH + k], gs[2 * a.PH + k], gs[3 * a.PH + k], a.c_in != nullptr ? a.c_in[so + k] : 0.f, c2, h2);
       a.c_out[so + k] = c2;
       a.h_out[so + k] = h2;
       xs[k] = h2;                              // input of the next layer

@@ -350,19 +350,15 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
     GAM_RC_MARK(T_GATES);
       ++xc;
       for (int ii = tid; i0 + ii < i1; ii += 256) {   // cell update of my units (gate order i, f, g, o)
-        const float ig = gam_sigmoid_exact(gates[ii]), fg = gam_sigmoid_exact(gates[nI + ii]);
-        const float gg = tanhf(gates[2 * nI + ii]), og = gam_sigmoid_exact(gates[3 * nI + ii]);
-        const float cn = fg * c_s[ii] + ig * gg;
-        const float hn = og * tanhf(cn);
+        float cn, hn;
+        gam_lstm_cell<true>(gates[ii], gates[nI + ii], gates[2 * nI + ii], gates[3 * nI + ii], c_s[ii], cn, hn);
         cn_s[ii] = cn;
 #if GAM_RC_AUDIT
         {
           const volatile float* gv = gates;
           const volatile float* cv = c_s;
-          const float ig2 = gam_sigmoid_exact(gv[ii]), fg2 = gam_sigmoid_exact(gv[nI + ii]);
-          const float gg2 = tanhf(gv[2 * nI + ii]), og2 = gam_sigmoid_exact(gv[3 * nI + ii]);
-          const float cn2 = fg2 * cv[ii] + ig2 * gg2;
-          const float hn2 = og2 * tanhf(cn2);
+          float cn2, hn2;
+          gam_lstm_cell<true>(gv[ii], gv[nI + ii], gv[2 * nI + ii], gv[3 * nI + ii], cv[ii], cn2, hn2);
           if (__float_as_uint(cn2) != __float_as_uint(cn) || __float_as_uint(hn2) != __float_as_uint(hn)) GAM_RC_LOG(3, ii, hn, hn2, __float_as_uint(cn), __float_as_uint(cn2));
           au_hn[ii >> 8] = hn; au_cn[ii >> 8] = cn;
         }
@@ -587,12 +583,7 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
           const float x = lr[vl];
           if (x > best) { best = x; bi = v0 + vl; }   // (ascending vl per lane: the first maximum stays)
         }
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-      }
+      gam_first_max<16>(best, bi);
       float se = 0.f;
       if (a.dump != nullptr) {
         if (f < W)

@@ -97,7 +97,8 @@ __global__ __launch_bounds__(256) void gam_rnnt_tf_predict_kernel(GamRnntTfArgs 
 #pragma unroll
       for (int j = 0; j < NR; ++j)
         acc[j] = l == 0 ? a.gate_tab[(size_t)label * G + roff[j]] : a.bias_x[(size_t)(l - 1) * G + roff[j]];
-      // acc[row] += sum_k Wt[k][row] vec[k]: 16 k x NR rows in flight, every load unconditional (gam_rnnt_greedy_kernel's matvec)
+      // acc[row] += sum_k Wt[k][row] vec[k]: 16 k x NR rows in flight, every load unconditional.  gam_decode.h's gam_rnnt_layer_step holds the
+      // same step; this kernel keeps its own text because it measured 1.4 % slower on the shared one
       auto matvec = [&](const float* __restrict__ wt, const float* vec) {
         for (int k0 = 0; k0 < H; k0 += 16) {
           float w[16][NR];
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256) void gam_rnnt_tf_predict_kernel(GamRnntTfArgs 
       __syncthreads();
       for (int i = tid; i < H; i += 256) {
         float c2, h2;
-        gam_lstm_cell(gates[i], gates[H + i], gates[2 * H + i], gates[3 * H + i], hs[H + i], c2, h2);
+        gam_lstm_cell<false>(gates[i], gates[H + i], gates[2 * H + i], gates[3 * H + i], hs[H + i], c2, h2);
         hs[H + i] = c2;
         hs[i] = h2;
         if (l == L - 1) gb[(size_t)u * H + i] = h2;
@@ -208,10 +209,7 @@ __global__ __launch_bounds__(256) void gam_rnnt_lattice_kernel(GamRnntLatArgs a)
         const f32x4 ef = gam_rc_lds4(enl + rt * LD + k0);
         const float z0 = fmaxf(ef.x + pf.x, 0.f), z1 = fmaxf(ef.y + pf.y, 0.f);
         const float z2 = fmaxf(ef.z + pf.z, 0.f), z3 = fmaxf(ef.w + pf.w, 0.f);
-        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(z0, wf.x, acc[rt], 0, 0, 0);
-        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(z1, wf.y, acc[rt], 0, 0, 0);
-        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(z2, wf.z, acc[rt], 0, 0, 0);
-        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(z3, wf.w, acc[rt], 0, 0, 0);
+        acc[rt] = gam_mfma4(acc[rt], z0, z1, z2, z3, wf);
       }
       wf = wn;
     }

@@ -136,10 +136,6 @@ static inline size_t gam_rb_ws_floats(int W, int S, int V, int H, int JH, int L)
   return gam_rb_pool(W, S) * ((size_t)L * 2 * H + JH) + Wp * (size_t)((V + 3) & ~3);
 }
 
-__device__ __forceinline__ f32x4 gam_rb_lds4(const float* p) {
-  return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>((__attribute__((address_space(3))) const void*)(p));
-}
-
 // acc[g][rt] += A[16 rt + i][k] * Wt[k][g * H + j0 + c] over k < H: A rows from LDS (row stride H + 4), Wt k-major with 4H columns.
 // MFMA lane (i = lane & 15, q = lane >> 4): A row i, weight column j0 + i, k = k0 + 4 q + e in the e-th MFMA of a group of four.
 template <int RT>
@@ -154,14 +150,9 @@ __device__ __forceinline__ void gam_rb_gates_mm(f32x4 (&acc)[4][2], const float*
       for (int g = 0; g < 4; ++g) w[g][e] = Wt[(size_t)(k0 + 4 * lg4 + e) * G + g * H + j0 + li];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-      const f32x4 a = gam_rb_lds4(A + (16 * rt + li) * ALD + k0 + 4 * lg4);
+      const f32x4 a = gam_rc_lds4(A + (16 * rt + li) * ALD + k0 + 4 * lg4);
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[g][0], acc[g][rt], 0, 0, 0);
-        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[g][1], acc[g][rt], 0, 0, 0);
-        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[g][2], acc[g][rt], 0, 0, 0);
-        acc[g][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[g][3], acc[g][rt], 0, 0, 0);
-      }
+      for (int g = 0; g < 4; ++g) acc[g][rt] = gam_mfma4(acc[g][rt], a, w[g]);
     }
   }
 }
@@ -324,12 +315,11 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
             if (row < n) {
               const int ps = par[row];
               const float c0 = ps >= 0 ? slots[(size_t)ps * SS + (size_t)l * 2 * H + H + j0 + li] : 0.f;
-              const float ig = gam_sigmoid_exact(acc[0][rt][r]), fg = gam_sigmoid_exact(acc[1][rt][r]);
-              const float gg = tanhf(acc[2][rt][r]), og = gam_sigmoid_exact(acc[3][rt][r]);
-              const float c2 = fg * c0 + ig * gg;
+              float c2, h2;
+              gam_lstm_cell<false>(acc[0][rt][r], acc[1][rt][r], acc[2][rt][r], acc[3][rt][r], c0, c2, h2);
               float* sd = slots + (size_t)dst[row] * SS + (size_t)l * 2 * H;
               sd[H + j0 + li] = c2;
-              sd[j0 + li] = og * tanhf(c2);
+              sd[j0 + li] = h2;
             }
           }
       }
@@ -354,13 +344,7 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) w[e] = a.wpred_t[(size_t)(k0 + 4 * lg4 + e) * JH + c0 + li];
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          const f32x4 av = gam_rb_lds4(hr + (16 * rt + li) * (H + 4) + k0 + 4 * lg4);
-          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, w[0], acc[rt], 0, 0, 0);
-          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, w[1], acc[rt], 0, 0, 0);
-          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, w[2], acc[rt], 0, 0, 0);
-          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, w[3], acc[rt], 0, 0, 0);
-        }
+        for (int rt = 0; rt < RT; ++rt) acc[rt] = gam_mfma4(acc[rt], gam_rc_lds4(hr + (16 * rt + li) * (H + 4) + k0 + 4 * lg4), w);
       }
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt)
@@ -424,13 +408,7 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
           for (int k0 = 0; k0 < JH; k0 += 16) {
             const f32x4 wf = *reinterpret_cast<const f32x4*>(wr + k0);
 #pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-              const f32x4 zf = gam_rb_lds4(zr + (16 * rt + li) * (JH + 4) + k0 + 4 * lg4);
-              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.x, wf.x, acc[rt], 0, 0, 0);
-              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.y, wf.y, acc[rt], 0, 0, 0);
-              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.z, wf.z, acc[rt], 0, 0, 0);
-              acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(zf.w, wf.w, acc[rt], 0, 0, 0);
-            }
+            for (int rt = 0; rt < RT; ++rt) acc[rt] = gam_mfma4(acc[rt], gam_rc_lds4(zr + (16 * rt + li) * (JH + 4) + k0 + 4 * lg4), wf);
           }
           if (v < V) {
             const float bo = a.bout[v];

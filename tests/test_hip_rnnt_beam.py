@@ -358,3 +358,74 @@ def test_model_hotword_makes_a_chosen_word_appear(tmp_path):
     plain = model.transcribe(wpath).text
     assert model.head.engine._hotwords_key[0] == ()
     assert word not in plain or word in greedy
+
+
+# ---- greedy decode on a head with pred_hidden = joint_hidden = 512: gam_rnnt_greedy_kernel's eight-rows-per-thread instantiation
+# (pred_hidden in (320, 512]), which no published checkpoint and no other test reaches.
+GREEDY512_SEED = 0                # chosen on the CPU: by the float64 reference alone no utterance has a near-tie (smallest margin 1.4e-2)
+GREEDY512_BLANK_BIAS = 9.0        # between the emission-heavy default and the blank-dominant 14: blanks and tokens both occur
+GREEDY_MIN_MARGIN = 2e-3          # tests/golden/cases.py RNNT_MIN_MARGIN
+
+
+def _greedy512_inputs(L):
+    """(cfg, state dict, encoded [4, D, 40], enc_len) of the seeded H = JH = 512, V = 34 head."""
+    from gigaam_amd import synth
+    cfg = synth.model_cfg("v2_rnnt", n_layers=1)
+    cfg["head"]["decoder"]["num_classes"] = cfg["head"]["joint"]["num_classes"] = 34
+    cfg["head"]["decoder"]["pred_rnn_layers"] = L
+    cfg["head"]["decoder"]["pred_hidden"] = cfg["head"]["joint"]["pred_hidden"] = 512
+    cfg["head"]["joint"]["joint_hidden"] = 512
+    sd = synth.make_state_dict(cfg, seed=500 + L, rnnt_blank_bias=GREEDY512_BLANK_BIAS)
+    rng = np.random.default_rng(GREEDY512_SEED * 10 + L)
+    encoded = rng.standard_normal((4, cfg["encoder"]["d_model"], 40)).astype(np.float32)
+    return cfg, sd, encoded, [40, 23, 1, 0]
+
+
+def _greedy_ref(head, encoded, T, S):
+    """The float64 greedy decode of one utterance (reference decoding.py's loop: at most S symbols per frame, the first maximum
+    wins): ids, frames and the smallest top-1 / top-2 margin over its joint steps."""
+    encp = R.encoder_projection(head, encoded)
+    pred = R.Predictor(head)
+    blank = head["out_w"].shape[0] - 1
+    y, frames, margin = (), [], np.inf
+    for t in range(T):
+        for _ in range(S):
+            lp = R.joint_lp(head, encp[t], pred(y))
+            k = int(np.argmax(lp))
+            top2 = np.partition(lp, -2)[-2:]
+            margin = min(margin, float(top2[1] - top2[0]))
+            if k == blank:
+                break
+            y += (k,)
+            frames.append(t)
+    return list(y), frames, margin
+
+
+@pytest.mark.parametrize("L", [1, 2])
+def test_greedy_with_512_hidden_units_matches_float64_reference(L):
+    """eng.rnnt_greedy on the one-workgroup kernel (cluster size 0), ragged lengths with 0 and 1: ids, frames and counts are exact for
+    every utterance whose float64 top-1 / top-2 margin exceeds 2e-3 on every step; at most one of the four may fall under it."""
+    from gigaam_amd.engine import HipEngine, build_config
+    S = 3
+    cfg, sd, encoded, enc_len = _greedy512_inputs(L)
+    head = R.head_from_state_dict(sd, L)
+    eng = HipEngine(build_config(cfg["preprocessor"], cfg["encoder"], cfg["head"]), sd, torch.device("cuda:0"))
+    eng.set_rnnt_cluster(0)
+    dec = eng.rnnt_greedy(torch.from_numpy(encoded), torch.tensor(enc_len, dtype=torch.int32), S)
+    torch.cuda.synchronize()
+    ids, frames, counts = dec.ids.cpu().numpy(), dec.frames.cpu().numpy(), dec.counts.cpu().numpy()
+    excused, n_tok, n_blank = 0, 0, 0
+    for b, T in enumerate(enc_len):
+        want_ids, want_frames, margin = _greedy_ref(head, encoded[b], T, S)
+        n_tok += len(want_ids)
+        n_blank += T - len(set(want_frames))
+        if margin <= GREEDY_MIN_MARGIN:
+            excused += 1
+            continue
+        n = int(counts[b])
+        assert n == len(want_ids), (L, b, n, len(want_ids))
+        assert ids[b, :n].tolist() == want_ids, (L, b)
+        assert frames[b, :n].tolist() == want_frames, (L, b)
+    report(f"rnnt_greedy_h512_L{L}", excused=excused, tokens=n_tok, blank_frames=n_blank)
+    assert n_tok > 0 and n_blank > 0, (n_tok, n_blank)     # the decode emits both
+    assert excused <= 1, excused
