@@ -2510,9 +2510,15 @@ int gam_emo_probs(gam_handle* h, const float* encoded, const int32_t* enc_len, i
 
 int gam_op_gemm(gam_handle* h, const float* A, const float* W, const float* bias, float* C, int M, int N, int K, int act,
                 void* stream) {
+  return gam_op_gemm_ex(h, A, W, bias, nullptr, 1.0f, C, M, N, K, act, stream);
+}
+
+int gam_op_gemm_ex(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha, float* C, int M,
+                   int N, int K, int act, void* stream) {
   if (!h) return -1;
   HIPCHK(h, hipSetDevice(h->device));
   GamGemmArgs g = gemm_args(A, K, W, bias, C, N, M, N, K);
+  g.R = R; g.ldr = N; g.alpha = alpha;
   hipStream_t s = (hipStream_t)stream;
   // the exact-fp32 kernel: the exact mode, and the shapes the LDS-DMA kernel cannot take (its epilogue moves 4-column pieces)
   if (!split_mode(h) || K % 32 != 0 || N % 4 != 0) return gemm(h, s, g, act);

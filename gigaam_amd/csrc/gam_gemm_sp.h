@@ -1,8 +1,8 @@
 // gam_gemm_sp.h -- the split-fp16 GEMM: (64 MT) x (64 NW) block tiles fed entirely by
 // LDS-DMA (global_load_lds_dwordx4), two or three LDS stages, one barrier per k-tile.
 //
-// Three-term split ("f16x3") on the fp16 matrix cores (v_mfma_f32_32x32x16_f16, 16x the
-// per-instruction rate of the fp32 MFMA), fp32 accumulate:
+// Three-term split ("f16x3") on the fp16 matrix cores (v_mfma_f32_16x16x32_f16, 16x the
+// rate of the fp32 MFMA), fp32 accumulate:
 //
 //   a = a_hi + a_lo,  w * 2^s = w_hi + w_lo      (hi = fp16(x), lo = fp16(x - hi))
 //   a.w ~= (a_hi.w_hi + a_hi.w_lo + a_lo.w_hi) * 2^-s
@@ -23,14 +23,23 @@
 // into LDS -- no staging registers, no ds_write pass, no conversion in the GEMM.  (A 128x128
 // register-staged kernel measured TD/TCP-bound on exactly that traffic: profiles/r01_f16x3_*.)
 //
-// LDS image: rows of 128 B (8 slots of 16 B), slot' = slot ^ ((row >> 1) & 7).  LDS-DMA writes
-// lane-linear, so the XOR is applied to the per-lane SOURCE address; fragment reads apply the same
-// XOR and every 16-lane service group of a ds_read_b128 (rows distinct mod 16) covers all 16 slots
-// of the 256-byte bank row exactly once: conflict-free without padding.
+// LDS image: rows of 128 B (8 slots of 16 B), slot' = slot ^ key(row), key bits (r1, r2 ^ r4, r3) of the row's index in its
+// operand's block tile (gam_sp_key).  LDS-DMA writes lane-linear, so the XOR is applied to the per-lane SOURCE address; fragment
+// reads apply the same XOR.  Conflicts, re-derived for the rows the 16x16x32 fragments read: lane l reads operand row i = l & 15 at
+// logical slot 4 plane + (l >> 4), and a ds_read_b128 is served in four 16-lane groups, lanes {0-3, 12-15, 20-27} etc. -- i in
+// {0-3, 12-15} at slot s and i in {4-11} at slot s ^ 1.  A group is conflict-free when (row & 1, slot') differ over its 16 lanes.
+//   activation block: rows 16 b + i, key = (i1, i2 ^ b0, i3); the s ^ 1 lanes are those with i2 ^ i3 = 1, so the low slot bits are
+//     (i1 ^ i2 ^ i3, i2 ^ b0, i3) with row parity i0: a bijection of i.
+//   W block 2 p + t: rows 32 p + 8 (i >> 2) + 4 t + (i & 3) (the row order that gives a lane 8 consecutive C columns, see the
+//     epilogue), i.e. r0 = i0, r1 = i1, r2 = t, r3 = i2, r4 = i3: key = (i1, t ^ i3, i2) -> (i1 ^ i2 ^ i3, t ^ i3, i2): a bijection.
+//     (The r4 term is what this row order needs: with the plain (row >> 1) & 7 rows i and i + 8 of the block collide.)
+// Conflict-free without padding for both operands.
 //
-// 2 (M) x NW (N) waves; a wave owns (32 MT) x 64 outputs = MT x 2 MFMA tiles, 3 MFMAs per tile per
-// k16-step.  At NW = 4 (256-wide tiles, one workgroup per CU) the bytes moved per FLOP are half
+// 2 (M) x NW (N) waves; a wave owns (32 MT) x 64 outputs = 2 MT x 4 blocks of 16 x 16, 3 MFMAs per block per
+// 32-deep k-tile.  At NW = 4 (256-wide tiles, one workgroup per CU) the bytes moved per FLOP are half
 // those of a 128 x 128 tile; the k-tile after next lands while the current one is multiplied.
+// Why this MFMA shape: same cycles per FLOP as 32x32x16, same LDS bytes, but under the power cap the chip holds a higher clock
+// on it (measurements: profiles/mfma16_gemm_ab.md).
 // MT in {2,3,4} and NW in {2,4} are picked per launch (gam_gemm_sp_pick) to minimise the tail of the
 // last round of tiles.
 #pragma once
@@ -42,7 +51,7 @@
 #endif
 
 // -DGAM_SP_INSTRUMENT=1 compiles the GAM_SP_DBG experiment switches in (1: skip the epilogue, 2: one
-// k-tile only, 4: per-phase clock64 counters written into the last C row, 8: drop the in-loop barrier).
+// k-tile only, 4: clock64 counters of the k-tile's first half / barrier / second half, written into the last C row, 8: drop the in-loop barrier).
 // They produced profiles/r01_gemm_sp_clock_random_vs_zero.txt; production builds carry none of it.
 #ifndef GAM_SP_INSTRUMENT
 #define GAM_SP_INSTRUMENT 0
@@ -76,6 +85,9 @@ struct GamGemmSpCfg {
   static constexpr int NWI = BN / 8 / NWAVES;   // W DMA pieces per wave per k-tile
 };
 
+// XOR key of the LDS image: slot' = slot ^ gam_sp_key(row), row = the row's index in its operand's block tile.  Bits (r1, r2 ^ r4, r3).
+__device__ __forceinline__ int gam_sp_key(int row) { return ((row >> 1) & 7) ^ ((row >> 3) & 2); }
+
 // NS = LDS stages.  2: the k-tile after next lands while the current one is multiplied -- enough for the 8-wave tiles, whose
 // k-tile takes 1.4-1.8 us of MFMA work.  3 (r04, the 4-wave tiles of small grids): a 128 x 128 k-tile is 0.3 us of MFMA work but
 // its 32 KB take ~0.8 us from issue to landed, and with two stages exactly ONE k-tile of fetch is in flight, so the loop ran at
@@ -88,7 +100,7 @@ struct GamGemmSpCfg {
 // reduction length: a row's 128-byte share of a "k-tile" holds 64 consecutive fp16 values instead of 32 (hi, lo) pairs, so the
 // DMA, the LDS image, the swizzle and the fragment reads are exactly those of the three-term kernel -- what used to be the lo
 // half of the line is simply the next 32 k-values -- and the MFMA stream multiplies (first half x first half) + (second half x
-// second half): two MFMAs per 32 x 32 x 32 block instead of three per 32 x 32 x 16.  Per unit of K: a third of the matrix
+// second half): two K = 32 MFMAs per 16 x 16 x 64 block instead of three per 16 x 16 x 32.  Per unit of K: a third of the matrix
 // work, half the operand bytes.  (A first version kept the sp32 operands and fetched only the hi half of every line: a 64-byte
 // piece of each 128-byte line costs the memory path the whole line, and the kernel ran at half the delivery rate --
 // profiles/r04_fastmode.txt.)
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
   GAM_SP_TL(0);
 
   // ---- DMA sources.  Piece q of an operand = tile rows 8q .. 8q+7; this wave moves pieces
-  //      q = wave + NWAVES i.  Lane l -> row 8q + (l>>3), LDS slot' l&7, source slot (l&7) ^ ((row>>1)&7).
+  //      q = wave + NWAVES i.  Lane l -> row 8q + (l>>3), LDS slot' l&7, source slot (l&7) ^ gam_sp_key(row).
   //      Addresses = wave-uniform tile base (SGPR pair) + 32-bit lane offset.
   auto a_row_off = [&](int m) -> size_t {
     m = m < g.M ? m : g.M - 1;
@@ -153,25 +165,25 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
 #pragma unroll
   for (int i = 0; i < NAI; ++i) {
     const int row = 8 * (wave + NWAVES * i) + (lane >> 3);
-    const int slot = (lane & 7) ^ ((row >> 1) & 7);
+    const int slot = (lane & 7) ^ gam_sp_key(row);
     a_src[i] = (unsigned)((a_row_off(m0 + row) - a_tile0) * 4) + slot * 16;
   }
 #pragma unroll
   for (int i = 0; i < NWI; ++i) {
     const int row = 8 * (wave + NWAVES * i) + (lane >> 3);
-    const int slot = (lane & 7) ^ ((row >> 1) & 7);
+    const int slot = (lane & 7) ^ gam_sp_key(row);
     int n = n0 + row;
     n = n < g.N ? n : g.N - 1;
     w_src[i] = (unsigned)(n - n0) * (unsigned)g.K * 4u + slot * 16;
   }
 
-  f32x16 acc[MT][2];
+  f32x4 acc[2 * MT][4];   // [16-row block of C][16-column block]: the wave's (32 MT) x 64 outputs
 #pragma unroll
-  for (int i = 0; i < MT; ++i)
+  for (int i = 0; i < 2 * MT; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
   // split-K (grid.y = g.splitk slices, small grids: a few utterances per GPU): this workgroup contracts k-tiles
   // [kt_first, kt_first + nk) and leaves raw partial sums in g.partial[slice]; gam_splitk_reduce_kernel sums the slices in
@@ -214,68 +226,101 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
     dma_advance();
   };
 
-  // ---- fragment addressing: lane -> row (lane&31), k-half kg = lane>>5; slot = plane*4 + 2*ks + kg
-  const int sx = (lane >> 1) & 7;
-  const int kg = lane >> 5;
-  const int rowb = (lane & 31) * 128;
-  const int o_h0 = rowb + (((0 + kg) ^ sx) << 4), o_h1 = rowb + (((2 + kg) ^ sx) << 4);
-  const int o_l0 = rowb + (((4 + kg) ^ sx) << 4), o_l1 = rowb + (((6 + kg) ^ sx) << 4);
-  const int a_base = wm * (BM / 2) * 128;
+  // ---- fragment addressing (v_mfma_f32_16x16x32_f16: lane l supplies operand row l & 15, halves k = 8 (l >> 4) .. + 7):
+  //      one ds_read_b128 = logical slot 4 plane + (l >> 4) of a row.  Activation block i = tile rows a_base + 16 i + (l & 15).
+  //      W block T = 2 p + t = tile rows w_base + 32 p + 8 ((l & 15) >> 2) + 4 t + (l & 3): lane group l >> 4 = q then holds the
+  //      C columns 32 p + 8 q + 4 t .. + 3 of block T, i.e. EIGHT consecutive columns over the block pair (2 p, 2 p + 1).
+  const int fi = lane & 15, fg = lane >> 4;
+  const int wr = 8 * (fi >> 2) + (fi & 3);
+  int o_a[2][2], o_w[2][2];   // [plane][row bit 4 of the block (i & 1) | t]
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+      o_a[pl][x] = fi * 128 + (((4 * pl + fg) ^ gam_sp_key(fi + 16 * x)) << 4);
+      o_w[pl][x] = (wr + 4 * x) * 128 + (((4 * pl + fg) ^ gam_sp_key(wr + 4 * x)) << 4);
+    }
+  const int a_base = wm * (BM / 2) * 128;   // (BM / 2 = 32 MT rows: a multiple of 32, so row bit 4 of block i is i & 1)
   const int w_base = Cfg::A_BYTES + wn * 64 * 128;
 
-  // Two fragment sets (k16-step 0 / 1 of a k-tile), two MFMA phases per k-tile:
-  //   phase 0: MFMAs on set 0, reading set 1 (same tile) in between
-  //   vmcnt(0) + lgkmcnt(0) + barrier      -- tile kt+1 landed everywhere, stage kt&1 has no reader left
-  //   phase 1: MFMAs on set 1, in between: read set 0 of tile kt+1, then DMA tile kt+2 -> stage kt&1
+  // ONE fragment set (a whole k-tile of 16x16x32 operands is 16 MT + 32 registers: two do not fit beside the 32 MT accumulators).
+  // The k-tile's MFMAs run as four quadrants of the wave tile -- activation halves M0 / M1 (MT blocks each) x W halves N0 / N1
+  // (two blocks each) -- and an operand half is refilled for the next k-tile as soon as its last MFMA has issued:
+  //   quadrant 1 (M0,N0): reads N1, then M1 (both of THIS tile: their registers were busy to the end of the last one)
+  //   quadrant 2 (M0,N1): MFMAs only
+  //   vmcnt + lgkmcnt(0) + barrier     -- tile kt+1 landed everywhere, stage of tile kt has no reader left
+  //   quadrant 3 (M1,N0): reads M0 of tile kt+1, then DMA pieces of tile kt+NS -> stage of tile kt
+  //   quadrant 4 (M1,N1): reads N0 of tile kt+1, then the rest of the DMA pieces
+  // The last quadrant shares no operand half with the first, so one loop body serves every k-tile.  Per accumulator the order
+  // is the same everywhere: k-tiles ascending, terms hi.hi, lo_w.hi_a, hi_w.lo_a.
   // Everything that is not an MFMA is issued one or two items at a time BETWEEN MFMAs: an LDS-DMA piece
   // costs the issuing wave ~60+ cycles, and with the whole refill issued in one block after the barrier
   // both waves of a SIMD sat in it together and the matrix pipe idled ~600 of every 3500 cycles
-  // (clock64 instrumentation, GAM_SP_INSTRUMENT build with GAM_SP_DBG=4).  Fragment reads get >= 2/3 of a phase to land.
-  gam_half8 fah[2][MT], fal[2][MT], fbh[2][2], fbl[2][2];
+  // (clock64 instrumentation, GAM_SP_INSTRUMENT build with GAM_SP_DBG=4).
+  gam_half8 fah[2 * MT], fal[2 * MT], fwh[4], fwl[4];
   constexpr int NTERM = H16 ? 2 : 3;
-  constexpr int NM = 2 * NTERM * MT;  // MFMAs per phase: terms x MT x 2 tiles
-  constexpr int NR = 2 * MT + 4;    // fragment reads per set
-  constexpr int NG = NAI + NWI;     // DMA pieces per wave per k-tile
-  // first MFMA slot that carries a DMA piece: behind the reads where the phase is long enough (three terms), beside them otherwise
-  constexpr int G0 = ((NR + 1) / 2 + NG <= NM) ? (NR + 1) / 2 : 0;
-  static_assert((NR + 1) / 2 <= NM && G0 + NG <= NM, "phase too short for its reads + DMA pieces");
+  constexpr int QM = 2 * NTERM * MT;  // MFMAs per quadrant: terms x MT x 2 blocks
+  constexpr int NG = NAI + NWI;       // DMA pieces per wave per k-tile
+  // One item per MFMA slot: a 16x16x32 MFMA holds the vector issue for 8 of its 16 cycles, which hides one ds_read_b128, not two
+  // (with one wave per SIMD -- the 4-wave tiles of small grids -- whatever does not fit is exposed).  Quadrant 3 carries its 2 MT
+  // reads, then DMA pieces; quadrant 4 its 4 reads, then the remaining pieces.
+  constexpr int G3 = QM - 2 * MT;     // DMA pieces carried by quadrant 3
+  static_assert(4 + 2 * MT <= QM && G3 + QM - 4 >= NG, "quadrant too short for its reads + DMA pieces");
 #define GAM_SPLD(P) (*reinterpret_cast<const gam_half8*>(P))
   // (plain ifs on unrolled loop counters, not nested generic lambdas: those push the fragment arrays to scratch)
-#define GAM_SP_RDITEM(S, Q, ST, OH, OL)                                                           \
+  // read item Q of W half NH: blocks 2 NH, 2 NH + 1, hi plane first
+#define GAM_SP_RDW(NH, Q, ST)                                                                     \
   {                                                                                               \
     const int q_ = (Q);                                                                           \
-    if (q_ < 2) fbh[S][q_ & 1] = GAM_SPLD((ST) + w_base + (q_ & 1) * 4096 + (OH));                 \
-    else if (q_ < MT + 2) fah[S][(q_ + MT - 2) % MT] = GAM_SPLD((ST) + a_base + ((q_ + MT - 2) % MT) * 4096 + (OH)); \
-    else if (q_ < MT + 4) fbl[S][(q_ - MT) & 1] = GAM_SPLD((ST) + w_base + ((q_ - MT) & 1) * 4096 + (OL)); \
-    else fal[S][(q_ + MT - 4) % MT] = GAM_SPLD((ST) + a_base + ((q_ + MT - 4) % MT) * 4096 + (OL)); \
+    if (q_ < 2) fwh[2 * (NH) + (q_ & 1)] = GAM_SPLD((ST) + w_base + (NH) * 4096 + o_w[0][q_ & 1]);  \
+    else fwl[2 * (NH) + (q_ & 1)] = GAM_SPLD((ST) + w_base + (NH) * 4096 + o_w[1][q_ & 1]);         \
   }
-#define GAM_SP_MFMA(S, T)                                                                         \
+  // read item Q of activation half MH: blocks MH MT .. MH MT + MT - 1, hi plane first
+#define GAM_SP_RDA(MH, Q, ST)                                                                     \
   {                                                                                               \
-    const int term_ = (T) / (2 * MT), i_ = ((T) % (2 * MT)) / 2, j_ = (T) & 1;                    \
-    /* three terms: hi.hi, lo_w.hi_a, hi_w.lo_a;  H16: first-half x first-half, second-half x second-half */ \
-    acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term_ == 1 ? fbl[S][j_] : fbh[S][j_],    \
-                                                         (H16 ? term_ == 1 : term_ == 2) ? fal[S][i_] : fah[S][i_], acc[i_][j_], 0, 0, 0); \
+    const int q_ = (Q), i_ = (MH) * MT + q_ % MT;                                                 \
+    if (q_ < MT) fah[i_] = GAM_SPLD((ST) + a_base + i_ * 2048 + o_a[0][i_ & 1]);                  \
+    else fal[i_] = GAM_SPLD((ST) + a_base + i_ * 2048 + o_a[1][i_ & 1]);                          \
   }
-  // phase<S, DMA>: MFMAs of set S; reads of set 1-S from (rst, roh, rol); DMA pieces of the next tile -> stage istage
-  auto phase = [&](auto setc, auto dmac, const unsigned char* rst, int roh, int rol, int istage) {
-    constexpr int S = decltype(setc)::value, R = 1 - S;
-    constexpr bool DMA = decltype(dmac)::value;
-    const unsigned char* ab = Ab;
-    const unsigned char* wb = Wb;
-    unsigned char* sb = gam_smem_sp;
-    if constexpr (DMA) {
-      ab = Ab + dma_ka();
-      wb = Wb + (size_t)d_kt * 128;
-      sb = gam_smem_sp + istage * Cfg::STAGE + wave * 1024;
-      dma_advance();
+#define GAM_SP_MFMA(MH, NH, T)                                                                    \
+  {                                                                                               \
+    const int term_ = (T) / (2 * MT), i_ = (MH) * MT + ((T) % (2 * MT)) / 2, j_ = 2 * (NH) + ((T) & 1); \
+    /* three terms: hi.hi, lo_w.hi_a, hi_w.lo_a;  H16: first-half x first-half, second-half x second-half */ \
+    acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(term_ == 1 ? fwl[j_] : fwh[j_],          \
+                                                         (H16 ? term_ == 1 : term_ == 2) ? fal[i_] : fah[i_], acc[i_][j_], 0, 0, 0); \
+  }
+  // first half of a k-tile: quadrants (M0, N0) and (M0, N1); reads N1 and M1 of this tile (stage st)
+  auto half0 = [&](const unsigned char* st) {
+#pragma unroll
+    for (int t = 0; t < QM; ++t) {
+      GAM_SP_MFMA(0, 0, t);
+      if (t < 4) GAM_SP_RDW(1, t, st)
+      else if (t < 4 + 2 * MT) GAM_SP_RDA(1, t - 4, st)
+      __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int t = 0; t < NM; ++t) {
-      GAM_SP_MFMA(S, t);
-      if (2 * t < NR) GAM_SP_RDITEM(R, 2 * t, rst, roh, rol);
-      if (2 * t + 1 < NR) GAM_SP_RDITEM(R, 2 * t + 1, rst, roh, rol);
-      if (DMA && t >= G0 && t - G0 < NG) {
-        const int gi = t - G0;
+    for (int t = 0; t < QM; ++t) {
+      GAM_SP_MFMA(0, 1, t);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // second half: quadrants (M1, N0) and (M1, N1); reads M0 and N0 of the next tile (stage sn); DMA -> stage istage
+  auto half1 = [&](const unsigned char* sn, int istage) {
+    const unsigned char* ab = Ab + dma_ka();
+    const unsigned char* wb = Wb + (size_t)d_kt * 128;
+    unsigned char* sb = gam_smem_sp + istage * Cfg::STAGE + wave * 1024;
+    dma_advance();
+#pragma unroll
+    for (int u = 0; u < 2 * QM; ++u) {
+      if (u < QM) {
+        GAM_SP_MFMA(1, 0, u);
+        if (u < 2 * MT) GAM_SP_RDA(0, u, sn)
+      } else {
+        GAM_SP_MFMA(1, 1, u - QM);
+        if (u - QM < 4) GAM_SP_RDW(0, u - QM, sn)
+      }
+      const int gi = u < QM ? u - 2 * MT : (u - QM < 4 ? -1 : G3 + u - QM - 4);
+      if (gi >= 0 && gi < NG) {
         if (gi < NAI)
           __builtin_amdgcn_global_load_lds((glb_ptr_t)(ab + a_src[gi % NAI]), (lds_ptr_t)(sb + gi * (NWAVES * 1024)), 16, 0, 0);
         else
@@ -285,14 +330,10 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  using C0_ = std::integral_constant<int, 0>;
-  using C1_ = std::integral_constant<int, 1>;
-  using T_ = std::integral_constant<bool, true>;
-  using F_ = std::integral_constant<bool, false>;
 
   long long t_bar = 0, t_mm0 = 0, t_mm1 = 0, t_start = 0, w_start = 0;
   if (GAM_SP_DBG(g) & 4) { t_start = clock64(); w_start = wall_clock64(); }
-  // static priority for the later-dispatched half of the workgroup's waves (the arbitration loser on every phase:
+  // static priority for the later-dispatched half of the workgroup's waves (the arbitration loser on every half:
   // MI355X_MICROARCH.md "Two waves per SIMD", item 4)
   if (GAM_SP_INSTRUMENT && g.prio && wave >= NWAVES / 2) __builtin_amdgcn_s_setprio(1);   // (r02 experiment, instrumented builds only)
   // in-loop wait: everything but the newest (NS - 2) k-tiles' DMA pieces of this wave has landed (vmcnt counts in issue order)
@@ -307,8 +348,11 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VMW) : "memory");   // tiles 0 and 1 have landed for every wave
   }
   GAM_SP_TL(1);
+  // a k-tile starts on (M0, N0)
 #pragma unroll
-  for (int q = 0; q < NR; ++q) GAM_SP_RDITEM(0, q, gam_smem_sp, o_h0, o_l0);
+  for (int q = 0; q < 2 * MT; ++q) GAM_SP_RDA(0, q, gam_smem_sp);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) GAM_SP_RDW(0, q, gam_smem_sp);
   const int nk_run = (GAM_SP_DBG(g) & 2) ? 1 : nk;
   int s_cur = 0;       // LDS stage of k-tile kt
   for (int kt = 0; kt < nk_run; ++kt) {
@@ -317,11 +361,10 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
     const unsigned char* sn = gam_smem_sp + s_nxt * Cfg::STAGE;
     long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     if (GAM_SP_DBG(g) & 4) c0 = clock64();
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): set 0 landed (read >= 2/3 of a phase ago)
-    phase(C0_{}, F_{}, st, o_h1, o_l1, 0);
+    half0(st);
     if (GAM_SP_DBG(g) & 4) c1 = clock64();
     // vmcnt by hand: this wave's DMA pieces of tile kt+1 have landed (hipcc does not order an LDS-DMA against the
-    // ds_reads behind a later barrier); lgkmcnt(0): set 1 is in registers
+    // ds_reads behind a later barrier); lgkmcnt(0): this wave's last reads of tile kt are in registers
     if constexpr (NS == 2) {
       __builtin_amdgcn_s_waitcnt(0x0070);
       if (!(GAM_SP_DBG(g) & 8)) __syncthreads();
@@ -330,22 +373,23 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
     }
     if (GAM_SP_DBG(g) & 4) c2 = clock64();
     // Unconditional (one copy of the MFMA stream; a second, DMA-less copy behind a branch made hipcc
-    // double-buffer the accumulators): past the end the set-0 reads fetch stale LDS that is never used
+    // double-buffer the accumulators): past the end the reads fetch stale LDS that is never used
     // and the DMA re-fetches the last k-tile into a stage nobody reads again (drained before the epilogue).
     // The refill goes to the stage of tile kt: every wave has read its last fragments before the barrier above.
-    phase(C1_{}, T_{}, sn, o_h0, o_l0, s_cur);
+    half1(sn, s_cur);
     if (GAM_SP_DBG(g) & 4) { c3 = clock64(); t_mm0 += c1 - c0; t_bar += c2 - c1; t_mm1 += c3 - c2; }
     s_cur = s_nxt;
   }
   if ((GAM_SP_DBG(g) & 4) && lane == 0 && (lid == 0 || lid == (int)gridDim.x - 1)) {
-    // [total clk, total wall(100 MHz), phase 0, barrier, phase 1] of one wave
+    // [total clk, total wall(100 MHz), first half, barrier, second half] of one wave
     float* d = g.C + (size_t)(g.M - 1) * g.ldc + (lid == 0 ? 0 : 64) + wave * 8;
     d[0] = (float)(clock64() - t_start); d[1] = (float)(wall_clock64() - w_start);
     d[2] = (float)t_mm0; d[3] = (float)t_bar; d[4] = (float)t_mm1;
     return;
   }
 #undef GAM_SPLD
-#undef GAM_SP_RDITEM
+#undef GAM_SP_RDW
+#undef GAM_SP_RDA
 #undef GAM_SP_MFMA
   // every LDS-DMA piece of this wave has landed (a workgroup must not retire with DMA writes in flight: its LDS
   // could already belong to the next one); no barrier -- the epilogue below touches no shared memory
@@ -356,114 +400,113 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
   if ((GAM_SP_DBG(g) & 1) && acc[0][0][0] != 123.456f) return;
 
   // ---- epilogue, straight from the accumulators.  The MFMAs run with the operands SWAPPED (W fragment as the A
-  //      operand, activation fragment as B), i.e. they accumulate C^T tiles: lane l then owns ONE row of C
-  //      (m = l & 31 of the 32 x 32 tile) and, per register quad g = r >> 2, FOUR CONSECUTIVE columns
-  //      n = 8 g + 4 (l >> 5) + (r & 3).  Bias / residual / C therefore move as 16-byte vectors with no transpose:
-  //      the former per-wave LDS round trip (96 ds_write_b32 + 24 ds_read_b128 per wave, 8 waves on one LDS) cost
-  //      5.0 of the 7.3 us a 192 x 256 tile spent here (profiles/r03_gemm_timeline.txt); lanes l and l + 32 write
-  //      adjacent 16-byte pieces of a row, the four quads complete its 128-byte line.
+  //      operand, activation fragment as B), i.e. they accumulate C^T blocks: lane l then owns ONE row of C per block row
+  //      (m = 16 i + (l & 15)) and, in block T = 2 p + t, the FOUR CONSECUTIVE columns 32 p + 8 (l >> 4) + 4 t + r (r = register;
+  //      the W rows were dealt to the A-operand rows that way, see the fragment addressing).  Bias / residual / C therefore move
+  //      as 16-byte vectors with no transpose: the former per-wave LDS round trip (96 ds_write_b32 + 24 ds_read_b128 per wave, 8
+  //      waves on one LDS) cost 5.0 of the 7.3 us a 192 x 256 tile spent here (profiles/r03_gemm_timeline.txt).
   // (r04, tried and dropped: requesting the bias pieces and the row scales of the 4-wave tiles in front of the first k-tile, so
   //  that the epilogue of a small-grid launch does not start with an L2 round trip -- 32 + MT more live registers, same-box A/B
   //  6.22-6.24 vs 6.24-6.25 ms at 4 x 20 s, 2.85 vs 2.89 ms for one clip: nothing; profiles/r04_ab_experiments.txt)
-  // r04: EIGHT consecutive columns per lane.  Lanes l and l + 32 hold the two halves of every 8-column group of their (common) row;
-  // one v_permlane32_swap per register trades the second half of the even group against the first half of the odd one, after
-  // which lane l < 32 owns columns 16 p .. 16 p + 7 and lane l + 32 columns 16 p + 8 .. 16 p + 15 of each 32-column block: bias /
-  // residual / C move as pairs of adjacent 16-byte pieces (64 contiguous bytes per row per instruction instead of 32), and an
-  // sp32 / fp16 result as ONE 16-byte store per plane instead of two 8-byte ones (the store path, not the arithmetic, is what an
-  // epilogue costs: profiles/r03_gemm_timeline.txt).  (semantics probed on the device, tools/permlane_probe.hip: after the instruction
-  // vdst = [vdst(0..31) | vsrc(0..31)], vsrc = [vdst(32..63) | vsrc(32..63)].)  Same values, same roundings: bit-identical results.
-  // Inline asm, not __builtin_amdgcn_permlane32_swap: hipcc 7.2 miscompiles a SEQUENCE of the builtin on vector elements (every
-  // element comes back as element 0 -- reproduced in isolation by the probe).  The asm reads MFMA results and the hazard
-  // recognizer does not look inside asm: two s_nop 15 cover the XDL-write -> VALU-read wait states of the last MFMAs.
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int pq = 0; pq < 2; ++pq)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float x = acc[i][j][8 * pq + r], y = acc[i][j][8 * pq + 4 + r];
-          asm volatile("v_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-          acc[i][j][8 * pq + r] = x;
-          acc[i][j][8 * pq + 4 + r] = y;
-        }
-  const int lrow = lane & 31, lq8 = (lane >> 5) * 8;
+  // r04: EIGHT consecutive columns per lane -- the blocks 2 p and 2 p + 1 hold the two halves of the lane's 8-column group: bias /
+  // residual / C move as pairs of adjacent 16-byte pieces (the four lane groups complete a row's 128-byte line per instruction pair),
+  // and an sp32 / fp16 result as ONE 16-byte store per plane instead of two 8-byte ones (the store path, not the arithmetic, is what
+  // an epilogue costs: profiles/r03_gemm_timeline.txt).  On the 32x32x16 shape this took a v_permlane32_swap per register; here it is
+  // address arithmetic alone.
+  const int lrow = lane & 15, lq8 = (lane >> 4) * 8;
   const float accscale = g.wscale_inv;
-  // piece (j, pq, hf): columns nw + 32 j + 16 pq + lq8 + 4 hf .. + 3  =  accumulator registers 8 pq + 4 hf .. + 3
-  f32x4 bv[2][2][2];
+  // piece (p, hf): columns nw + 32 p + lq8 + 4 hf .. + 3  =  accumulator block 2 p + hf
+  f32x4 bv[2][2];
 #pragma unroll
-  for (int j = 0; j < 2; ++j)
+  for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
-    for (int pq = 0; pq < 2; ++pq)
+    for (int hf = 0; hf < 2; ++hf) {
+      const int col = nw + 32 * pp + lq8 + 4 * hf;
+      bv[pp][hf] = (g.bias != nullptr && col < g.N) ? *reinterpret_cast<const f32x4*>(g.bias + col) : (f32x4){0.f, 0.f, 0.f, 0.f};   // N % 4 == 0
+    }
+  // Row data of all 2 MT rows first -- validity, mask, output row, per-row factor -- so that the a_rs / lens loads of every row
+  // are in flight together: inside the row loop each would sit behind the previous row's stores (C may alias anything), one
+  // exposed L2 round trip per row, and the 16-row blocks make twice as many rows per lane as the 32-row blocks did.
+  // (utterance, frame) of a row: ONE division per lane -- a lane's rows are 16 apart, so the next row's pair follows by a
+  // conditional subtraction (utterances of fewer than 16 rows divide again); the mask test tt / fdiv >= len is tt >= len fdiv.
+  // A split-K slice needs neither (it stores raw sums of every row below M).  Measured on the small grids, where the epilogue
+  // is a visible share of a launch: profiles/mfma16_gemm_ab.md, section 4.
+  const bool part = g.partial != nullptr;
+  const bool need_bt = !part && (g.lens != nullptr || g.remap);
+  bool r_ok[2 * MT], r_masked[2 * MT];
+  long r_orow[2 * MT];
+  float r_rsc[2 * MT];
+  int bb = 0, tt = 0;
+  if (need_bt) { bb = (mw + lrow) / g.rpb; tt = (mw + lrow) - bb * g.rpb; }
 #pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const int col = nw + 32 * j + 16 * pq + lq8 + 4 * hf;
-        bv[j][pq][hf] = (g.bias != nullptr && col < g.N) ? *reinterpret_cast<const f32x4*>(g.bias + col) : (f32x4){0.f, 0.f, 0.f, 0.f};   // N % 4 == 0
-      }
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int row = mw + 32 * i + lrow;
-    if (row >= g.M) continue;
-    bool masked = false, skip = false;
+  for (int i = 0; i < 2 * MT; ++i) {
+    const int row = mw + 16 * i + lrow;
+    bool ok = row < g.M, masked = false;
     long orow = row;
-    if (g.lens != nullptr || g.remap) {
-      const int bb = row / g.rpb, tt = row - bb * g.rpb;
-      if (g.lens != nullptr) masked = (tt / g.fdiv) >= g.lens[bb];
-      if (g.remap) {
-        skip = tt >= g.rows_valid;
-        orow = (long)bb * g.out_rpb + tt + g.out_shift;
+    if (need_bt) {
+      if (i > 0) {
+        tt += 16;
+        if (g.rpb < 16) { bb = row / g.rpb; tt = row - bb * g.rpb; }
+        else if (tt >= g.rpb) { tt -= g.rpb; ++bb; }
+      }
+      if (ok) {
+        if (g.lens != nullptr) masked = tt >= g.lens[bb] * g.fdiv;
+        if (g.remap) {
+          if (tt >= g.rows_valid) ok = false;
+          orow = (long)bb * g.out_rpb + tt + g.out_shift;
+        }
       }
     }
-    if (skip && g.partial == nullptr) continue;
     // per-row factor (weight scale x the A operand's row scale)
-    const float rsc = accscale * (g.a_rs != nullptr ? g.a_rs[row] : 1.0f);
-    if (g.partial != nullptr) {   // split-K slice: scaled raw sums; bias / activation / residual belong to the reduce pass
-      float* P = g.partial + ((size_t)blockIdx.y * (size_t)g.M + (size_t)row) * (size_t)g.N;
+    r_rsc[i] = accscale * ((ok && g.a_rs != nullptr) ? g.a_rs[row] : 1.0f);
+    r_ok[i] = ok; r_masked[i] = masked; r_orow[i] = orow;
+  }
+  if (part) {   // split-K slice: scaled raw sums; bias / activation / residual belong to the reduce pass
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+    for (int i = 0; i < 2 * MT; ++i) {
+      if (!r_ok[i]) continue;
+      float* P = g.partial + ((size_t)blockIdx.y * (size_t)g.M + (size_t)(mw + 16 * i + lrow)) * (size_t)g.N;
 #pragma unroll
-        for (int pq = 0; pq < 2; ++pq)
+      for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
-          for (int hf = 0; hf < 2; ++hf) {
-            const int ecol = nw + 32 * j + 16 * pq + lq8 + 4 * hf, r0 = 8 * pq + 4 * hf;
-            if (ecol < g.N)
-              *reinterpret_cast<f32x4*>(P + ecol) = (f32x4){acc[i][j][r0], acc[i][j][r0 + 1], acc[i][j][r0 + 2], acc[i][j][r0 + 3]} * rsc;
-          }
-      continue;
+        for (int hf = 0; hf < 2; ++hf) {
+          const int ecol = nw + 32 * pp + lq8 + 4 * hf;
+          if (ecol < g.N) *reinterpret_cast<f32x4*>(P + ecol) = acc[i][2 * pp + hf] * r_rsc[i];
+        }
     }
-    f32x4 rv[2][2][2];
-    if (g.R != nullptr) {   // all eight residual pieces of the row in flight before the first use
+  }
+  // the four residual pieces of row I -> D; the pieces of row i + 1 are requested BEFORE row i is stored (a lane reads and writes
+  // only its own elements, so R == C is safe), which keeps one row of residual in flight behind every row of stores
+#define GAM_SP_LDR(I, D)                                                                          \
+  _Pragma("unroll") for (int pp = 0; pp < 2; ++pp) _Pragma("unroll") for (int hf = 0; hf < 2; ++hf) { \
+    const int col = nw + 32 * pp + lq8 + 4 * hf;                                                  \
+    D[pp][hf] = (r_ok[I] && col < g.N) ? *reinterpret_cast<const f32x4*>(g.R + r_orow[I] * g.ldr + col) : (f32x4){0.f, 0.f, 0.f, 0.f}; \
+  }
+  f32x4 rv[2][2], rn[2][2];
+  const bool resid = g.R != nullptr && !part;
+  if (resid) GAM_SP_LDR(0, rv);
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+  for (int i = 0; i < 2 * MT; ++i) {
+    if (resid && i + 1 < 2 * MT) GAM_SP_LDR(i + 1, rn);
+    const bool masked = r_masked[i];
+    const long orow = r_orow[i];
+    const float rsc = r_rsc[i];
+    if (r_ok[i] && !part) {
 #pragma unroll
-        for (int pq = 0; pq < 2; ++pq)
-#pragma unroll
-          for (int hf = 0; hf < 2; ++hf) {
-            const int col = nw + 32 * j + 16 * pq + lq8 + 4 * hf;
-            rv[j][pq][hf] = col < g.N ? *reinterpret_cast<const f32x4*>(g.R + orow * g.ldr + col) : (f32x4){0.f, 0.f, 0.f, 0.f};
-          }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int pq = 0; pq < 2; ++pq) {
-        const int ecol = nw + 32 * j + 16 * pq + lq8;      // first of this lane's eight columns
+      for (int pp = 0; pp < 2; ++pp) {
+        const int ecol = nw + 32 * pp + lq8;                 // first of this lane's eight columns
         if (ecol >= g.N) continue;
         const bool both = ecol + 4 < g.N;                    // (N % 8 == 4: the last group has its first half only)
         f32x4 v[2];
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-          const int r0 = 8 * pq + 4 * hf;
-          f32x4 t = (f32x4){acc[i][j][r0], acc[i][j][r0 + 1], acc[i][j][r0 + 2], acc[i][j][r0 + 3]};
-          t = t * rsc + bv[j][pq][hf];
+          f32x4 t = acc[i][2 * pp + hf];
+          t = t * rsc + bv[pp][hf];
           if (ACT == GAM_ACT_SILU) { t.x = gam_silu(t.x); t.y = gam_silu(t.y); t.z = gam_silu(t.z); t.w = gam_silu(t.w); }
           if (ACT == GAM_ACT_RELU) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
           if (masked) t = (f32x4){0.f, 0.f, 0.f, 0.f};
           t = t * g.alpha;
-          if (g.R != nullptr) t += rv[j][pq][hf];
+          if (resid) t += rv[pp][hf];
           if (!both && hf == 1) t = (f32x4){0.f, 0.f, 0.f, 0.f};
           v[hf] = t;
         }
@@ -491,7 +534,15 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
           if (both) *reinterpret_cast<f32x4*>(g.C + orow * g.ldc + ecol + 4) = v[1];
         }
       }
+    }
+    if (resid && i + 1 < 2 * MT) {
+#pragma unroll
+      for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) rv[pp][hf] = rn[pp][hf];
+    }
   }
+#undef GAM_SP_LDR
 #if GAM_SP_INSTRUMENT
   if (GAM_SP_DBG(g) & 16) { __builtin_amdgcn_s_waitcnt(0x0070); __syncthreads(); }   // stores issued AND acknowledged by every wave
   GAM_SP_TL(3);

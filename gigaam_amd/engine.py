@@ -1307,16 +1307,20 @@ class HipEngine:
         self._check(rc, "gam_rnnt_joint")
         return out
 
-    def op_gemm(self, a: Tensor, w: Tensor, bias: Optional[Tensor] = None, act: int = 0) -> Tensor:
+    def op_gemm(self, a: Tensor, w: Tensor, bias: Optional[Tensor] = None, act: int = 0, resid: Optional[Tensor] = None,
+                alpha: float = 1.0) -> Tensor:
+        """alpha * act(a @ w.T + bias) + resid (the encoder's residual epilogue when ``resid`` is given)."""
         a = self._dev(a, torch.float32)
         w = self._dev(w, torch.float32)
         bias = None if bias is None else self._dev(bias, torch.float32)
+        resid = None if resid is None else self._dev(resid, torch.float32)
         m, k = a.shape
         n = w.shape[0]
         out = torch.empty((m, n), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            rc = self.lib.gam_op_gemm(self._h, _ptr(a), _ptr(w), _ptr(bias), _ptr(out), m, n, k, act, self._stream())
-        self._check(rc, "gam_op_gemm")
+            rc = self.lib.gam_op_gemm_ex(self._h, _ptr(a), _ptr(w), _ptr(bias), _ptr(resid), alpha, _ptr(out), m, n, k, act,
+                                         self._stream())
+        self._check(rc, "gam_op_gemm_ex")
         return out
 
     def op_attention(self, q: Tensor, k: Tensor, v: Tensor, lens: Optional[Tensor] = None) -> Tensor:

@@ -396,7 +396,7 @@ int gam_emo_probs(gam_handle* h, const float* encoded, const int32_t* enc_len, i
 
 /* Arithmetic of the dense contractions (every other kernel is plain fp32):
  *   GAM_GEMM_F32   -- v_mfma_f32_32x32x2_f32, bit-for-bit an fp32 fmaf chain.
- *   GAM_GEMM_F16X3 -- three-term split on v_mfma_f32_32x32x16_f16 with fp32 accumulation
+ *   GAM_GEMM_F16X3 -- three-term split on v_mfma_f32_16x16x32_f16 with fp32 accumulation
  *                     (a = a_hi + a_lo, w = w_hi + w_lo; the a_lo.w_lo term, ~2^-22 relative,
  *                     is dropped): fp32-equivalent accuracy at several times the rate.
  *   GAM_GEMM_F16   -- OPT-IN speed mode (r04), never the default: ONE fp16 MFMA per product on plain-fp16 operands (the
@@ -429,6 +429,11 @@ int gam_get_gemm_mode(const gam_handle* h);
  * C[M,N] = act(A[M,K] . W[N,K]^T + bias) (act: 0 none, 1 SiLU, 2 ReLU); K % 32 == 0. */
 int gam_op_gemm(gam_handle* h, const float* A, const float* W, const float* bias, float* C,
                 int M, int N, int K, int act, void* stream);
+/* Kernel-level test entry like gam_op_gemm, with the encoder's residual epilogue: C = alpha * act(A . W^T + bias) + R
+ * (R f32 [M,N] dense, row pitch N, or NULL).  R is handed to the launchers as given: the split-fp16 kernel's launcher rejects
+ * an R that is not 16-byte aligned (the call fails, nothing is launched); the exact-fp32 kernel reads it element-wise. */
+int gam_op_gemm_ex(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha,
+                   float* C, int M, int N, int K, int act, void* stream);
 
 /* Raw attention entry for kernel-level tests: q, k, v, ctx f32 [B*T, H*48] token-major
  * (head h = columns 48h..48h+47), lens i32 [B] valid keys per utterance or NULL (no mask);
