@@ -6,8 +6,13 @@ CPU fallback, and every method raises if the library or the GPU call fails.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-from typing import Any, Dict, Mapping, Optional, Tuple
+import functools
+import math
+import os
+import threading
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -79,7 +84,132 @@ _DTYPES = {
 }
 
 
-class Decoded(tuple):
+_I32, _F32, _F64 = torch.int32, torch.float32, torch.float64
+_NP_DTYPES = {_I32: np.int32, _F32: np.float32, _F64: np.float64}
+
+
+class _Layout:
+    """The fields of ONE i32 buffer, stated ONCE per class: ``DIMS`` names the dimensions, ``FIELDS`` lists (name, shape, dtype) in buffer
+    order -- the shape in names of dimensions or plain ints; the dtype i32, or f32 / f64 whose bits lie in the i32 words (an f64 field
+    must start on an even word).  A fourth entry names a dimension: where that is false the field is absent (no words, None).  From
+    that one statement come the words to allocate (``words``), the views of the device buffer and the same views of its numpy copy
+    on the host (``views``): the three cannot disagree."""
+    DIMS: Tuple[str, ...] = ()
+    FIELDS: Tuple[tuple, ...] = ()
+
+    @classmethod
+    def _dims(cls, *dims) -> Dict[str, int]:
+        return dict(zip(cls.DIMS, dims))
+
+    @classmethod
+    @functools.lru_cache(maxsize=256)      # (a decode loop asks for the same few dimensions again and again)
+    def layout(cls, *dims) -> Tuple[Tuple[tuple, ...], Tuple[int, ...], int]:
+        """(((name, first word, words, shape or None, dtype), ...) in buffer order, the words of each, words of the whole buffer)"""
+        d, fields, o = cls._dims(*dims), [], 0
+        for name, shape, dtype, *present in cls.FIELDS:
+            if present and not d[present[0]]:
+                fields.append((name, o, 0, None, dtype))
+                continue
+            shape = tuple(s if isinstance(s, int) else d[s] for s in shape)
+            n = math.prod(shape) * (2 if dtype is _F64 else 1)
+            if dtype is _F64 and o % 2:
+                raise GigaAMHipError(f"{cls.__name__}.{name}: an f64 field must start on an even word, not {o}")
+            fields.append((name, o, n, shape, dtype))
+            o += n
+        return tuple(fields), tuple(f[2] for f in fields), o
+
+    @classmethod
+    def words(cls, *dims) -> int:
+        return cls.layout(*dims)[2]
+
+    @staticmethod
+    def views(layout: tuple, buf) -> Dict[str, Any]:
+        """{name: its words of ``buf`` in its dtype and shape} -- ``buf`` the device buffer or its numpy copy on the host."""
+        fields, sizes, words = layout
+        on_host, out = isinstance(buf, np.ndarray), {}
+        if on_host:
+            parts = [buf[o: o + n] for _, o, n, _, _ in fields]
+        else:       # (ONE split for all the fields: a slice each is a torch call each, and those are what building a result costs)
+            parts = (buf if buf.shape[0] == words else buf[:words]).split_with_sizes(sizes)
+        for (name, _, _, shape, dtype), v in zip(fields, parts):
+            if shape is None:
+                out[name] = None
+                continue
+            if dtype is not _I32:
+                v = v.view(_NP_DTYPES[dtype] if on_host else dtype)
+            if len(shape) > 1:
+                v = v.reshape(shape) if on_host else v.view(shape)
+            out[name] = v
+        return out
+
+
+class _Packed(_Layout):
+    """A decode result whose outputs are views of ONE i32 device buffer (constructor: the buffer, then ``DIMS``, which become
+    attributes), so that it reaches the host in one copy; its flag word is the one-word field ``ext``."""
+
+    @classmethod
+    def empty(cls, device, *dims, **kw):
+        """Allocate the buffer for ``dims`` on ``device`` and construct the result over it."""
+        return cls(torch.empty((cls.words(*dims),), dtype=_I32, device=device), *dims, **kw)
+
+    def flag_word(self) -> Tensor:
+        """The device word (i32 [1]) that receives the range flag."""
+        return self.ext
+
+    def _bind(self, buf: Tensor, *dims) -> None:
+        self._layout = self.layout(*dims)
+        self.__dict__.update(zip(self.DIMS, dims))
+        self.__dict__.update(self.views(self._layout, buf))
+
+    def _host_fields(self, buf: Tensor, **more: Tensor) -> Dict[str, Any]:
+        """One blocking D2H of ``buf`` (and of each tensor of ``more``, a copy each under its own name) -> its fields as numpy views
+        of the one host array, with ``flag`` in place of the flag word ``ext``."""
+        arr, *rest = _to_host((buf, *more.values()), self.event)
+        h = self.views(self._layout, arr)
+        flag = HipEngine._flag_of(int(h.pop("ext")[-1]))
+        if more:
+            h.update(zip(more, rest))
+        h["flag"] = flag
+        return h
+
+
+def _to_host(tensors: Sequence[Tensor], event, then: Optional[Callable[[List[np.ndarray]], Sequence[Tensor]]] = None,
+             also_record: Sequence[Tensor] = ()) -> List[np.ndarray]:
+    """THE device-to-host path of every decode result: blocking copies of ``tensors`` on the device's collect stream
+    (``aux_streams``: a queue of its own), which waits for ``event`` -- the result's own completion, not whatever the caller has
+    enqueued since (see ``_fetch_flag``) -- or, without one, for the caller's current stream; then ``record_stream`` on each
+    (allocated on the launch stream, last read on this one).  ``then(arrays)``: further tensors to copy behind the same wait, for
+    a result whose first block tells how much of the rest is worth copying; it runs with the collect stream current, what it
+    makes there needs no ``record_stream``, and what it reads there is named in ``also_record``.  CPU tensors are returned as
+    they are (``.numpy()``), no stream is touched."""
+    if not tensors[0].is_cuda:
+        out = [t.numpy() for t in tensors]
+        return out + [t.numpy() for t in then(out)] if then else out
+    dev = tensors[0].device
+    side = HipEngine._collect_stream(dev)
+    launch = torch.cuda.current_stream(dev) if event is None else None     # (here: inside the block below the current stream is ``side``)
+    with torch.cuda.stream(side):
+        if event is not None:
+            side.wait_event(event)
+        else:
+            side.wait_stream(launch)
+        out = [t.cpu().numpy() for t in tensors]
+        if then:
+            out += [t.cpu().numpy() for t in then(out)]
+    for t in tensors:
+        t.record_stream(side)
+    for t in also_record:
+        t.record_stream(side)
+    return out
+
+
+def _rows(ids_a: np.ndarray, fr_a: np.ndarray, counts: List[int]) -> List[Tuple[List[int], List[int]]]:
+    """[(ids, frames)] host lists of the first ``counts[i]`` columns of row i (numpy row slices convert to lists at half the cost of
+    per-row Tensor.tolist(): 0.33 -> 0.17 ms at 32 x 502)."""
+    return [(ids_a[i, :c].tolist(), fr_a[i, :c].tolist()) for i, c in enumerate(counts)]
+
+
+class Decoded(tuple, _Layout):
     """What ``ctc_greedy`` / ``rnnt_greedy`` return.  Unpacks as ``(ids, frames, counts)`` (``+ (dump, dump_count)`` when a
     logits dump was asked for) and carries the decode's two hidden companions as EXPLICIT fields -- they used to hang off the
     ``counts`` view as Python attributes, which any ``torch.cat`` / slice / unpack-and-repack dropped silently (ADVICE r3,
@@ -93,6 +223,13 @@ class Decoded(tuple):
 
     Pass the object itself to ``HipEngine.collect`` / ``shard.range_flag_of``; three bare tensors are accepted too, but then
     nothing is known about a flag or an event (a plain blocking copy on the current stream)."""
+    DIMS = ("b", "cap")
+    # ids | frames | counts + flag word: the prefix ``collect`` reads, of the greedy decodes' buffer and of ``BeamDecoded``'s
+    FIELDS = (("ids", ("b", "cap"), _I32), ("frames", ("b", "cap"), _I32), ("ext", ("b1",), _I32))
+
+    @classmethod
+    def _dims(cls, b: int, cap: int) -> Dict[str, int]:
+        return {"b": b, "cap": cap, "b1": b + 1}
 
     def __new__(cls, ids: Tensor, frames: Tensor, counts: Tensor, ext: Optional[Tensor] = None, event=None, stream=None,
                 dump: Optional[Tensor] = None, dump_count: Optional[Tensor] = None, whole: Optional[Tensor] = None):
@@ -103,6 +240,14 @@ class Decoded(tuple):
         self.whole = whole
         return self
 
+    @staticmethod
+    def packed(device, b: int, cap: int) -> "Decoded":
+        """A greedy decode's result over ONE new buffer for ``cap`` tokens per utterance (``whole``); no event yet."""
+        _, sizes, words = Decoded.layout(b, cap)
+        whole = torch.empty((words,), dtype=_I32, device=device)
+        ids, frames, ext = whole.split_with_sizes(sizes)      # (FIELDS' three, without ``views``' dict: bench.py's step makes this call)
+        return Decoded(ids.view(b, cap), frames.view(b, cap), ext[:b], ext, whole=whole)
+
     ids = property(lambda self: self[0])
     frames = property(lambda self: self[1])
     counts = property(lambda self: self[2])
@@ -112,279 +257,178 @@ class Decoded(tuple):
         return None if self.ext is None else self.ext[-1:]
 
 
-class Aligned:
+class Aligned(_Packed):
     """What ``ctc_align`` / ``op_ctc_align`` return: every output of the alignment kernel as a view of ONE i32 device buffer
     (``whole``) that reaches the host in ONE copy (``host``), like ``Decoded.whole``.  Layout: frame_labels [B, T'] | tok_first
     [B, Umax] | tok_last [B, Umax] | status [B] | score [B] (f32 bits) | loglik [B] (f32 bits) | range flag word."""
+    DIMS = ("b", "tp", "umax")
+    FIELDS = (("frame_labels", ("b", "tp"), _I32), ("tok_first", ("b", "umax"), _I32), ("tok_last", ("b", "umax"), _I32),
+              ("status", ("b",), _I32), ("score", ("b",), _F32), ("loglik", ("b",), _F32), ("ext", (1,), _I32))
 
     def __init__(self, whole: Tensor, b: int, tp: int, umax: int, event=None, stream=None):
-        self.whole, self.b, self.tp, self.umax, self.event, self.stream = whole, b, tp, umax, event, stream
-        o = 0
-
-        def take(n: int) -> Tensor:
-            nonlocal o
-            o += n
-            return whole[o - n: o]
-
-        self.frame_labels = take(b * tp).view(b, tp)
-        self.tok_first = take(b * umax).view(b, umax)
-        self.tok_last = take(b * umax).view(b, umax)
-        self.status = take(b)
-        self.score = take(b).view(torch.float32)
-        self.loglik = take(b).view(torch.float32)
-        self.ext = take(1)
+        self.whole, self.event, self.stream = whole, event, stream
+        self._bind(whole, b, tp, umax)
 
     def host(self) -> Dict[str, Any]:
         """One blocking D2H of the whole result, on the collect stream behind the alignment's own completion event -> numpy arrays
         (``frame_labels``, ``tok_first``, ``tok_last``, ``status``, ``score``, ``loglik``) and ``flag`` (the split-fp16
         range flag of the encoder run that produced the log-probs: True = repeat under GAM_GEMM_F32)."""
-        side = HipEngine._collect_stream(self.whole.device)
-        with torch.cuda.stream(side):
-            if self.event is not None:
-                side.wait_event(self.event)
-            else:
-                side.wait_stream(torch.cuda.current_stream(self.whole.device))
-            arr = self.whole.cpu().numpy()
-        self.whole.record_stream(side)
-        b, tp, um = self.b, self.tp, self.umax
-        o = [0]
-
-        def take(n: int):
-            o[0] += n
-            return arr[o[0] - n: o[0]]
-
-        out = {"frame_labels": take(b * tp).reshape(b, tp), "tok_first": take(b * um).reshape(b, um),
-               "tok_last": take(b * um).reshape(b, um), "status": take(b),
-               "score": take(b).view(np.float32), "loglik": take(b).view(np.float32)}
-        out["flag"] = HipEngine._flag_of(int(take(1)[0]))
-        return out
+        return self._host_fields(self.whole)
 
 
-class KeywordHits:
+class KeywordHits(_Packed):
     """What ``ctc_kws`` / ``op_ctc_kws`` return: the hits of every (utterance, keyword) pair as views of ONE i32 device buffer
     (``whole``) that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: n_hits [B, K] | hit_frames [B, K, H, 2]
     (start, end) | hit_score [B, K, H] (f32 bits) | range flag word.  ``dense_score`` f32 / ``dense_start`` i32 [B, K, T'] (the
     per-frame E_t / S_t of gam_kws.h) are tensors of their own, present only when they were asked for."""
+    DIMS = ("b", "k", "max_hits")
+    FIELDS = (("n_hits", ("b", "k"), _I32), ("hit_frames", ("b", "k", "h", 2), _I32), ("hit_score", ("b", "k", "h"), _F32),
+              ("ext", (1,), _I32))
+
+    @classmethod
+    def _dims(cls, b: int, k: int, max_hits: int) -> Dict[str, int]:
+        # (max_hits outside [1, 64] is the library's error; the buffers only must not be negative.  The attribute keeps the caller's value)
+        return {"b": b, "k": k, "h": max(max_hits, 0)}
 
     def __init__(self, whole: Tensor, b: int, k: int, max_hits: int, dense_score: Optional[Tensor] = None,
                  dense_start: Optional[Tensor] = None, event=None, stream=None):
-        self.whole, self.b, self.k, self.max_hits, self.event, self.stream = whole, b, k, max_hits, event, stream
+        self.whole, self.event, self.stream = whole, event, stream
         self.dense_score, self.dense_start = dense_score, dense_start
-        n = b * k
-        self.n_hits = whole[:n].view(b, k)
-        mh = max(max_hits, 0)
-        self.hit_frames = whole[n: n + 2 * n * mh].view(b, k, mh, 2)
-        self.hit_score = whole[n + 2 * n * mh: n + 3 * n * mh].view(torch.float32).view(b, k, mh)
-        self.ext = whole[n + 3 * n * mh:]
+        self._bind(whole, b, k, max_hits)
 
     def host(self) -> Dict[str, Any]:
         """One blocking D2H of the hits, on the collect stream behind the search's own completion event -> numpy arrays ``n_hits``
         [B, K], ``hit_frames`` [B, K, H, 2], ``hit_score`` [B, K, H] and ``flag`` (the split-fp16 range flag of the encoder run that
         produced the log-probs: True = repeat under GAM_GEMM_F32).  With dense outputs: ``dense_score`` / ``dense_start`` too (a
         copy each).  Never the log-probs."""
-        side = HipEngine._collect_stream(self.whole.device)
-        with torch.cuda.stream(side):
-            if self.event is not None:
-                side.wait_event(self.event)
-            else:
-                side.wait_stream(torch.cuda.current_stream(self.whole.device))
-            arr = self.whole.cpu().numpy()
-            dense = [None if t is None else t.cpu().numpy() for t in (self.dense_score, self.dense_start)]
-        for t in (self.whole, self.dense_score, self.dense_start):
-            if t is not None:
-                t.record_stream(side)
-        b, k, mh = self.b, self.k, self.max_hits
-        n = b * k
-        out = {"n_hits": arr[:n].reshape(b, k), "hit_frames": arr[n: n + 2 * n * mh].reshape(b, k, mh, 2),
-               "hit_score": arr[n + 2 * n * mh: n + 3 * n * mh].view(np.float32).reshape(b, k, mh)}
-        if dense[0] is not None:
-            out["dense_score"], out["dense_start"] = dense
-        out["flag"] = HipEngine._flag_of(int(arr[-1]))
-        return out
+        if self.dense_score is None:
+            return self._host_fields(self.whole)
+        return self._host_fields(self.whole, dense_score=self.dense_score, dense_start=self.dense_start)
 
 
-class AlignedLong:
+class AlignedLong(_Packed):
     """What ``op_ctc_align_long`` returns: every output of the long-utterance alignment as a view of ONE i32 device buffer (``whole``)
     that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: score (f64 bits, 2 words) | loglik (f64 bits, 2 words) |
     status | range flag word | frame_labels [T] | tok_first [U] | tok_last [U]."""
+    DIMS = ("t", "u")
+    FIELDS = (("score", (1,), _F64), ("loglik", (1,), _F64), ("status", (1,), _I32), ("ext", (1,), _I32),
+              ("frame_labels", ("t",), _I32), ("tok_first", ("u",), _I32), ("tok_last", ("u",), _I32))
 
     def __init__(self, whole: Tensor, t: int, u: int, event=None, stream=None):
-        self.whole, self.t, self.u, self.event, self.stream = whole, t, u, event, stream
-        self.score = whole[0:2].view(torch.float64)
-        self.loglik = whole[2:4].view(torch.float64)
-        self.status = whole[4:5]
-        self.ext = whole[5:6]
-        self.frame_labels = whole[6: 6 + t]
-        self.tok_first = whole[6 + t: 6 + t + u]
-        self.tok_last = whole[6 + t + u: 6 + t + 2 * u]
+        self.whole, self.event, self.stream = whole, event, stream
+        self._bind(whole, t, u)
 
     def host(self) -> Dict[str, Any]:
         """One blocking D2H of the whole result, on the collect stream behind the alignment's own completion event -> ``frame_labels``,
         ``tok_first``, ``tok_last`` (numpy i32), ``status`` (int), ``score`` / ``loglik`` (Python floats from the float64 outputs) and
         ``flag`` (as ``Aligned.host``)."""
-        side = HipEngine._collect_stream(self.whole.device)
-        with torch.cuda.stream(side):
-            if self.event is not None:
-                side.wait_event(self.event)
-            else:
-                side.wait_stream(torch.cuda.current_stream(self.whole.device))
-            arr = self.whole.cpu().numpy()
-        self.whole.record_stream(side)
-        t, u = self.t, self.u
-        return {"score": float(arr[0:2].view(np.float64)[0]), "loglik": float(arr[2:4].view(np.float64)[0]), "status": int(arr[4]),
-                "flag": HipEngine._flag_of(int(arr[5])), "frame_labels": arr[6: 6 + t], "tok_first": arr[6 + t: 6 + t + u],
-                "tok_last": arr[6 + t + u: 6 + t + 2 * u]}
+        h = self._host_fields(self.whole)
+        h["score"], h["loglik"], h["status"] = float(h["score"][0]), float(h["loglik"][0]), int(h["status"][0])
+        return h
 
 
-class RnntAligned:
+class RnntAligned(_Packed):
     """What ``rnnt_align`` / ``op_rnnt_align`` / ``op_rnnt_lattice_align`` return: every output of the transducer alignment as a view of
     ONE i32 device buffer (``whole``) that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: tok_frame [B, Umax] |
     status [B] | score [B] (f32 bits) | loglik [B] (f32 bits) | range flag word.  ``lattice`` (``op_rnnt_align(want_lattice=True)``):
     the (log P(blank), log P(next token)) lattice f32 [B, T', Umax + 1, 2] on the device."""
+    DIMS = ("b", "umax")
+    FIELDS = (("tok_frame", ("b", "umax"), _I32), ("status", ("b",), _I32), ("score", ("b",), _F32), ("loglik", ("b",), _F32),
+              ("ext", (1,), _I32))
 
     def __init__(self, whole: Tensor, b: int, umax: int, event=None, stream=None):
-        self.whole, self.b, self.umax, self.event, self.stream = whole, b, umax, event, stream
+        self.whole, self.event, self.stream = whole, event, stream
         self.lattice: Optional[Tensor] = None
-        self.tok_frame = whole[: b * umax].view(b, umax)
-        o = b * umax
-        self.status = whole[o: o + b]
-        self.score = whole[o + b: o + 2 * b].view(torch.float32)
-        self.loglik = whole[o + 2 * b: o + 3 * b].view(torch.float32)
-        self.ext = whole[o + 3 * b: o + 3 * b + 1]
+        self._bind(whole, b, umax)
 
     def host(self) -> Dict[str, Any]:
         """One blocking D2H of the whole result, on the collect stream behind the alignment's own completion event -> numpy arrays
         (``tok_frame``, ``status``, ``score``, ``loglik``) and ``flag`` (the split-fp16 range flag, as ``Aligned.host``)."""
-        side = HipEngine._collect_stream(self.whole.device)
-        with torch.cuda.stream(side):
-            if self.event is not None:
-                side.wait_event(self.event)
-            else:
-                side.wait_stream(torch.cuda.current_stream(self.whole.device))
-            arr = self.whole.cpu().numpy()
-        self.whole.record_stream(side)
-        b, um = self.b, self.umax
-        o = b * um
-        return {"tok_frame": arr[:o].reshape(b, um), "status": arr[o: o + b], "score": arr[o + b: o + 2 * b].view(np.float32),
-                "loglik": arr[o + 2 * b: o + 3 * b].view(np.float32), "flag": HipEngine._flag_of(int(arr[o + 3 * b]))}
+        return self._host_fields(self.whole)
 
 
-class Confidence:
+class Confidence(_Packed):
     """What ``ctc_confidence`` / ``op_ctc_confidence`` / ``rnnt_confidence`` / ``op_rnnt_confidence`` return: the token confidences of a
     finished decode as views of ONE i32 device buffer (``whole``) that reaches the host in ONE copy (``host``), like ``Aligned``.
     Layout: conf [B, cap] (f32 bits) | span [B, cap] (CTC only) | status [B] | range flag word."""
+    DIMS = ("b", "cap", "has_span")
+    FIELDS = (("conf", ("b", "cap"), _F32), ("span", ("b", "cap"), _I32, "has_span"), ("status", ("b",), _I32), ("ext", (1,), _I32))
 
     def __init__(self, whole: Tensor, b: int, cap: int, has_span: bool, event=None, stream=None):
-        self.whole, self.b, self.cap, self.has_span, self.event, self.stream = whole, b, cap, has_span, event, stream
-        n = b * cap
-        self.conf = whole[:n].view(torch.float32).view(b, cap)
-        self.span = whole[n: 2 * n].view(b, cap) if has_span else None
-        o = 2 * n if has_span else n
-        self.status = whole[o: o + b]
-        self.ext = whole[o + b: o + b + 1]
+        self.whole, self.event, self.stream = whole, event, stream
+        self._bind(whole, b, cap, has_span)
 
     def host(self) -> Dict[str, Any]:
         """One blocking D2H of the whole result, on the collect stream behind the pass's own completion event -> numpy arrays
         (``conf`` f32 [B, cap], ``span`` i32 [B, cap] or None, ``status`` i32 [B]) and ``flag`` (the split-fp16 range flag, as
         ``Aligned.host``)."""
-        side = HipEngine._collect_stream(self.whole.device)
-        with torch.cuda.stream(side):
-            if self.event is not None:
-                side.wait_event(self.event)
-            else:
-                side.wait_stream(torch.cuda.current_stream(self.whole.device))
-            arr = self.whole.cpu().numpy()
-        self.whole.record_stream(side)
-        b, n = self.b, self.b * self.cap
-        o = 2 * n if self.has_span else n
-        return {"conf": arr[:n].view(np.float32).reshape(b, self.cap), "span": arr[n: 2 * n].reshape(b, self.cap) if self.has_span else None,
-                "status": arr[o: o + b], "flag": HipEngine._flag_of(int(arr[o + b]))}
+        return self._host_fields(self.whole)
 
 
-class BeamDecoded(Decoded):
+class BeamDecoded(Decoded, _Packed):
     """What ``ctc_beam`` / ``op_ctc_beam`` / ``rnnt_beam`` / ``op_rnnt_beam`` return: a ``Decoded`` (ids, frames, counts + range flag word: ``collect``, ``finish`` and the
     word builder take it as they take a greedy decode) whose buffer goes on with ``score`` and ``logp`` f32 [B] (``buf``: ids [B, cap] |
     frames [B, cap] | counts [B] | flag word | score bits [B] | logp bits [B]).  ``host`` brings all of it to the host in ONE copy."""
+    FIELDS = Decoded.FIELDS + (("score", ("b",), _F32), ("logp", ("b",), _F32))
 
     def __new__(cls, buf: Tensor, b: int, tp: int, event=None, stream=None):
         # (tp: the width of ids / frames -- T' for CTC, T' * max_symbols for RNN-T)
-        n0 = 2 * b * tp + b + 1
-        ids, frames, ext = buf[: b * tp].view(b, tp), buf[b * tp: 2 * b * tp].view(b, tp), buf[2 * b * tp: n0]
-        self = Decoded.__new__(cls, ids, frames, ext[:b], ext, event, stream, whole=buf[:n0])
-        self.buf = buf
-        self.score = buf[n0: n0 + b].view(torch.float32)
-        self.logp = buf[n0 + b: n0 + 2 * b].view(torch.float32)
+        layout = cls.layout(b, tp)
+        v = cls.views(layout, buf)
+        self = Decoded.__new__(cls, v["ids"], v["frames"], v["ext"][:b], v["ext"], event, stream, whole=buf[: Decoded.words(b, tp)])
+        self.buf, self.score, self.logp, self._layout = buf, v["score"], v["logp"], layout
         return self
 
     def host(self) -> Dict[str, Any]:
         """One blocking D2H of the whole result, on the collect stream behind the beam search's own completion event -> ``rows``
         [(ids, frames)] host lists, ``score`` / ``logp`` numpy f32 [B] and ``flag`` (the split-fp16 range flag, as ``collect``)."""
-        side = HipEngine._collect_stream(self.buf.device)
-        with torch.cuda.stream(side):
-            if self.event is not None:
-                side.wait_event(self.event)
-            else:
-                side.wait_stream(torch.cuda.current_stream(self.buf.device))
-            arr = self.buf.cpu().numpy()
-        self.buf.record_stream(side)
-        b, tp = self.ids.shape
-        n0 = 2 * b * tp + b + 1
-        n = arr[2 * b * tp: n0 - 1].tolist()
-        ids_h, fr_h = arr[: b * tp].reshape(b, tp), arr[b * tp: 2 * b * tp].reshape(b, tp)
-        return {"rows": [(ids_h[i, :c].tolist(), fr_h[i, :c].tolist()) for i, c in enumerate(n)],
-                "score": arr[n0: n0 + b].view(np.float32).copy(), "logp": arr[n0 + b: n0 + 2 * b].view(np.float32).copy(),
-                "flag": HipEngine._flag_of(int(arr[n0 - 1]))}
+        arr, = _to_host((self.buf,), self.event)
+        h = self.views(self._layout, arr)
+        n = h["ext"].tolist()
+        flag = HipEngine._flag_of(n.pop())
+        return {"rows": _rows(h["ids"], h["frames"], n), "score": h["score"].copy(), "logp": h["logp"].copy(), "flag": flag}
 
 
-class NBestDecoded:
+class NBestDecoded(_Packed):
     """What ``ctc_beam_nbest`` / ``op_ctc_beam_nbest`` / ``rnnt_beam_nbest`` / ``op_rnnt_beam_nbest`` return: the ``n`` best hypotheses
     of each final beam, on the device.  ``ids`` / ``frames`` i32 [B, n, cap]; the small block ``small`` is ONE i32 buffer: n_hyp [B] |
     counts [B, n] | score bits [B, n] | logp bits [B, n] | range flag word.  Row 0 of every utterance is the 1-best search's result."""
+    DIMS = ("b", "n")
+    FIELDS = (("n_hyp", ("b",), _I32), ("counts", ("b", "n"), _I32), ("score", ("b", "n"), _F32), ("logp", ("b", "n"), _F32),
+              ("ext", (1,), _I32))
 
     def __init__(self, tok: Tensor, small: Tensor, event=None, stream=None):
         # (tok: i32 [2, B, n, cap], ids | frames)
         _, b, n, cap = tok.shape
-        self.tok, self.ids, self.frames, self.small, self.b, self.n, self.cap = tok, tok[0], tok[1], small, b, n, cap
+        self.tok, self.ids, self.frames, self.small, self.cap = tok, tok[0], tok[1], small, cap
         self.event, self.stream = event, stream
-        bn = b * n
-        self.n_hyp = small[:b]
-        self.counts = small[b: b + bn].view(b, n)
-        self.score = small[b + bn: b + 2 * bn].view(torch.float32).view(b, n)
-        self.logp = small[b + 2 * bn: b + 3 * bn].view(torch.float32).view(b, n)
-        self.ext = small[b + 3 * bn: b + 3 * bn + 1]
+        self._bind(small, b, n)
         self.copied_bytes = 0     # what the last ``host()`` brought over
 
-    def flag_word(self) -> Tensor:
-        return self.ext
+    @classmethod
+    def empty(cls, device, b: int, n: int, cap: int) -> "NBestDecoded":
+        return cls(torch.empty((2, b, n, cap), dtype=_I32, device=device), torch.empty((cls.words(b, n),), dtype=_I32, device=device))
 
     def host(self) -> Dict[str, Any]:
         """At most TWO blocking D2H copies, on the collect stream behind the search's own completion event: the small block, then
         columns [0, longest hypothesis) of ids | frames ([B, n, cap] can be tens of MB for RNN-T and is never copied whole) ->
         ``rows`` [b][r] = (ids, frames) host lists for r < n_hyp[b], ``score`` / ``logp`` numpy f32 [B, n] (-inf past n_hyp),
         ``n_hyp`` numpy i32 [B] and ``flag`` (the split-fp16 range flag, as ``collect``)."""
-        side = HipEngine._collect_stream(self.small.device)
-        b, n, bn = self.b, self.n, self.b * self.n
-        with torch.cuda.stream(side):
-            if self.event is not None:
-                side.wait_event(self.event)
-            else:
-                side.wait_stream(torch.cuda.current_stream(self.small.device))
-            arr = self.small.cpu().numpy()
-            self.copied_bytes = arr.nbytes
-            n_hyp = arr[:b].copy()
-            counts = arr[b: b + bn].reshape(b, n)
-            m = int(counts.max()) if bn else 0
-            tok = None
-            if m > 0:
-                tok = self.tok[..., :m].contiguous().cpu().numpy()
-                self.copied_bytes += tok.nbytes
-        for t in (self.small, self.tok):
-            t.record_stream(side)
-        rows = [[(tok[0, i, r, :counts[i, r]].tolist(), tok[1, i, r, :counts[i, r]].tolist()) if counts[i, r] else ([], [])
-                 for r in range(int(n_hyp[i]))] for i in range(b)]
-        return {"rows": rows, "score": arr[b + bn: b + 2 * bn].view(np.float32).reshape(b, n).copy(),
-                "logp": arr[b + 2 * bn: b + 3 * bn].view(np.float32).reshape(b, n).copy(), "n_hyp": n_hyp,
-                "flag": HipEngine._flag_of(int(arr[b + 3 * bn]))}
+        h: Dict[str, Any] = {}
+
+        def used_columns(arrs: List[np.ndarray]) -> List[Tensor]:
+            h.update(self.views(self._layout, arrs[0]))
+            m = int(h["counts"].max()) if h["counts"].size else 0
+            return [self.tok[..., :m].contiguous()] if m > 0 else []
+
+        arr, *tok = _to_host((self.small,), self.event, then=used_columns, also_record=(self.tok,))
+        tok = tok[0] if tok else None
+        self.copied_bytes = arr.nbytes + (0 if tok is None else tok.nbytes)
+        n_hyp, counts = h["n_hyp"].copy(), h["counts"].tolist()      # (lists: a numpy scalar per index costs more than the row it cuts)
+        rows = [[(tok[0, i, r, :c].tolist(), tok[1, i, r, :c].tolist()) if c else ([], []) for r, c in enumerate(counts[i][:nh])]
+                for i, nh in enumerate(n_hyp.tolist())]
+        return {"rows": rows, "score": h["score"].copy(), "logp": h["logp"].copy(), "n_hyp": n_hyp,
+                "flag": HipEngine._flag_of(int(h["ext"][0]))}
 
 
 def _ptr(t: Optional[Tensor]) -> C.c_void_p:
@@ -416,7 +460,6 @@ class HipEngine:
             rc = self.lib.gam_set_weight(self._h, key.encode(), C.c_void_p(t.data_ptr()), _DTYPES[t.dtype], shape, t.dim())
             self._check(rc, f"gam_set_weight({key})")
         self._check(self.lib.gam_finalize(self._h), "gam_finalize")
-        import os
         # the cluster size in force outside an overlapped decode: what gam_create read from the environment (clamped like it does), then
         # whatever the caller set through set_rnnt_cluster -- an overlapped decode restores THIS, not the environment's value
         self._rnnt_cluster_user = max(-1, min(8, int(os.environ.get("GAM_RNNT_CLUSTER", "-1"))))
@@ -464,30 +507,57 @@ class HipEngine:
             self._check(self.lib.gam_range_flag(self._h, C.byref(out), self._stream()), "gam_range_flag")
         return self._flag_of(out.value)
 
-    def _counts_with_flag(self, b: int) -> Tuple[Tensor, Tensor]:
-        """counts i32 [b] as a view of a [b + 1] buffer whose last element receives the range flag
-        (gam_range_flag_fetch) -- ``collect`` then brings both to the host in ONE copy."""
-        ext = torch.empty((b + 1,), dtype=torch.int32, device=self.device)
-        return ext[:b], ext
-
-    def _fetch_flag(self, ext: Tensor):
-        """Move the range flag into ``ext``'s tail word and record "this decode is complete" on the stream it ran on;
-        returns (event, stream) for the ``Decoded`` object.  ``collect`` waits for the event on a side stream, so a caller
+    def _fetch_flag(self, word: Tensor):
+        """Move the range flag into ``word`` (the result's ``flag_word()``, i32 [1]) and record "this decode is complete" on the
+        stream it ran on; returns (event, stream) for the result object.  ``collect`` waits for the event on a side stream, so a caller
         that has already launched the next batch (model.transcribe_longform, shard.run_sharded, bench.py configs 4 / 5) is not
         held until that next batch has finished too -- a ``.cpu()`` on the launch stream is ordered behind everything enqueued
         there, which made the "launch n, then collect n-1" pipelines wait for batch n (measured: +3.9 ms per 33 ms step)."""
-        rc = self.lib.gam_range_flag_fetch(self._h, C.c_void_p(ext.data_ptr() + 4 * (ext.numel() - 1)), self._stream())
+        rc = self.lib.gam_range_flag_fetch(self._h, _ptr(word), self._stream())
         self._check(rc, "gam_range_flag_fetch")
         st = torch.cuda.current_stream(self.device)
         evt = torch.cuda.Event()
         evt.record(st)
         return evt, st
 
+    def _finish(self, out, consume_flag: bool):
+        """The tail of every decode-class call but the overlapped ``rnnt_greedy``: fill the result's flag word and set its completion
+        ``event`` / ``stream``, on the current stream.  ``consume_flag``: the call ran the encoder's GEMMs -- move the range flag into
+        the word (``_fetch_flag``); otherwise (an ``op_*`` call: no encoder ran) the word is 0.  No kernel writes that word, so where
+        in the call's own stream order it is filled does not matter."""
+        word = out.flag_word()
+        if consume_flag:
+            out.event, out.stream = self._fetch_flag(word)
+        else:
+            word.zero_()
+            out.stream = torch.cuda.current_stream(self.device)
+            out.event = torch.cuda.Event()
+            out.event.record(out.stream)
+        return out
+
+    # the three forms a decode-class call takes its input in -> the device tensors and the dimensions
+    def _in_encoded(self, encoded: Tensor, enc_len: Optional[Tensor]):
+        """encoded f32 [B, d_model, T'], enc_len i32 [B] (or None) -> (encoded, enc_len, B, T')"""
+        encoded = self._dev(encoded, torch.float32)
+        b, _, tp = encoded.shape
+        return encoded, None if enc_len is None else self._dev(enc_len, torch.int32), b, tp
+
+    def _in_log_probs(self, log_probs: Tensor, enc_len: Tensor):
+        """log_probs f32 [B, T', V], enc_len i32 [B] -> (log_probs, enc_len, B, T', V)"""
+        log_probs = self._dev(log_probs, torch.float32)
+        return (log_probs, self._dev(enc_len, torch.int32), *log_probs.shape)
+
+    def _in_encp(self, encp: Tensor, enc_len: Tensor):
+        """encp f32 [B, T', joint_hidden], enc_len i32 [B] -> (encp, enc_len, B, T')"""
+        encp = self._dev(encp, torch.float32)
+        b, tp, jh = encp.shape
+        if jh != self.cfg.joint_hidden:
+            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        return encp, self._dev(enc_len, torch.int32), b, tp
+
     _aux_streams: Dict[int, Tuple["torch.cuda.Stream", "torch.cuda.Stream", "torch.cuda.Stream"]] = {}
-    import threading as _threading
-    _aux_lock = _threading.Lock()
-    import os as _os
-    ONE_COPY_BYTES = int(_os.environ.get("GAM_ONE_COPY_BYTES", str(256 * 1024)))   # decodes up to this size reach the host in one copy (collect); 0: A/B switch
+    _aux_lock = threading.Lock()
+    ONE_COPY_BYTES = int(os.environ.get("GAM_ONE_COPY_BYTES", str(256 * 1024)))   # decodes up to this size reach the host in one copy (collect); 0: A/B switch
 
     @classmethod
     def aux_streams(cls, device: torch.device) -> Tuple["torch.cuda.Stream", "torch.cuda.Stream", "torch.cuda.Stream"]:
@@ -500,7 +570,6 @@ class HipEngine:
         key = device.index if device.index is not None else torch.cuda.current_device()
         st = cls._aux_streams.get(key)
         if st is None:
-            import os
             with cls._aux_lock:      # (two threads building their first engine at once must end up with ONE trio)
                 st = cls._aux_streams.get(key)
                 if st is None:
@@ -535,42 +604,32 @@ class HipEngine:
         src = ext if ext is not None else counts
         if whole is not None and evt is not None and whole.is_cuda and whole.numel() * 4 <= HipEngine.ONE_COPY_BYTES:
             # one blocking D2H of the whole decode (a second and third round trip cost more than the unused tail of ids / frames)
-            side = HipEngine._collect_stream(whole.device)
-            with torch.cuda.stream(side):
-                side.wait_event(evt)
-                host = whole.cpu()
-            whole.record_stream(side)
-            b, cap = ids.shape
-            arr = host.numpy()      # (zero-copy; numpy row slices convert to lists at half the cost of per-row Tensor.tolist(): 0.33 -> 0.17 ms at 32 x 502)
-            n = arr[2 * b * cap:].tolist()
+            arr, = _to_host((whole,), evt)      # (zero-copy numpy; the row conversion's timing: _rows)
+            h = Decoded.views(Decoded.layout(*ids.shape), arr)
+            n = h["ext"].tolist()
             flag = HipEngine._flag_of(n.pop())
             if n and min(n) < 0:
                 raise GigaAMHipError("decode left an utterance undecoded (counts = -1)")
-            ids_h, fr_h = arr[: b * cap].reshape(b, cap), arr[b * cap: 2 * b * cap].reshape(b, cap)
-            return [(ids_h[i, :c].tolist(), fr_h[i, :c].tolist()) for i, c in enumerate(n)], flag
-        if evt is not None and ids.is_cuda:
-            side = HipEngine._collect_stream(ids.device)
-            with torch.cuda.stream(side):
+            return _rows(h["ids"], h["frames"], n), flag
+        # counts (+ flag word) first, then the used columns of ids and of frames: on the collect stream behind the decode's own event, or ...
+        side = HipEngine._collect_stream(ids.device) if evt is not None and ids.is_cuda else None
+        if side is None and ids.is_cuda:
+            # ... bare tensors carry no completion event: the decode may have run on the engine's side stream, which a .cpu() on the
+            # CURRENT stream is not ordered behind -- wait for the whole device rather than read half-written counts
+            torch.cuda.synchronize(ids.device)
+        with contextlib.nullcontext() if side is None else torch.cuda.stream(side):
+            if side is not None:
                 side.wait_event(evt)
-                n = src.cpu().tolist()
-                flag = HipEngine._flag_of(n.pop()) if ext is not None else False
-                width = max(n) if n else 0
-                ids_h, fr_h = ids[:, :width].cpu(), frames[:, :width].cpu()
-            for t in (ids, frames, src):
-                t.record_stream(side)
-        else:
-            if ids.is_cuda:
-                # bare tensors carry no completion event: the decode may have run on the engine's side stream, which a .cpu() on the
-                # CURRENT stream is not ordered behind -- wait for the whole device rather than read half-written counts
-                torch.cuda.synchronize(ids.device)
             n = src.cpu().tolist()
             flag = HipEngine._flag_of(n.pop()) if ext is not None else False
             width = max(n) if n else 0
             ids_h, fr_h = ids[:, :width].cpu(), frames[:, :width].cpu()
+        if side is not None:
+            for t in (ids, frames, src):
+                t.record_stream(side)
         if n and min(n) < 0:   # cannot happen: gam_rnnt_greedy repairs failed clusters itself (gam_api.hip launch_single)
             raise GigaAMHipError("RNN-T decode left an utterance undecoded (counts = -1)")
-        ids_a, fr_a = ids_h.numpy(), fr_h.numpy()
-        return [(ids_a[i, :c].tolist(), fr_a[i, :c].tolist()) for i, c in enumerate(n)], flag
+        return _rows(ids_h.numpy(), fr_h.numpy(), n), flag
 
     def feat_frames(self, n_samples: int) -> int:
         return int(self.lib.gam_feat_frames(self._h, n_samples))
@@ -636,8 +695,7 @@ class HipEngine:
         return (enc, elen, tok) if want_tokens else (enc, elen)
 
     def ctc_head(self, encoded: Tensor) -> Tensor:
-        encoded = self._dev(encoded, torch.float32)
-        b, _, tp = encoded.shape
+        encoded, _, b, tp = self._in_encoded(encoded, None)
         out = torch.empty((b, tp, self.cfg.num_classes), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_ctc_head(self._h, _ptr(encoded), b, tp, _ptr(out), self._stream())
@@ -647,9 +705,7 @@ class HipEngine:
     def emo_probs(self, encoded: Tensor, enc_len: Optional[Tensor] = None) -> Tensor:
         """[B,d_model,T'] -> class probabilities [B,num_classes] (mean over time, Linear, softmax);
         enc_len restricts the mean to each utterance's valid frames (None = all T')."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = None if enc_len is None else self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         out = torch.empty((b, self.cfg.num_classes), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_emo_probs(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(out), self._stream())
@@ -657,21 +713,16 @@ class HipEngine:
         return out
 
     def ctc_greedy(self, encoded: Tensor, enc_len: Tensor) -> Decoded:
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
-        whole = torch.empty((2 * b * tp + b + 1,), dtype=torch.int32, device=self.device)     # ids | frames | counts + flag word
-        ids, frames, ext = whole[: b * tp].view(b, tp), whole[b * tp: 2 * b * tp].view(b, tp), whole[2 * b * tp:]
-        counts = ext[:b]
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
+        out = Decoded.packed(self.device, b, tp)
         with torch.cuda.device(self.device):
-            rc = self.lib.gam_ctc_greedy(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(ids), _ptr(frames),
-                                         _ptr(counts), self._stream())
+            rc = self.lib.gam_ctc_greedy(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(out.ids), _ptr(out.frames),
+                                         _ptr(out.counts), self._stream())
             self._check(rc, "gam_ctc_greedy")
-            evt, st = self._fetch_flag(ext)
-        return Decoded(ids, frames, counts, ext, evt, st, whole=whole)
+            return self._finish(out, True)
 
-    def _align_buffers(self, b: int, tp: int, targets, target_len):
-        """targets: [B, Umax] ints or a list of B int lists; target_len [B] (None: the rows' lengths) -> device i32 tensors + Aligned buffer."""
+    def _pad_targets(self, b: int, targets, target_len) -> Tuple[Tensor, Tensor]:
+        """targets: [B, Umax] ints or a list of B int lists; target_len [B] (None: the rows' lengths) -> device i32 [B, Umax], [B]."""
         if isinstance(targets, Tensor):
             tgt = targets.reshape(b, -1)
             tlen = torch.full((b,), tgt.shape[1], dtype=torch.int32) if target_len is None else target_len
@@ -684,10 +735,7 @@ class HipEngine:
                 if len(t):
                     tgt[i, : len(t)] = torch.as_tensor(list(t), dtype=torch.int32)
             tlen = torch.tensor([len(t) for t in targets], dtype=torch.int32) if target_len is None else target_len
-        tgt, tlen = self._dev(tgt, torch.int32), self._dev(tlen, torch.int32)
-        um = tgt.shape[1]
-        whole = torch.empty((b * tp + 2 * b * um + 3 * b + 1,), dtype=torch.int32, device=self.device)
-        return tgt, tlen, Aligned(whole, b, tp, um)
+        return self._dev(tgt, torch.int32), self._dev(tlen, torch.int32)
 
     def _launch_align(self, fn, first, enc_len: Tensor, b: int, tp: int, extra, tgt: Tensor, tlen: Tensor, out: Aligned, what: str) -> None:
         rc = fn(self._h, _ptr(first), _ptr(enc_len), b, tp, *extra, _ptr(tgt), _ptr(tlen), out.umax, _ptr(out.frame_labels),
@@ -698,29 +746,22 @@ class HipEngine:
         """CTC forced alignment of known targets (gam_ctc_align): the CTC head, its log-softmax and the alignment kernel, no host sync.
         ``targets``: i32 [B, Umax] (entries past ``target_len[b]`` are ignored) or a list of B token-id lists.  The split-fp16 range
         flag is CONSUMED as ``ctc_greedy`` does: it lands in the result's last word (``Aligned.host()['flag']``)."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
-        tgt, tlen, out = self._align_buffers(b, tp, targets, target_len)
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
+        tgt, tlen = self._pad_targets(b, targets, target_len)
+        out = Aligned.empty(self.device, b, tp, tgt.shape[1])
         with torch.cuda.device(self.device):
             self._launch_align(self.lib.gam_ctc_align, encoded, enc_len, b, tp, (), tgt, tlen, out, "gam_ctc_align")
-            out.event, out.stream = self._fetch_flag(out.ext)
-        return out
+            return self._finish(out, True)
 
     def op_ctc_align(self, log_probs: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None) -> Aligned:
         """gam_op_ctc_align: the alignment kernel alone on caller-supplied log-probs [B, T', V] (used as they are).  The result's flag
         word is 0 (no encoder ran)."""
-        log_probs = self._dev(log_probs, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, v = log_probs.shape
-        tgt, tlen, out = self._align_buffers(b, tp, targets, target_len)
+        log_probs, enc_len, b, tp, v = self._in_log_probs(log_probs, enc_len)
+        tgt, tlen = self._pad_targets(b, targets, target_len)
+        out = Aligned.empty(self.device, b, tp, tgt.shape[1])
         with torch.cuda.device(self.device):
-            out.ext.zero_()
             self._launch_align(self.lib.gam_op_ctc_align, log_probs, enc_len, b, tp, (v,), tgt, tlen, out, "gam_op_ctc_align")
-            st = torch.cuda.current_stream(self.device)
-            out.event, out.stream = torch.cuda.Event(), st
-            out.event.record(st)
-        return out
+            return self._finish(out, False)
 
     def op_ctc_align_long(self, log_probs: Tensor, targets, consume_flag: bool = False) -> AlignedLong:
         """gam_op_ctc_align_long: CTC forced alignment of ONE long utterance, log-probs f32 [T, V] (used as they are) against ``targets``
@@ -732,20 +773,12 @@ class HipEngine:
         tgt = self._dev(targets if isinstance(targets, Tensor) else torch.tensor([int(i) for i in targets], dtype=torch.int32),
                         torch.int32).reshape(-1)
         u = tgt.numel()
-        out = AlignedLong(torch.empty((6 + t + 2 * u,), dtype=torch.int32, device=self.device), t, u)
+        out = AlignedLong.empty(self.device, t, u)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_op_ctc_align_long(self._h, _ptr(log_probs), t, v, _ptr(tgt), u, _ptr(out.frame_labels), _ptr(out.tok_first),
                                                 _ptr(out.tok_last), _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
             self._check(rc, "gam_op_ctc_align_long")
-            if consume_flag:
-                # (the flag word sits inside ``whole``, not at its end: hand _fetch_flag a view that ends there)
-                out.event, out.stream = self._fetch_flag(out.whole[:6])
-            else:
-                out.ext.zero_()
-                st = torch.cuda.current_stream(self.device)
-                out.event, out.stream = torch.cuda.Event(), st
-                out.event.record(st)
-        return out
+            return self._finish(out, consume_flag)
 
     def set_ctc_align_workspace(self, nbytes: int = 0) -> None:
         """Bytes of workspace ``op_ctc_align_long`` may take (gam_set_ctc_align_workspace; 0: the default, 3 GiB).  A call that needs
@@ -758,46 +791,28 @@ class HipEngine:
         if self.lib.gam_tune_ctc_align_long(int(sb), int(tt)) != 0:
             raise GigaAMHipError(f"gam_tune_ctc_align_long: sb={sb} must be 0 or a multiple of 64 in [64, 3072], tt={tt} must be >= 0")
 
-    def _rnnt_align_buffers(self, b: int, targets, target_len):
-        """As ``_align_buffers``: device targets / lengths and the ``RnntAligned`` result buffer."""
-        tgt, tlen, _ = self._align_buffers(b, 0, targets, target_len)
-        um = tgt.shape[1]
-        return tgt, tlen, RnntAligned(torch.empty((b * um + 3 * b + 1,), dtype=torch.int32, device=self.device), b, um)
-
-    def _op_align_done(self, out: "RnntAligned") -> "RnntAligned":
-        out.ext.zero_()
-        st = torch.cuda.current_stream(self.device)
-        out.event, out.stream = torch.cuda.Event(), st
-        out.event.record(st)
-        return out
-
     def rnnt_align(self, encoded: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None) -> "RnntAligned":
         """Transducer forced alignment of known targets (gam_rnnt_align): the encoder projection, the teacher-forced predictor, the
         fused joint lattice and its sweep, no host sync.  ``targets``: i32 [B, Umax] (entries past ``target_len[b]`` are ignored) or
         a list of B token-id lists.  ``max_symbols_per_step`` does not bound the lattice; hotwords and the LM are not read.  The
         split-fp16 range flag is CONSUMED as ``rnnt_greedy`` does: it lands in the result's last word."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
-        tgt, tlen, out = self._rnnt_align_buffers(b, targets, target_len)
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
+        tgt, tlen = self._pad_targets(b, targets, target_len)
+        out = RnntAligned.empty(self.device, b, tgt.shape[1])
         with torch.cuda.device(self.device):
             rc = self.lib.gam_rnnt_align(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(tgt), _ptr(tlen), out.umax, _ptr(out.tok_frame),
                                          _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
             self._check(rc, "gam_rnnt_align")
-            out.event, out.stream = self._fetch_flag(out.ext)
-        return out
+            return self._finish(out, True)
 
     def op_rnnt_align(self, encp: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None,
                       want_lattice: bool = False) -> "RnntAligned":
         """gam_op_rnnt_align: the same from a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with this engine's
         predictor and joint weights.  ``want_lattice``: also keep the (log P(blank), log P(next token)) lattice the call swept
         (``RnntAligned.lattice``, f32 [B, T', Umax + 1, 2] on the device).  The flag word is 0."""
-        encp = self._dev(encp, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, jh = encp.shape
-        if jh != self.cfg.joint_hidden:
-            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
-        tgt, tlen, out = self._rnnt_align_buffers(b, targets, target_len)
+        encp, enc_len, b, tp = self._in_encp(encp, enc_len)
+        tgt, tlen = self._pad_targets(b, targets, target_len)
+        out = RnntAligned.empty(self.device, b, tgt.shape[1])
         with torch.cuda.device(self.device):
             if want_lattice:
                 out.lattice = torch.empty((b, tp, out.umax + 1, 2), dtype=torch.float32, device=self.device)
@@ -805,7 +820,7 @@ class HipEngine:
                                             _ptr(out.tok_frame), _ptr(out.score), _ptr(out.loglik), _ptr(out.status),
                                             _ptr(out.lattice), self._stream())
             self._check(rc, "gam_op_rnnt_align")
-            return self._op_align_done(out)
+            return self._finish(out, False)
 
     def op_rnnt_lattice_align(self, lattice: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None,
                               num_classes: Optional[int] = None) -> "RnntAligned":
@@ -815,7 +830,8 @@ class HipEngine:
         lattice = self._dev(lattice, torch.float32)
         enc_len = self._dev(enc_len, torch.int32)
         b, tp, u1, two = lattice.shape
-        tgt, tlen, out = self._rnnt_align_buffers(b, targets, target_len)
+        tgt, tlen = self._pad_targets(b, targets, target_len)
+        out = RnntAligned.empty(self.device, b, tgt.shape[1])
         if two != 2 or u1 != out.umax + 1:
             raise GigaAMHipError(f"lattice must be [B, T', Umax + 1 = {out.umax + 1}, 2], got {tuple(lattice.shape)}")
         with torch.cuda.device(self.device):
@@ -823,7 +839,7 @@ class HipEngine:
                                                     _ptr(tlen), out.umax, _ptr(out.tok_frame), _ptr(out.score), _ptr(out.loglik),
                                                     _ptr(out.status), self._stream())
             self._check(rc, "gam_op_rnnt_lattice_align")
-            return self._op_align_done(out)
+            return self._finish(out, False)
 
     def set_rnnt_align_workspace(self, nbytes: int = 0) -> None:
         """Bytes of lattice one slice of ``rnnt_align`` / ``op_rnnt_align`` may take (gam_set_rnnt_align_workspace; 0: the default,
@@ -874,19 +890,6 @@ class HipEngine:
             ids, frames = ids[:, :cap_max], frames[:, :cap_max]
         return self._dev(ids, torch.int32), self._dev(frames, torch.int32), self._dev(torch.as_tensor(counts), torch.int32)
 
-    def _confidence_out(self, b: int, cap: int, has_span: bool) -> "Confidence":
-        return Confidence(torch.empty(((2 if has_span else 1) * b * cap + b + 1,), dtype=torch.int32, device=self.device), b, cap, has_span)
-
-    def _confidence_done(self, out: "Confidence", consumed_flag: bool) -> "Confidence":
-        if consumed_flag:
-            out.event, out.stream = self._fetch_flag(out.ext)
-        else:
-            out.ext.zero_()
-            st = torch.cuda.current_stream(self.device)
-            out.event, out.stream = torch.cuda.Event(), st
-            out.event.record(st)
-        return out
-
     def ctc_confidence(self, encoded: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob",
                        aggregation: str = "mean") -> "Confidence":
         """Token confidences of a finished CTC decode (gam_ctc_confidence): the CTC head, its log-softmax, one pass over the log-probs
@@ -894,31 +897,27 @@ class HipEngine:
         ``counts``) as tensors or lists -- e.g. a transcript's ids at ``ctc_align``'s first frames.  ``measure``: "prob" | "entropy";
         ``aggregation`` over a token's span: "mean" | "min" | "prod".  The split-fp16 range flag is CONSUMED as ``ctc_greedy`` does."""
         m, a = self._confidence_codes(measure, aggregation)
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts)
-        out = self._confidence_out(b, ids.shape[1], True)
+        out = Confidence.empty(self.device, b, ids.shape[1], True)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_ctc_confidence(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap, m, a,
                                              _ptr(out.conf), _ptr(out.span), _ptr(out.status), self._stream())
             self._check(rc, "gam_ctc_confidence")
-            return self._confidence_done(out, True)
+            return self._finish(out, True)
 
     def op_ctc_confidence(self, log_probs: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob",
                           aggregation: str = "mean") -> "Confidence":
         """gam_op_ctc_confidence: the same on caller-supplied log-probs [B, T', V] (used as they are).  The flag word is 0."""
         m, a = self._confidence_codes(measure, aggregation)
-        log_probs = self._dev(log_probs, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, v = log_probs.shape
+        log_probs, enc_len, b, tp, v = self._in_log_probs(log_probs, enc_len)
         ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts)
-        out = self._confidence_out(b, ids.shape[1], True)
+        out = Confidence.empty(self.device, b, ids.shape[1], True)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_op_ctc_confidence(self._h, _ptr(log_probs), _ptr(enc_len), b, tp, v, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap,
                                                 m, a, _ptr(out.conf), _ptr(out.span), _ptr(out.status), self._stream())
             self._check(rc, "gam_op_ctc_confidence")
-            return self._confidence_done(out, False)
+            return self._finish(out, False)
 
     def rnnt_confidence(self, encoded: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob") -> "Confidence":
         """Token confidences of a finished RNN-T decode (gam_rnnt_confidence): the encoder projection, the teacher-forced predictor
@@ -927,53 +926,45 @@ class HipEngine:
         ``rnnt_align``'s frames.  At most 1024 tokens per utterance: a wider decode buffer is read up to there, and an utterance
         that holds more gets status 0.  The split-fp16 range flag is CONSUMED as ``rnnt_greedy`` does."""
         m, _ = self._confidence_codes(measure, "mean")
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts, self.MAX_RNNT_CONFIDENCE_TOKENS)
-        out = self._confidence_out(b, ids.shape[1], False)
+        out = Confidence.empty(self.device, b, ids.shape[1], False)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_rnnt_confidence(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap, m,
                                               _ptr(out.conf), _ptr(out.status), self._stream())
             self._check(rc, "gam_rnnt_confidence")
-            return self._confidence_done(out, True)
+            return self._finish(out, True)
 
     def op_rnnt_confidence(self, encp: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob") -> "Confidence":
         """gam_op_rnnt_confidence: the same from a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with this engine's
         predictor and joint weights.  The flag word is 0."""
         m, _ = self._confidence_codes(measure, "mean")
-        encp = self._dev(encp, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, jh = encp.shape
-        if jh != self.cfg.joint_hidden:
-            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        encp, enc_len, b, tp = self._in_encp(encp, enc_len)
         ids, fr, cnt = self._confidence_tokens(b, decoded, frames, counts, self.MAX_RNNT_CONFIDENCE_TOKENS)
-        out = self._confidence_out(b, ids.shape[1], False)
+        out = Confidence.empty(self.device, b, ids.shape[1], False)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_op_rnnt_confidence(self._h, _ptr(encp), _ptr(enc_len), b, tp, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap, m,
                                                  _ptr(out.conf), _ptr(out.status), self._stream())
             self._check(rc, "gam_op_rnnt_confidence")
-            return self._confidence_done(out, False)
+            return self._finish(out, False)
 
     MAX_BEAM = 32     # include/gigaam_hip.h gam_ctc_beam
 
     MAX_SYMBOLS_BEAM = 16     # include/gigaam_hip.h gam_rnnt_beam
 
-    def _beam_out(self, b: int, cap: int, beam_size: int, max_symbols: Optional[int] = None) -> BeamDecoded:
-        """Check the width (and the RNN-T search's ``max_symbols``); the result buffers for ``cap`` tokens per utterance."""
+    def _check_beam(self, beam_size: int, max_symbols: Optional[int] = None, n_best: Optional[int] = None) -> None:
+        """The beam width, ``n_best`` of an N-best search and ``max_symbols`` of an RNN-T search, each where it is given."""
         if not 1 <= int(beam_size) <= self.MAX_BEAM:
             raise GigaAMHipError(f"beam_size {beam_size} outside [1, {self.MAX_BEAM}]")
+        if n_best is not None and not 1 <= int(n_best) <= int(beam_size):
+            raise GigaAMHipError(f"n_best {n_best} outside [1, beam_size = {beam_size}]")
         if max_symbols is not None and not 1 <= int(max_symbols) <= self.MAX_SYMBOLS_BEAM:
             raise GigaAMHipError(f"max_symbols {max_symbols} outside [1, {self.MAX_SYMBOLS_BEAM}] for the RNN-T beam search")
-        return BeamDecoded(torch.empty((2 * b * cap + 3 * b + 1,), dtype=torch.int32, device=self.device), b, cap)
 
-    def _op_beam_done(self, out: BeamDecoded) -> BeamDecoded:
-        """An ``op_*`` search ran no encoder: zero the flag word, record the completion event."""
-        out.ext[-1:].zero_()
-        st = torch.cuda.current_stream(self.device)
-        out.event, out.stream = torch.cuda.Event(), st
-        out.event.record(st)
-        return out
+    def _beam_out(self, b: int, cap: int, beam_size: int, max_symbols: Optional[int] = None) -> BeamDecoded:
+        """Check the width (and the RNN-T search's ``max_symbols``); the result buffers for ``cap`` tokens per utterance."""
+        self._check_beam(beam_size, max_symbols)
+        return BeamDecoded.empty(self.device, b, cap)
 
     def _launch_beam(self, fn, first, enc_len: Tensor, b: int, tp: int, extra, beam_size: int, what: str) -> BeamDecoded:
         out = self._beam_out(b, tp, beam_size)
@@ -985,94 +976,62 @@ class HipEngine:
     def ctc_beam(self, encoded: Tensor, enc_len: Tensor, beam_size: int) -> BeamDecoded:
         """CTC prefix beam search (gam_ctc_beam): the CTC head, its log-softmax and the beam kernel, no host sync; the hotword set of
         ``set_hotwords`` applies.  The split-fp16 range flag is CONSUMED as ``ctc_greedy`` does: it lands in the flag word."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         with torch.cuda.device(self.device):
-            out = self._launch_beam(self.lib.gam_ctc_beam, encoded, enc_len, b, tp, (), beam_size, "gam_ctc_beam")
-            out.event, out.stream = self._fetch_flag(out.ext)
-        return out
+            return self._finish(self._launch_beam(self.lib.gam_ctc_beam, encoded, enc_len, b, tp, (), beam_size, "gam_ctc_beam"), True)
 
     def op_ctc_beam(self, log_probs: Tensor, enc_len: Tensor, beam_size: int) -> BeamDecoded:
         """gam_op_ctc_beam: the beam kernel alone on caller-supplied log-probs [B, T', V] (used as they are).  The flag word is 0."""
-        log_probs = self._dev(log_probs, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, v = log_probs.shape
+        log_probs, enc_len, b, tp, v = self._in_log_probs(log_probs, enc_len)
         with torch.cuda.device(self.device):
-            return self._op_beam_done(self._launch_beam(self.lib.gam_op_ctc_beam, log_probs, enc_len, b, tp, (v,), beam_size,
-                                                        "gam_op_ctc_beam"))
+            return self._finish(self._launch_beam(self.lib.gam_op_ctc_beam, log_probs, enc_len, b, tp, (v,), beam_size, "gam_op_ctc_beam"), False)
 
     def rnnt_beam(self, encoded: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int) -> BeamDecoded:
         """RNN-T beam search (gam_rnnt_beam): the encoder projection GEMM and the beam kernel, no host sync; the hotword set of
         ``set_hotwords`` and the LM of ``set_lm`` apply.  ids / frames are [B, T' * max_symbols].  The split-fp16 range flag is
         CONSUMED as ``rnnt_greedy`` does: it lands in the flag word."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         with torch.cuda.device(self.device):
             out = self._beam_out(b, tp * int(max_symbols), beam_size, max_symbols)
             rc = self.lib.gam_rnnt_beam(self._h, _ptr(encoded), _ptr(enc_len), b, tp, int(beam_size), int(max_symbols), _ptr(out.ids),
                                         _ptr(out.frames), _ptr(out.counts), _ptr(out.score), _ptr(out.logp), self._stream())
             self._check(rc, "gam_rnnt_beam")
-            out.event, out.stream = self._fetch_flag(out.ext)
-        return out
+            return self._finish(out, True)
 
     def op_rnnt_beam(self, encp: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int) -> BeamDecoded:
         """gam_op_rnnt_beam: the beam kernel alone on a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with this
         engine's predictor and joint weights (and the hotwords / LM set on it).  The flag word is 0."""
-        encp = self._dev(encp, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, jh = encp.shape
-        if jh != self.cfg.joint_hidden:
-            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        encp, enc_len, b, tp = self._in_encp(encp, enc_len)
         with torch.cuda.device(self.device):
             out = self._beam_out(b, tp * int(max_symbols), beam_size, max_symbols)
             rc = self.lib.gam_op_rnnt_beam(self._h, _ptr(encp), _ptr(enc_len), b, tp, int(beam_size), int(max_symbols), _ptr(out.ids),
                                            _ptr(out.frames), _ptr(out.counts), _ptr(out.score), _ptr(out.logp), self._stream())
             self._check(rc, "gam_op_rnnt_beam")
-            return self._op_beam_done(out)
+            return self._finish(out, False)
 
     def _nbest_out(self, b: int, cap: int, beam_size: int, n_best: int, max_symbols: Optional[int] = None) -> NBestDecoded:
         """Check the width, ``n_best`` (and the RNN-T search's ``max_symbols``); the result buffers for ``n_best`` hypotheses of ``cap``
         tokens per utterance."""
-        if not 1 <= int(beam_size) <= self.MAX_BEAM:
-            raise GigaAMHipError(f"beam_size {beam_size} outside [1, {self.MAX_BEAM}]")
-        if not 1 <= int(n_best) <= int(beam_size):
-            raise GigaAMHipError(f"n_best {n_best} outside [1, beam_size = {beam_size}]")
-        if max_symbols is not None and not 1 <= int(max_symbols) <= self.MAX_SYMBOLS_BEAM:
-            raise GigaAMHipError(f"max_symbols {max_symbols} outside [1, {self.MAX_SYMBOLS_BEAM}] for the RNN-T beam search")
-        n = int(n_best)
-        return NBestDecoded(torch.empty((2, b, n, cap), dtype=torch.int32, device=self.device),
-                            torch.empty((b + 3 * b * n + 1,), dtype=torch.int32, device=self.device))
+        self._check_beam(beam_size, max_symbols, n_best)
+        return NBestDecoded.empty(self.device, b, int(n_best), cap)
 
     def _launch_nbest(self, fn, what: str, first: Tensor, enc_len: Tensor, b: int, tp: int, extra, out: NBestDecoded, op: bool) -> NBestDecoded:
         rc = fn(self._h, _ptr(first), _ptr(enc_len), b, tp, *extra, out.n, _ptr(out.ids), _ptr(out.frames), _ptr(out.counts),
                 _ptr(out.score), _ptr(out.logp), _ptr(out.n_hyp), self._stream())
         self._check(rc, what)
-        if op:      # no encoder ran: zero the flag word, record the completion event
-            out.ext.zero_()
-            st = torch.cuda.current_stream(self.device)
-            out.event, out.stream = torch.cuda.Event(), st
-            out.event.record(st)
-        else:
-            out.event, out.stream = self._fetch_flag(out.ext)
-        return out
+        return self._finish(out, not op)
 
     def ctc_beam_nbest(self, encoded: Tensor, enc_len: Tensor, beam_size: int, n_best: int) -> NBestDecoded:
         """``ctc_beam`` returning the ``n_best`` (<= ``beam_size``) best prefixes of each final beam (gam_ctc_beam_nbest), no host
         sync; hypothesis 0 is ``ctc_beam``'s result bit for bit.  The range flag lands in the flag word, as in ``ctc_beam``."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         with torch.cuda.device(self.device):
             out = self._nbest_out(b, tp, beam_size, n_best)
             return self._launch_nbest(self.lib.gam_ctc_beam_nbest, "gam_ctc_beam_nbest", encoded, enc_len, b, tp, (int(beam_size),), out, False)
 
     def op_ctc_beam_nbest(self, log_probs: Tensor, enc_len: Tensor, beam_size: int, n_best: int) -> NBestDecoded:
         """gam_op_ctc_beam_nbest: the N-best beam kernel alone on caller-supplied log-probs [B, T', V].  The flag word is 0."""
-        log_probs = self._dev(log_probs, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, v = log_probs.shape
+        log_probs, enc_len, b, tp, v = self._in_log_probs(log_probs, enc_len)
         with torch.cuda.device(self.device):
             out = self._nbest_out(b, tp, beam_size, n_best)
             return self._launch_nbest(self.lib.gam_op_ctc_beam_nbest, "gam_op_ctc_beam_nbest", log_probs, enc_len, b, tp,
@@ -1081,9 +1040,7 @@ class HipEngine:
     def rnnt_beam_nbest(self, encoded: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int, n_best: int) -> NBestDecoded:
         """``rnnt_beam`` returning the ``n_best`` (<= ``beam_size``) best hypotheses of each final beam (gam_rnnt_beam_nbest), no host
         sync; hypothesis 0 is ``rnnt_beam``'s result bit for bit.  ids / frames are [B, n_best, T' * max_symbols]."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         with torch.cuda.device(self.device):
             out = self._nbest_out(b, tp * int(max_symbols), beam_size, n_best, max_symbols)
             return self._launch_nbest(self.lib.gam_rnnt_beam_nbest, "gam_rnnt_beam_nbest", encoded, enc_len, b, tp,
@@ -1092,15 +1049,20 @@ class HipEngine:
     def op_rnnt_beam_nbest(self, encp: Tensor, enc_len: Tensor, beam_size: int, max_symbols: int, n_best: int) -> NBestDecoded:
         """gam_op_rnnt_beam_nbest: the N-best beam kernel alone on a caller-supplied encoder projection encp f32 [B, T', joint_hidden],
         as ``op_rnnt_beam``.  The flag word is 0."""
-        encp = self._dev(encp, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, jh = encp.shape
-        if jh != self.cfg.joint_hidden:
-            raise GigaAMHipError(f"encp must be [B, T', {self.cfg.joint_hidden}], got {tuple(encp.shape)}")
+        encp, enc_len, b, tp = self._in_encp(encp, enc_len)
         with torch.cuda.device(self.device):
             out = self._nbest_out(b, tp * int(max_symbols), beam_size, n_best, max_symbols)
             return self._launch_nbest(self.lib.gam_op_rnnt_beam_nbest, "gam_op_rnnt_beam_nbest", encp, enc_len, b, tp,
                                       (int(beam_size), int(max_symbols)), out, True)
+
+    @staticmethod
+    def _flat_phrases(phrases):
+        """Token-id lists -> (all tokens end to end, the first token of every phrase + the total) as C i32 arrays."""
+        flat = [c for p in phrases for c in p]
+        offs = [0]
+        for p in phrases:
+            offs.append(offs[-1] + len(p))
+        return (C.c_int32 * max(len(flat), 1))(*flat), (C.c_int32 * len(offs))(*offs)
 
     def set_hotwords(self, phrases, boost: float = 2.0) -> None:
         """Hotword phrases (token-id lists) for the beam search, each matched token worth ``boost`` (gam_set_hotwords); an empty
@@ -1109,12 +1071,7 @@ class HipEngine:
         prev = getattr(self, "_hotwords_key", None)
         if key == prev or (not key[0] and (prev is None or not prev[0])):     # (no set and none uploaded: nothing to clear)
             return
-        flat = [c for p in key[0] for c in p]
-        offs = [0]
-        for p in key[0]:
-            offs.append(offs[-1] + len(p))
-        tok = (C.c_int32 * max(len(flat), 1))(*flat)
-        off = (C.c_int32 * len(offs))(*offs)
+        tok, off = self._flat_phrases(key[0])
         self._check(self.lib.gam_set_hotwords(self._h, tok, off, len(key[0]), C.c_float(key[1])), "gam_set_hotwords")
         self._hotwords_key = key
 
@@ -1131,12 +1088,7 @@ class HipEngine:
         prev = getattr(self, "_keywords_key", None)
         if key == prev or (not kws and (prev is None or not prev[0])):     # (no set and none uploaded: nothing to clear)
             return
-        flat = [c for p in kws for c in p]
-        offs = [0]
-        for p in kws:
-            offs.append(offs[-1] + len(p))
-        tok = (C.c_int32 * max(len(flat), 1))(*flat)
-        off = (C.c_int32 * len(offs))(*offs)
+        tok, off = self._flat_phrases(kws)
         msc = (C.c_float * max(len(kws), 1))(*ms.tolist())
         self._check(self.lib.gam_set_keywords(self._h, tok, off, len(kws), msc), "gam_set_keywords")
         self._keywords_key = key
@@ -1144,44 +1096,34 @@ class HipEngine:
     def _kws_out(self, b: int, tp: int, max_hits: int, dense: bool) -> KeywordHits:
         key = getattr(self, "_keywords_key", None)
         k = len(key[0]) if key else 0
-        max_hits = int(max_hits)          # (no set, or max_hits outside [1, 64]: the library's errors; the buffers only must not be negative)
-        whole = torch.empty((b * k * (1 + 3 * max(max_hits, 0)) + 1,), dtype=torch.int32, device=self.device)
         ds = torch.empty((b, k, tp), dtype=torch.float32, device=self.device) if dense else None
         dst = torch.empty((b, k, tp), dtype=torch.int32, device=self.device) if dense else None
-        return KeywordHits(whole, b, k, max_hits, ds, dst)
+        # (no set, or max_hits outside [1, 64]: the library's errors)
+        return KeywordHits.empty(self.device, b, k, int(max_hits), dense_score=ds, dense_start=dst)
 
     def ctc_kws(self, encoded: Tensor, enc_len: Tensor, max_hits: int = 8, dense: bool = False) -> KeywordHits:
         """Keyword search on the encoder output (gam_ctc_kws): the CTC head, its log-softmax and the search kernels, no host sync;
         the set of ``set_keywords`` is searched in every utterance.  ``dense``: also return the per-frame scores and starts.  The
         split-fp16 range flag is CONSUMED as ``ctc_align`` does: it lands in the result's last word (``KeywordHits.host()['flag']``)."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         out = self._kws_out(b, tp, max_hits, dense)
         with torch.cuda.device(self.device):
             rc = self.lib.gam_ctc_kws(self._h, _ptr(encoded), _ptr(enc_len), b, tp, out.max_hits, _ptr(out.hit_frames), _ptr(out.hit_score),
                                       _ptr(out.n_hits), _ptr(out.dense_score), _ptr(out.dense_start), self._stream())
             self._check(rc, "gam_ctc_kws")
-            out.event, out.stream = self._fetch_flag(out.ext)
-        return out
+            return self._finish(out, True)
 
     def op_ctc_kws(self, log_probs: Tensor, enc_len: Tensor, max_hits: int = 8, dense: bool = False) -> KeywordHits:
         """gam_op_ctc_kws: the search kernels alone on caller-supplied log-probs [B, T', V] (used as they are).  The result's flag word
         is 0 (no encoder ran)."""
-        log_probs = self._dev(log_probs, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, tp, v = log_probs.shape
+        log_probs, enc_len, b, tp, v = self._in_log_probs(log_probs, enc_len)
         out = self._kws_out(b, tp, max_hits, dense)
         with torch.cuda.device(self.device):
-            out.ext.zero_()
             rc = self.lib.gam_op_ctc_kws(self._h, _ptr(log_probs), _ptr(enc_len), b, tp, v, out.max_hits, _ptr(out.hit_frames),
                                          _ptr(out.hit_score), _ptr(out.n_hits), _ptr(out.dense_score), _ptr(out.dense_start),
                                          self._stream())
             self._check(rc, "gam_op_ctc_kws")
-            st = torch.cuda.current_stream(self.device)
-            out.event, out.stream = torch.cuda.Event(), st
-            out.event.record(st)
-        return out
+            return self._finish(out, False)
 
     def set_lm(self, lm=None, tokenizer=None, weight: float = 0.5, word_bonus: float = 1.0) -> None:
         """An n-gram LM (``lm.NgramLM``) for the beam search, its words spelt by ``tokenizer`` (gam_set_lm); None clears it.
@@ -1214,7 +1156,6 @@ class HipEngine:
     def side_cluster(b: int, side_cus: int) -> int:
         """Cluster size of an OVERLAPPED decode: the clusters of ``b`` utterances (8 utterance columns x ceil(b / 8) rows x C
         workgroups, one per CU -- gam_api.hip) together hold at most ``side_cus`` compute units; at least 1."""
-        import os
         if "GAM_DEBUG_SIDE_CLUSTER" in os.environ:      # debug: force the overlapped decode's cluster size (0 = one-workgroup kernel)
             return int(os.environ["GAM_DEBUG_SIDE_CLUSTER"])
         return max(1, min(8, side_cus // (8 * ((b + 7) // 8))))
@@ -1232,25 +1173,21 @@ class HipEngine:
         small clusters may resolve a near-tie (top-1 / top-2 margin below ~1e-5) differently from the full-size clusters' -- inside the 1e-3 logit
         bar, and the reason bench.py and the tests compare overlapped and serial decodes at equal cluster size.  Decode-class calls of one handle
         are ordered by the library whatever streams they run on (gam_api.hip DecodeScope)."""
-        encoded = self._dev(encoded, torch.float32)
-        enc_len = self._dev(enc_len, torch.int32)
-        b, _, tp = encoded.shape
+        encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         cap = tp * max_symbols
         main = torch.cuda.current_stream(self.device)
         side = self._decode_side_stream() if overlap else None
         # ids | frames | counts + flag word as views of ONE buffer (allocated on the launch stream): a small decode reaches the host in one copy
-        whole = torch.empty((2 * b * cap + b + 1,), dtype=torch.int32, device=self.device)
-        ext = whole[2 * b * cap:]
-        counts = ext[:b]
+        ids, frames, counts = out = Decoded.packed(self.device, b, cap)
+        whole, word = out.whole, out.flag_word()
         if overlap:
             with torch.cuda.device(self.device):
-                self._fetch_flag(ext)            # on the launch stream: this batch's own flag (its event is not the decode's)
+                self._fetch_flag(word)           # on the launch stream: this batch's own flag (its event is not the decode's)
             side.wait_stream(main)
             c_side = self.side_cluster(b, side_cus if side_cus > 0 else (96 if self.cfg.num_classes <= 64 else 160))
             self._check(self.lib.gam_set_rnnt_cluster(self._h, c_side), "gam_set_rnnt_cluster")     # (for this call only: restored below)
         try:
             with torch.cuda.stream(side) if overlap else torch.cuda.device(self.device):
-                ids, frames = whole[: b * cap].view(b, cap), whole[b * cap: 2 * b * cap].view(b, cap)
                 dump = dcount = None
                 if dump_cap > 0:
                     dump = torch.zeros((b, dump_cap, self.cfg.num_classes), dtype=torch.float32, device=self.device)
@@ -1265,11 +1202,11 @@ class HipEngine:
                     for t in (encoded, enc_len, whole):    # allocated on the launch stream, last used on the side stream
                         t.record_stream(st)
                 else:
-                    evt, st = self._fetch_flag(ext)
+                    evt, st = self._fetch_flag(word)
         finally:
             if overlap:
                 self._check(self.lib.gam_set_rnnt_cluster(self._h, self._rnnt_cluster_user), "gam_set_rnnt_cluster")
-        return Decoded(ids, frames, counts, ext, evt, st, dump, dcount, whole=whole)
+        return Decoded(ids, frames, counts, out.ext, evt, st, dump, dcount, whole=whole)
 
     def rnnt_predict(self, labels: Optional[Tensor], state: Optional[Tuple[Tensor, Tensor]], batch_size: int = 1):
         """One predictor step (reference RNNTDecoder.predict, gigaam/decoder.py:85-102): labels i [B] or None (zero input),
