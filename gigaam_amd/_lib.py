@@ -36,6 +36,16 @@ class GamConfig(C.Structure):
 
 # name -> (restype, argtypes); every symbol include/gigaam_hip.h declares
 _P = C.c_void_p
+
+
+class GamLnOp(C.Structure):
+    """gam_ln_op of include/gigaam_hip.h: the argument block of gam_op_layernorm (device pointers as integers, 0 = NULL)."""
+    _fields_ = ([(n, _P) for n in ("x", "out1", "out2", "w1", "b1", "w2", "b2", "rcos", "rsin", "row_t", "rs", "part", "pbias", "presid",
+                                   "xstore")]
+                + [(n, C.c_int32) for n in ("mode", "rows", "d", "split1", "split2", "dk", "ta", "rope_rows", "nsplit")]
+                + [("eps", C.c_float), ("palpha", C.c_float)])
+
+
 SIGNATURES = {
     "gam_abi_version": (C.c_int, []),
     "gam_create": (C.c_int, [C.POINTER(GamConfig), C.c_int, C.POINTER(_P)]),
@@ -93,6 +103,8 @@ SIGNATURES = {
     "gam_op_gemm_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gam_op_attention": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "gam_op_attention_ex": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gam_op_layernorm": (C.c_int, [_P, C.POINTER(GamLnOp), _P]),
+    "gam_op_convmod": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gam_tune_sp": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "gam_plan_sp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gam_plan_sp_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -2593,6 +2593,68 @@ int gam_op_attention_ex(gam_handle* h, const float* q, const float* k, const flo
   return 0;
 }
 
+int gam_op_layernorm(gam_handle* h, const gam_ln_op* op, void* stream) {
+  if (!h) return -1;
+  if (!op) return fail(h, -1, "layernorm: null argument block");
+  const gam_ln_op& o = *op;
+  if (o.mode < 0 || o.mode > 2) return fail(h, -1, "layernorm: mode %d outside 0..2", o.mode);
+  if (o.rows <= 0 || o.d <= 0) return fail(h, -1, "layernorm: bad shape rows %d d %d", o.rows, o.d);
+  if (o.split1 < 0 || o.split1 > 2 || o.split2 < 0 || o.split2 > 2)
+    return fail(h, -1, "layernorm: store format %d / %d outside 0..2", o.split1, o.split2);
+  if (!o.out1 || !o.w1 || !o.b1) return fail(h, -1, "layernorm: out1 / w1 / b1 are mandatory");
+  if (!o.part && !o.x) return fail(h, -1, "layernorm: x is mandatory without part");
+  if (o.part && o.mode != 2 && !o.xstore) return fail(h, -1, "layernorm: part without xstore");
+  if (o.mode != 0 && !o.out2) return fail(h, -1, "layernorm: mode %d needs out2", o.mode);
+  if (o.mode == 2 && (!o.w2 || !o.b2)) return fail(h, -1, "layernorm: mode 2 needs w2 / b2");
+  if (o.mode == 1) {
+    if (!o.rcos || !o.rsin || o.rope_rows <= 0) return fail(h, -1, "layernorm: mode 1 needs rcos / rsin of rope_rows > 0 rows");
+    if (o.dk <= 0) return fail(h, -1, "layernorm: mode 1 needs dk > 0");
+    if (!o.row_t && o.ta <= 0) return fail(h, -1, "layernorm: mode 1 needs row_t or ta > 0");
+  }
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };   // (float4 loads and stores; null passes)
+  if (!al16(o.x) || !al16(o.out1) || !al16(o.out2) || !al16(o.w1) || !al16(o.b1) || !al16(o.w2) || !al16(o.b2) || !al16(o.rcos) ||
+      !al16(o.rsin) || !al16(o.part) || !al16(o.pbias) || !al16(o.presid) || !al16(o.xstore))
+    return fail(h, -1, "layernorm: operands must be 16-byte aligned");
+  HIPCHK(h, hipSetDevice(h->device));
+  GamLnArgs a;
+  memset(&a, 0, sizeof a);
+  a.x = o.x; a.out1 = o.out1; a.out2 = o.out2; a.w1 = o.w1; a.b1 = o.b1; a.w2 = o.w2; a.b2 = o.b2;
+  a.rcos = o.rcos; a.rsin = o.rsin; a.rows = o.rows; a.d = o.d; a.ta = o.ta; a.dk = o.dk; a.eps = o.eps;
+  a.split1 = o.split1; a.split2 = o.split2; a.rs = o.rs; a.rope_rows = o.rope_rows;
+  a.part = o.part; a.nsplit = o.nsplit; a.pbias = o.pbias; a.presid = o.presid; a.palpha = o.palpha; a.xstore = o.xstore;
+  a.row_t = o.row_t;
+  hipError_t e = gam_launch_layernorm(a, o.mode, (hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail(h, -2, "layernorm launch (mode %d, rows %d, d %d, dk %d, split %d/%d, nsplit %d): %s", o.mode, o.rows, o.d, o.dk,
+                o.split1, o.split2, o.part ? o.nsplit : 0, hipGetErrorString(e));
+  return 0;
+}
+
+int gam_op_convmod(gam_handle* h, const float* u, float* z, const float* dw_w, const float* dw_b, const float* n_scale,
+                   const float* n_shift, const int32_t* lens, const int32_t* cu, int B, int Ta, int Tv, int d, int ks, int layer_norm,
+                   int z_split, void* stream) {
+  if (!h) return -1;
+  if (!h->finalized) return fail(h, -1, "gam_op_convmod before gam_finalize");   // (the range flag is allocated there)
+  if (!u || !z || !dw_w || !dw_b || !n_scale || !n_shift || !lens) return fail(h, -1, "conv module: null operand");
+  if (B <= 0 || Ta <= 0 || Tv <= 0 || d <= 0) return fail(h, -1, "conv module: bad shape B %d Ta %d Tv %d d %d", B, Ta, Tv, d);
+  if (cu == nullptr && Tv > Ta) return fail(h, -1, "conv module: Tv %d > Ta %d in the padded layout", Tv, Ta);
+  if (z_split < 0 || z_split > 2) return fail(h, -1, "conv module: store format %d outside 0..2", z_split);
+  if (z_split && d % 32 != 0) return fail(h, -1, "conv module: a split-fp16 z needs d %% 32 == 0 (d = %d)", d);
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  // the BatchNorm kernel and the 4-channel LayerNorm kernel move f32x4; the element-wise LayerNorm kernel (d % 4 != 0) does not
+  if (d % 4 == 0 && (!al16(u) || !al16(z) || !al16(dw_b) || !al16(n_scale) || !al16(n_shift)))
+    return fail(h, -1, "conv module: operands must be 16-byte aligned");
+  HIPCHK(h, hipSetDevice(h->device));
+  GamConvModArgs cm;
+  memset(&cm, 0, sizeof cm);
+  cm.u = u; cm.z = z; cm.dw_w = dw_w; cm.dw_b = dw_b; cm.n_scale = n_scale; cm.n_shift = n_shift;
+  cm.lens = lens; cm.cu = cu; cm.B = B; cm.Ta = Ta; cm.Tv = Tv; cm.d = d; cm.ks = ks; cm.eps = 1e-5f;
+  cm.z_split = z_split; cm.range_flag = h->use_range ? h->range_flag : nullptr;
+  hipError_t e = gam_launch_convmod(cm, layer_norm != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(h, -2, "conv-module launch (k=%d, d=%d, %s): %s", ks, d, layer_norm ? "LayerNorm" : "BatchNorm", hipGetErrorString(e));
+  return 0;
+}
+
 int gam_set_gemm_mode(gam_handle* h, int mode) {
   if (!h || (mode != GAM_GEMM_F32 && mode != GAM_GEMM_F16X3 && mode != GAM_GEMM_F16)) return fail(h, -1, "unknown GEMM mode %d", mode);
   h->gemm_mode = mode;

@@ -235,7 +235,11 @@ __global__ __launch_bounds__(256) void gam_convmod_ln_kernel(GamConvModArgs a) {
 #pragma unroll
       for (int i = 0; i < TT; ++i) {
         const int t = t0 + i;
-        if (t < rlim) gam_store1(a.z, (rowbase + t) * (size_t)a.d, c, gam_silu((y[ci][i] - mean[i]) * rstd[i] * g + be), a.z_split);
+        if (t < rlim) {
+          const float v = gam_silu((y[ci][i] - mean[i]) * rstd[i] * g + be);
+          gam_range_note(a.range_flag, v, 0.f, 0.f, 0.f);   // z feeds the pointwise-conv2 GEMM unscaled (as in the other two kernels)
+          gam_store1(a.z, (rowbase + t) * (size_t)a.d, c, v, a.z_split);
+        }
       }
     }
   }
@@ -357,6 +361,10 @@ static inline hipError_t gam_launch_convmod(const GamConvModArgs& a, int layer_n
       hipLaunchKernelGGL(gam_convmod_ln_kernel<31>, grid, dim3(256), sm, s, a);
     } else if (a.ks == 9) {
       const size_t sm = ((8 + 8) * a.d + 32) * sizeof(float);
+      if (sm > 64 * 1024) {   // d = 1023 (65 600 B): beyond what a launch gets without the opt-in, like k = 31
+        static std::atomic<unsigned long long> attr_devs9{0};
+        if (hipError_t e = gam_set_max_lds(reinterpret_cast<const void*>(gam_convmod_ln_kernel<9>), 160 * 1024, attr_devs9)) return e;
+      }
       hipLaunchKernelGGL(gam_convmod_ln_kernel<9>, grid, dim3(256), sm, s, a);
     } else return hipErrorInvalidValue;
   }

@@ -1288,6 +1288,47 @@ class HipEngine:
         self._check(rc, "gam_op_attention_ex")
         return out
 
+    def _op_ptr(self, what: str, name: str, t: Optional[Tensor], dtype: torch.dtype = torch.float32) -> Optional[int]:
+        """Device address of a caller-owned operand of a raw op (written or read in place: no copy may be made), None = NULL."""
+        if t is None:
+            return None
+        if not (t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()):
+            raise GigaAMHipError(f"{what}: {name} must be a contiguous {dtype} tensor on {self.device}")
+        return t.data_ptr()
+
+    def op_layernorm(self, mode: int, rows: int, d: int, x: Optional[Tensor], out1: Tensor, w1: Tensor, b1: Tensor, *,
+                     out2: Optional[Tensor] = None, w2: Optional[Tensor] = None, b2: Optional[Tensor] = None, split1: int = 0,
+                     split2: int = 0, rs: Optional[Tensor] = None, rcos: Optional[Tensor] = None, rsin: Optional[Tensor] = None,
+                     dk: int = 0, ta: int = 0, rope_rows: Optional[int] = None, row_t: Optional[Tensor] = None,
+                     part: Optional[Tensor] = None, nsplit: int = 0, pbias: Optional[Tensor] = None, presid: Optional[Tensor] = None,
+                     palpha: float = 1.0, xstore: Optional[Tensor] = None, eps: float = 1e-5) -> None:
+        """gam_op_layernorm (include/gigaam_hip.h): one launch of the LayerNorm family on the caller's device tensors, which are
+        written in place (out1 may be x; buffers may be longer than ``rows`` rows).  ``rope_rows`` defaults to the rows of rcos."""
+        what = "op_layernorm"
+        op = _lib.GamLnOp()
+        for name, t in (("x", x), ("out1", out1), ("out2", out2), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("rcos", rcos),
+                        ("rsin", rsin), ("rs", rs), ("part", part), ("pbias", pbias), ("presid", presid), ("xstore", xstore)):
+            setattr(op, name, self._op_ptr(what, name, t))
+        op.row_t = self._op_ptr(what, "row_t", row_t, torch.int32)
+        op.mode, op.rows, op.d, op.split1, op.split2, op.dk, op.ta, op.nsplit = mode, rows, d, split1, split2, dk, ta, nsplit
+        op.rope_rows = (0 if rcos is None else rcos.shape[0]) if rope_rows is None else rope_rows
+        op.eps, op.palpha = eps, palpha
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_layernorm(self._h, C.byref(op), self._stream())
+        self._check(rc, "gam_op_layernorm")
+
+    def op_convmod(self, u: Tensor, z: Tensor, dw_w: Tensor, dw_b: Tensor, n_scale: Tensor, n_shift: Tensor, lens: Tensor, B: int,
+                   Ta: int, Tv: int, d: int, ks: int, layer_norm: bool, z_split: int = 0, cu: Optional[Tensor] = None) -> None:
+        """gam_op_convmod (include/gigaam_hip.h): the fused conv-module middle on the caller's device tensors; z is written in place
+        (it may be longer than the rows the launch owns).  A value beyond fp16's safe range raises the handle's range flag."""
+        what = "op_convmod"
+        ptrs = [self._op_ptr(what, n, t) for n, t in (("u", u), ("z", z), ("dw_w", dw_w), ("dw_b", dw_b), ("n_scale", n_scale),
+                                                      ("n_shift", n_shift))]
+        ptrs += [self._op_ptr(what, "lens", lens, torch.int32), self._op_ptr(what, "cu", cu, torch.int32)]
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_convmod(self._h, *ptrs, B, Ta, Tv, d, ks, int(bool(layer_norm)), z_split, self._stream())
+        self._check(rc, "gam_op_convmod")
+
     # ------------------------------------------------------------------ profiling
     def profile_enable(self, on=True) -> None:
         """True/1: time every launch; 2: GEMM family only; False/0: off."""

@@ -452,6 +452,57 @@ int gam_op_attention_ex(gam_handle* h, const float* q, const float* k, const flo
                         const int32_t* lens, const int32_t* cu, int B, int Ta, int Tv, int H, const float* pbuf,
                         const float* pos_u, const float* pos_v, void* stream);
 
+/* Raw LayerNorm entry for kernel-level tests and microbenchmarks: every form the encoder launches (gam_norm.h), on the caller's
+ * DEVICE pointers.  All float pointers 16-byte aligned; nothing is allocated.
+ *   mode 0: out1 = LN(x; w1, b1).
+ *   mode 1: out1 = LN(x; w1, b1) and out2 = rotary(out1): per head of dk columns (dk % 8 == 0, d % dk == 0)
+ *           out2 = y cos + rotate_half(y) sin with cos / sin rows rcos / rsin f32 [rope_rows, dk/2] (the first dk/2 columns of the
+ *           reference's tables) taken at frame min(t, rope_rows - 1), t = row_t[row] (i32 [rows]) or row % ta when row_t is NULL.
+ *   mode 2: out1 = LN(x; w1, b1) (out1 == x allowed: the encoder's norm_out runs in place) and out2 = LN(out1; w2, b2).
+ * x, out1, out2: [rows, d] dense, d % 4 == 0, d <= 1024.  split1 / split2: store format of out1 / out2 -- 0 fp32, 1 the sp32
+ * split-fp16 operand layout (per 32 columns [hi x32 | lo x32] halfs in the 128 bytes of the fp32 values), 2 dense fp16 in the first
+ * half of the row's bytes; 1 and 2 need d % 32 == 0.  rs (f32 [rows], may be NULL): the per-row power-of-two scale of the GEMM
+ * operand -- the operand is stored multiplied by 2^e with max|row| 2^e in [2^7, 2^8) and rs[row] = 2^-e (mode 0: out1; mode 1:
+ * out1 and out2 with one scale; mode 2: out2 only).
+ * part (may be NULL): the fused split-K reduce -- the row is resid + palpha (sum of the nsplit slices of part [nsplit][rows][d], in
+ * slice order, + pbias [d]) instead of x's; it is stored to xstore [rows, d] (modes 0 and 1; mode 2 writes it normalised to out1) and
+ * then normalised.  pbias and presid [rows, d] are mandatory with part.
+ * A shape the launcher refuses (d % 4, d > 1024, a split output with d % 32 != 0, dk % 8, part without bias / residual) fails with
+ * a message; nothing is launched. */
+typedef struct gam_ln_op {
+  const float* x;
+  float* out1;
+  float* out2;
+  const float* w1;
+  const float* b1;
+  const float* w2;
+  const float* b2;
+  const float* rcos;
+  const float* rsin;
+  const int32_t* row_t;
+  float* rs;
+  const float* part;
+  const float* pbias;
+  const float* presid;
+  float* xstore;
+  int32_t mode, rows, d, split1, split2, dk, ta, rope_rows, nsplit;
+  float eps, palpha;
+} gam_ln_op;
+int gam_op_layernorm(gam_handle* h, const gam_ln_op* op, void* stream);
+
+/* Raw entry of the fused conv-module middle (gam_convmod.h) for kernel-level tests and microbenchmarks:
+ * z = SiLU(norm(depthwise_conv_ks(mask(GLU(u))) + dw_b)) on DEVICE pointers.  u f32 [rows, 2d] (the pointwise-conv1 output), z
+ * [rows, d] in store format z_split (0 / 1 / 2 as above; 1 and 2 need d % 32 == 0), dw_w [d, ks], dw_b [d]; layer_norm = 0:
+ * BatchNorm as the folded affine y n_scale + n_shift (d % 64 == 0, ks in {5, 9, 31}); 1: LayerNorm over the d channels with weight
+ * n_scale and bias n_shift, eps 1e-5 (d <= 1024, ks in {5, 9, 31}).  lens i32 [B]: klen_b = min(lens[b], Tv) valid frames, frames
+ * outside [0, klen_b) enter the taps as zeros whatever u holds there.  cu (i32 [B], may be NULL): packed rows -- utterance b is rows
+ * cu[b] .. cu[b] + klen_b - 1 and Ta >= every klen_b sizes the grid; NULL: rows b Ta .. b Ta + Ta - 1 (Tv <= Ta), all Ta rows are
+ * written and rows t >= klen_b carry no defined value.  With d % 4 == 0 the float pointers are 16-byte aligned.  A value beyond
+ * +-60000 in a stored row sets the handle's range flag exactly as inside gam_encode.  Nothing is allocated. */
+int gam_op_convmod(gam_handle* h, const float* u, float* z, const float* dw_w, const float* dw_b, const float* n_scale,
+                   const float* n_shift, const int32_t* lens, const int32_t* cu, int B, int Ta, int Tv, int d, int ks,
+                   int layer_norm, int z_split, void* stream);
+
 /* Tuning hook of the large-M GEMM (tools/smallm_sweep.py): force the tile shape (mt in 2..4 rows of 64, nw in {2, 4}
  * columns of 64) and / or the split-K factor of every following launch in this process; 0 = planned per launch (default). */
 int gam_tune_sp(int mt, int nw, int splitk);
