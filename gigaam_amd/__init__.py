@@ -1,7 +1,8 @@
 """gigaam_amd -- MI355X-native drop-in for GigaAM's inference hot path.
 
 Public surface = the reference's (gigaam/__init__.py:15-22): ``load_model``,
-``GigaAM``, ``GigaAMASR``, ``load_audio``, ``format_time``.  The log-mel frontend,
+``GigaAM``, ``GigaAMASR``, ``load_audio``, ``format_time``, plus the native audio ingest
+(``decode_audio``, ``resample``, ``read_wav``, ``set_audio_backend``: gigaam_amd/audio.py).  The log-mel frontend,
 Conformer encoder and CTC / RNN-T greedy decoders run as hand-written gfx950 HIP
 kernels in ``libgigaam_hip.so`` (C ABI: include/gigaam_hip.h).  There is no CPU
 path: without the built library and a ROCm GPU every compute call raises.
@@ -14,12 +15,13 @@ from typing import Any, Optional, Union
 
 import torch
 
+from .audio import decode_audio, read_wav, resample, set_audio_backend
 from .lm import NgramLM
 from .model import GigaAM, GigaAMASR, GigaAMEmo
 from .preprocess import load_audio
 from .types import ConfidenceResult, KeywordHit, KeywordSearchResult, LongformAlignmentResult, ScoredWord
 
-__all__ = ["GigaAM", "GigaAMASR", "GigaAMEmo", "NgramLM", "ConfidenceResult", "KeywordHit", "KeywordSearchResult", "LongformAlignmentResult", "ScoredWord", "load_audio", "format_time", "load_model", "model_from_checkpoint"]
+__all__ = ["GigaAM", "GigaAMASR", "GigaAMEmo", "NgramLM", "ConfidenceResult", "KeywordHit", "KeywordSearchResult", "LongformAlignmentResult", "ScoredWord", "load_audio", "decode_audio", "resample", "read_wav", "set_audio_backend", "format_time", "load_model", "model_from_checkpoint"]
 
 _CACHE_DIR = os.path.expanduser("~/.cache/gigaam")
 # md5 of the reference's published checkpoints (gigaam/__init__.py:28-41)

@@ -21,6 +21,8 @@ NORM_BATCH, NORM_LAYER = 0, 1
 HEAD_NONE, HEAD_CTC, HEAD_RNNT, HEAD_EMO = 0, 1, 2, 3
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_F64, DTYPE_I64 = 0, 1, 2, 3, 4
 GEMM_F32, GEMM_F16X3, GEMM_F16 = 0, 1, 2
+RS_U8, RS_I16, RS_I24, RS_I32, RS_F32, RS_MULAW, RS_ALAW = range(7)
+RS_FORM_SINGLE, RS_FORM_TABLE, RS_FORM_ROWS = 0, 1, 2
 PF_CLASSES = ["gemm", "conv2", "attn", "norm", "convmod", "stem", "frontend", "decode", "misc", "align_bt", "align_out"]
 
 
@@ -109,6 +111,11 @@ SIGNATURES = {
     "gam_plan_sp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gam_plan_sp_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gam_tune_sp_stages": (C.c_int, [C.c_int]),
+    "gam_resample_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gam_resample_tile": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gam_resample_table": (C.c_int, [C.c_int, C.c_int, _P, _P]),
+    "gam_resample_out_len": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    "gam_op_resample": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
     "gam_profile_enable": (C.c_int, [_P, C.c_int]),
     "gam_profile_pause": (C.c_int, [_P, C.c_int]),
     "gam_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -33,6 +33,7 @@
 #include "gam_gemm_sp.h"
 #include "gam_norm.h"
 #include "gam_pack.h"
+#include "gam_resample.h"
 #include "gam_stem.h"
 
 namespace {
@@ -2740,6 +2741,45 @@ int gam_plan_sp_ex(int M, int N, int K, int n_cu, int* mt, int* nw, int* splitk,
   const GamSpPlan p = gam_gemm_sp_plan(M, N, K, 0, n_cu > 0 ? n_cu : 256);
   *mt = p.mt; *nw = p.nw; *splitk = p.s; *stages = p.ns;
   return 0;
+}
+
+int gam_resample_plan(int rate_in, int rate_out, int* up, int* down, int* taps) {
+  GamRsPlan p;
+  const int rc = gam_rs_plan(rate_in, rate_out, &p);
+  if (rc != 0) return rc;
+  if (up) *up = (int)p.N;
+  if (down) *down = (int)p.O;
+  if (taps) *taps = p.K;
+  return 0;
+}
+
+int gam_resample_tile(int rate_in, int rate_out, int* tile, int* form) {
+  GamRsPlan p;
+  const int rc = gam_rs_plan(rate_in, rate_out, &p);
+  if (rc != 0) return rc;
+  if (tile) *tile = p.tile;
+  if (form) *form = p.form;
+  return 0;
+}
+
+int gam_resample_table(int rate_in, int rate_out, float* coeff, int32_t* first) {
+  GamRsPlan p;
+  const int rc = gam_rs_plan(rate_in, rate_out, &p);
+  if (rc != 0) return rc;
+  if (!coeff || !first) return -1;
+  gam_rs_table(p, coeff, first);
+  return 0;
+}
+
+int64_t gam_resample_out_len(int rate_in, int rate_out, int64_t n_in) {
+  GamRsPlan p;
+  if (gam_rs_plan(rate_in, rate_out, &p) != 0) return -1;
+  return gam_rs_out_len(p, n_in);
+}
+
+int gam_op_resample(const void* src, int fmt, int channels, int channel, const int64_t* len_in, int B, int64_t frames, int rate_in, int rate_out,
+                    const float* coeff, const int32_t* first, float* dst, int64_t L_out, int64_t* len_out, void* stream) {
+  return gam_rs_run(src, fmt, channels, channel, len_in, B, frames, rate_in, rate_out, coeff, first, dst, L_out, len_out, (hipStream_t)stream);
 }
 
 int gam_profile_enable(gam_handle* h, int on) {

@@ -15,34 +15,50 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
+from . import audio
 from .engine import HipEngine, build_config
 
 SAMPLE_RATE = 16000
 
 
-def load_audio(audio_path: str, sample_rate: int = SAMPLE_RATE) -> Tensor:
-    """Decode to mono ``sample_rate`` PCM16 and scale by 1/32768 (reference
-    preprocess.py:12-40 pipes the file through ffmpeg).  Where no ffmpeg binary
-    exists (this image), a PCM16 mono WAV at the right rate is read with the
-    stdlib ``wave`` module -- identical samples, no resampling -- and anything
-    else raises the reference's ``RuntimeError("Failed to load audio")``."""
-    if shutil.which("ffmpeg") is not None:
-        cmd = ["ffmpeg", "-nostdin", "-threads", "0", "-i", audio_path, "-f", "s16le", "-ac", "1",
-               "-acodec", "pcm_s16le", "-ar", str(sample_rate), "-"]
-        try:
-            raw = subprocess.run(cmd, capture_output=True, check=True).stdout
-        except subprocess.CalledProcessError as exc:
-            raise RuntimeError("Failed to load audio") from exc
-        pcm = np.frombuffer(raw, dtype=np.int16)
+def _ffmpeg_pcm16(audio_path: str, sample_rate: int) -> np.ndarray:
+    cmd = ["ffmpeg", "-nostdin", "-threads", "0", "-i", audio_path, "-f", "s16le", "-ac", "1",
+           "-acodec", "pcm_s16le", "-ar", str(sample_rate), "-"]
+    try:
+        raw = subprocess.run(cmd, capture_output=True, check=True).stdout
+    except (subprocess.CalledProcessError, OSError) as exc:
+        raise RuntimeError("Failed to load audio") from exc
+    return np.frombuffer(raw, dtype=np.int16)
+
+
+def _plain_pcm16(audio_path: str, sample_rate: int) -> Optional[np.ndarray]:
+    """The samples of a mono PCM16 WAV at ``sample_rate`` (stdlib ``wave``), or None for any other file."""
+    try:
+        with wave.open(audio_path, "rb") as wf:
+            if wf.getnchannels() == 1 and wf.getsampwidth() == 2 and wf.getframerate() == sample_rate:
+                return np.frombuffer(wf.readframes(wf.getnframes()), dtype=np.int16)
+    except (wave.Error, OSError, EOFError):
+        pass
+    return None
+
+
+def load_audio(audio_path: str, sample_rate: int = SAMPLE_RATE, backend: Optional[str] = None) -> Tensor:
+    """A file as mono fp32 at ``sample_rate`` on the CPU.  ``backend`` (default: ``audio.set_audio_backend`` / ``GAM_AUDIO_BACKEND``):
+
+    ``"ffmpeg"``  decode to mono ``sample_rate`` PCM16 and scale by 1/32768 (reference preprocess.py:12-40 pipes the file through ffmpeg);
+    ``"native"``  ``audio.decode_audio``: our WAV reader and the GPU conversion / downmix / resampling kernel (a file already at the rate
+                  needs no GPU);
+    ``"auto"``    ffmpeg where it is installed; without it a PCM16 mono WAV at the right rate is read with the stdlib ``wave`` module
+                  -- identical samples, no resampling -- and every other file goes the native way.
+
+    What cannot be read raises the reference's ``RuntimeError("Failed to load audio")``."""
+    backend = audio.get_audio_backend() if backend is None else audio._check_backend(backend)
+    if backend == "ffmpeg" or (backend == "auto" and shutil.which("ffmpeg") is not None):
+        pcm: Optional[np.ndarray] = _ffmpeg_pcm16(audio_path, sample_rate)
     else:
-        try:
-            with wave.open(audio_path, "rb") as wf:
-                ok = wf.getnchannels() == 1 and wf.getsampwidth() == 2 and wf.getframerate() == sample_rate
-                if not ok:
-                    raise RuntimeError("ffmpeg is not installed and the file is not mono PCM16 at the target rate")
-                pcm = np.frombuffer(wf.readframes(wf.getnframes()), dtype=np.int16)
-        except (wave.Error, OSError, EOFError) as exc:
-            raise RuntimeError("Failed to load audio") from exc
+        pcm = _plain_pcm16(audio_path, sample_rate) if backend == "auto" else None
+    if pcm is None:
+        return audio.decode_audio(audio_path, sample_rate).cpu()
     return torch.from_numpy(pcm.astype(np.float32)) / 32768.0
 
 

@@ -516,6 +516,39 @@ int gam_plan_sp(int M, int N, int K, int n_cu, int* mt, int* nw, int* splitk);
 int gam_plan_sp_ex(int M, int N, int K, int n_cu, int* mt, int* nw, int* splitk, int* stages);
 int gam_tune_sp_stages(int stages);
 
+/* ---- audio ingest: raw interleaved frames -> mono fp32 at another rate (gam_resample.h; handle-free like gam_plan_sp) ----------
+ * Band-limited interpolation with a Hann-windowed sinc, the definition and defaults of torchaudio.functional.resample
+ * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99): with g = gcd(rate_in, rate_out), O = rate_in / g, N = rate_out / g,
+ * f = 0.99 min(O, N) and x[m] = 0 outside [0, n_in),
+ *     y[j] = (f / O) sum_m x[m] sinc(pi t) cos^2(pi t / 12),  t = f (m / O - j / N),  over |t| < 6,   j < n_out = ceil(N n_in / O).
+ * The filter is a table of N rows (one per phase j mod N) of K taps, computed in fp64 and rounded to fp32, plus the first input
+ * offset of each row: output j = q N + p reads x[first[p] + q O + k], k < K.  Equal rates are the identity (N = O = K = 1).
+ *
+ * gam_resample_plan    host arithmetic: *up = N, *down = O, *taps = K.  -1: a rate outside 1..384000; -2: a table of more than
+ *                      2^18 entries (N K), which no call accepts.
+ * gam_resample_tile    the launch a rate pair gets: outputs per workgroup, and the kernel form -- 0: N = 1 (one coefficient row,
+ *                      read lane-uniformly), 1: N > 1 with the whole table in LDS, 2: N > 1 with only the tile's rows in LDS.
+ * gam_resample_table   coeff f32 [N K] and first i32 [N] (HOST pointers).
+ * gam_resample_out_len ceil(N n_in / O) in 64 bits; -1 for a refused rate pair.
+ * gam_op_resample      src: B rows of `frames` interleaved frames of `channels` samples (DEVICE; row pitch frames * channels *
+ *                      sample bytes) in format fmt; channel = -1 takes the mean of the channels (an fp32 sum in channel order times
+ *                      1.0f / channels -- not a layout-aware matrix), channel = k takes channel k; the downmix precedes the filter.
+ *                      len_in (device i64 [B], or NULL = every row holds `frames`): row b reads only its first len_in[b] frames, the
+ *                      rest of the row counts as zeros whatever it holds.  coeff / first: the table of gam_resample_table, on the
+ *                      DEVICE.  dst f32 [B, L_out]: y for j < len_out[b] = min(ceil(N len_in[b] / O), L_out), zeros up to L_out;
+ *                      len_out (device i64 [B]) may be NULL.  Frame indices and byte offsets are 64-bit.  Asynchronous on `stream`;
+ *                      nothing is allocated.  -1: bad argument, -2: refused rate pair, -3: the launch failed.
+ * Sample formats -> fp32: u8 (v - 128) / 128; i16 v / 32768; i24 (3 bytes, little-endian) v / 8388608; i32 float(v) 2^-31; f32 as it
+ * is; G.711 mu-law and A-law decoded to their 16-bit value, / 32768. */
+enum { GAM_RS_FMT_U8 = 0, GAM_RS_FMT_I16 = 1, GAM_RS_FMT_I24 = 2, GAM_RS_FMT_I32 = 3, GAM_RS_FMT_F32 = 4, GAM_RS_FMT_MULAW = 5,
+       GAM_RS_FMT_ALAW = 6 };
+int gam_resample_plan(int rate_in, int rate_out, int* up, int* down, int* taps);
+int gam_resample_tile(int rate_in, int rate_out, int* tile, int* form);
+int gam_resample_table(int rate_in, int rate_out, float* coeff, int32_t* first);
+int64_t gam_resample_out_len(int rate_in, int rate_out, int64_t n_in);
+int gam_op_resample(const void* src, int fmt, int channels, int channel, const int64_t* len_in, int B, int64_t frames, int rate_in,
+                    int rate_out, const float* coeff, const int32_t* first, float* dst, int64_t L_out, int64_t* len_out, void* stream);
+
 /* Per-kernel-class HIP-event timing on the launch stream (bench.py's roofline leg).
  * gam_profile_enable(h,1) starts collecting for every launch, (h,2) for the GEMM family only
  * (fewer event packets inside a timed region), (h,0) stops; gam_profile_read synchronises the events and
