@@ -17,6 +17,9 @@
 // Infeasible utterances -- T < U + #{i : y_i == y_{i-1}}, a target id outside [0, V-2], target_len outside [0, Umax], or no
 // path of finite score -- get status 0, score = loglik = -inf, frame labels and token frames -1; target entries past
 // target_len[b] are never read.  U = 0 is the all-blank path; T = 0 with U = 0 scores 0.
+//
+// The STAR variant (gam_ctc_align_star / gam_op_ctc_align_star) admits target id V, the wildcard of gam_trellis.h, whose emission is
+// star[b, t]; everything else, the statuses included, is as above with [0, V-2] + {V} for the ids.
 #pragma once
 #include "gam_trellis.h"
 
@@ -38,6 +41,12 @@ struct GamAlignArgs {
   float* score;              // [B]
   float* loglik;             // [B]
   int* status;               // [B]
+  static constexpr bool kStar = false;
+};
+// the STAR variant's arguments: the old kernels keep their kernarg layout
+struct GamAlignStarArgs : GamAlignArgs {
+  const float* star;         // [B, Tp] the emission of a wildcard state (target id V) per frame, read as it is
+  static constexpr bool kStar = true;
 };
 
 // LDS bytes of one workgroup (host and device carve it the same way)
@@ -46,8 +55,30 @@ static inline size_t gam_align_lds_bytes(bool bp_lds, int Tp, int nchunk, int sp
   return (bp_lds ? (size_t)Tp * nchunk * 16 : 0) + 16 * sp + GAM_TRELLIS_WM * sizeof(float) + 64 + (((size_t)Tp * 2 + 15) & ~(size_t)15);
 }
 
-template <bool BP_LDS, int SPT>   // SPT states per thread: S_max <= SPT * blockDim
-__global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlignArgs a) {
+// Wildcard row: star[b, t] = max_v lp[b, t, v] - penalty for t < enc_len[b] (enc_len NULL: every row), 0 past it (never read).  One
+// wave per row with coalesced reads, as gam_kws_rowmax_kernel -- a sibling, because that one leaves the rows past enc_len unwritten and
+// writes {m, blank - m} pairs the keyword search reads as they are.
+__global__ __launch_bounds__(256) void gam_ctc_star_row_kernel(const float* __restrict__ lp, const int* __restrict__ enc_len, int Tp, int V,
+                                                               long rows, float penalty, float* __restrict__ star) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int b = (int)(row / Tp), t = (int)(row - (long)b * Tp);
+  if (enc_len != nullptr && t >= enc_len[b]) {
+    if (lane == 0) star[row] = 0.f;
+    return;
+  }
+  const float* p = lp + (size_t)row * V;
+  float m = -INFINITY;
+  for (int v = lane; v < V; v += 64) m = fmaxf(m, p[v]);
+  m = gam_wave_max(m);
+  if (lane == 0) star[row] = m - penalty;
+}
+
+// Args = GamAlignStarArgs: the STAR variant (target id V is the wildcard, gam_trellis.h), launched only by the star entry points.
+template <bool BP_LDS, int SPT, typename Args = GamAlignArgs>   // SPT states per thread: S_max <= SPT * blockDim
+__global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(Args a) {
+  constexpr bool STAR = Args::kStar;
   extern __shared__ uint4 gam_smem_align[];
   unsigned char* smem = reinterpret_cast<unsigned char*>(gam_smem_align);
   const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
@@ -79,7 +110,7 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
     int reps = 0, bad = 0;
     for (int u = tid; u < U; u += nt) {
       const int v = y[u];
-      bad |= (v < 0 || v > V - 2);
+      bad |= gam_ctc_bad_id<STAR>(v, V);
       reps += (u > 0 && y[u - 1] == v);
     }
     if (reps) atomicAdd(&misc[0], reps);
@@ -121,12 +152,19 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
 
   // Emission loads are unconditional (a row index clamped to T - 1, inactive states read the blank column): a load under a branch makes
   // hipcc wait for every load in flight at its first use, which would serialise the prefetch.
+  // STAR: the load stays ONE unconditional load per state, from the state's own (base, stride) -- gam_ctc_star_src.
   const float* lpb = a.lp + (size_t)b * Tp * V;
+  const float* src[SPT];
+  int stride[SPT];
+  if constexpr (STAR) gam_ctc_star_src<SPT>(lpb, a.star + (size_t)b * Tp, V, lab, src, stride);
   float e[GAM_ALIGN_PF][SPT];
 #pragma unroll
   for (int k = 0; k < GAM_ALIGN_PF; ++k)
 #pragma unroll
-    for (int i = 0; i < SPT; ++i) e[k][i] = lpb[(size_t)(k < T ? k : T - 1) * V + lab[i]];
+    for (int i = 0; i < SPT; ++i) {
+      if constexpr (STAR) e[k][i] = src[i][(size_t)(k < T ? k : T - 1) * stride[i]];
+      else e[k][i] = lpb[(size_t)(k < T ? k : T - 1) * V + lab[i]];
+    }
 
   double offD = 0.0, offA = 0.0;   // what the renormalisations subtracted so far
   for (int t0 = 0; t0 < T; t0 += GAM_ALIGN_PF) {
@@ -153,7 +191,10 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_kernel(GamAlig
       // the row t + PF replaces the one just used (its load is in flight during the next PF - 1 steps)
       const int tn = t + GAM_ALIGN_PF < T ? t + GAM_ALIGN_PF : T - 1;
 #pragma unroll
-      for (int i = 0; i < SPT; ++i) e[k][i] = lpb[(size_t)tn * V + lab[i]];
+      for (int i = 0; i < SPT; ++i) {
+        if constexpr (STAR) e[k][i] = src[i][(size_t)tn * stride[i]];
+        else e[k][i] = lpb[(size_t)tn * V + lab[i]];
+      }
       gam_trellis_wm_publish(wm, cur, lane, wave, lmD, lmA);
 #pragma unroll
       for (int i = 0; i < SPT; ++i) {

@@ -60,6 +60,12 @@ struct GamAlignLongArgs {
   double* score;
   double* loglik;
   int* status;
+  static constexpr bool kStar = false;
+};
+// the STAR variant's arguments (target id V is the wildcard, gam_trellis.h): the old kernels keep their kernarg layout
+struct GamAlignLongStarArgs : GamAlignLongArgs {
+  const float* star;         // [T] the emission of a wildcard state per frame, read as it is
+  static constexpr bool kStar = true;
 };
 
 // threads and states per thread of a block's workgroup: SB <= spt * nt, spt <= 3, nt a multiple of 64 up to 1024
@@ -77,13 +83,14 @@ __device__ __forceinline__ bool gam_align_long_feasible(const GamAlignLongArgs& 
   return gam_ctc_feasible(a.T, a.U, a.ctrl[0], a.ctrl[1]);
 }
 
-// repeats and bad ids of the target (U > 0)
+// repeats and bad ids of the target (U > 0); STAR: id V is the wildcard
+template <bool STAR = false>
 __global__ __launch_bounds__(256) void gam_ctc_align_long_prep_kernel(GamAlignLongArgs a) {
   const int u = blockIdx.x * 256 + threadIdx.x;
   int rep = 0, bad = 0;
   if (u < a.U) {
     const int v = a.targets[u];
-    bad = v < 0 || v > a.V - 2;
+    bad = gam_ctc_bad_id<STAR>(v, a.V);
     rep = u > 0 && a.targets[u - 1] == v;
   }
   const unsigned long long mr = __ballot(rep), mb = __ballot(bad);
@@ -94,8 +101,10 @@ __global__ __launch_bounds__(256) void gam_ctc_align_long_prep_kernel(GamAlignLo
 }
 
 // launch d of the sweep: workgroup x is tile (j, k) = (jlo + x, d - j), jlo = max(0, d - (nT - 1))
-template <int SPT>
-__global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_kernel(GamAlignLongArgs a, int d) {
+// Args = GamAlignLongStarArgs: the STAR variant, launched only by gam_op_ctc_align_long_star.
+template <int SPT, typename Args = GamAlignLongArgs>
+__global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_kernel(Args a, int d) {
+  constexpr bool STAR = Args::kStar;
   extern __shared__ uint4 gam_smem_align_long[];
   if (!gam_align_long_feasible(a)) return;       // (before any emission load: a bad id would index outside lp)
   const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
@@ -155,14 +164,21 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_ker
   __syncthreads();
 
   // Emission and edge loads are unconditional (a row index clamped to t1 - 1, inactive states read the blank column): see gam_align.h
+  // STAR: one unconditional load per state from the state's own (base, stride) -- gam_ctc_star_src
   const int ie = (sb - 1) / nt, te = (sb - 1) % nt;   // who holds local state SB - 1
+  const float* src[SPT];
+  int stride[SPT];
+  if constexpr (STAR) gam_ctc_star_src<SPT>(a.lp, a.star, V, lab, src, stride);
   float e[GAM_ALIGN_PF][SPT];
   double2 ne[GAM_ALIGN_PF];
 #pragma unroll
   for (int q = 0; q < GAM_ALIGN_PF; ++q) {
     const int tq = t0 + q < t1 ? t0 + q : t1 - 1;
 #pragma unroll
-    for (int i = 0; i < SPT; ++i) e[q][i] = a.lp[(size_t)tq * V + lab[i]];
+    for (int i = 0; i < SPT; ++i) {
+      if constexpr (STAR) e[q][i] = src[i][(size_t)tq * stride[i]];
+      else e[q][i] = a.lp[(size_t)tq * V + lab[i]];
+    }
     ne[q] = eg[tq];
   }
 
@@ -196,7 +212,10 @@ __global__ __launch_bounds__(GAM_ALIGN_MAX_NT) void gam_ctc_align_long_sweep_ker
       // the row t + PF replaces the one just used (its load is in flight during the next PF - 1 steps)
       const int tn = t + GAM_ALIGN_PF < t1 ? t + GAM_ALIGN_PF : t1 - 1;
 #pragma unroll
-      for (int i = 0; i < SPT; ++i) e[q][i] = a.lp[(size_t)tn * V + lab[i]];
+      for (int i = 0; i < SPT; ++i) {
+        if constexpr (STAR) e[q][i] = src[i][(size_t)tn * stride[i]];
+        else e[q][i] = a.lp[(size_t)tn * V + lab[i]];
+      }
       ne[q] = eg[tn];
       gam_trellis_wm_publish(wm, cur, lane, wave, lmD, lmA);
 #pragma unroll

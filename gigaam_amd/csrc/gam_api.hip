@@ -134,6 +134,7 @@ struct gam_handle {
   // workspace (grow-only)
   DevBuf wavp, spec, img, c2, xin, y1, x, y, yr, hbuf, qkv, ctx, ubuf, zbuf, tok, logits, encp, pbuf, aplanes;
   DevBuf op_planes, op_sp, splitk_ws;   // gam_op_gemm operand planes; split-K partial sums
+  DevBuf align_star;                    // wildcard emissions of gam_ctc_align_star, B x T' floats (gam_ctc_star_row_kernel)
   DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
   DevBuf align_long_ws;                 // long-utterance CTC alignment (gam_align_long.h): backpointers | edges | rows | offsets | path | ctrl
   size_t al_ws_limit = GAM_AL_WS_DEFAULT;   // bytes that workspace may take (gam_set_ctc_align_workspace; GAM_CTC_ALIGN_WS at gam_create)
@@ -592,6 +593,7 @@ void gam_destroy(gam_handle* h) {
   if (h->hw_trie) hipFree(h->hw_trie);
   if (h->kw_dev) hipFree(h->kw_dev);
   if (h->kws_mb.p) hipFree(h->kws_mb.p);
+  if (h->align_star.p) hipFree(h->align_star.p);
   if (h->lm_cls) hipFree(h->lm_cls);
   if (h->lm_wt) hipFree(h->lm_wt);
   if (h->lm_ng) hipFree(h->lm_ng);
@@ -1466,10 +1468,10 @@ int gam_ctc_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, 
 }
 
 // CTC forced alignment over log-probs [B, Tp, V] (gam_align.h): one workgroup per utterance.  Decode class (the caller holds a DecodeScope):
-// the backpointer scratch is the handle's.
+// the backpointer scratch is the handle's.  star != NULL: the STAR variant of the kernel (target id V is the wildcard, emission star [B, Tp]).
 static int ctc_align_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* targets,
                             const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last,
-                            float* score, float* loglik, int32_t* status, hipStream_t s) {
+                            float* score, float* loglik, int32_t* status, hipStream_t s, const float* star = nullptr) {
   if (B <= 0 || Tp <= 0 || V < 2) return fail(h, -1, "CTC alignment: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
   if (Tp > GAM_ALIGN_MAX_T) return fail(h, -1, "CTC alignment: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_ALIGN_MAX_T);
   if (Umax < 0 || Umax > GAM_ALIGN_MAX_U) return fail(h, -1, "CTC alignment: Umax=%d tokens outside [0, %d]", Umax, GAM_ALIGN_MAX_U);
@@ -1483,7 +1485,8 @@ static int ctc_align_launch(gam_handle* h, const float* lp, const int32_t* enc_l
   const bool bp_lds = gam_align_lds_bytes(true, (int)Tp, nchunk, spt, nt) <= GAM_ALIGN_LDS_MAX;
   const size_t sm = gam_align_lds_bytes(bp_lds, (int)Tp, nchunk, spt, nt);
   if (sm > GAM_ALIGN_LDS_MAX) return fail(h, -1, "CTC alignment: T'=%lld x Umax=%d needs %zu bytes of LDS", (long long)Tp, Umax, sm);
-  GamAlignArgs a;
+  GamAlignStarArgs a;          // (the plain kernels take its GamAlignArgs base)
+  a.star = star;
   a.lp = lp; a.enc_len = enc_len; a.targets = targets; a.target_len = target_len;
   a.Tp = (int)Tp; a.V = V; a.Umax = Umax; a.nchunk = nchunk; a.bp_glob = nullptr;
   a.frame_labels = frame_labels; a.tok_first = tok_first; a.tok_last = tok_last; a.score = score; a.loglik = loglik; a.status = status;
@@ -1491,13 +1494,19 @@ static int ctc_align_launch(gam_handle* h, const float* lp, const int32_t* enc_l
     if (int r = ensure(h, h->align_bp, (size_t)B * Tp * nchunk * 4 + 64)) return r;
     a.bp_glob = reinterpret_cast<uint4*>(h->align_bp.p);
   }
-  static std::atomic<unsigned long long> lds_set[6];
+  static std::atomic<unsigned long long> lds_set[12];
   const int which = (bp_lds ? 3 : 0) + (spt - 1);
   void (*const kerns[6])(GamAlignArgs) = {gam_ctc_align_kernel<false, 1>, gam_ctc_align_kernel<false, 2>, gam_ctc_align_kernel<false, 3>,
                                           gam_ctc_align_kernel<true, 1>, gam_ctc_align_kernel<true, 2>, gam_ctc_align_kernel<true, 3>};
-  if (sm > 64 * 1024) HIPCHK(h, gam_set_max_lds((const void*)kerns[which], GAM_ALIGN_LDS_MAX, lds_set[which]));
+  void (*const skerns[6])(GamAlignStarArgs) = {
+      gam_ctc_align_kernel<false, 1, GamAlignStarArgs>, gam_ctc_align_kernel<false, 2, GamAlignStarArgs>,
+      gam_ctc_align_kernel<false, 3, GamAlignStarArgs>, gam_ctc_align_kernel<true, 1, GamAlignStarArgs>,
+      gam_ctc_align_kernel<true, 2, GamAlignStarArgs>,  gam_ctc_align_kernel<true, 3, GamAlignStarArgs>};
+  if (sm > 64 * 1024)
+    HIPCHK(h, gam_set_max_lds(star ? (const void*)skerns[which] : (const void*)kerns[which], GAM_ALIGN_LDS_MAX, lds_set[(star ? 6 : 0) + which]));
   ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * smax * 4.0);
-  hipLaunchKernelGGL(kerns[which], dim3(B), dim3(nt), sm, s, a);
+  if (star) hipLaunchKernelGGL(skerns[which], dim3(B), dim3(nt), sm, s, a);
+  else hipLaunchKernelGGL(kerns[which], dim3(B), dim3(nt), sm, s, static_cast<const GamAlignArgs&>(a));
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -1522,18 +1531,71 @@ int gam_op_ctc_align(gam_handle* h, const float* log_probs, const int32_t* enc_l
                           status, s);
 }
 
-// CTC forced alignment of ONE long utterance (gam_align_long.h): the anti-diagonal sweep launches, the backtrack and the outputs kernel on
-// one stream.  Decode class: the workspace is the handle's.
-int gam_op_ctc_align_long(gam_handle* h, const float* log_probs, int64_t T, int V, const int32_t* targets, int U, int32_t* frame_labels,
-                          int32_t* tok_first, int32_t* tok_last, double* score, double* loglik, int32_t* status, void* stream) {
+// ---- wildcard tokens (target id V; gam_trellis.h).  Additions: the entry points above keep rejecting id V.
+static int ctc_star_penalty_check(gam_handle* h, float penalty) {
+  if (!std::isfinite(penalty) || penalty < 0.f) return fail(h, -1, "CTC wildcard: penalty %g must be finite and >= 0", (double)penalty);
+  return 0;
+}
+
+// star[row] = max_v lp[row, v] - penalty over rows = B * Tp (enc_len NULL: every row is valid)
+static int ctc_star_row_launch(gam_handle* h, const float* lp, const int32_t* enc_len, int B, int64_t Tp, int V, float penalty, float* star,
+                               hipStream_t s) {
+  const long rows = (long)B * Tp;
+  if (rows == 0) return 0;
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * V * 4.0);
+  hipLaunchKernelGGL(gam_ctc_star_row_kernel, dim3(gam_cdiv(rows, 4)), dim3(256), 0, s, lp, enc_len, (int)Tp, V, rows, penalty, star);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_op_ctc_star_row(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, float penalty,
+                        float* star_lp, void* stream) {
   GAM_DECODE_ENTRY(h, stream);
+  if (B <= 0 || Tp < 0 || V < 2 || (int64_t)B * Tp > 2147483647ll * 4)
+    return fail(h, -1, "CTC wildcard row: bad shape B=%d T'=%lld V=%d", B, (long long)Tp, V);
+  if (int r = ctc_star_penalty_check(h, penalty)) return r;
+  if (Tp > 0 && (!log_probs || !star_lp)) return fail(h, -1, "CTC wildcard row: NULL buffer");
+  return ctc_star_row_launch(h, log_probs, enc_len, B, Tp, V, penalty, star_lp, s);
+}
+
+int gam_ctc_align_star(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                       const int32_t* target_len, int Umax, float penalty, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last,
+                       float* score, float* loglik, int32_t* status, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (Tp > GAM_ALIGN_MAX_T || Umax < 0 || Umax > GAM_ALIGN_MAX_U)
+    return fail(h, -1, "CTC alignment: T'=%lld / Umax=%d beyond the limits (%d / %d)", (long long)Tp, Umax, GAM_ALIGN_MAX_T, GAM_ALIGN_MAX_U);
+  if (int r = ctc_star_penalty_check(h, penalty)) return r;
+  if (!enc_len) return fail(h, -1, "CTC alignment: NULL buffer");
+  if (int r = ctc_log_probs(h, encoded, B, Tp, nullptr, s)) return r;
+  const int V = h->cfg.num_classes;
+  if (int r = ensure(h, h->align_star, (size_t)B * Tp + 64)) return r;
+  if (int r = ctc_star_row_launch(h, h->logits.p, enc_len, B, Tp, V, penalty, h->align_star.p, s)) return r;
+  return ctc_align_launch(h, h->logits.p, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score,
+                          loglik, status, s, h->align_star.p);
+}
+
+int gam_op_ctc_align_star(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const float* star_lp,
+                          const int32_t* targets, const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first,
+                          int32_t* tok_last, float* score, float* loglik, int32_t* status, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (!star_lp) return fail(h, -1, "CTC alignment: NULL buffer");
+  return ctc_align_launch(h, log_probs, enc_len, B, Tp, V, targets, target_len, Umax, frame_labels, tok_first, tok_last, score, loglik,
+                          status, s, star_lp);
+}
+
+// CTC forced alignment of ONE long utterance (gam_align_long.h): the anti-diagonal sweep launches, the backtrack and the outputs kernel on
+// one stream.  Decode class: the workspace is the handle's.  wild: the STAR variants of the prep and sweep kernels, emissions star [T].
+static int ctc_align_long_launch(gam_handle* h, const float* log_probs, int64_t T, int V, bool wild, const float* star, const int32_t* targets, int U,
+                                 int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, double* score, double* loglik,
+                                 int32_t* status, hipStream_t s) {
   if (T < 0 || T > 2147483647ll || V < 2 || U < 0 || U > (1 << 30) - 1)
     return fail(h, -1, "long CTC alignment: bad shape T=%lld V=%d U=%d", (long long)T, V, U);
   if (!score || !loglik || !status || (T > 0 && (!log_probs || !frame_labels)) || (U > 0 && (!targets || !tok_first || !tok_last)))
     return fail(h, -1, "long CTC alignment: NULL buffer");
   const GamAlignLongForce& frc = gam_align_long_force();
   const int fsb = frc.sb.load(), ftt = frc.tt.load();
-  GamAlignLongArgs a;
+  GamAlignLongStarArgs a;      // (the plain kernels take its GamAlignLongArgs base)
+  a.star = star;
   a.lp = log_probs; a.targets = targets; a.T = (int)T; a.V = V; a.U = U;
   a.sb = fsb ? fsb : GAM_AL_SB_DEFAULT;
   a.tt = ftt ? ftt : GAM_AL_TT_DEFAULT;
@@ -1563,25 +1625,49 @@ int gam_op_ctc_align_long(gam_handle* h, const float* log_probs, int64_t T, int 
   gam_align_long_shape(a.sb, &nt, &spt);
   const size_t sm = gam_align_long_lds_bytes(spt, nt);
   HIPCHK(h, hipMemsetAsync(a.ctrl, 0, 16, s));
-  if (U > 0) hipLaunchKernelGGL(gam_ctc_align_long_prep_kernel, dim3(gam_cdiv(U, 256)), dim3(256), 0, s, a);
+  const GamAlignLongArgs& a0 = a;
+  if (U > 0) {
+    if (wild) hipLaunchKernelGGL(gam_ctc_align_long_prep_kernel<true>, dim3(gam_cdiv(U, 256)), dim3(256), 0, s, a0);
+    else hipLaunchKernelGGL(gam_ctc_align_long_prep_kernel<false>, dim3(gam_cdiv(U, 256)), dim3(256), 0, s, a0);
+  }
   if (T > 0 && T >= U) {      // (T < U is infeasible whatever the ids are: the outputs kernel alone reports it)
     ProfScope ps(h, s, GAM_PF_DECODE, (double)T * (double)S * 4.0);
     for (int d = 0; d < a.nT + a.nS - 1; ++d) {
       const int jlo = std::max(0, d - (a.nT - 1)), jhi = std::min(a.nS - 1, d);
-      if (spt == 1) hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<1>, dim3(jhi - jlo + 1), dim3(nt), sm, s, a, d);
-      else if (spt == 2) hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<2>, dim3(jhi - jlo + 1), dim3(nt), sm, s, a, d);
-      else hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<3>, dim3(jhi - jlo + 1), dim3(nt), sm, s, a, d);
+      const dim3 grid(jhi - jlo + 1);
+      if (wild) {
+        if (spt == 1) hipLaunchKernelGGL((gam_ctc_align_long_sweep_kernel<1, GamAlignLongStarArgs>), grid, dim3(nt), sm, s, a, d);
+        else if (spt == 2) hipLaunchKernelGGL((gam_ctc_align_long_sweep_kernel<2, GamAlignLongStarArgs>), grid, dim3(nt), sm, s, a, d);
+        else hipLaunchKernelGGL((gam_ctc_align_long_sweep_kernel<3, GamAlignLongStarArgs>), grid, dim3(nt), sm, s, a, d);
+      } else if (spt == 1) hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<1>, grid, dim3(nt), sm, s, a0, d);
+      else if (spt == 2) hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<2>, grid, dim3(nt), sm, s, a0, d);
+      else hipLaunchKernelGGL(gam_ctc_align_long_sweep_kernel<3>, grid, dim3(nt), sm, s, a0, d);
     }
   }
   if (T > 0 && T >= U) {
     ProfScope ps(h, s, GAM_PF_ALIGN_BT, (double)T * 16.0);
-    hipLaunchKernelGGL(gam_ctc_align_long_backtrack_kernel, dim3(1), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(gam_ctc_align_long_backtrack_kernel, dim3(1), dim3(64), 0, s, a0);
   }
   const int64_t n_out = std::max<int64_t>(std::max<int64_t>(T, U), 1);
   ProfScope ps(h, s, GAM_PF_ALIGN_OUT, (double)T * 8.0 + (double)U * 8.0);
-  hipLaunchKernelGGL(gam_ctc_align_long_outputs_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(gam_ctc_align_long_outputs_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, a0);
   HIPCHK(h, hipGetLastError());
   return 0;
+}
+
+int gam_op_ctc_align_long(gam_handle* h, const float* log_probs, int64_t T, int V, const int32_t* targets, int U, int32_t* frame_labels,
+                          int32_t* tok_first, int32_t* tok_last, double* score, double* loglik, int32_t* status, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  return ctc_align_long_launch(h, log_probs, T, V, false, nullptr, targets, U, frame_labels, tok_first, tok_last, score, loglik, status, s);
+}
+
+int gam_op_ctc_align_long_star(gam_handle* h, const float* log_probs, int64_t T, int V, const float* star_lp, const int32_t* targets, int U,
+                               int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, double* score, double* loglik,
+                               int32_t* status, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (T > 0 && !star_lp) return fail(h, -1, "long CTC alignment: NULL buffer");
+  return ctc_align_long_launch(h, log_probs, T, V, true, star_lp, targets, U, frame_labels, tok_first, tok_last, score, loglik,
+                               status, s);
 }
 
 int gam_set_ctc_align_workspace(gam_handle* h, int64_t bytes) {

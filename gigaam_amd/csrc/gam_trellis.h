@@ -13,6 +13,11 @@
 // predecessors prefer s over s-1 over s-2; at the end prefer S-1 over S-2.  Backpointers: the decrement 0 / 1 / 2 as 2 bits per
 // (t, s), stored as two 64-bit ballots per 64-state chunk {bit0 lo, bit0 hi, bit1 lo, bit1 hi}.  Feasible: T >= U + #{i : y_i ==
 // y_{i-1}} and every id in [0, V-2].
+//
+// The wildcard (the STAR variants of both CTC kernels).  Target id V, one past blank, is an ordinary token in all of the above -- it
+// takes a frame, blanks may flank it, two adjacent wildcards are a repeat, it counts in U -- except that its emission at frame t is
+// star[t], a per-frame value of the caller's, not a column of lp.  Nothing of (b) .. (e) changes: gam_ctc_lanes compares labels and V is
+// a label like any other.  What changes is where a state's emission is loaded from: gam_ctc_star_src below.
 #pragma once
 #include "gam_common.h"
 
@@ -63,6 +68,25 @@ __device__ __forceinline__ void gam_ctc_lanes(const int* y, int blank, int S, in
     lab[i] = tok ? y[(s - 1) >> 1] : blank;
     skip[i] = tok && s >= 3 && y[(s - 1) >> 1] != y[(s - 3) >> 1];
   }
+}
+
+// STAR variants: where each of this thread's states reads its emission.  Frame t of a state is src[t * stride]: (lp + label, V) for a
+// label or blank, (star, 1) for the wildcard label V.  One unconditional load per state and step, as without wildcards; no select and
+// no scalar load on the step's chain.
+template <int SPT>
+__device__ __forceinline__ void gam_ctc_star_src(const float* lp, const float* star, int V, const int (&lab)[SPT], const float* (&src)[SPT],
+                                                 int (&stride)[SPT]) {
+#pragma unroll
+  for (int i = 0; i < SPT; ++i) {
+    const bool w = lab[i] == V;
+    src[i] = w ? star : lp + lab[i];
+    stride[i] = w ? 1 : V;
+  }
+}
+// the bad-id rule: [0, V-2] are labels, V-1 is blank, V is the wildcard where the kernel is a STAR variant
+template <bool STAR>
+__device__ __forceinline__ bool gam_ctc_bad_id(int v, int V) {
+  return STAR ? (v < 0 || v > V || v == V - 1) : (v < 0 || v > V - 2);
 }
 
 // ------------------------------------------------------------------ (c) CTC: one frame of one state

@@ -269,18 +269,22 @@ class CTCGreedyDecoding(_BeamInputs):
     MAX_ALIGN_TOKENS = 1024     # include/gigaam_hip.h gam_ctc_align
 
     @torch.inference_mode()
-    def align(self, head: CTCHead, encoded: Tensor, lengths: Tensor, targets: List[List[int]]):
+    def align(self, head: CTCHead, encoded: Tensor, lengths: Tensor, targets: List[List[int]], star_penalty: Optional[float] = None):
         """CTC forced alignment of known token ids (one list per utterance) on the device (gam_ctc_align), ONE D2H for the
         result.  Returns per utterance ``(ids, first_frames, last_frames, score, loglik, feasible)``: the first / last encoder frame
         of each token's run on the best path, that path's log-prob, log p(ids | audio) (= -ctc_loss) and whether any path exists
-        (if not: empty frame lists, -inf scores).  Raises ``RangeOverflow`` like ``finish``."""
+        (if not: empty frame lists, -inf scores).  Raises ``RangeOverflow`` like ``finish``.
+        ``star_penalty`` (>= 0): gam_ctc_align_star -- id ``num_classes`` in a target is a wildcard (gigaam_amd/wildcard.py)."""
         c = head.num_classes
         assert c == len(self.tokenizer) + 1, f"Num classes {c} != len(vocab)+1 {len(self.tokenizer)+1}"
         targets = [[int(t) for t in ids] for ids in targets]
         too_long = [len(t) for t in targets if len(t) > self.MAX_ALIGN_TOKENS]
         if too_long:
             raise ValueError(f"forced alignment takes at most {self.MAX_ALIGN_TOKENS} tokens per utterance (got {max(too_long)})")
-        h = head.engine.ctc_align(encoded, lengths, targets).host()
+        if star_penalty is None:
+            h = head.engine.ctc_align(encoded, lengths, targets).host()
+        else:
+            h = head.engine.ctc_align(encoded, lengths, targets, star_penalty=star_penalty).host()
         if h["flag"]:
             raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
         out = []

@@ -742,32 +742,69 @@ class HipEngine:
                 _ptr(out.tok_first), _ptr(out.tok_last), _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
         self._check(rc, what)
 
-    def ctc_align(self, encoded: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None) -> Aligned:
+    def ctc_star_row(self, log_probs: Tensor, enc_len: Optional[Tensor] = None, penalty: float = math.log(2)) -> Tensor:
+        """gam_op_ctc_star_row: the wildcard's emission row ``max_v log_probs[..., v] - penalty`` (f32 on the device) for ``star=`` of
+        ``op_ctc_align`` / ``op_ctc_align_long``.  log_probs [B, T', V] with ``enc_len`` [B] -> [B, T'] (0 on the frames past
+        ``enc_len``), or [T, V] (one long utterance, every row valid) -> [T].  ``penalty`` >= 0 and finite; no host sync."""
+        log_probs = self._dev(log_probs, torch.float32)
+        if log_probs.dim() == 2:
+            (tp, v), b, enc_len = log_probs.shape, 1, None
+            out = torch.empty((tp,), dtype=torch.float32, device=self.device)
+        else:
+            b, tp, v = log_probs.shape
+            enc_len = None if enc_len is None else self._dev(enc_len, torch.int32)
+            out = torch.empty((b, tp), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_ctc_star_row(self._h, _ptr(log_probs), _ptr(enc_len), b, tp, v, float(penalty),
+                                              _ptr(out), self._stream())
+        self._check(rc, "gam_op_ctc_star_row")
+        return out
+
+    def ctc_align(self, encoded: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None,
+                  star_penalty: Optional[float] = None) -> Aligned:
         """CTC forced alignment of known targets (gam_ctc_align): the CTC head, its log-softmax and the alignment kernel, no host sync.
         ``targets``: i32 [B, Umax] (entries past ``target_len[b]`` are ignored) or a list of B token-id lists.  The split-fp16 range
-        flag is CONSUMED as ``ctc_greedy`` does: it lands in the result's last word (``Aligned.host()['flag']``)."""
+        flag is CONSUMED as ``ctc_greedy`` does: it lands in the result's last word (``Aligned.host()['flag']``).
+        ``star_penalty`` (a float >= 0): gam_ctc_align_star -- target id V (``num_classes``) is a wildcard whose emission is the
+        frame's best log-prob minus the penalty; the result holds V on its frames and its run in ``tok_first`` / ``tok_last``."""
         encoded, enc_len, b, tp = self._in_encoded(encoded, enc_len)
         tgt, tlen = self._pad_targets(b, targets, target_len)
         out = Aligned.empty(self.device, b, tp, tgt.shape[1])
         with torch.cuda.device(self.device):
-            self._launch_align(self.lib.gam_ctc_align, encoded, enc_len, b, tp, (), tgt, tlen, out, "gam_ctc_align")
+            if star_penalty is None:
+                self._launch_align(self.lib.gam_ctc_align, encoded, enc_len, b, tp, (), tgt, tlen, out, "gam_ctc_align")
+            else:
+                rc = self.lib.gam_ctc_align_star(self._h, _ptr(encoded), _ptr(enc_len), b, tp, _ptr(tgt), _ptr(tlen), out.umax,
+                                                 float(star_penalty), _ptr(out.frame_labels), _ptr(out.tok_first), _ptr(out.tok_last),
+                                                 _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
+                self._check(rc, "gam_ctc_align_star")
             return self._finish(out, True)
 
-    def op_ctc_align(self, log_probs: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None) -> Aligned:
+    def op_ctc_align(self, log_probs: Tensor, enc_len: Tensor, targets, target_len: Optional[Tensor] = None,
+                     star: Optional[Tensor] = None) -> Aligned:
         """gam_op_ctc_align: the alignment kernel alone on caller-supplied log-probs [B, T', V] (used as they are).  The result's flag
-        word is 0 (no encoder ran)."""
+        word is 0 (no encoder ran).  ``star`` (f32 [B, T'], used as it is; ``ctc_star_row`` makes one): gam_op_ctc_align_star --
+        target id V is a wildcard whose emission at frame t is ``star[b, t]``."""
         log_probs, enc_len, b, tp, v = self._in_log_probs(log_probs, enc_len)
         tgt, tlen = self._pad_targets(b, targets, target_len)
         out = Aligned.empty(self.device, b, tp, tgt.shape[1])
         with torch.cuda.device(self.device):
-            self._launch_align(self.lib.gam_op_ctc_align, log_probs, enc_len, b, tp, (v,), tgt, tlen, out, "gam_op_ctc_align")
+            if star is None:
+                self._launch_align(self.lib.gam_op_ctc_align, log_probs, enc_len, b, tp, (v,), tgt, tlen, out, "gam_op_ctc_align")
+            else:
+                star = self._dev(star, torch.float32)
+                if tuple(star.shape) != (b, tp):
+                    raise GigaAMHipError(f"star must be [{b}, {tp}], got {tuple(star.shape)}")
+                self._launch_align(self.lib.gam_op_ctc_align_star, log_probs, enc_len, b, tp, (v, _ptr(star)), tgt, tlen, out,
+                                   "gam_op_ctc_align_star")
             return self._finish(out, False)
 
-    def op_ctc_align_long(self, log_probs: Tensor, targets, consume_flag: bool = False) -> AlignedLong:
+    def op_ctc_align_long(self, log_probs: Tensor, targets, consume_flag: bool = False, star: Optional[Tensor] = None) -> AlignedLong:
         """gam_op_ctc_align_long: CTC forced alignment of ONE long utterance, log-probs f32 [T, V] (used as they are) against ``targets``
         (token ids: a list or an i32 tensor [U]), tiled over the whole GPU (gam_align_long.h); no host sync.  ``consume_flag``: move
         the split-fp16 range flag of the encoder runs that produced the log-probs into the result's flag word (as ``ctc_align`` does);
-        otherwise the word is 0."""
+        otherwise the word is 0.  ``star`` (f32 [T], used as it is): gam_op_ctc_align_long_star -- target id V is a wildcard whose
+        emission at frame t is ``star[t]``."""
         log_probs = self._dev(log_probs, torch.float32)
         t, v = log_probs.shape
         tgt = self._dev(targets if isinstance(targets, Tensor) else torch.tensor([int(i) for i in targets], dtype=torch.int32),
@@ -775,9 +812,18 @@ class HipEngine:
         u = tgt.numel()
         out = AlignedLong.empty(self.device, t, u)
         with torch.cuda.device(self.device):
-            rc = self.lib.gam_op_ctc_align_long(self._h, _ptr(log_probs), t, v, _ptr(tgt), u, _ptr(out.frame_labels), _ptr(out.tok_first),
-                                                _ptr(out.tok_last), _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
-            self._check(rc, "gam_op_ctc_align_long")
+            if star is None:
+                rc = self.lib.gam_op_ctc_align_long(self._h, _ptr(log_probs), t, v, _ptr(tgt), u, _ptr(out.frame_labels), _ptr(out.tok_first),
+                                                    _ptr(out.tok_last), _ptr(out.score), _ptr(out.loglik), _ptr(out.status), self._stream())
+                self._check(rc, "gam_op_ctc_align_long")
+            else:
+                star = self._dev(star, torch.float32).reshape(-1)
+                if star.numel() != t:
+                    raise GigaAMHipError(f"star must be [{t}], got {tuple(star.shape)}")
+                rc = self.lib.gam_op_ctc_align_long_star(self._h, _ptr(log_probs), t, v, _ptr(star), _ptr(tgt), u, _ptr(out.frame_labels),
+                                                         _ptr(out.tok_first), _ptr(out.tok_last), _ptr(out.score), _ptr(out.loglik),
+                                                         _ptr(out.status), self._stream())
+                self._check(rc, "gam_op_ctc_align_long_star")
             return self._finish(out, consume_flag)
 
     def set_ctc_align_workspace(self, nbytes: int = 0) -> None:

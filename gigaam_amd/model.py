@@ -16,6 +16,7 @@ from . import decoder as _decoder
 from . import decoding as _decoding
 from . import encoder as _encoder
 from . import preprocess as _preprocess
+from . import wildcard as _wildcard
 from ._lib import GigaAMHipError
 from .engine import HipEngine, build_config
 from .preprocess import SAMPLE_RATE, load_audio
@@ -437,45 +438,75 @@ class GigaAMASR(GigaAM):
         if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
             raise TypeError("forced alignment needs a CTC head")
 
+    @property
+    def wildcard_id(self) -> int:
+        """The token id of a wildcard in a forced-alignment target: V = the number of classes, one past blank."""
+        self._require_ctc()
+        return len(self.decoding.tokenizer) + 1
+
+    def _wildcard_setup(self, texts, wildcard: Optional[str], wildcard_penalty: float):
+        """(token-id lists, the penalty when wildcards are enabled else None) of an alignment; every error that needs no audio."""
+        tok = self.decoding.tokenizer
+        enabled = wildcard is not None or wildcard_penalty is not _wildcard.DEFAULT_PENALTY
+        penalty = _wildcard.check(tok, wildcard, wildcard_penalty)
+        wid = self.wildcard_id
+        return [_wildcard.encode(tok, t, wildcard, wid, enabled) for t in texts], (penalty if enabled else None)
+
     @torch.inference_mode()
-    def align(self, wav_file: str, text: Union[str, List[int]]) -> AlignmentResult:
+    def align(self, wav_file: str, text: Union[str, List[int]], wildcard: Optional[str] = None,
+              wildcard_penalty: float = _wildcard.DEFAULT_PENALTY) -> AlignmentResult:
         """Align ``text`` (a string in the model's vocabulary, or token ids) to a clip of at most 25 s.  Words are built as
         ``transcribe(word_timestamps=True)`` builds them, from each token's first frame on the best path.  Raises ``ValueError``
-        for a longer clip, for characters outside the vocabulary, or for a text that no alignment can fit into the clip."""
+        for a longer clip, for characters outside the vocabulary, or for a text that no alignment can fit into the clip.
+
+        ``wildcard`` (a string the tokenizer cannot spell, e.g. ``"*"``): a PARTIAL transcript -- wherever it stands in ``text``,
+        audio the transcript does not cover may pass; each wildcard takes at least one frame and comes back as a ``Gap`` in
+        ``gaps``.  ``wildcard_penalty`` (>= 0, default ln 2): the price per frame a wildcard pays against the frame's best label.
+        Token-id lists may hold ``model.wildcard_id`` when either keyword is given."""
         self._require_ctc()
         wav, length = self._prepare_wav_f32(wav_file)
         if length.item() > LONGFORM_THRESHOLD:
             raise ValueError("Too long wav file for forced alignment (at most 25 s).")
-        res = self.align_batch(wav, length, [text])[0]
+        res = self.align_batch(wav, length, [text], wildcard=wildcard, wildcard_penalty=wildcard_penalty)[0]
         if not res.feasible:
             raise ValueError(f"the text ({len(res.token_ids)} tokens) cannot be aligned to this audio: too long for it")
         return res
 
     @torch.inference_mode()
-    def align_batch(self, wav: Tensor, lengths: Tensor, texts: Sequence[Union[str, List[int]]]) -> List[AlignmentResult]:
+    def align_batch(self, wav: Tensor, lengths: Tensor, texts: Sequence[Union[str, List[int]]], wildcard: Optional[str] = None,
+                    wildcard_penalty: float = _wildcard.DEFAULT_PENALTY) -> List[AlignmentResult]:
         """Batched ``align`` on a collated batch (wav [B,L] zero padded, len [B]); ``texts`` holds a ``str`` or token ids per
-        utterance.  An utterance no alignment fits gets ``feasible=False`` (empty words, -inf scores) instead of an error."""
+        utterance.  An utterance no alignment fits gets ``feasible=False`` (empty words, -inf scores) instead of an error.
+        ``wildcard`` / ``wildcard_penalty``: as ``align``."""
         self._require_ctc()
         if len(texts) != wav.shape[0]:
             raise ValueError(f"{len(texts)} texts for a batch of {wav.shape[0]}")
         tok = self.decoding.tokenizer
-        targets = [tok.encode(t) if isinstance(t, str) else [int(i) for i in t] for t in texts]
+        targets, penalty = self._wildcard_setup(texts, wildcard, wildcard_penalty)
 
         def run():
             # as launch_batch: sample counts on the host give a ragged batch packed rows
             host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
             encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
-            return self.decoding.align(self.head, encoded, encoded_len, targets), encoded_len
+            if penalty is None:
+                return self.decoding.align(self.head, encoded, encoded_len, targets), encoded_len
+            return self.decoding.align(self.head, encoded, encoded_len, targets, star_penalty=penalty), encoded_len
 
         rows, encoded_len = self._with_f32_fallback(run, "this batch was")
         from .timestamps_utils import compute_frame_shift, frames_to_words
 
         wl, el = lengths.tolist(), encoded_len.tolist()
         out: List[AlignmentResult] = []
-        for i, (ids, first, _last, score, loglik, ok) in enumerate(rows):
-            words = frames_to_words(tok, ids, first, compute_frame_shift(int(wl[i]), int(el[i]))) if ok else []
-            out.append(AlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_frames=first, score=score,
-                                       log_likelihood=loglik, feasible=ok))
+        for i, (ids, first, last, score, loglik, ok) in enumerate(rows):
+            if penalty is None:
+                words = frames_to_words(tok, ids, first, compute_frame_shift(int(wl[i]), int(el[i]))) if ok else []
+                out.append(AlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_frames=first, score=score,
+                                           log_likelihood=loglik, feasible=ok))
+                continue
+            wid = self.wildcard_id
+            words, gaps = _wildcard.short_result(tok, ids, first, last, compute_frame_shift(int(wl[i]), int(el[i])), wid) if ok else ([], [])
+            out.append(AlignmentResult(text=_wildcard.text_of(tok, ids, wid, wildcard), words=words, token_ids=ids, token_frames=first,
+                                       score=score, log_likelihood=loglik, feasible=ok, gaps=gaps))
         return out
 
     # ---- keyword search: does a phrase occur, where, and how sure (gam_ctc_kws)
@@ -811,7 +842,8 @@ class GigaAMASR(GigaAM):
         return LongformTranscriptionResult(segments=self._with_f32_fallback(run, "the file was"))
 
     @torch.inference_mode()
-    def align_longform(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int = 16, **kwargs: Any) -> LongformAlignmentResult:
+    def align_longform(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int = 16, wildcard: Optional[str] = None,
+                       wildcard_penalty: float = _wildcard.DEFAULT_PENALTY, **kwargs: Any) -> LongformAlignmentResult:
         """Align ``text`` (a string in the model's vocabulary, or token ids) to a recording of any length: forced alignment of the
         WHOLE text against the WHOLE recording (``align`` stops at 25 s and 1024 tokens).  Segmentation keywords as for
         ``transcribe_longform`` (``speech_regions=``, ``vad=``, the pack_regions keywords; the same pyannote / EnergyVAD default).
@@ -823,6 +855,9 @@ class GigaAMASR(GigaAM):
         its region's start + its frame inside the region x that region's frame shift; words follow the rule of
         ``transcribe(word_timestamps=True)`` on those file times.
 
+        ``wildcard`` / ``wildcard_penalty``: as ``align`` -- a partial transcript; each wildcard comes back as a ``Gap`` in ``gaps``
+        (file times; it may start in one speech region and end in another: ``segment`` / ``end_segment``), and no word spans a gap.
+
         Raises ``ValueError`` for characters outside the vocabulary, for a text that no alignment fits into the speech found, for a
         non-empty text when no speech was found, and for a lattice beyond the workspace cap (the message carries the needed and
         the allowed bytes; ``HipEngine.set_ctc_align_workspace`` / GAM_CTC_ALIGN_WS raise it); ``TypeError`` on RNN-T models."""
@@ -833,13 +868,15 @@ class GigaAMASR(GigaAM):
 
         self._require_ctc()
         tok = self.decoding.tokenizer
-        ids = tok.encode(text) if isinstance(text, str) else [int(i) for i in text]
+        (ids,), penalty = self._wildcard_setup([text], wildcard, wildcard_penalty)
+        wid = self.wildcard_id
+        text_out = tok.decode(ids) if penalty is None else _wildcard.text_of(tok, ids, wid, wildcard)
         self._default_vad(kwargs, "align_longform")
         segments, boundaries = segment_audio_file(wav_file, SAMPLE_RATE, device=self._device, **kwargs)
         if not segments:
             if ids:
                 raise ValueError(f"no speech found in the recording: the text ({len(ids)} tokens) cannot be aligned to it")
-            return LongformAlignmentResult(text=tok.decode(ids), words=[], token_ids=ids, token_segments=[], token_frames=[], token_times=[],
+            return LongformAlignmentResult(text=text_out, words=[], token_ids=ids, token_segments=[], token_frames=[], token_times=[],
                                            score=0.0, log_likelihood=0.0, segments=[], feasible=True)
         eng = self.head.engine
 
@@ -853,7 +890,11 @@ class GigaAMASR(GigaAM):
                 valid = torch.arange(lp.shape[1], device=lp.device)[None, :] < encoded_len[:, None]
                 rows.append(lp[valid])                                             # each utterance's valid rows, utterance after utterance
                 seg_frames.append(encoded_len)
-            out = eng.op_ctc_align_long(torch.cat(rows, dim=0), ids, consume_flag=True)
+            lp_all = torch.cat(rows, dim=0)
+            if penalty is None:
+                out = eng.op_ctc_align_long(lp_all, ids, consume_flag=True)
+            else:
+                out = eng.op_ctc_align_long(lp_all, ids, consume_flag=True, star=eng.ctc_star_row(lp_all, None, penalty))
             h = out.host()
             if h["flag"]:
                 raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
@@ -873,7 +914,14 @@ class GigaAMASR(GigaAM):
         shifts = [compute_frame_shift(int(seg.shape[0]), int(n)) if n else 0.0 for seg, n in zip(segments, seg_frames)]
         token_segments, token_frames, token_times = concat_frames_to_segments(h["tok_first"].tolist(), seg_frames,
                                                                               [b[0] for b in boundaries], shifts)
-        words, segs = longform_words(tok, ids, token_segments, token_frames, boundaries, shifts)
-        return LongformAlignmentResult(text=tok.decode(ids), words=words, token_ids=ids, token_segments=token_segments,
+        if penalty is None:
+            words, segs = longform_words(tok, ids, token_segments, token_frames, boundaries, shifts)
+            return LongformAlignmentResult(text=text_out, words=words, token_ids=ids, token_segments=token_segments,
+                                           token_frames=token_frames, token_times=token_times, score=h["score"],
+                                           log_likelihood=h["loglik"], segments=segs, feasible=True)
+        last_segments, last_frames, _ = concat_frames_to_segments(h["tok_last"].tolist(), seg_frames, [b[0] for b in boundaries], shifts)
+        words, segs, gaps = _wildcard.longform_result(tok, ids, token_segments, token_frames, last_segments, last_frames, boundaries,
+                                                      shifts, wid)
+        return LongformAlignmentResult(text=text_out, words=words, token_ids=ids, token_segments=token_segments,
                                        token_frames=token_frames, token_times=token_times, score=h["score"],
-                                       log_likelihood=h["loglik"], segments=segs, feasible=True)
+                                       log_likelihood=h["loglik"], segments=segs, feasible=True, gaps=gaps)

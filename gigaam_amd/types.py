@@ -3,7 +3,7 @@ behaviour as the reference's gigaam/types.py:18-68 (boundary types)."""
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Iterator, List, Optional, Sequence
 
 
@@ -24,13 +24,31 @@ class TranscriptionResult:
 
 
 @dataclass
+class Gap:
+    """The stretch of audio a wildcard of a partial transcript took (``align(..., wildcard="*")``): ``start_frame`` / ``end_frame`` are
+    the first and the last encoder frame of the wildcard's run on the best path, ``start`` / ``end`` their times by the rule of
+    words (``start_frame`` x frame shift, (``end_frame`` + 1) x frame shift).  In a longform result the times are file times, the
+    frames count inside speech regions ``segment`` (where the gap starts) and ``end_segment`` (where it ends: a gap may run across
+    regions)."""
+    start: float
+    end: float
+    start_frame: int
+    end_frame: int
+    segment: Optional[int] = None
+    end_segment: Optional[int] = None
+
+
+@dataclass
 class AlignmentResult:
     """``GigaAMASR.align``: a known transcript placed on the audio by CTC forced alignment.  ``token_frames``: the first encoder
     frame of each token on the best path; ``score``: that path's log-prob; ``log_likelihood``: log p(text | audio) over all paths
     (= -CTC loss); ``feasible``: False when no path exists (the text is too long for the audio) -- then ``words`` and
     ``token_frames`` are empty and both scores are -inf.
     ``GigaAMASR.rnnt_align`` returns the same for RNN-T heads (transducer forced alignment): ``token_frames`` are then the frames at
-    which the tokens are emitted on the best path, ``log_likelihood`` is -RNN-T loss, and every clip with a frame is feasible."""
+    which the tokens are emitted on the best path, ``log_likelihood`` is -RNN-T loss, and every clip with a frame is feasible.
+    With wildcards (``align(..., wildcard=)``): ``token_ids`` holds ``model.wildcard_id`` at a wildcard and ``token_frames`` its first
+    frame, ``gaps`` one ``Gap`` per wildcard in order, ``text`` the pieces joined by the wildcard string; no word spans a gap; ``score``
+    and ``log_likelihood`` are those of the lattice with the wildcards in it -- no longer the log-probability of a text."""
     text: str
     words: List[Word]
     token_ids: List[int]
@@ -38,6 +56,7 @@ class AlignmentResult:
     score: float
     log_likelihood: float
     feasible: bool
+    gaps: List[Gap] = field(default_factory=list)
 
     def __str__(self) -> str:
         return self.text
@@ -178,6 +197,7 @@ class LongformAlignmentResult:
     log_likelihood: float
     segments: List[Segment]
     feasible: bool
+    gaps: List[Gap] = field(default_factory=list)     # one per wildcard (``align_longform(..., wildcard=)``), as ``AlignmentResult.gaps``
 
     def __str__(self) -> str:
         return self.text

@@ -163,6 +163,30 @@ int gam_set_ctc_align_workspace(gam_handle* h, int64_t bytes);
  * the frames per tile (tt >= 1) of every following call in this process; 0 = planned (1024 x 256).  Returns -1 for other values. */
 int gam_tune_ctc_align_long(int sb, int tt);
 
+/* Wildcard tokens: forced alignment of a PARTIAL transcript (gigaam_amd/csrc/gam_trellis.h).  In the *_star entry points target id V,
+ * one past blank (= V - 1), is a wildcard: an ordinary CTC token -- at least one frame, blanks may flank it, the s - 2 skip applies
+ * between it and a differing neighbour, two adjacent wildcards are a repeat, it counts in U and in T >= U + repeats -- whose emission at
+ * frame t is star_lp[t] instead of a column of the log-probs.  frame_labels holds V on its frames, tok_first / tok_last its run.
+ * score / loglik are those of the augmented lattice: with a wildcard, loglik is no longer the log-probability of a text.
+ * Everything else -- outputs, statuses, limits, workspace cap, gam_tune_ctc_align_long, decode class, no host synchronisation -- is the
+ * sibling's.  The entry points without _star keep rejecting id V.
+ *   star_lp: device f32 [B, T'] (op level) / [T] (long): the emission of a wildcard state per frame, read as it is.
+ * gam_op_ctc_star_row writes star_lp[b, t] = max_v log_probs[b, t, v] - penalty for t < enc_len[b] and 0 past it (enc_len NULL: every
+ * row is valid; the long path calls it with B = 1, T' = T).  penalty >= 0 and finite, else an error: the greedy path's log-prob minus a
+ * fixed price per frame, so a frame goes to the wildcard only where the transcript's own label is less than exp(-penalty) times as
+ * likely as the frame's best label.  gam_ctc_align_star = the CTC head, its log-softmax, that row and the STAR sweep on the stream. */
+int gam_op_ctc_star_row(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, float penalty,
+                        float* star_lp, void* stream);
+int gam_ctc_align_star(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
+                       const int32_t* target_len, int Umax, float penalty, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last,
+                       float* score, float* loglik, int32_t* status, void* stream);
+int gam_op_ctc_align_star(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const float* star_lp,
+                          const int32_t* targets, const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first,
+                          int32_t* tok_last, float* score, float* loglik, int32_t* status, void* stream);
+int gam_op_ctc_align_long_star(gam_handle* h, const float* log_probs, int64_t T, int V, const float* star_lp, const int32_t* targets, int U,
+                               int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, double* score, double* loglik,
+                               int32_t* status, void* stream);
+
 /* Keyword search over the CTC posteriors (gigaam_amd/csrc/gam_kws.h holds the contract): for every (utterance, keyword) pair, where
  * the keyword occurs and how well it scores.  Runs the CTC head, its log-softmax, a row-maximum pre-pass and ONE search kernel (a
  * wave per pair: a CTC Viterbi over the keyword's tokens with a free start and a free end, blank = V - 1).  Emissions are
