@@ -173,7 +173,10 @@ struct gam_handle {
   int use_graph = 1;            // GAM_GRAPH=0 disables
   int graph_max_rows = 2048;    // only below the large-batch (sp32) regime
   uint64_t ws_generation = 0;   // bumped by every workspace (re)allocation
-  struct GraphEntry { uint64_t gen = 0; int seen = 0; hipGraphExec_t exec = nullptr; };
+  struct GraphEntry {
+    enum Seen { UNSEEN, SEEN_ONCE, PLAIN_ONLY };   // first sight: plain launches; second: capture; PLAIN_ONLY: capture refused or cache full
+    uint64_t gen = 0; Seen seen = UNSEEN; hipGraphExec_t exec = nullptr;   // (exec set: replayed from the third sight on)
+  };
   std::map<std::vector<int>, GraphEntry> graphs;
   long graph_replays = 0, graph_captures_failed = 0;
   int graph_count = 0;          // instantiated graphs alive (capped at 32 shapes)
@@ -1040,31 +1043,66 @@ int gam_frontend(gam_handle* h, const float* wav, const int64_t* wav_len, int B,
 }
 
 // -----------------------------------------------------------------------------------
-static int encode_impl(gam_handle* h, const float* feat, const int64_t* feat_len, int B, int64_t T, float* encoded,
-                       int32_t* enc_len, int n_layers_run, float* tokens_out, hipStream_t s, const int64_t* feat_len_host = nullptr) {
-  if (!h || !h->finalized) return fail(h, -1, "gam_encode before gam_finalize");
-  if (!h->has_encoder) return fail(h, -1, "this handle was finalized without encoder weights");
+// The encoder's host path (DESIGN.md "Encoder host path").  encode_impl is a sequence of named pieces with explicit inputs:
+//   enc_plan       shape arithmetic and every choice (row layout, operand formats, graph regime); no HIP call
+//   enc_workspace  every buffer the call touches, sized from the plan; nothing is allocated behind it
+//   enc_lengths -> enc_stem (stem_conv2d | stem_conv1d, + the gather into packed rows)
+//   run_layers     ffn_block, attn_block, conv_block, ffn_block, norm_out_block per layer; replay_layers replays it as a hipGraph
+//   enc_outputs    channel-first, token-major, lengths
+struct EncPlan {
+  int B;
+  int64_t T;
+  int T1, Tv;             // frames after the first / second stride-2 stage
+  int Ta, N;              // row stride per utterance of every token-major buffer, N = B * Ta rows in the padded layout
+  int NR, Tmax;           // rows the layers run on and rows of the longest utterance: (N, Ta) padded, (valid frames, longest) packed
+  int T1a;                // conv1d stem: stage-1 rows per utterance (0 for conv2d)
+  int D, DFF, F, H, dk, nl;
+  bool conv2d, rel, packed;
+  bool sp;                // the encoder GEMMs take sp32 operands (split-fp16 modes, D and DFF multiples of 32)
+  int spf;                // operand format the producers write (gam_common.h gam_store4): 0 fp32, 1 (hi, lo) pairs, 2 plain fp16
+  bool sp_stem;           // conv1d stem: xin and y1 hold sp32
+  bool graph;             // the layer sequence of this shape is captured and replayed (replay_layers)
+};
+
+struct EncBufs {          // device pointers into the handle's workspace, valid for this call
+  int *len0, *len1, *len2, *elen;   // the lens block
+  int *cu, *row_t, *row_src;        // packed rows (gam_pack.h); null in the padded layout
+  float* rs;                        // per-row 2^-e of the LayerNorm-produced GEMM operands; null without sp32 operands or GAM_ROWSCALE=0
+};
+
+struct EncCtx {           // what a layer block reads; passed by const reference
+  EncPlan p;
+  EncBufs w;
+  GamLnArgs ln;           // the fields every LayerNorm of the layer sequence shares
+};
+
+static int enc_plan(gam_handle* h, int B, int64_t T, int n_layers_run, const int64_t* feat_len_host, EncPlan& p) {
   const gam_config& c = h->cfg;
   if (B <= 0 || T <= 0) return fail(h, -1, "bad shape B=%d T=%lld", B, (long long)T);
-  HIPCHK(h, hipSetDevice(h->device));
-  const int D = c.d_model, C = D, F = c.feat_in, H = c.n_heads, dk = D / H, DFF = D * c.ff_expansion_factor;
-  const int T1 = (int)half_up(T), T2 = (int)half_up(T1), Tv = T2;
-  if (Tv > c.pos_emb_max_len) return fail(h, -1, "%d encoder frames exceed pos_emb_max_len %d", Tv, c.pos_emb_max_len);
-  if (Tv <= 0) return fail(h, -1, "no encoder frames");
-  const bool conv2d = c.subsampling == GAM_SUBS_CONV2D;
+  p.B = B; p.T = T;
+  p.D = c.d_model; p.F = c.feat_in; p.H = c.n_heads; p.dk = p.D / p.H; p.DFF = p.D * c.ff_expansion_factor;
+  p.T1 = (int)half_up(T); p.Tv = (int)half_up(p.T1);
+  if (p.Tv > c.pos_emb_max_len) return fail(h, -1, "%d encoder frames exceed pos_emb_max_len %d", p.Tv, c.pos_emb_max_len);
+  if (p.Tv <= 0) return fail(h, -1, "no encoder frames");
+  p.conv2d = c.subsampling == GAM_SUBS_CONV2D;
+  p.rel = c.self_attention_model == GAM_ATT_REL_POS;
+  p.nl = n_layers_run < 0 ? c.n_layers : std::min(n_layers_run, c.n_layers);
   // Ta: per-utterance row stride of every token-major buffer (>= T' ; the extra rows are
   // treated as padding).  conv2d: image rows per utterance = 2*Ta >= T1 + 2.
   // conv1d: stage-1 output rows per utterance = 2*Ta >= T1 + 4.
-  int Ta = conv2d ? std::max(Tv + 1, (T1 + 3) / 2) : std::max(Tv, (T1 + 5) / 2);
-  const int N = B * Ta;
+  p.Ta = p.conv2d ? std::max(p.Tv + 1, (p.T1 + 3) / 2) : std::max(p.Tv, (p.T1 + 5) / 2);
+  p.N = B * p.Ta;
+  // conv1d: stage-1 input rows per utterance: 2*T1a >= T + 2*pad ; stage-1 output = stage-2 input rows: 2*Ta
+  const int pad = (c.subs_kernel_size - 1) / 2;
+  p.T1a = p.conv2d ? 0 : std::max(p.T1, (int)((T + 2 * pad + 1) / 2));
   // Packed rows (gam_pack.h): with the lengths known on the HOST (gam_encode_varlen) a ragged batch runs its layers on the valid frames
   // only -- NR rows instead of N, utterance b at rows cu[b] .. -- when that drops at least 3 % of the rows.  Equal-length batches, single
   // utterances and callers without host lengths keep the padded layout (and its results, bit for bit).
-  bool packed = false;
-  int NR = N, Tmax = Ta;
+  p.packed = false;
+  p.NR = p.N; p.Tmax = p.Ta;
   // (below graph_max_rows the step is launch-bound and replayed as a hipGraph keyed on the padded shape: fewer rows buy nothing there and a
   //  row count in the key would defeat the replay -- packed rows start where the graph regime ends; GAM_PACK=2 forces them at any size: tests)
-  const bool pack_regime = h->use_pack >= 2 || !h->use_graph || N >= h->graph_max_rows;
+  const bool pack_regime = h->use_pack >= 2 || !h->use_graph || p.N >= h->graph_max_rows;
   if (feat_len_host != nullptr && h->use_pack && pack_regime && B > 1 && B <= 1024) {
     long long sum = 0;
     int mx = 0;
@@ -1074,321 +1112,391 @@ static int encode_impl(gam_handle* h, const float* feat, const int64_t* feat_len
       sum += l2;
       mx = std::max(mx, l2);
     }
-    if (sum > 0 && sum * 100 <= (long long)N * 97) { packed = true; NR = (int)sum; Tmax = mx; }
+    if (sum > 0 && sum * 100 <= (long long)p.N * 97) { p.packed = true; p.NR = (int)sum; p.Tmax = mx; }
   }
-  h->last_rows = NR;
-  h->last_rows_padded = N;
-
-  if (B > h->lens_cap) {
-    if (h->lens) HIPCHK(h, hipFree(h->lens));
-    h->lens = nullptr;
-    HIPCHK(h, hipMalloc(&h->lens, (size_t)4 * B * sizeof(int)));
-    h->lens_cap = B;
-    ++h->ws_generation;   // captured graphs hold the old pointer
-  }
-  int *len0 = h->lens, *len1 = h->lens + h->lens_cap, *len2 = h->lens + 2 * h->lens_cap, *elen = h->lens + 3 * h->lens_cap;
-  if (int r = ensure(h, h->x, (size_t)N * D)) return r;
-  if (int r = ensure(h, h->y, (size_t)N * D)) return r;
-  if (int r = ensure(h, h->yr, (size_t)N * D)) return r;
-  if (int r = ensure(h, h->hbuf, (size_t)N * DFF)) return r;
-  if (int r = ensure(h, h->qkv, (size_t)N * 3 * D)) return r;
-  if (int r = ensure(h, h->ctx, (size_t)N * D)) return r;
-  if (int r = ensure(h, h->ubuf, (size_t)N * 2 * D)) return r;
-  if (int r = ensure(h, h->zbuf, (size_t)N * D)) return r;
-  if (int r = ensure(h, h->rsbuf, (size_t)N + 64)) return r;
-  if (packed)
-    if (int r = ensure(h, h->pack_idx, (size_t)1032 + 2 * (size_t)N)) return r;
-  int* const cu = packed ? reinterpret_cast<int*>(h->pack_idx.p) : nullptr;
-  int* const row_t = packed ? cu + 1032 : nullptr;
-  int* const row_src = packed ? row_t + N : nullptr;
-
-  {
-    ProfScope ps(h, s, GAM_PF_MISC, 0.0);
-    hipLaunchKernelGGL(gam_lengths_kernel, dim3(gam_cdiv(B, 64)), dim3(64), 0, s, (const long long*)feat_len, B, (int)T, 2,
-                       len0, len1, len2, elen);
-    HIPCHK(h, hipGetLastError());
-    if (packed) {
-      hipLaunchKernelGGL(gam_pack_index_kernel, dim3(1), dim3(256), 0, s, len2, B, Ta, NR, cu, row_t, row_src, h->range_flag);
-      HIPCHK(h, hipGetLastError());
-    }
-  }
-
   // Split-fp16 modes: every encoder GEMM runs on the LDS-DMA kernel of gam_gemm_sp.h, and the kernels that
   // produce its A operands (LayerNorm, SiLU epilogue, attention, conv module, stem) write them in the
   // sp32 split layout instead of fp32 -- same bytes, no conversion pass.
-  const bool sp = split_mode(h) && D % 32 == 0 && DFF % 32 == 0;
+  p.sp = split_mode(h) && p.D % 32 == 0 && p.DFF % 32 == 0;
   // operand format the producers write (gam_common.h gam_store4).  Format 2 (plain fp16, GAM_GEMM_F16) packs 64 k-values into
   // the 128-byte line of a k-tile, so every reduction length / row pitch must be a multiple of 64; a model whose d_model or
   // FFN width is 32 x an odd number keeps the three-term kernels for its GEMMs in that mode (as gam_op_gemm does)
   // instead of failing half-way through a batch with the stem image already written as fp16.
-  const bool f16_fmt_ok = D % 64 == 0 && DFF % 64 == 0;   // (C == D: the stem's channel count)
-  const int spf = sp ? (h->gemm_mode == GAM_GEMM_F16 && f16_fmt_ok ? 2 : 1) : 0;
-  auto sp_a = [&](GamGemmArgs& g) { if (sp) { g.Asp = reinterpret_cast<const _Float16*>(g.A); g.a_fmt = spf; } };
+  const bool f16_fmt_ok = p.D % 64 == 0 && p.DFF % 64 == 0;   // (the stem's channel count is D)
+  p.spf = p.sp ? (h->gemm_mode == GAM_GEMM_F16 && f16_fmt_ok ? 2 : 1) : 0;
+  // conv1d stem: both GEMMs read overlapping rows (lda = 2F / 2C < K).  In the split modes xin and y1 hold sp32 (a row starts on a
+  // 32-element block of the flat buffer, F % 32 == 0), and both GEMMs are three-term in the one-term mode too.
+  p.sp_stem = p.sp && p.F % 32 == 0;
+  // Small batches: the layer sequence is replayed as one hipGraph (see gam_handle::use_graph).  (packed rows: the row count is part of
+  // every launch)
+  p.graph = h->use_graph && !h->prof_on && p.nl > 0 && p.N < h->graph_max_rows && !p.packed;
+  return 0;
+}
 
-  // ------------------------------ stem ------------------------------
-  if (conv2d) {
-    const int FP = h->f1 + 1, F2 = h->f2;
-    if (int r = ensure(h, h->img, ((size_t)B * 2 * Ta + 2) * FP * C)) return r;
-    if (int r = ensure(h, h->c2, (size_t)N * F2 * C)) return r;
-    {
-      GamConv1Args a;
-      a.feat = feat; a.img = h->img.p; a.w = h->c1_w; a.bias = h->c1_b; a.len0 = len0; a.len1 = len1;
-      a.B = B; a.T = (int)T; a.F = F; a.Ta = Ta; a.FP = FP; a.C = C; a.T1 = T1;
-      a.img_split = (sp && C % 32 == 0) ? spf : 0;
-      a.range_flag = h->use_range ? h->range_flag : nullptr;
-      ProfScope ps(h, s, GAM_PF_STEM, (double)B * 2 * Ta * FP * C * 4.0);
-      if (a.img_split == 2) hipLaunchKernelGGL(gam_conv2d1_kernel<2>, dim3(2 * Ta, B), dim3(256), 0, s, a);
-      else if (a.img_split == 1) hipLaunchKernelGGL(gam_conv2d1_kernel<1>, dim3(2 * Ta, B), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(gam_conv2d1_kernel<0>, dim3(2 * Ta, B), dim3(256), 0, s, a);
-      HIPCHK(h, hipGetLastError());
-      // two slack rows past the last utterance (read by its padding frame only)
-      // two slack rows past the last utterance (read by its padding frame only); the dense fp16 image ends at half the offset
-      const size_t img_end = (size_t)B * 2 * Ta * FP * C;
-      HIPCHK(h, hipMemsetAsync(a.img_split == 2 ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(h->img.p) + img_end) : h->img.p + img_end, 0,
-                               (size_t)2 * FP * C * sizeof(float), s));
-    }
-    GamGemmArgs g = gemm_args(h->img.p, 0, h->c2_w, h->c2_b, h->c2.p, C, N * F2, C, 9 * C);
-    g.a_mode = 1; g.conv_fp = FP; g.conv_c = C; g.conv_f2 = F2;
-    g.lens = len2; g.rpb = Ta * F2; g.fdiv = F2;
-    g.skip_pad = packed ? 1 : 0;      // 16-frame row tiles behind an utterance's last frame: 12 rounds of tiles shrink with the batch's padding
-    if (sp && C % 32 == 0) { sp_a(g); g.c_split = spf; }
-    g.c_guard = 1;
-    if (int r = gemm(h, s, g, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c2)) return r;
-    GamGemmArgs l = gemm_args(h->c2.p, (long)F2 * C, h->lin_w, h->lin_b, packed ? h->y.p : h->x.p, D, N, D, F2 * C);
-    if (sp && C % 32 == 0) sp_a(l);
-    if (int r = gemm(h, s, l, GAM_ACT_NONE, GAM_PF_GEMM, &h->s_lin)) return r;
+// Everything the call touches exists behind this function: the stem, the layers and a capture allocate nothing.
+static int enc_workspace(gam_handle* h, const EncPlan& p, EncBufs& w) {
+  const size_t B = p.B, N = p.N, D = p.D, Ta = p.Ta;
+  if (p.B > h->lens_cap) {
+    if (h->lens) HIPCHK(h, hipFree(h->lens));
+    h->lens = nullptr;
+    HIPCHK(h, hipMalloc(&h->lens, (size_t)4 * B * sizeof(int)));
+    h->lens_cap = p.B;
+    ++h->ws_generation;   // captured graphs hold the old pointer
+  }
+  w.len0 = h->lens; w.len1 = h->lens + h->lens_cap; w.len2 = h->lens + 2 * h->lens_cap; w.elen = h->lens + 3 * h->lens_cap;
+  if (int r = ensure(h, h->x, N * D)) return r;
+  if (int r = ensure(h, h->y, N * D)) return r;
+  if (int r = ensure(h, h->yr, N * D)) return r;
+  if (int r = ensure(h, h->hbuf, N * p.DFF)) return r;
+  if (int r = ensure(h, h->qkv, N * 3 * D)) return r;
+  if (int r = ensure(h, h->ctx, N * D)) return r;
+  if (int r = ensure(h, h->ubuf, N * 2 * D)) return r;
+  if (int r = ensure(h, h->zbuf, N * D)) return r;
+  if (int r = ensure(h, h->rsbuf, N + 64)) return r;
+  if (p.packed)
+    if (int r = ensure(h, h->pack_idx, (size_t)1032 + 2 * N)) return r;
+  w.cu = p.packed ? reinterpret_cast<int*>(h->pack_idx.p) : nullptr;
+  w.row_t = p.packed ? w.cu + 1032 : nullptr;
+  w.row_src = p.packed ? w.row_t + N : nullptr;
+  // sp32 operands: every LayerNorm hands its GEMMs a per-row power-of-two scale (gam_row_scale; the exact-fp32 kernel undoes none)
+  w.rs = p.sp && h->use_rowscale ? h->rsbuf.p : nullptr;
+  if (p.conv2d) {   // the zero-bordered image (+ two slack rows) and Conv2d#2's output
+    if (int r = ensure(h, h->img, (B * 2 * Ta + 2) * (h->f1 + 1) * D)) return r;
+    if (int r = ensure(h, h->c2, N * h->f2 * D)) return r;
   } else {
-    const int ks = c.subs_kernel_size, pad = (ks - 1) / 2;
-    // stage-1 input rows per utterance: 2*T1a >= T + 2*pad ; stage-1 output = stage-2 input rows: 2*Ta
-    const int T1a = std::max(T1, (int)((T + 2 * pad + 1) / 2));
-    if (int r = ensure(h, h->xin, ((size_t)B * 2 * T1a + 8) * F)) return r;
-    if (int r = ensure(h, h->y1, ((size_t)B * 2 * Ta + 8) * C)) return r;
-    // Both GEMMs read overlapping rows (lda = 2F / 2C < K).  In the split modes xin and y1 hold sp32 (a row starts on a 32-element
-    // block of the flat buffer, F % 32 == 0), and both GEMMs are three-term in the one-term mode too.  All-zero bits are an sp32 zero.
-    const bool sp_stem = sp && F % 32 == 0;
-    {
-      ProfScope ps(h, s, GAM_PF_STEM, (double)B * T * F * 8.0);
-      HIPCHK(h, hipMemsetAsync(h->xin.p, 0, ((size_t)B * 2 * T1a + 8) * F * sizeof(float), s));
-      HIPCHK(h, hipMemsetAsync(h->y1.p, 0, ((size_t)B * 2 * Ta + 8) * C * sizeof(float), s));
-      dim3 grid(gam_cdiv(T, 32), gam_cdiv(F, 32), B);
-      int* const rf = h->use_range ? h->range_flag : nullptr;
-      if (sp_stem) hipLaunchKernelGGL(gam_feat_to_rows_kernel<1>, grid, dim3(256), 0, s, feat, h->xin.p, len0, B, F, (int)T, 2 * T1a, pad, rf);
-      else hipLaunchKernelGGL(gam_feat_to_rows_kernel<0>, grid, dim3(256), 0, s, feat, h->xin.p, len0, B, F, (int)T, 2 * T1a, pad, rf);
-      HIPCHK(h, hipGetLastError());
-    }
-    GamGemmArgs g1 = gemm_args(h->xin.p, 2L * F, h->c1_w, h->c1_b, h->y1.p, C, B * T1a, C, ks * F);
-    g1.lens = len1; g1.rpb = T1a; g1.fdiv = 1;
-    g1.remap = 1; g1.out_rpb = 2 * Ta; g1.out_shift = pad; g1.rows_valid = std::min(T1a, 2 * Ta - pad);
-    if (sp_stem) { g1.Asp = reinterpret_cast<const _Float16*>(g1.A); g1.a_fmt = 1; g1.c_split = 1; }
-    g1.c_guard = 1;
-    if (int r = gemm(h, s, g1, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c1)) return r;
-    GamGemmArgs g2 = gemm_args(h->y1.p, 2L * C, h->c2_w, h->c2_b, packed ? h->y.p : h->x.p, D, N, D, ks * C);
-    g2.lens = len2; g2.rpb = Ta; g2.fdiv = 1;
-    if (sp_stem) { g2.Asp = reinterpret_cast<const _Float16*>(g2.A); g2.a_fmt = 1; }
-    if (int r = gemm(h, s, g2, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c2)) return r;
+    if (int r = ensure(h, h->xin, (B * 2 * p.T1a + 8) * p.F)) return r;
+    if (int r = ensure(h, h->y1, (B * 2 * Ta + 8) * D)) return r;
   }
-  if (packed) {   // the stem's padded rows -> packed rows (the only copy the layout costs: 2 x NR x D x 4 bytes)
-    ProfScope ps(h, s, GAM_PF_STEM, (double)NR * D * 8.0);
-    hipLaunchKernelGGL(gam_gather_rows_kernel, dim3(std::min(4096, gam_cdiv(NR * (D / 4), 256))), dim3(256), 0, s, h->y.p, row_src, h->x.p, NR, D);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (p.rel)
+    if (int r = ensure(h, h->pbuf, (size_t)(2 * p.Tv - 1) * D)) return r;
+  if (p.graph)   // the largest split-K partial sums of a layer GEMM: a capture may not allocate
+    if (int r = ensure(h, h->splitk_ws, (size_t)16 * N * std::max(p.DFF, 2 * p.D) + 64)) return r;
+  return 0;
+}
 
-  // ------------------------------ Conformer layers ------------------------------
-  const int nl = n_layers_run < 0 ? c.n_layers : std::min(n_layers_run, c.n_layers);
-  const bool rel = c.self_attention_model == GAM_ATT_REL_POS;
-  if (rel) {
-    if (int r = ensure(h, h->pbuf, (size_t)(2 * Tv - 1) * D)) return r;
-  }
-  auto run_layers = [&](hipStream_t ls) -> int {
-  hipStream_t s = ls;   // (shadows the caller's stream: the capture runs on a private one)
+static GamLnArgs enc_ln_args(const gam_handle* h, const EncPlan& p, const EncBufs& w) {
   GamLnArgs ln;
   memset(&ln, 0, sizeof ln);
-  ln.rows = NR; ln.d = D; ln.ta = Ta; ln.row_t = row_t; ln.dk = dk; ln.eps = 1e-5f; ln.rcos = h->rot_cos; ln.rsin = h->rot_sin;
-  ln.rope_rows = c.pos_emb_max_len;
-  // sp32 operands: every LayerNorm hands its GEMMs a per-row power-of-two scale (gam_row_scale; the exact-fp32 kernel undoes none)
-  float* const rs = sp && h->use_rowscale ? h->rsbuf.p : nullptr;
-  ln.rs = rs;
-  if (nl > 0) {
-    GamLnArgs a = ln;
-    a.x = h->x.p; a.out1 = h->y.p; a.w1 = h->layers[0].ln_ff1_w; a.b1 = h->layers[0].ln_ff1_b;
-    a.split1 = spf;
-    if (int r = layernorm(h, s, a, 0)) return r;
+  ln.rows = p.NR; ln.d = p.D; ln.ta = p.Ta; ln.row_t = w.row_t; ln.dk = p.dk; ln.eps = 1e-5f; ln.rcos = h->rot_cos; ln.rsin = h->rot_sin;
+  ln.rope_rows = h->cfg.pos_emb_max_len;
+  ln.rs = w.rs;
+  return ln;
+}
+
+static int enc_lengths(gam_handle* h, hipStream_t s, const EncPlan& p, const EncBufs& w, const int64_t* feat_len) {
+  ProfScope ps(h, s, GAM_PF_MISC, 0.0);
+  hipLaunchKernelGGL(gam_lengths_kernel, dim3(gam_cdiv(p.B, 64)), dim3(64), 0, s, (const long long*)feat_len, p.B, (int)p.T, 2,
+                     w.len0, w.len1, w.len2, w.elen);
+  HIPCHK(h, hipGetLastError());
+  if (p.packed) {
+    hipLaunchKernelGGL(gam_pack_index_kernel, dim3(1), dim3(256), 0, s, w.len2, p.B, p.Ta, p.NR, w.cu, w.row_t, w.row_src, h->range_flag);
+    HIPCHK(h, hipGetLastError());
   }
+  return 0;
+}
+
+// The operand formats of one encoder GEMM: A as sp32 in format a_fmt (0: A stays fp32) with its per-row scale, C's store format and
+// the range guard on C.
+static inline void gemm_formats(GamGemmArgs& g, int a_fmt, const float* a_rs, int c_split, int c_guard) {
+  if (a_fmt) { g.Asp = reinterpret_cast<const _Float16*>(g.A); g.a_fmt = a_fmt; }
+  g.a_rs = a_rs; g.c_split = c_split; g.c_guard = c_guard;
+}
+
+// ------------------------------ stem ------------------------------
+// (C == D, and sp already implies D % 32 == 0: the image and both GEMMs' operands are sp32 whenever sp is set)
+static int stem_conv2d(gam_handle* h, hipStream_t s, const EncPlan& p, const EncBufs& w, const float* feat) {
+  const int B = p.B, Ta = p.Ta, N = p.N, C = p.D, D = p.D, FP = h->f1 + 1, F2 = h->f2;
+  {
+    GamConv1Args a;
+    a.feat = feat; a.img = h->img.p; a.w = h->c1_w; a.bias = h->c1_b; a.len0 = w.len0; a.len1 = w.len1;
+    a.B = B; a.T = (int)p.T; a.F = p.F; a.Ta = Ta; a.FP = FP; a.C = C; a.T1 = p.T1;
+    a.img_split = p.spf;
+    a.range_flag = h->use_range ? h->range_flag : nullptr;
+    ProfScope ps(h, s, GAM_PF_STEM, (double)B * 2 * Ta * FP * C * 4.0);
+    if (a.img_split == 2) hipLaunchKernelGGL(gam_conv2d1_kernel<2>, dim3(2 * Ta, B), dim3(256), 0, s, a);
+    else if (a.img_split == 1) hipLaunchKernelGGL(gam_conv2d1_kernel<1>, dim3(2 * Ta, B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gam_conv2d1_kernel<0>, dim3(2 * Ta, B), dim3(256), 0, s, a);
+    HIPCHK(h, hipGetLastError());
+    // two slack rows past the last utterance (read by its padding frame only); the dense fp16 image ends at half the offset
+    const size_t img_end = (size_t)B * 2 * Ta * FP * C;
+    HIPCHK(h, hipMemsetAsync(a.img_split == 2 ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(h->img.p) + img_end) : h->img.p + img_end, 0,
+                             (size_t)2 * FP * C * sizeof(float), s));
+  }
+  GamGemmArgs g = gemm_args(h->img.p, 0, h->c2_w, h->c2_b, h->c2.p, C, N * F2, C, 9 * C);
+  g.a_mode = 1; g.conv_fp = FP; g.conv_c = C; g.conv_f2 = F2;
+  g.lens = w.len2; g.rpb = Ta * F2; g.fdiv = F2;
+  g.skip_pad = p.packed ? 1 : 0;      // 16-frame row tiles behind an utterance's last frame: 12 rounds of tiles shrink with the batch's padding
+  gemm_formats(g, p.spf, nullptr, p.spf, 1);
+  if (int r = gemm(h, s, g, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c2)) return r;
+  GamGemmArgs l = gemm_args(h->c2.p, (long)F2 * C, h->lin_w, h->lin_b, p.packed ? h->y.p : h->x.p, D, N, D, F2 * C);
+  gemm_formats(l, p.spf, nullptr, 0, 0);
+  return gemm(h, s, l, GAM_ACT_NONE, GAM_PF_GEMM, &h->s_lin);
+}
+
+static int stem_conv1d(gam_handle* h, hipStream_t s, const EncPlan& p, const EncBufs& w, const float* feat) {
+  const int B = p.B, Ta = p.Ta, T1a = p.T1a, N = p.N, C = p.D, D = p.D, F = p.F;
+  const int64_t T = p.T;
+  const int ks = h->cfg.subs_kernel_size, pad = (ks - 1) / 2;
+  const int fmt = p.sp_stem ? 1 : 0;   // (all-zero bits are an sp32 zero: the memsets serve both formats)
+  {
+    ProfScope ps(h, s, GAM_PF_STEM, (double)B * T * F * 8.0);
+    HIPCHK(h, hipMemsetAsync(h->xin.p, 0, ((size_t)B * 2 * T1a + 8) * F * sizeof(float), s));
+    HIPCHK(h, hipMemsetAsync(h->y1.p, 0, ((size_t)B * 2 * Ta + 8) * C * sizeof(float), s));
+    dim3 grid(gam_cdiv(T, 32), gam_cdiv(F, 32), B);
+    int* const rf = h->use_range ? h->range_flag : nullptr;
+    if (p.sp_stem) hipLaunchKernelGGL(gam_feat_to_rows_kernel<1>, grid, dim3(256), 0, s, feat, h->xin.p, w.len0, B, F, (int)T, 2 * T1a, pad, rf);
+    else hipLaunchKernelGGL(gam_feat_to_rows_kernel<0>, grid, dim3(256), 0, s, feat, h->xin.p, w.len0, B, F, (int)T, 2 * T1a, pad, rf);
+    HIPCHK(h, hipGetLastError());
+  }
+  GamGemmArgs g1 = gemm_args(h->xin.p, 2L * F, h->c1_w, h->c1_b, h->y1.p, C, B * T1a, C, ks * F);
+  g1.lens = w.len1; g1.rpb = T1a; g1.fdiv = 1;
+  g1.remap = 1; g1.out_rpb = 2 * Ta; g1.out_shift = pad; g1.rows_valid = std::min(T1a, 2 * Ta - pad);
+  gemm_formats(g1, fmt, nullptr, fmt, 1);
+  if (int r = gemm(h, s, g1, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c1)) return r;
+  GamGemmArgs g2 = gemm_args(h->y1.p, 2L * C, h->c2_w, h->c2_b, p.packed ? h->y.p : h->x.p, D, N, D, ks * C);
+  g2.lens = w.len2; g2.rpb = Ta; g2.fdiv = 1;
+  gemm_formats(g2, fmt, nullptr, 0, 0);
+  return gemm(h, s, g2, GAM_ACT_RELU, GAM_PF_CONV2, &h->s_c2);
+}
+
+static int enc_stem(gam_handle* h, hipStream_t s, const EncPlan& p, const EncBufs& w, const float* feat) {
+  if (int r = p.conv2d ? stem_conv2d(h, s, p, w, feat) : stem_conv1d(h, s, p, w, feat)) return r;
+  if (p.packed) {   // the stem's padded rows -> packed rows (the only copy the layout costs: 2 x NR x D x 4 bytes)
+    ProfScope ps(h, s, GAM_PF_STEM, (double)p.NR * p.D * 8.0);
+    hipLaunchKernelGGL(gam_gather_rows_kernel, dim3(std::min(4096, gam_cdiv(p.NR * (p.D / 4), 256))), dim3(256), 0, s, h->y.p, w.row_src, h->x.p, p.NR, p.D);
+    HIPCHK(h, hipGetLastError());
+  }
+  return 0;
+}
+
+// ------------------------------ Conformer layers ------------------------------
+// One builder and launcher per non-GEMM kernel family, shared by the layer blocks and the gam_op_* entry points (which make
+// their own argument checks and open no ProfScope).  dk is GAM_ATT_DK for every handle (gam_create).
+static int launch_attention(gam_handle* h, hipStream_t s, const float* q, const float* k, const float* v, long ldq, float* ctx, int ctx_split,
+                            const int* lens, const int* cu, int B, int Ta, int Tv, int H, const float* pbuf, const float* pos_u,
+                            const float* pos_v) {
+  const int D = H * GAM_ATT_DK;
+  GamAttnArgs at;
+  memset(&at, 0, sizeof at);
+  at.q = q; at.k = k; at.v = v; at.ctx = ctx; at.ctx_split = ctx_split; at.lens = lens; at.cu = cu;
+  at.B = B; at.Ta = Ta; at.Tv = Tv; at.H = H; at.ldq = ldq; at.ldv = ldq; at.ldo = D;
+  at.scale = 1.0f / sqrtf((float)GAM_ATT_DK);
+  at.pbuf = pbuf; at.pos_u = pos_u; at.pos_v = pos_v; at.ldp = D;
+  hipError_t e = gam_launch_attn_mode(at, GAM_ATT_DK, split_mode(h), s, h->gemm_mode == GAM_GEMM_F16 ? 1 : 3, h->ncu);
+  if (e != hipSuccess) return fail(h, -2, "attention launch: %s", hipGetErrorString(e));
+  return 0;
+}
+
+// (returns the launch's error: the encoder and gam_op_convmod word their failures differently)
+static hipError_t launch_convmod(gam_handle* h, hipStream_t s, const float* u, float* z, const float* dw_w, const float* dw_b, const float* n_scale,
+                                 const float* n_shift, const int* lens, const int* cu, int B, int Ta, int Tv, int d, int ks, bool layer_norm,
+                                 int z_split) {
+  GamConvModArgs cm;
+  memset(&cm, 0, sizeof cm);
+  cm.u = u; cm.z = z; cm.dw_w = dw_w; cm.dw_b = dw_b; cm.n_scale = n_scale; cm.n_shift = n_shift;
+  cm.lens = lens; cm.cu = cu; cm.B = B; cm.Ta = Ta; cm.Tv = Tv; cm.d = d; cm.ks = ks; cm.eps = 1e-5f;
+  cm.z_split = z_split; cm.range_flag = h->use_range ? h->range_flag : nullptr;
+  return gam_launch_convmod(cm, layer_norm, s);
+}
+
+// LayerNorm of x into the GEMM operand y
+static int norm_to_y(gam_handle* h, hipStream_t s, const EncCtx& c, const float* w, const float* b, PendingReduce* pend) {
+  GamLnArgs a = c.ln;
+  a.x = h->x.p; a.out1 = h->y.p; a.w1 = w; a.b1 = b;
+  a.split1 = c.p.spf;
+  return layernorm(h, s, a, 0, pend);
+}
+
+// x += 0.5 * W2 silu(W1 y + b1) + b2, y = the LayerNorm of x (already applied)
+static int ffn_block(gam_handle* h, hipStream_t s, const EncCtx& c, const float* w1, const float* b1, const W16& s_w1, const float* w2,
+                     const float* b2, const W16& s_w2, PendingReduce* pend) {
+  const int D = c.p.D, DFF = c.p.DFF, NR = c.p.NR, spf = c.p.spf;
+  GamGemmArgs g = gemm_args(h->y.p, D, w1, b1, h->hbuf.p, DFF, NR, DFF, D);
+  gemm_formats(g, spf, c.w.rs, spf, 1);
+  if (int r = gemm(h, s, g, GAM_ACT_SILU, GAM_PF_GEMM, &s_w1)) return r;
+  GamGemmArgs g2 = gemm_args(h->hbuf.p, DFF, w2, b2, h->x.p, D, NR, D, DFF);
+  g2.R = h->x.p; g2.ldr = D; g2.alpha = 0.5f;
+  gemm_formats(g2, spf, nullptr, 0, 0);
+  return gemm(h, s, g2, GAM_ACT_NONE, GAM_PF_GEMM, &s_w2, pend);
+}
+
+static int attn_block(gam_handle* h, hipStream_t s, const EncCtx& c, const LayerW& L, PendingReduce* pend) {
+  const EncPlan& p = c.p;
+  const int D = p.D, NR = p.NR, Tv = p.Tv, spf = p.spf;
+  float* const rs = c.w.rs;
+  GamLnArgs a = c.ln;
+  a.x = h->x.p; a.out1 = h->y.p; a.out2 = h->yr.p; a.w1 = L.ln_att_w; a.b1 = L.ln_att_b;
+  a.split1 = spf; a.split2 = spf;
+  if (int r = layernorm(h, s, a, p.rel ? 0 : 1, pend)) return r;
+  // rotary: q,k project the rotated copy, v the plain one; rel_pos: all three project y.  One [N, 3D] result q | k | v.
+  // q, k and v are split to fp16 unscaled by the attention kernel: range guard on all of them.
+  const bool one_launch = p.rel || (p.sp && (2 * D) % 256 == 0);   // (the operand switch sits on a tile boundary of either tile width)
+  if (one_launch) {
+    GamGemmArgs gq = gemm_args(p.rel ? h->y.p : h->yr.p, D, L.wqkv, L.bqkv, h->qkv.p, 3 * D, NR, 3 * D, D);
+    gemm_formats(gq, spf, rs, 0, 1);
+    if (!p.rel) { gq.Asp2 = reinterpret_cast<const _Float16*>(h->y.p); gq.n_switch = 2 * D; }
+    if (int r = gemm(h, s, gq, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wqkv)) return r;
+  } else {
+    GamGemmArgs gq = gemm_args(h->yr.p, D, L.wqkv, L.bqkv, h->qkv.p, 3 * D, NR, 2 * D, D);
+    gemm_formats(gq, spf, rs, 0, 1);
+    if (int r = gemm(h, s, gq, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wqkv)) return r;
+    W16 wv16 = L.s_wqkv;   // rows 2D .. 3D of the same planes
+    const size_t off = (size_t)2 * D * D;
+    wv16.h16 += off;
+    if (wv16.sp) wv16.sp += 2 * off;
+    GamGemmArgs gv = gemm_args(h->y.p, D, L.wqkv + off, L.bqkv + 2 * D, h->qkv.p + 2 * D, 3 * D, NR, D, D);
+    gemm_formats(gv, spf, rs, 0, 1);
+    if (int r = gemm(h, s, gv, GAM_ACT_NONE, GAM_PF_GEMM, &wv16)) return r;
+  }
+  if (p.rel) {  // P = linear_pos(pos_emb) for relative positions -(T'-1) .. T'-1 (no bias)
+    const size_t pe0 = (size_t)(h->cfg.pos_emb_max_len - 1 - (Tv - 1)) * D;
+    GamGemmArgs gp = gemm_args(h->rel_pe + pe0, D, L.wpos, nullptr, h->pbuf.p, D, 2 * Tv - 1, D, D);
+    if (p.sp) { gp.Asp = reinterpret_cast<const _Float16*>(h->rel_pe_sp + pe0); gp.a_fmt = 1; }   // (three-term in the one-term mode too)
+    if (int r = gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wpos)) return r;
+  }
+  {
+    ProfScope ps(h, s, GAM_PF_ATTN, 4.0 * (double)p.B * p.H * (double)Tv * Tv * p.dk);
+    // (encoder.py:620-624: no mask at batch 1)
+    if (int r = launch_attention(h, s, h->qkv.p, h->qkv.p + D, h->qkv.p + 2 * D, 3 * D, h->ctx.p, spf, p.B > 1 ? c.w.len2 : nullptr, c.w.cu, p.B,
+                                 p.packed ? p.Tmax : p.Ta, Tv, p.H, p.rel ? h->pbuf.p : nullptr, L.pos_u, L.pos_v))
+      return r;
+  }
+  GamGemmArgs go = gemm_args(h->ctx.p, D, L.wo, L.bo, h->x.p, D, NR, D, D);
+  go.R = h->x.p; go.ldr = D;
+  gemm_formats(go, spf, nullptr, 0, 0);
+  return gemm(h, s, go, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wo, pend);
+}
+
+static int conv_block(gam_handle* h, hipStream_t s, const EncCtx& c, const LayerW& L, PendingReduce* pend) {
+  const EncPlan& p = c.p;
+  const int D = p.D, NR = p.NR, ks = h->cfg.conv_kernel_size;
+  if (int r = norm_to_y(h, s, c, L.ln_conv_w, L.ln_conv_b, pend)) return r;
+  GamGemmArgs g1 = gemm_args(h->y.p, D, L.pw1_w, L.pw1_b, h->ubuf.p, 2 * D, NR, 2 * D, D);
+  gemm_formats(g1, p.spf, c.w.rs, 0, 0);
+  if (int r = gemm(h, s, g1, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_pw1)) return r;
+  {
+    ProfScope ps(h, s, GAM_PF_CONVMOD, (double)NR * D * 3 * 4.0);
+    hipError_t e = launch_convmod(h, s, h->ubuf.p, h->zbuf.p, L.dw_w, L.dw_b, L.cn_scale, L.cn_shift, c.w.len2, c.w.cu, p.B,
+                                  p.packed ? p.Tmax : p.Ta, p.Tv, D, ks, h->cfg.conv_norm_type == GAM_NORM_LAYER, p.spf);
+    if (e != hipSuccess) return fail(h, -2, "conv-module launch (k=%d): %s", ks, hipGetErrorString(e));
+  }
+  GamGemmArgs g2 = gemm_args(h->zbuf.p, D, L.pw2_w, L.pw2_b, h->x.p, D, NR, D, D);
+  g2.R = h->x.p; g2.ldr = D;
+  gemm_formats(g2, p.spf, nullptr, 0, 0);
+  return gemm(h, s, g2, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_pw2, pend);
+}
+
+// norm_out in place, fused with the next layer's norm_feed_forward1 into y when there is one
+static int norm_out_block(gam_handle* h, hipStream_t s, const EncCtx& c, const LayerW& L, const LayerW* next, PendingReduce* pend) {
+  GamLnArgs a = c.ln;
+  a.x = h->x.p; a.out1 = h->x.p; a.w1 = L.ln_out_w; a.b1 = L.ln_out_b;
+  if (next != nullptr) {
+    a.out2 = h->y.p; a.w2 = next->ln_ff1_w; a.b2 = next->ln_ff1_b;
+    a.split2 = c.p.spf;
+    return layernorm(h, s, a, 2, pend);
+  }
+  a.rs = nullptr;   // the last norm_out feeds no GEMM
+  return layernorm(h, s, a, 0, pend);
+}
+
+static int run_layers(gam_handle* h, hipStream_t s, const EncCtx& c) {
+  const int nl = c.p.nl;
+  if (nl > 0)
+    if (int r = norm_to_y(h, s, c, h->layers[0].ln_ff1_w, h->layers[0].ln_ff1_b, nullptr)) return r;
   PendingReduce pend;    // the split-K slices of the residual GEMM just launched, summed by the LayerNorm that follows it
   for (int li = 0; li < nl; ++li) {
     const LayerW& L = h->layers[li];
-    // --- FFN 1 (macaron half step) ---
-    {
-      GamGemmArgs g = gemm_args(h->y.p, D, L.ff1_w1, L.ff1_b1, h->hbuf.p, DFF, NR, DFF, D);
-      sp_a(g); g.c_split = spf; g.a_rs = rs; g.c_guard = 1;
-      if (int r = gemm(h, s, g, GAM_ACT_SILU, GAM_PF_GEMM, &L.s_ff1_w1)) return r;
-      GamGemmArgs g2 = gemm_args(h->hbuf.p, DFF, L.ff1_w2, L.ff1_b2, h->x.p, D, NR, D, DFF);
-      g2.R = h->x.p; g2.ldr = D; g2.alpha = 0.5f;
-      sp_a(g2);
-      if (int r = gemm(h, s, g2, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_ff1_w2, &pend)) return r;
-    }
-    // --- self attention ---
-    {
-      GamLnArgs a = ln;
-      a.x = h->x.p; a.out1 = h->y.p; a.out2 = h->yr.p; a.w1 = L.ln_att_w; a.b1 = L.ln_att_b;
-      a.split1 = spf; a.split2 = spf;
-      if (int r = layernorm(h, s, a, rel ? 0 : 1, &pend)) return r;
-      // rotary: q,k project the rotated copy, v the plain one; rel_pos: all three project y.  One [N, 3D] result q | k | v.
-      // q, k and v are split to fp16 unscaled by the attention kernel: range guard on all of them.
-      const bool one_launch = rel || (sp && (2 * D) % 256 == 0);   // (the operand switch sits on a tile boundary of either tile width)
-      if (one_launch) {
-        GamGemmArgs gq = gemm_args(rel ? h->y.p : h->yr.p, D, L.wqkv, L.bqkv, h->qkv.p, 3 * D, NR, 3 * D, D);
-        sp_a(gq); gq.a_rs = rs; gq.c_guard = 1;
-        if (!rel) { gq.Asp2 = reinterpret_cast<const _Float16*>(h->y.p); gq.n_switch = 2 * D; }
-        if (int r = gemm(h, s, gq, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wqkv)) return r;
-      } else {
-        GamGemmArgs gq = gemm_args(h->yr.p, D, L.wqkv, L.bqkv, h->qkv.p, 3 * D, NR, 2 * D, D);
-        sp_a(gq); gq.a_rs = rs; gq.c_guard = 1;
-        if (int r = gemm(h, s, gq, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wqkv)) return r;
-        W16 wv16 = L.s_wqkv;   // rows 2D .. 3D of the same planes
-        const size_t off = (size_t)2 * D * D;
-        wv16.h16 += off;
-        if (wv16.sp) wv16.sp += 2 * off;
-        GamGemmArgs gv = gemm_args(h->y.p, D, L.wqkv + off, L.bqkv + 2 * D, h->qkv.p + 2 * D, 3 * D, NR, D, D);
-        sp_a(gv); gv.a_rs = rs; gv.c_guard = 1;
-        if (int r = gemm(h, s, gv, GAM_ACT_NONE, GAM_PF_GEMM, &wv16)) return r;
-      }
-      if (rel) {  // P = linear_pos(pos_emb) for relative positions -(T'-1) .. T'-1 (no bias)
-        const size_t pe0 = (size_t)(c.pos_emb_max_len - 1 - (Tv - 1)) * D;
-        GamGemmArgs gp = gemm_args(h->rel_pe + pe0, D, L.wpos, nullptr, h->pbuf.p, D, 2 * Tv - 1, D, D);
-        if (sp) { gp.Asp = reinterpret_cast<const _Float16*>(h->rel_pe_sp + pe0); gp.a_fmt = 1; }   // (three-term in the one-term mode too)
-        if (int r = gemm(h, s, gp, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wpos)) return r;
-      }
-      GamAttnArgs at;
-      memset(&at, 0, sizeof at);
-      at.q = h->qkv.p; at.k = h->qkv.p + D; at.v = h->qkv.p + 2 * D; at.ctx = h->ctx.p; at.ctx_split = spf;
-      at.lens = B > 1 ? len2 : nullptr;  // encoder.py:620-624: no mask at batch 1
-      at.cu = cu; at.B = B; at.Ta = packed ? Tmax : Ta; at.Tv = Tv; at.H = H; at.ldq = 3 * D; at.ldv = 3 * D; at.ldo = D;
-      at.scale = 1.0f / sqrtf((float)dk);
-      at.pbuf = rel ? h->pbuf.p : nullptr; at.pos_u = L.pos_u; at.pos_v = L.pos_v; at.ldp = D;
-      {
-        ProfScope ps(h, s, GAM_PF_ATTN, 4.0 * (double)B * H * (double)Tv * Tv * dk);
-        hipError_t e = gam_launch_attn_mode(at, dk, split_mode(h), s, h->gemm_mode == GAM_GEMM_F16 ? 1 : 3, h->ncu);
-        if (e != hipSuccess) return fail(h, -2, "attention launch: %s", hipGetErrorString(e));
-      }
-      GamGemmArgs go = gemm_args(h->ctx.p, D, L.wo, L.bo, h->x.p, D, NR, D, D);
-      go.R = h->x.p; go.ldr = D;
-      sp_a(go);
-      if (int r = gemm(h, s, go, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_wo, &pend)) return r;
-    }
-    // --- convolution module ---
-    {
-      GamLnArgs a = ln;
-      a.x = h->x.p; a.out1 = h->y.p; a.w1 = L.ln_conv_w; a.b1 = L.ln_conv_b;
-      a.split1 = spf;
-      if (int r = layernorm(h, s, a, 0, &pend)) return r;
-      GamGemmArgs g1 = gemm_args(h->y.p, D, L.pw1_w, L.pw1_b, h->ubuf.p, 2 * D, NR, 2 * D, D);
-      sp_a(g1); g1.a_rs = rs;
-      if (int r = gemm(h, s, g1, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_pw1)) return r;
-      GamConvModArgs cm;
-      cm.u = h->ubuf.p; cm.z = h->zbuf.p; cm.dw_w = L.dw_w; cm.dw_b = L.dw_b; cm.n_scale = L.cn_scale; cm.n_shift = L.cn_shift;
-      cm.lens = len2; cm.cu = cu; cm.B = B; cm.Ta = packed ? Tmax : Ta; cm.Tv = Tv; cm.d = D; cm.ks = c.conv_kernel_size; cm.eps = 1e-5f;
-      cm.z_split = spf; cm.range_flag = h->use_range ? h->range_flag : nullptr;
-      {
-        ProfScope ps(h, s, GAM_PF_CONVMOD, (double)NR * D * 3 * 4.0);
-        hipError_t e = gam_launch_convmod(cm, c.conv_norm_type == GAM_NORM_LAYER, s);
-        if (e != hipSuccess) return fail(h, -2, "conv-module launch (k=%d): %s", cm.ks, hipGetErrorString(e));
-      }
-      GamGemmArgs g2 = gemm_args(h->zbuf.p, D, L.pw2_w, L.pw2_b, h->x.p, D, NR, D, D);
-      g2.R = h->x.p; g2.ldr = D;
-      sp_a(g2);
-      if (int r = gemm(h, s, g2, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_pw2, &pend)) return r;
-    }
-    // --- FFN 2 ---
-    {
-      GamLnArgs a = ln;
-      a.x = h->x.p; a.out1 = h->y.p; a.w1 = L.ln_ff2_w; a.b1 = L.ln_ff2_b;
-      a.split1 = spf;
-      if (int r = layernorm(h, s, a, 0, &pend)) return r;
-      GamGemmArgs g = gemm_args(h->y.p, D, L.ff2_w1, L.ff2_b1, h->hbuf.p, DFF, NR, DFF, D);
-      sp_a(g); g.c_split = spf; g.a_rs = rs; g.c_guard = 1;
-      if (int r = gemm(h, s, g, GAM_ACT_SILU, GAM_PF_GEMM, &L.s_ff2_w1)) return r;
-      GamGemmArgs g2 = gemm_args(h->hbuf.p, DFF, L.ff2_w2, L.ff2_b2, h->x.p, D, NR, D, DFF);
-      g2.R = h->x.p; g2.ldr = D; g2.alpha = 0.5f;
-      sp_a(g2);
-      if (int r = gemm(h, s, g2, GAM_ACT_NONE, GAM_PF_GEMM, &L.s_ff2_w2, &pend)) return r;
-    }
-    // --- norm_out (+ next layer's norm_feed_forward1) ---
-    {
-      GamLnArgs a = ln;
-      a.x = h->x.p; a.out1 = h->x.p; a.w1 = L.ln_out_w; a.b1 = L.ln_out_b;
-      if (li + 1 < nl) {
-        a.out2 = h->y.p; a.w2 = h->layers[li + 1].ln_ff1_w; a.b2 = h->layers[li + 1].ln_ff1_b;
-        a.split2 = spf;
-        if (int r = layernorm(h, s, a, 2, &pend)) return r;
-      } else {
-        a.rs = nullptr;   // the last norm_out feeds no GEMM
-        if (int r = layernorm(h, s, a, 0, &pend)) return r;
-      }
-    }
+    if (int r = ffn_block(h, s, c, L.ff1_w1, L.ff1_b1, L.s_ff1_w1, L.ff1_w2, L.ff1_b2, L.s_ff1_w2, &pend)) return r;   // macaron half step
+    if (int r = attn_block(h, s, c, L, &pend)) return r;
+    if (int r = conv_block(h, s, c, L, &pend)) return r;
+    if (int r = norm_to_y(h, s, c, L.ln_ff2_w, L.ln_ff2_b, &pend)) return r;
+    if (int r = ffn_block(h, s, c, L.ff2_w1, L.ff2_b1, L.s_ff2_w1, L.ff2_w2, L.ff2_b2, L.s_ff2_w2, &pend)) return r;
+    if (int r = norm_out_block(h, s, c, L, li + 1 < nl ? &h->layers[li + 1] : nullptr, &pend)) return r;
   }
   return flush_pending(h, s, &pend);   // (nothing is pending after a norm_out; kept so that a future reordering cannot lose a reduce)
-  };
+}
 
-  // Small batches: replay the layer sequence as one hipGraph (see gam_handle::use_graph).
-  bool replayed = false;
-  if (h->use_graph && !h->prof_on && nl > 0 && N < h->graph_max_rows && !packed) {   // (packed rows: the row count is part of every launch)
-    // every workspace the captured launches touch must exist before the capture (no allocation inside)
-    if (int r = ensure(h, h->splitk_ws, (size_t)16 * N * std::max(DFF, 2 * D) + 64)) return r;
-    const GamSpForce& frc = gam_sp_force();   // (a plan forced through gam_tune_sp after a capture must not replay the old tiling)
-    const std::vector<int> key = {B, Ta, Tv, nl, h->gemm_mode, (int)sp, h->use_splitk, h->fuse_reduce, frc.mt.load(), frc.nw.load(), frc.s.load(), frc.ns.load()};
-    gam_handle::GraphEntry& ge = h->graphs[key];
-    if (ge.gen != h->ws_generation) {   // a buffer moved since this entry was made
-      if (ge.exec) { hipGraphExecDestroy(ge.exec); --h->graph_count; }
-      ge = gam_handle::GraphEntry();
-      ge.gen = h->ws_generation;
-    }
-    if (ge.exec == nullptr && ge.seen == 1 && h->graph_count >= 32) ge.seen = 2;   // cache full: plain launches
-    if (ge.exec == nullptr && ge.seen == 1) {
-      hipGraph_t graph = nullptr;
-      if (h->cap_stream == nullptr && hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) != hipSuccess)
-        h->cap_stream = nullptr;
-      if (h->cap_stream != nullptr && hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-        const int r = run_layers(h->cap_stream);     // recorded, not executed
-        const hipError_t e = hipStreamEndCapture(h->cap_stream, &graph);
-        if (r == 0 && e == hipSuccess && graph != nullptr && h->ws_generation == ge.gen &&
-            hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0) != hipSuccess)
-          ge.exec = nullptr;
-        if (graph) hipGraphDestroy(graph);
-      }
-      (void)hipGetLastError();               // a refused capture must not poison the launches below
-      if (ge.exec == nullptr) { ge.seen = 2; ++h->graph_captures_failed; }
-      else ++h->graph_count;   // capture failed: never try this shape again
-    }
-    if (ge.exec != nullptr) {
-      HIPCHK(h, hipGraphLaunch(ge.exec, s));
-      replayed = true;
-      ++h->graph_replays;
-    } else if (ge.seen == 0) {
-      ge.seen = 1;
-    }
+// Small batches: replay the layer sequence as one hipGraph (see gam_handle::use_graph).  *replayed = the layers ran from a graph;
+// otherwise the caller launches them.
+static int replay_layers(gam_handle* h, hipStream_t s, const EncCtx& c, bool* replayed) {
+  typedef gam_handle::GraphEntry Entry;
+  const EncPlan& p = c.p;
+  *replayed = false;
+  if (!p.graph) return 0;
+  const GamSpForce& frc = gam_sp_force();   // (a plan forced through gam_tune_sp after a capture must not replay the old tiling)
+  const std::vector<int> key = {p.B, p.Ta, p.Tv, p.nl, h->gemm_mode, (int)p.sp, h->use_splitk, h->fuse_reduce, frc.mt.load(), frc.nw.load(), frc.s.load(), frc.ns.load()};
+  Entry& ge = h->graphs[key];
+  if (ge.gen != h->ws_generation) {   // a buffer moved since this entry was made
+    if (ge.exec) { hipGraphExecDestroy(ge.exec); --h->graph_count; }
+    ge = Entry();
+    ge.gen = h->ws_generation;
   }
-  if (!replayed)
-    if (int r = run_layers(s)) return r;
-
-  // ------------------------------ outputs ------------------------------
-  {
-    ProfScope ps(h, s, GAM_PF_MISC, (double)B * Tv * D * 8.0);
-    if (encoded && packed) {
-      hipLaunchKernelGGL(gam_unpack_transpose_kernel, dim3(gam_cdiv(D, 32), gam_cdiv(Tv, 32), B), dim3(256), 0, s, h->x.p, cu, len2, encoded, Tv, D);
-      HIPCHK(h, hipGetLastError());
-    } else if (encoded) {
-      hipError_t e = gam_launch_transpose(h->x.p, encoded, B, Tv, D, (size_t)Ta * D, D, (size_t)D * Tv, Tv, s);
-      if (e != hipSuccess) return fail(h, -2, "transpose launch: %s", hipGetErrorString(e));
+  if (ge.exec == nullptr && ge.seen == Entry::SEEN_ONCE && h->graph_count >= 32) ge.seen = Entry::PLAIN_ONLY;   // cache full: plain launches
+  if (ge.exec == nullptr && ge.seen == Entry::SEEN_ONCE) {
+    hipGraph_t graph = nullptr;
+    if (h->cap_stream == nullptr && hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) != hipSuccess)
+      h->cap_stream = nullptr;
+    if (h->cap_stream != nullptr && hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
+      const int r = run_layers(h, h->cap_stream, c);     // recorded, not executed
+      const hipError_t e = hipStreamEndCapture(h->cap_stream, &graph);
+      if (r == 0 && e == hipSuccess && graph != nullptr && h->ws_generation == ge.gen &&
+          hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0) != hipSuccess)
+        ge.exec = nullptr;
+      if (graph) hipGraphDestroy(graph);
     }
-    if (tokens_out && packed) {
-      hipLaunchKernelGGL(gam_unpack_rows_kernel, dim3(std::min(4096, gam_cdiv(B * Tv * (D / 4), 256))), dim3(256), 0, s, h->x.p, cu, len2, tokens_out, B, Tv, D);
-      HIPCHK(h, hipGetLastError());
-    } else if (tokens_out)
-      HIPCHK(h, hipMemcpy2DAsync(tokens_out, (size_t)Tv * D * 4, h->x.p, (size_t)Ta * D * 4, (size_t)Tv * D * 4, B, hipMemcpyDeviceToDevice, s));
-    if (enc_len) HIPCHK(h, hipMemcpyAsync(enc_len, elen, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    (void)hipGetLastError();               // a refused capture must not poison the launches below
+    if (ge.exec == nullptr) { ge.seen = Entry::PLAIN_ONLY; ++h->graph_captures_failed; }   // capture failed: never try this shape again
+    else ++h->graph_count;
+  }
+  if (ge.exec != nullptr) {
+    HIPCHK(h, hipGraphLaunch(ge.exec, s));
+    *replayed = true;
+    ++h->graph_replays;
+  } else if (ge.seen == Entry::UNSEEN) {
+    ge.seen = Entry::SEEN_ONCE;
   }
   return 0;
+}
+
+// ------------------------------ outputs ------------------------------
+// channel-first `encoded`, token-major `tokens_out` and `enc_len`, each optional, from padded or packed rows
+static int enc_outputs(gam_handle* h, hipStream_t s, const EncPlan& p, const EncBufs& w, float* encoded, float* tokens_out, int32_t* enc_len) {
+  const int B = p.B, Ta = p.Ta, Tv = p.Tv, D = p.D;
+  ProfScope ps(h, s, GAM_PF_MISC, (double)B * Tv * D * 8.0);
+  if (encoded && p.packed) {
+    hipLaunchKernelGGL(gam_unpack_transpose_kernel, dim3(gam_cdiv(D, 32), gam_cdiv(Tv, 32), B), dim3(256), 0, s, h->x.p, w.cu, w.len2, encoded, Tv, D);
+    HIPCHK(h, hipGetLastError());
+  } else if (encoded) {
+    hipError_t e = gam_launch_transpose(h->x.p, encoded, B, Tv, D, (size_t)Ta * D, D, (size_t)D * Tv, Tv, s);
+    if (e != hipSuccess) return fail(h, -2, "transpose launch: %s", hipGetErrorString(e));
+  }
+  if (tokens_out && p.packed) {
+    hipLaunchKernelGGL(gam_unpack_rows_kernel, dim3(std::min(4096, gam_cdiv(B * Tv * (D / 4), 256))), dim3(256), 0, s, h->x.p, w.cu, w.len2, tokens_out, B, Tv, D);
+    HIPCHK(h, hipGetLastError());
+  } else if (tokens_out)
+    HIPCHK(h, hipMemcpy2DAsync(tokens_out, (size_t)Tv * D * 4, h->x.p, (size_t)Ta * D * 4, (size_t)Tv * D * 4, B, hipMemcpyDeviceToDevice, s));
+  if (enc_len) HIPCHK(h, hipMemcpyAsync(enc_len, w.elen, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+static int encode_impl(gam_handle* h, const float* feat, const int64_t* feat_len, int B, int64_t T, float* encoded,
+                       int32_t* enc_len, int n_layers_run, float* tokens_out, hipStream_t s, const int64_t* feat_len_host = nullptr) {
+  if (!h || !h->finalized) return fail(h, -1, "gam_encode before gam_finalize");
+  if (!h->has_encoder) return fail(h, -1, "this handle was finalized without encoder weights");
+  EncCtx c;
+  if (int r = enc_plan(h, B, T, n_layers_run, feat_len_host, c.p)) return r;
+  HIPCHK(h, hipSetDevice(h->device));
+  h->last_rows = c.p.NR;
+  h->last_rows_padded = c.p.N;
+  if (int r = enc_workspace(h, c.p, c.w)) return r;
+  c.ln = enc_ln_args(h, c.p, c.w);
+  if (int r = enc_lengths(h, s, c.p, c.w, feat_len)) return r;
+  if (int r = enc_stem(h, s, c.p, c.w, feat)) return r;
+  bool replayed = false;
+  if (int r = replay_layers(h, s, c, &replayed)) return r;
+  if (!replayed)
+    if (int r = run_layers(h, s, c)) return r;
+  return enc_outputs(h, s, c.p, c.w, encoded, tokens_out, enc_len);
 }
 
 int gam_encode(gam_handle* h, const float* feat, const int64_t* feat_len, int B, int64_t T, float* encoded, int32_t* enc_len,
@@ -2645,15 +2753,7 @@ int gam_op_attention(gam_handle* h, const float* q, const float* k, const float*
   if (!h) return -1;
   if (B <= 0 || T <= 0 || H <= 0) return fail(h, -1, "bad attention shape");
   HIPCHK(h, hipSetDevice(h->device));
-  GamAttnArgs at;
-  memset(&at, 0, sizeof at);
-  const int D = H * GAM_ATT_DK;
-  at.q = q; at.k = k; at.v = v; at.ctx = ctx; at.lens = lens;
-  at.B = B; at.Ta = T; at.Tv = T; at.H = H; at.ldq = D; at.ldv = D; at.ldo = D;
-  at.scale = 1.0f / sqrtf((float)GAM_ATT_DK);
-  hipError_t e = gam_launch_attn_mode(at, GAM_ATT_DK, split_mode(h), (hipStream_t)stream, h->gemm_mode == GAM_GEMM_F16 ? 1 : 3, h->ncu);
-  if (e != hipSuccess) return fail(h, -2, "attention launch: %s", hipGetErrorString(e));
-  return 0;
+  return launch_attention(h, (hipStream_t)stream, q, k, v, H * GAM_ATT_DK, ctx, 0, lens, nullptr, B, T, T, H, nullptr, nullptr, nullptr);
 }
 
 int gam_op_attention_ex(gam_handle* h, const float* q, const float* k, const float* v, int64_t ldq, float* ctx, const int32_t* lens,
@@ -2669,15 +2769,7 @@ int gam_op_attention_ex(gam_handle* h, const float* q, const float* k, const flo
   if (!al16(q) || !al16(k) || !al16(v) || !al16(ctx) || (pbuf && (!al16(pbuf) || !al16(pos_u) || !al16(pos_v))))
     return fail(h, -1, "attention: operands must be 16-byte aligned");
   HIPCHK(h, hipSetDevice(h->device));
-  GamAttnArgs at;
-  memset(&at, 0, sizeof at);
-  at.q = q; at.k = k; at.v = v; at.ctx = ctx; at.lens = lens; at.cu = cu;
-  at.B = B; at.Ta = Ta; at.Tv = Tv; at.H = H; at.ldq = ldq; at.ldv = ldq; at.ldo = D;
-  at.scale = 1.0f / sqrtf((float)GAM_ATT_DK);
-  at.pbuf = pbuf; at.pos_u = pos_u; at.pos_v = pos_v; at.ldp = D;
-  hipError_t e = gam_launch_attn_mode(at, GAM_ATT_DK, split_mode(h), (hipStream_t)stream, h->gemm_mode == GAM_GEMM_F16 ? 1 : 3, h->ncu);
-  if (e != hipSuccess) return fail(h, -2, "attention launch: %s", hipGetErrorString(e));
-  return 0;
+  return launch_attention(h, (hipStream_t)stream, q, k, v, (long)ldq, ctx, 0, lens, cu, B, Ta, Tv, H, pbuf, pos_u, pos_v);
 }
 
 int gam_op_layernorm(gam_handle* h, const gam_ln_op* op, void* stream) {
@@ -2732,12 +2824,7 @@ int gam_op_convmod(gam_handle* h, const float* u, float* z, const float* dw_w, c
   if (d % 4 == 0 && (!al16(u) || !al16(z) || !al16(dw_b) || !al16(n_scale) || !al16(n_shift)))
     return fail(h, -1, "conv module: operands must be 16-byte aligned");
   HIPCHK(h, hipSetDevice(h->device));
-  GamConvModArgs cm;
-  memset(&cm, 0, sizeof cm);
-  cm.u = u; cm.z = z; cm.dw_w = dw_w; cm.dw_b = dw_b; cm.n_scale = n_scale; cm.n_shift = n_shift;
-  cm.lens = lens; cm.cu = cu; cm.B = B; cm.Ta = Ta; cm.Tv = Tv; cm.d = d; cm.ks = ks; cm.eps = 1e-5f;
-  cm.z_split = z_split; cm.range_flag = h->use_range ? h->range_flag : nullptr;
-  hipError_t e = gam_launch_convmod(cm, layer_norm != 0, (hipStream_t)stream);
+  hipError_t e = launch_convmod(h, (hipStream_t)stream, u, z, dw_w, dw_b, n_scale, n_shift, lens, cu, B, Ta, Tv, d, ks, layer_norm != 0, z_split);
   if (e != hipSuccess) return fail(h, -2, "conv-module launch (k=%d, d=%d, %s): %s", ks, d, layer_norm ? "LayerNorm" : "BatchNorm", hipGetErrorString(e));
   return 0;
 }

@@ -12,7 +12,7 @@ import sys
 B, SEC, D, H = 32, 20.0, 768, 16
 T = 2001                      # log-mel frames of a 20 s utterance (hop 160, center=True)
 T1, TV = 1001, 501
-TA = 502                      # row stride per utterance (gam_api.hip encode_impl)
+TA = 502                      # row stride per utterance (gam_api.hip enc_plan: EncPlan::Ta)
 N = B * TA                    # token rows
 FP, F2 = 33, 16               # stage-1 feature bins + border, stage-2 bins
 NF, LDS = 201, 404            # DFT bins, spectrum row pitch (floats)
