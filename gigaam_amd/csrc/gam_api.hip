@@ -48,9 +48,28 @@ struct HostTensor {
   }
 };
 
+// One device allocation.  It frees itself and cannot be copied: whatever the handle holds as a DevBuf, or in a container of them, goes
+// with `delete h` (DESIGN.md "Handle memory").
 struct DevBuf {
   float* p = nullptr;
   size_t cap = 0;  // floats
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }   // (o frees what this held)
+  ~DevBuf() { (void)release(); }
+  hipError_t release() {
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr; cap = 0;
+    return e;
+  }
+  // The one way a buffer gets memory: what it held is freed first, its contents are not kept.
+  hipError_t alloc(size_t floats) {
+    hipError_t e = release();
+    if (e == hipSuccess) e = hipMalloc(&p, floats * sizeof(float));
+    if (e == hipSuccess) cap = floats; else p = nullptr;
+    return e;
+  }
+  template <class T> T* as() const { return reinterpret_cast<T*>(p); }   // the typed view of a buffer of ints / table slots
 };
 
 struct W16 {            // split-fp16 operand of one weight matrix (gam_gemm_sp.h): W * 2^s = hi + lo
@@ -82,7 +101,7 @@ struct gam_handle {
   bool finalized = false;
   bool has_encoder = false, has_head = false;
   std::map<std::string, HostTensor> staged;
-  std::vector<void*> owned;
+  std::vector<DevBuf> owned;   // every weight and table of gam_finalize (dev_upload); the float* / W16 members below are views into it
   std::string err;
 
   // frontend
@@ -144,18 +163,15 @@ struct gam_handle {
                                         // lattice of one slice, backpointers that do not fit the sweep kernel's LDS
   DevBuf cf_stats;                      // token confidence (gam_confidence.h): the CTC pass's per-frame (argmax, measure), B x T' x 8 bytes
   size_t ra_ws_limit = GAM_RA_WS_DEFAULT;   // bytes of lattice per slice (gam_set_rnnt_align_workspace; GAM_RNNT_ALIGN_WS at gam_create)
-  int* hw_trie = nullptr;               // hotword trie of gam_set_hotwords (CSR, gam_search.h): offsets | edges; NULL = no hotwords
-  size_t hw_cap = 0;                    // ints allocated at hw_trie
+  DevBuf hw_trie;                       // hotword trie of gam_set_hotwords (CSR, gam_search.h), ints: offsets | edges; empty = no hotwords
   int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
   float hw_boost = 0.f;
-  // the keyword set of gam_set_keywords (gam_kws.h): offsets [K + 1] | tokens | min_score [K] (f32 bits) in one buffer; NULL = no set
-  int* kw_dev = nullptr;
-  size_t kw_cap = 0;                    // ints allocated at kw_dev
+  // the keyword set of gam_set_keywords (gam_kws.h): offsets [K + 1] | tokens | min_score [K] (f32 bits) in one buffer of ints; empty = no set
+  DevBuf kw_dev;
   int kw_K = 0, kw_ntok = 0, kw_max_tok = -1;
   DevBuf kws_mb;                        // keyword search: per row {maximum, blank's emission}, B x T' x 8 bytes
-  // the n-gram LM of gam_set_lm (gam_search.h): token classes [lm_V], word / n-gram table slots; lm_ng NULL = no LM
-  int* lm_cls = nullptr;
-  void *lm_wt = nullptr, *lm_ng = nullptr;
+  // the n-gram LM of gam_set_lm (gam_search.h): token classes [lm_V], word / n-gram table slots (uint4); lm_ng empty = no LM
+  DevBuf lm_cls, lm_wt, lm_ng;
   int lm_V = 0, lm_wslots = 0, lm_wprobe = 0, lm_nslots = 0, lm_nprobe = 0, lm_order = 0, lm_bos = 0, lm_eos = 0, lm_unk = 0;
   float lm_unk_logp = 0.f, lm_alpha = 0.f, lm_beta = 0.f;
   DevBuf dec_splitk_ws;                 // split-K partial sums of the DECODE class's GEMMs: a decode may run on a side stream beside
@@ -181,8 +197,7 @@ struct gam_handle {
   long graph_replays = 0, graph_captures_failed = 0;
   int graph_count = 0;          // instantiated graphs alive (capped at 32 shapes)
   hipStream_t cap_stream = nullptr;   // private stream for captures (the caller's may be the legacy default stream)
-  int* lens = nullptr;  // 4 * maxB ints: len0, len1, len2, enc_len
-  int lens_cap = 0;
+  DevBuf lens;          // 4 * maxB ints: len0, len1, len2, enc_len
   DevBuf rsbuf, op_rs;  // per-row 2^-e of the LayerNorm-produced GEMM operand currently in y / yr; gam_op_gemm's
   int* range_flag = nullptr;   // device int: set when an unscaled sp32 tensor left fp16's range (gam_range_flag)
 
@@ -213,22 +228,32 @@ int fail(gam_handle* h, int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(h, -2, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// Every weight and table of gam_finalize reaches the device here: `alloc_bytes` >= `bytes` of memory that h->owned holds BEFORE anything
+// is copied into it (a failed copy leaks nothing), then `bytes` from `src` (NULL: no copy).  NULL: the allocation or the copy failed.
+void* dev_upload(gam_handle* h, const void* src, size_t bytes, size_t alloc_bytes) {
+  h->owned.emplace_back();
+  DevBuf& b = h->owned.back();
+  if (b.alloc((alloc_bytes + 3) / 4) != hipSuccess) return nullptr;
+  if (src && bytes && hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  return b.p;
+}
+
 float* upload(gam_handle* h, const std::vector<float>& v) {
-  float* d = nullptr;
-  if (hipMalloc(&d, std::max<size_t>(v.size(), 4) * sizeof(float)) != hipSuccess) return nullptr;
-  if (!v.empty() && hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-  h->owned.push_back(d);
-  return d;
+  return (float*)dev_upload(h, v.data(), v.size() * sizeof(float), std::max<size_t>(v.size(), 4) * sizeof(float));
+}
+
+// Grow-only: a buffer that already holds `floats` is left alone.  A workspace buffer that moves invalidates the captured graphs, which
+// hold its old pointer (ws_generation); the tables a kernel receives as launch arguments of a decode call do not (ensure_table).
+int ensure_table(gam_handle* h, DevBuf& b, size_t floats) {
+  if (floats <= b.cap) return 0;
+  HIPCHK(h, b.alloc(floats));
+  return 0;
 }
 
 int ensure(gam_handle* h, DevBuf& b, size_t floats) {
   if (floats <= b.cap) return 0;
-  if (b.p) HIPCHK(h, hipFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  HIPCHK(h, hipMalloc(&b.p, floats * sizeof(float)));
-  b.cap = floats;
-  ++h->ws_generation;   // captured graphs hold the old pointers
+  if (int r = ensure_table(h, b, floats)) return r;
+  ++h->ws_generation;
   return 0;
 }
 
@@ -272,9 +297,6 @@ float half_to_float(uint16_t x) {
   float r; memcpy(&r, &f, 4); return r;
 }
 
-
-float half_bits_to_float(uint16_t x) { return half_to_float(x); }
-
 // W * 2^shift = hi + lo with hi, lo in fp16; the power-of-two scale puts max|W| near 2^8 so
 // that lo (~2^-11 |W|) stays in the normal fp16 range for all but negligible entries.  K = the reduction length (row
 // pitch of W): the sp32 copy exists when K % 32 == 0.
@@ -292,7 +314,7 @@ int make_split(gam_handle* h, const std::vector<float>& w, W16& out, int K = 0, 
     const float v = w[i] * sc;
     const uint16_t hb = float_to_half_bits(v);
     hi[i] = hb;
-    lo[i] = float_to_half_bits(v - half_bits_to_float(hb));
+    lo[i] = float_to_half_bits(v - half_to_float(hb));
   }
   out.inv = ldexpf(1.0f, -shift);
   std::vector<uint16_t> hp(hi);
@@ -305,11 +327,8 @@ int make_split(gam_handle* h, const std::vector<float>& w, W16& out, int K = 0, 
           for (size_t j = 0; j < 64; ++j)
             hp[n * K + (cb * conv_taps + t) * 64 + j] = hi[n * K + t * C + cb * 64 + j];
   }
-  void* dp = nullptr;
-  if (hipMalloc(&dp, std::max<size_t>(w.size(), 8) * 2 + 64) != hipSuccess) return -2;
-  h->owned.push_back(dp);
-  if (hipMemcpy(dp, hp.data(), w.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -2;
-  out.h16 = (_Float16*)dp;
+  out.h16 = (_Float16*)dev_upload(h, hp.data(), w.size() * 2, std::max<size_t>(w.size(), 8) * 2 + 64);
+  if (!out.h16) return -2;
   if (K > 0 && K % 32 == 0 && w.size() % (size_t)K == 0) {
     // the same planes in the sp32 layout: row n, k-block kb -> [hi x32 | lo x32] (gam_gemm_sp.h)
     std::vector<uint16_t> sp(w.size() * 2);
@@ -324,11 +343,8 @@ int make_split(gam_handle* h, const std::vector<float>& w, W16& out, int K = 0, 
       sp[o] = hi[i];
       sp[o + 32] = lo[i];
     }
-    void* ds = nullptr;
-    if (hipMalloc(&ds, sp.size() * 2 + 64) != hipSuccess) return -2;
-    h->owned.push_back(ds);
-    if (hipMemcpy(ds, sp.data(), sp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return -2;
-    out.sp = (_Float16*)ds;
+    out.sp = (_Float16*)dev_upload(h, sp.data(), sp.size() * 2, sp.size() * 2 + 64);
+    if (!out.sp) return -2;
   }
   return 0;
 }
@@ -581,32 +597,13 @@ void gam_destroy(gam_handle* h) {
   audit_dump(h);
   fprintf(stderr, "[gam-audit] total: %ld of %ld cluster decodes logged at least one entry\n", h->audit_hit_decodes, h->audit_decodes);
 #endif
-  for (void* p : h->owned) hipFree(p);
-  DevBuf* bufs[] = {&h->wavp, &h->spec, &h->img, &h->c2, &h->xin, &h->y1, &h->x, &h->y, &h->yr, &h->hbuf,
-                    &h->qkv, &h->ctx, &h->ubuf, &h->zbuf, &h->tok, &h->logits, &h->encp, &h->pbuf, &h->aplanes, &h->op_planes, &h->op_sp, &h->splitk_ws, &h->dec_splitk_ws, &h->rsbuf, &h->op_rs, &h->rnnt_x, &h->rnnt_audit, &h->jz, &h->jp, &h->jl, &h->pack_idx};
-  for (DevBuf* b : bufs)
-    if (b->p) hipFree(b->p);
-  if (h->lens) hipFree(h->lens);
-  if (h->range_flag) hipFree(h->range_flag);
-  if (h->beam_nodes.p) hipFree(h->beam_nodes.p);
-  if (h->rb_ws.p) hipFree(h->rb_ws.p);
-  if (h->rb_nodes.p) hipFree(h->rb_nodes.p);
-  for (DevBuf* b : {&h->ra_g, &h->ra_pp, &h->ra_lat, &h->ra_bp, &h->cf_stats})
-    if (b->p) hipFree(b->p);
-  if (h->hw_trie) hipFree(h->hw_trie);
-  if (h->kw_dev) hipFree(h->kw_dev);
-  if (h->kws_mb.p) hipFree(h->kws_mb.p);
-  if (h->align_star.p) hipFree(h->align_star.p);
-  if (h->lm_cls) hipFree(h->lm_cls);
-  if (h->lm_wt) hipFree(h->lm_wt);
-  if (h->lm_ng) hipFree(h->lm_ng);
   for (auto& e : h->prof_events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (auto& g : h->graphs)
     if (g.second.exec) hipGraphExecDestroy(g.second.exec);
   if (h->cap_stream) hipStreamDestroy(h->cap_stream);
   if (h->dec_evt) hipEventDestroy(h->dec_evt);
   if (getenv("GAM_GRAPH_DEBUG")) fprintf(stderr, "[gam] graph replays %ld, failed captures %ld\n", h->graph_replays, h->graph_captures_failed);
-  delete h;
+  delete h;   // every device buffer is a DevBuf member or sits in `owned`: they free themselves
 }
 
 int gam_set_weight(gam_handle* h, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
@@ -628,352 +625,379 @@ int gam_set_weight(gam_handle* h, const char* key, const void* host_ptr, int dty
   return 0;
 }
 
-#define NEED(var, key, n)                                                                          \
-  const HostTensor* var = find(h, key);                                                            \
-  if (!var) return fail(h, -3, "missing weight %s", std::string(key).c_str());                     \
-  if (var->numel() != (int64_t)(n)) return fail(h, -3, "weight %s has %lld elements, expected %lld", std::string(key).c_str(), (long long)var->numel(), (long long)(n));
+// -----------------------------------------------------------------------------------
+// gam_finalize (DESIGN.md "Finalize pieces"): the staged host tensors become device weights.  A sequence of named pieces with explicit
+// inputs; each returns 0 or the code of its fail().
+//   fin_frontend                        DFT basis, mel filterbank (given, or mel_fallback), band table
+//   fin_stem_conv2d | fin_stem_conv1d   the subsampling stem's operands
+//   fin_layer                           one Conformer layer, (h, index) -> LayerW; fin_qkv and fin_conv_norm are its two non-trivial members
+//   fin_rotary | fin_rel_pos            the position table of the attention variant
+//   fin_head                            CTC / emotion: one upload_linear; RNN-T: fin_rnnt_head (lstm_input_table, fin_rnnt_upper)
+struct Dst {   // where the device pointer of an upload goes, and the name its failure message carries
+  float** p;
+  const char* name;
+};
+#define DST(member) Dst{&(member), #member}
 
-#define UP(dst, vec)                                   \
-  dst = upload(h, vec);                                \
-  if (!dst) return fail(h, -2, "device upload failed (%s)", #dst);
+static int need(gam_handle* h, const std::string& key, int64_t n, const HostTensor** t) {
+  *t = find(h, key);
+  if (!*t) return fail(h, -3, "missing weight %s", key.c_str());
+  if ((*t)->numel() != n) return fail(h, -3, "weight %s has %lld elements, expected %lld", key.c_str(), (long long)(*t)->numel(), (long long)n);
+  return 0;
+}
+
+static int upload_to(gam_handle* h, Dst dst, const std::vector<float>& v) {
+  *dst.p = upload(h, v);
+  return *dst.p ? 0 : fail(h, -2, "device upload failed (%s)", dst.name);
+}
+
+static int up_split(gam_handle* h, const std::vector<float>& w, W16* out, int K, int conv_taps = 0) {
+  return make_split(h, w, *out, K, conv_taps) ? fail(h, -2, "split upload failed") : 0;
+}
+
+// <prefix>.weight [nout, nin] and <prefix>.bias [nout] as they are; split != NULL: the weight's split-fp16 operand too (reduction length nin)
+static int upload_linear(gam_handle* h, const std::string& prefix, int64_t nout, int64_t nin, Dst w, Dst b, W16* split) {
+  const HostTensor *wt, *bt;
+  if (int r = need(h, prefix + ".weight", nout * nin, &wt)) return r;
+  if (int r = need(h, prefix + ".bias", nout, &bt)) return r;
+  if (int r = upload_to(h, w, wt->data)) return r;
+  if (int r = upload_to(h, b, bt->data)) return r;
+  return split ? up_split(h, wt->data, split, (int)nin) : 0;
+}
+
+static int upload_ln(gam_handle* h, const std::string& prefix, int D, Dst w, Dst b) { return upload_linear(h, prefix, D, 1, w, b, nullptr); }
+
+// [r][k] -> [k][r]
+static void transpose_rk(const float* in, size_t R, size_t K, float* out) {
+  for (size_t r = 0; r < R; ++r)
+    for (size_t k = 0; k < K; ++k) out[k * R + r] = in[r * K + k];
+}
+
+// [n][a][b] -> [n][b][a]: the two inner axes swapped
+static std::vector<float> swap_inner(const std::vector<float>& in, size_t N, size_t A, size_t B) {
+  std::vector<float> out(in.size());
+  for (size_t n = 0; n < N; ++n) transpose_rk(&in[n * A * B], A, B, &out[n * A * B]);
+  return out;
+}
+
+// [r][k] -> [k/4][r][4]: four consecutive k of a row side by side, the float4 the cluster decode kernel reads
+static std::vector<float> quad_rk(const std::vector<float>& in, size_t R, size_t K) {
+  std::vector<float> out(in.size());
+  for (size_t r = 0; r < R; ++r)
+    for (size_t k = 0; k < K; ++k) out[((k / 4) * R + r) * 4 + (k & 3)] = in[r * K + k];
+  return out;
+}
+
+// torchaudio melscale_fbanks(htk, norm=None, f_min 0, f_max sr/2) as [nf][n_mels]
+static std::vector<float> mel_fallback(const gam_config& c, int nf) {
+  std::vector<float> fb((size_t)nf * c.n_mels, 0.f);
+  const double fmax = c.sample_rate / 2.0, mmax = 2595.0 * log10(1.0 + fmax / 700.0);
+  std::vector<double> fpts(c.n_mels + 2);
+  for (int i = 0; i < c.n_mels + 2; ++i) fpts[i] = 700.0 * (pow(10.0, (mmax * i / (c.n_mels + 1)) / 2595.0) - 1.0);
+  for (int f = 0; f < nf; ++f) {
+    const double fr = (double)(c.sample_rate / 2) * f / (nf - 1);
+    for (int m = 0; m < c.n_mels; ++m) {
+      const double down = (fr - fpts[m]) / (fpts[m + 1] - fpts[m]), up = (fpts[m + 2] - fr) / (fpts[m + 2] - fpts[m + 1]);
+      fb[(size_t)f * c.n_mels + m] = (float)std::max(0.0, std::min(down, up));
+    }
+  }
+  return fb;
+}
+
+// window-folded DFT basis + mel filterbank
+static int fin_frontend(gam_handle* h) {
+  const gam_config& c = h->cfg;
+  const int n = c.n_fft, nf = n / 2 + 1;
+  h->nf = nf;
+  h->kpad = (n + 31) / 32 * 32;
+  std::vector<double> win(n);
+  if (const HostTensor* w = find(h, "preprocessor.featurizer.0.spectrogram.window")) {
+    if (w->numel() != n) return fail(h, -3, "window has %lld taps, expected %d", (long long)w->numel(), n);
+    for (int i = 0; i < n; ++i) win[i] = w->data[i];
+  } else {
+    for (int i = 0; i < n; ++i) win[i] = (double)(float)(0.5 - 0.5 * cos(2.0 * M_PI * i / n));  // periodic hann
+  }
+  std::vector<float> basis((size_t)2 * nf * h->kpad, 0.f);
+  for (int k = 0; k < nf; ++k)
+    for (int i = 0; i < n; ++i) {
+      const long ki = ((long)k * i) % n;  // exact angle reduction
+      const double ang = 2.0 * M_PI * (double)ki / n;
+      basis[(size_t)k * h->kpad + i] = (float)(win[i] * cos(ang));
+      basis[(size_t)(nf + k) * h->kpad + i] = (float)(-win[i] * sin(ang));
+    }
+  if (int r = upload_to(h, DST(h->dft_basis), basis)) return r;
+  const HostTensor* given = find(h, "preprocessor.featurizer.0.mel_scale.fb");
+  if (given && given->numel() != (int64_t)nf * c.n_mels) return fail(h, -3, "mel fb has %lld elements, expected %d", (long long)given->numel(), nf * c.n_mels);
+  const std::vector<float> fb = given ? given->data : mel_fallback(c, nf);
+  std::vector<int> band(3 * (size_t)c.n_mels, 0);
+  std::vector<float> wts;
+  for (int m = 0; m < c.n_mels; ++m) {
+    int lo = nf, hi = 0;
+    for (int f = 0; f < nf; ++f)
+      if (fb[(size_t)f * c.n_mels + m] != 0.f) { lo = std::min(lo, f); hi = std::max(hi, f + 1); }
+    if (hi <= lo) lo = hi = 0;
+    band[3 * m] = lo; band[3 * m + 1] = hi; band[3 * m + 2] = (int)wts.size();
+    for (int f = lo; f < hi; ++f) wts.push_back(fb[(size_t)f * c.n_mels + m]);
+  }
+  h->mel_nw = (int)wts.size();
+  if (int r = upload_to(h, DST(h->mel_wts), wts)) return r;
+  h->mel_band = (int*)dev_upload(h, band.data(), band.size() * sizeof(int), band.size() * sizeof(int));
+  return h->mel_band ? 0 : fail(h, -2, "mel band upload failed");
+}
+
+static int fin_stem_conv2d(gam_handle* h) {
+  const int C = h->cfg.d_model, D = h->cfg.d_model, F = h->cfg.feat_in;
+  const std::string pe = "encoder.pre_encode.";
+  h->f1 = (F + 1) / 2;
+  h->f2 = (h->f1 + 1) / 2;
+  const HostTensor *w0, *b0, *w2, *b2, *wl, *bl;
+  if (int r = need(h, pe + "conv.0.weight", (int64_t)C * 9, &w0)) return r;
+  if (int r = need(h, pe + "conv.0.bias", C, &b0)) return r;
+  if (int r = need(h, pe + "conv.2.weight", (int64_t)C * C * 9, &w2)) return r;
+  if (int r = need(h, pe + "conv.2.bias", C, &b2)) return r;
+  if (int r = need(h, pe + "out.weight", (int64_t)D * C * h->f2, &wl)) return r;
+  if (int r = need(h, pe + "out.bias", D, &bl)) return r;
+  if (int r = upload_to(h, DST(h->c1_w), w0->data)) return r;
+  if (int r = upload_to(h, DST(h->c1_b), b0->data)) return r;
+  const std::vector<float> t2 = swap_inner(w2->data, C, C, 9);   // [n][c][kh][kw] -> [n][kh*3+kw][c]
+  if (int r = upload_to(h, DST(h->c2_w), t2)) return r;
+  if (int r = up_split(h, t2, &h->s_c2, 9 * C, C % 32 == 0 ? 9 : 0)) return r;
+  if (int r = upload_to(h, DST(h->c2_b), b2->data)) return r;
+  const std::vector<float> l = swap_inner(wl->data, D, C, h->f2);   // [n][c][f] -> [n][f][c]: columns c*f2+f -> f*C+c (encoder.py:126-127 flattens channel-major)
+  if (int r = upload_to(h, DST(h->lin_w), l)) return r;
+  if (int r = up_split(h, l, &h->s_lin, C * h->f2)) return r;
+  return upload_to(h, DST(h->lin_b), bl->data);
+}
+
+static int fin_stem_conv1d(gam_handle* h) {
+  const int C = h->cfg.d_model, F = h->cfg.feat_in, ks = h->cfg.subs_kernel_size;
+  const std::string pe = "encoder.pre_encode.";
+  const HostTensor *w0, *b0, *w2, *b2;
+  if (int r = need(h, pe + "conv.0.weight", (int64_t)C * F * ks, &w0)) return r;
+  if (int r = need(h, pe + "conv.0.bias", C, &b0)) return r;
+  if (int r = need(h, pe + "conv.2.weight", (int64_t)C * C * ks, &w2)) return r;
+  if (int r = need(h, pe + "conv.2.bias", C, &b2)) return r;
+  const std::vector<float> r0 = swap_inner(w0->data, C, F, ks), r2 = swap_inner(w2->data, C, C, ks);   // [n][f][k] -> [n][k][f]
+  if (int r = upload_to(h, DST(h->c1_w), r0)) return r;
+  if (int r = up_split(h, r0, &h->s_c1, ks * F)) return r;
+  if (int r = upload_to(h, DST(h->c1_b), b0->data)) return r;
+  if (int r = upload_to(h, DST(h->c2_w), r2)) return r;
+  if (int r = up_split(h, r2, &h->s_c2, ks * C)) return r;
+  return upload_to(h, DST(h->c2_b), b2->data);
+}
+
+// rows [W_q; W_k; W_v] and their biases as one operand
+static int fin_qkv(gam_handle* h, const std::string& p, LayerW& L) {
+  const int D = h->cfg.d_model;
+  const HostTensor *wq, *bq, *wk, *bk, *wv, *bv;
+  if (int r = need(h, p + "self_attn.linear_q.weight", (int64_t)D * D, &wq)) return r;
+  if (int r = need(h, p + "self_attn.linear_q.bias", D, &bq)) return r;
+  if (int r = need(h, p + "self_attn.linear_k.weight", (int64_t)D * D, &wk)) return r;
+  if (int r = need(h, p + "self_attn.linear_k.bias", D, &bk)) return r;
+  if (int r = need(h, p + "self_attn.linear_v.weight", (int64_t)D * D, &wv)) return r;
+  if (int r = need(h, p + "self_attn.linear_v.bias", D, &bv)) return r;
+  std::vector<float> w(wq->data), b(bq->data);
+  w.insert(w.end(), wk->data.begin(), wk->data.end());
+  w.insert(w.end(), wv->data.begin(), wv->data.end());
+  b.insert(b.end(), bk->data.begin(), bk->data.end());
+  b.insert(b.end(), bv->data.begin(), bv->data.end());
+  if (int r = upload_to(h, DST(L.wqkv), w)) return r;
+  if (int r = upload_to(h, DST(L.bqkv), b)) return r;
+  return up_split(h, w, &L.s_wqkv, D);
+}
+
+// the conv module's norm as (scale, shift): BatchNorm folded with its running statistics, LayerNorm's affine pair as it is
+static int fin_conv_norm(gam_handle* h, const std::string& p, LayerW& L) {
+  const int D = h->cfg.d_model;
+  const HostTensor *g, *be;
+  if (int r = need(h, p + "conv.batch_norm.weight", D, &g)) return r;
+  if (int r = need(h, p + "conv.batch_norm.bias", D, &be)) return r;
+  if (h->cfg.conv_norm_type != GAM_NORM_BATCH) {
+    if (int r = upload_to(h, DST(L.cn_scale), g->data)) return r;
+    return upload_to(h, DST(L.cn_shift), be->data);
+  }
+  const HostTensor *rm, *rv;
+  if (int r = need(h, p + "conv.batch_norm.running_mean", D, &rm)) return r;
+  if (int r = need(h, p + "conv.batch_norm.running_var", D, &rv)) return r;
+  std::vector<float> sc(D), sh(D);
+  for (int i = 0; i < D; ++i) {
+    const float inv = 1.0f / sqrtf(rv->data[i] + 1e-5f);
+    sc[i] = g->data[i] * inv;
+    sh[i] = be->data[i] - rm->data[i] * sc[i];
+  }
+  if (int r = upload_to(h, DST(L.cn_scale), sc)) return r;
+  return upload_to(h, DST(L.cn_shift), sh);
+}
+
+static int fin_layer(gam_handle* h, int li, LayerW& L) {
+  const gam_config& c = h->cfg;
+  const int D = c.d_model, DFF = D * c.ff_expansion_factor;
+  const std::string p = "encoder.layers." + std::to_string(li) + ".";
+  memset(&L, 0, sizeof L);
+  if (int r = upload_ln(h, p + "norm_feed_forward1", D, DST(L.ln_ff1_w), DST(L.ln_ff1_b))) return r;
+  if (int r = upload_linear(h, p + "feed_forward1.linear1", DFF, D, DST(L.ff1_w1), DST(L.ff1_b1), &L.s_ff1_w1)) return r;
+  if (int r = upload_linear(h, p + "feed_forward1.linear2", D, DFF, DST(L.ff1_w2), DST(L.ff1_b2), &L.s_ff1_w2)) return r;
+  if (int r = upload_ln(h, p + "norm_self_att", D, DST(L.ln_att_w), DST(L.ln_att_b))) return r;
+  if (int r = fin_qkv(h, p, L)) return r;
+  if (int r = upload_linear(h, p + "self_attn.linear_out", D, D, DST(L.wo), DST(L.bo), &L.s_wo)) return r;
+  if (c.self_attention_model == GAM_ATT_REL_POS) {
+    const HostTensor *wp, *pu, *pv;
+    if (int r = need(h, p + "self_attn.linear_pos.weight", (int64_t)D * D, &wp)) return r;
+    if (int r = need(h, p + "self_attn.pos_bias_u", D, &pu)) return r;
+    if (int r = need(h, p + "self_attn.pos_bias_v", D, &pv)) return r;
+    if (int r = upload_to(h, DST(L.wpos), wp->data)) return r;
+    if (int r = up_split(h, wp->data, &L.s_wpos, D)) return r;
+    if (int r = upload_to(h, DST(L.pos_u), pu->data)) return r;
+    if (int r = upload_to(h, DST(L.pos_v), pv->data)) return r;
+  }
+  if (int r = upload_ln(h, p + "norm_conv", D, DST(L.ln_conv_w), DST(L.ln_conv_b))) return r;
+  if (int r = upload_linear(h, p + "conv.pointwise_conv1", 2 * D, D, DST(L.pw1_w), DST(L.pw1_b), &L.s_pw1)) return r;
+  if (int r = upload_linear(h, p + "conv.depthwise_conv", D, c.conv_kernel_size, DST(L.dw_w), DST(L.dw_b), nullptr)) return r;
+  if (int r = fin_conv_norm(h, p, L)) return r;
+  if (int r = upload_linear(h, p + "conv.pointwise_conv2", D, D, DST(L.pw2_w), DST(L.pw2_b), &L.s_pw2)) return r;
+  if (int r = upload_ln(h, p + "norm_feed_forward2", D, DST(L.ln_ff2_w), DST(L.ln_ff2_b))) return r;
+  if (int r = upload_linear(h, p + "feed_forward2.linear1", DFF, D, DST(L.ff2_w1), DST(L.ff2_b1), &L.s_ff2_w1)) return r;
+  if (int r = upload_linear(h, p + "feed_forward2.linear2", D, DFF, DST(L.ff2_w2), DST(L.ff2_b2), &L.s_ff2_w2)) return r;
+  return upload_ln(h, p + "norm_out", D, DST(L.ln_out_w), DST(L.ln_out_b));
+}
+
+// rotary table (encoder.py:342-355; base = pos_emb_max_len)
+static int fin_rotary(gam_handle* h) {
+  const int dk = h->cfg.d_model / h->cfg.n_heads, half = dk / 2, n = h->cfg.pos_emb_max_len;
+  std::vector<float> cs((size_t)n * half), sn((size_t)n * half);
+  for (int i = 0; i < half; ++i) {
+    const float inv_freq = 1.0f / powf((float)n, (float)(2 * i) / (float)dk);
+    for (int t = 0; t < n; ++t) {
+      const float fr = (float)t * inv_freq;
+      cs[(size_t)t * half + i] = (float)cos((double)fr);
+      sn[(size_t)t * half + i] = (float)sin((double)fr);
+    }
+  }
+  if (int r = upload_to(h, DST(h->rot_cos), cs)) return r;
+  return upload_to(h, DST(h->rot_sin), sn);
+}
+
+// RelPositionalEmbedding.create_pe (encoder.py:312-327): pe(r)[2i] = sin(r * w_i), pe(r)[2i+1] = cos(r * w_i),
+// w_i = exp(2i * -(ln 10000 / D)); rows ascending in r
+static int fin_rel_pos(gam_handle* h) {
+  const int D = h->cfg.d_model, n = h->cfg.pos_emb_max_len;
+  std::vector<float> pe((size_t)(2 * n - 1) * D);
+  for (int i = 0; i < D / 2; ++i) {
+    const float w = expf((float)(2 * i) * (float)(-(log(10000.0) / D)));
+    for (int r = -(n - 1); r <= n - 1; ++r) {
+      const float ang = (float)r * w;
+      pe[(size_t)(r + n - 1) * D + 2 * i] = (float)sin((double)ang);
+      pe[(size_t)(r + n - 1) * D + 2 * i + 1] = (float)cos((double)ang);
+    }
+  }
+  if (int r = upload_to(h, DST(h->rel_pe), pe)) return r;
+  // its sp32 copy, split by the kernel that splits every other fp32 operand (D % 32 == 0: a row starts on a 32-element block)
+  h->rel_pe_sp = (float*)dev_upload(h, nullptr, 0, pe.size() * sizeof(float));
+  if (!h->rel_pe_sp) return fail(h, -2, "device upload failed (h->rel_pe_sp)");
+  hipLaunchKernelGGL(gam_to_sp32_kernel, dim3((int)std::min<size_t>((pe.size() / 4 + 255) / 256, 4096)), dim3(256), 0, nullptr, h->rel_pe,
+                     reinterpret_cast<_Float16*>(h->rel_pe_sp), pe.size() / 4, (const float*)nullptr, D);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+// nn.LSTM layers 1 .. L-1 (decoder.py:78-83): transposed like W_hh, biases summed
+static int fin_rnnt_upper(gam_handle* h) {
+  const int PH = h->cfg.pred_hidden, LX = h->cfg.pred_rnn_layers - 1;
+  const size_t G = (size_t)4 * PH;
+  std::vector<float> wih_x(LX * PH * G), whh_x(LX * PH * G), bias_x(LX * G);
+  for (int l = 1; l <= LX; ++l) {
+    const std::string sfx = "_l" + std::to_string(l);
+    const HostTensor *wi, *wh, *bi, *bh;
+    if (int r = need(h, "head.decoder.lstm.weight_ih" + sfx, (int64_t)4 * PH * PH, &wi)) return r;
+    if (int r = need(h, "head.decoder.lstm.weight_hh" + sfx, (int64_t)4 * PH * PH, &wh)) return r;
+    if (int r = need(h, "head.decoder.lstm.bias_ih" + sfx, 4 * PH, &bi)) return r;
+    if (int r = need(h, "head.decoder.lstm.bias_hh" + sfx, 4 * PH, &bh)) return r;
+    transpose_rk(wi->data.data(), G, PH, &wih_x[(l - 1) * PH * G]);
+    transpose_rk(wh->data.data(), G, PH, &whh_x[(l - 1) * PH * G]);
+    for (size_t r = 0; r < G; ++r) bias_x[(l - 1) * G + r] = bi->data[r] + bh->data[r];
+  }
+  if (int r = upload_to(h, DST(h->lstm_wih_x), wih_x)) return r;
+  if (int r = upload_to(h, DST(h->lstm_whh_x), whh_x)) return r;
+  return upload_to(h, DST(h->lstm_bias_x), bias_x);
+}
+
+// The embedding folded into the first LSTM layer's input half: row v = W_ih emb[v] + b_ih + b_hh; row V (no token yet) = the biases
+static std::vector<float> lstm_input_table(const HostTensor* emb, const HostTensor* wih, const HostTensor* bih, const HostTensor* bhh, int V, int PH) {
+  std::vector<float> tab((size_t)(V + 1) * 4 * PH);
+  for (int v = 0; v <= V; ++v)
+    for (int r = 0; r < 4 * PH; ++r) {
+      float acc = 0.f;
+      if (v < V) {
+        const float* wr = &wih->data[(size_t)r * PH];
+        const float* e = &emb->data[(size_t)v * PH];
+        for (int k = 0; k < PH; ++k) acc = fmaf(wr[k], e[k], acc);
+      }
+      tab[(size_t)v * 4 * PH + r] = (acc + bih->data[r]) + bhh->data[r];
+    }
+  return tab;
+}
+
+static int fin_rnnt_head(gam_handle* h) {
+  const gam_config& c = h->cfg;
+  const int D = c.d_model, V = c.num_classes, PH = c.pred_hidden, JH = c.joint_hidden;
+  const HostTensor *emb, *wih, *whh, *bih, *bhh, *wp, *bp, *we, *bee, *wo, *bo;
+  if (int r = need(h, "head.decoder.embed.weight", (int64_t)V * PH, &emb)) return r;
+  if (int r = need(h, "head.decoder.lstm.weight_ih_l0", (int64_t)4 * PH * PH, &wih)) return r;
+  if (int r = need(h, "head.decoder.lstm.weight_hh_l0", (int64_t)4 * PH * PH, &whh)) return r;
+  if (int r = need(h, "head.decoder.lstm.bias_ih_l0", 4 * PH, &bih)) return r;
+  if (int r = need(h, "head.decoder.lstm.bias_hh_l0", 4 * PH, &bhh)) return r;
+  if (int r = need(h, "head.joint.pred.weight", (int64_t)JH * PH, &wp)) return r;
+  if (int r = need(h, "head.joint.pred.bias", JH, &bp)) return r;
+  if (int r = need(h, "head.joint.enc.weight", (int64_t)JH * D, &we)) return r;
+  if (int r = need(h, "head.joint.enc.bias", JH, &bee)) return r;
+  if (int r = need(h, "head.joint.joint_net.1.weight", (int64_t)V * JH, &wo)) return r;
+  if (int r = need(h, "head.joint.joint_net.1.bias", V, &bo)) return r;
+  if (c.pred_rnn_layers > 1)
+    if (int r = fin_rnnt_upper(h)) return r;
+  if (int r = upload_to(h, DST(h->lstm_whh_q), quad_rk(whh->data, 4 * PH, PH))) return r;
+  if (int r = upload_to(h, DST(h->jn_pred_q), quad_rk(wp->data, JH, PH))) return r;
+  if (int r = upload_to(h, DST(h->lstm_tab), lstm_input_table(emb, wih, bih, bhh, V, PH))) return r;
+  if (int r = upload_to(h, DST(h->lstm_whh_t), swap_inner(whh->data, 1, 4 * PH, PH))) return r;
+  if (int r = upload_to(h, DST(h->jn_pred_t), swap_inner(wp->data, 1, JH, PH))) return r;
+  if (int r = upload_to(h, DST(h->jn_pred_b), bp->data)) return r;
+  if (int r = upload_to(h, DST(h->jn_pred_w), wp->data)) return r;
+  if (int r = upload_to(h, DST(h->jn_enc_w), we->data)) return r;
+  if (int r = upload_to(h, DST(h->jn_enc_b), bee->data)) return r;
+  if (int r = upload_to(h, DST(h->jn_out_w), wo->data)) return r;
+  return upload_to(h, DST(h->jn_out_b), bo->data);
+}
+
+static int fin_head(gam_handle* h) {
+  const gam_config& c = h->cfg;
+  if (c.head_type == GAM_HEAD_CTC) return upload_linear(h, "head.decoder_layers.0", c.num_classes, c.d_model, DST(h->ctc_w), DST(h->ctc_b), nullptr);
+  if (c.head_type == GAM_HEAD_EMO) return upload_linear(h, "head", c.num_classes, c.d_model, DST(h->emo_w), DST(h->emo_b), nullptr);
+  return c.head_type == GAM_HEAD_RNNT ? fin_rnnt_head(h) : 0;
+}
 
 int gam_finalize(gam_handle* h) {
   if (!h) return -1;
   if (h->finalized) return 0;
   HIPCHK(h, hipSetDevice(h->device));
   const gam_config& c = h->cfg;
-  const int D = c.d_model, C = c.d_model, F = c.feat_in, H = c.n_heads, dk = D / H;
-
-  // ---------------- frontend: window-folded DFT basis + mel filterbank ----------------
-  {
-    const int n = c.n_fft, nf = n / 2 + 1;
-    h->nf = nf;
-    h->kpad = (n + 31) / 32 * 32;
-    std::vector<double> win(n);
-    if (const HostTensor* w = find(h, "preprocessor.featurizer.0.spectrogram.window")) {
-      if (w->numel() != n) return fail(h, -3, "window has %lld taps, expected %d", (long long)w->numel(), n);
-      for (int i = 0; i < n; ++i) win[i] = w->data[i];
-    } else {
-      for (int i = 0; i < n; ++i) win[i] = (double)(float)(0.5 - 0.5 * cos(2.0 * M_PI * i / n));  // periodic hann
-    }
-    std::vector<float> basis((size_t)2 * nf * h->kpad, 0.f);
-    for (int k = 0; k < nf; ++k)
-      for (int i = 0; i < n; ++i) {
-        const long ki = ((long)k * i) % n;  // exact angle reduction
-        const double ang = 2.0 * M_PI * (double)ki / n;
-        basis[(size_t)k * h->kpad + i] = (float)(win[i] * cos(ang));
-        basis[(size_t)(nf + k) * h->kpad + i] = (float)(-win[i] * sin(ang));
-      }
-    UP(h->dft_basis, basis);
-    std::vector<float> fb;
-    if (const HostTensor* f = find(h, "preprocessor.featurizer.0.mel_scale.fb")) {
-      if (f->numel() != (int64_t)nf * c.n_mels) return fail(h, -3, "mel fb has %lld elements, expected %d", (long long)f->numel(), nf * c.n_mels);
-      fb = f->data;
-    } else {
-      // torchaudio melscale_fbanks(htk, norm=None, f_min 0, f_max sr/2)
-      fb.assign((size_t)nf * c.n_mels, 0.f);
-      const double fmax = c.sample_rate / 2.0, mmax = 2595.0 * log10(1.0 + fmax / 700.0);
-      std::vector<double> fpts(c.n_mels + 2);
-      for (int i = 0; i < c.n_mels + 2; ++i) fpts[i] = 700.0 * (pow(10.0, (mmax * i / (c.n_mels + 1)) / 2595.0) - 1.0);
-      for (int f = 0; f < nf; ++f) {
-        const double fr = (double)(c.sample_rate / 2) * f / (nf - 1);
-        for (int m = 0; m < c.n_mels; ++m) {
-          const double down = (fr - fpts[m]) / (fpts[m + 1] - fpts[m]), up = (fpts[m + 2] - fr) / (fpts[m + 2] - fpts[m + 1]);
-          fb[(size_t)f * c.n_mels + m] = (float)std::max(0.0, std::min(down, up));
-        }
-      }
-    }
-    std::vector<int> band(3 * (size_t)c.n_mels, 0);
-    std::vector<float> wts;
-    for (int m = 0; m < c.n_mels; ++m) {
-      int lo = nf, hi = 0;
-      for (int f = 0; f < nf; ++f)
-        if (fb[(size_t)f * c.n_mels + m] != 0.f) { lo = std::min(lo, f); hi = std::max(hi, f + 1); }
-      if (hi <= lo) lo = hi = 0;
-      band[3 * m] = lo; band[3 * m + 1] = hi; band[3 * m + 2] = (int)wts.size();
-      for (int f = lo; f < hi; ++f) wts.push_back(fb[(size_t)f * c.n_mels + m]);
-    }
-    h->mel_nw = (int)wts.size();
-    UP(h->mel_wts, wts);
-    void* db = nullptr;
-    if (hipMalloc(&db, band.size() * sizeof(int)) != hipSuccess) return fail(h, -2, "mel band upload failed");
-    h->owned.push_back(db);
-    if (hipMemcpy(db, band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return fail(h, -2, "mel band upload failed");
-    h->mel_band = (int*)db;
+  if (int r = fin_frontend(h)) return r;
+  // A handle may carry only a subset of the operators (e.g. a stand-alone FeatureExtractor or ConformerEncoder module on the Python side).
+  const bool build_encoder = find(h, "encoder.pre_encode.conv.0.weight") != nullptr;
+  if (build_encoder) {
+    if (int r = c.subsampling == GAM_SUBS_CONV2D ? fin_stem_conv2d(h) : fin_stem_conv1d(h)) return r;
+    h->layers.resize(c.n_layers);
+    for (int li = 0; li < c.n_layers; ++li)
+      if (int r = fin_layer(h, li, h->layers[li])) return r;
+    if (int r = c.self_attention_model == GAM_ATT_ROTARY ? fin_rotary(h) : fin_rel_pos(h)) return r;
   }
-
-  // ---------------- stem ----------------
-  // A handle may carry only a subset of the operators (e.g. a stand-alone
-  // FeatureExtractor or ConformerEncoder module on the Python side).
-  const std::string pe = "encoder.pre_encode.";
-  const bool build_encoder = find(h, pe + "conv.0.weight") != nullptr;
-  if (!build_encoder) {
-    // nothing to do
-  } else if (c.subsampling == GAM_SUBS_CONV2D) {
-    h->f1 = (F + 1) / 2;
-    h->f2 = (h->f1 + 1) / 2;
-    NEED(w0, pe + "conv.0.weight", (int64_t)C * 9);
-    NEED(b0, pe + "conv.0.bias", C);
-    NEED(w2, pe + "conv.2.weight", (int64_t)C * C * 9);
-    NEED(b2, pe + "conv.2.bias", C);
-    NEED(wl, pe + "out.weight", (int64_t)D * C * h->f2);
-    NEED(bl, pe + "out.bias", D);
-    UP(h->c1_w, w0->data);
-    UP(h->c1_b, b0->data);
-    // [n][c][kh][kw] -> [n][kh*3+kw][c]
-    std::vector<float> r((size_t)C * 9 * C);
-    for (int n = 0; n < C; ++n)
-      for (int ci = 0; ci < C; ++ci)
-        for (int t = 0; t < 9; ++t) r[((size_t)n * 9 + t) * C + ci] = w2->data[((size_t)n * C + ci) * 9 + t];
-    UP(h->c2_w, r);
-    if (make_split(h, r, h->s_c2, 9 * C, C % 32 == 0 ? 9 : 0)) return fail(h, -2, "split upload failed");
-    UP(h->c2_b, b2->data);
-    // columns c*f2+f -> f*C+c (encoder.py:126-127 flattens channel-major)
-    std::vector<float> l((size_t)D * C * h->f2);
-    const int f2 = h->f2;
-    for (int n = 0; n < D; ++n)
-      for (int ci = 0; ci < C; ++ci)
-        for (int f = 0; f < f2; ++f) l[(size_t)n * C * f2 + (size_t)f * C + ci] = wl->data[(size_t)n * C * f2 + (size_t)ci * f2 + f];
-    UP(h->lin_w, l);
-    if (make_split(h, l, h->s_lin, C * h->f2)) return fail(h, -2, "split upload failed");
-    UP(h->lin_b, bl->data);
-  } else {
-    const int ks = c.subs_kernel_size;
-    NEED(w0, pe + "conv.0.weight", (int64_t)C * F * ks);
-    NEED(b0, pe + "conv.0.bias", C);
-    NEED(w2, pe + "conv.2.weight", (int64_t)C * C * ks);
-    NEED(b2, pe + "conv.2.bias", C);
-    // [n][f][k] -> [n][k][f]
-    std::vector<float> r0((size_t)C * ks * F), r2((size_t)C * ks * C);
-    for (int n = 0; n < C; ++n)
-      for (int f = 0; f < F; ++f)
-        for (int k = 0; k < ks; ++k) r0[((size_t)n * ks + k) * F + f] = w0->data[((size_t)n * F + f) * ks + k];
-    for (int n = 0; n < C; ++n)
-      for (int ci = 0; ci < C; ++ci)
-        for (int k = 0; k < ks; ++k) r2[((size_t)n * ks + k) * C + ci] = w2->data[((size_t)n * C + ci) * ks + k];
-    UP(h->c1_w, r0);
-    if (make_split(h, r0, h->s_c1, ks * F)) return fail(h, -2, "split upload failed");
-    UP(h->c1_b, b0->data);
-    UP(h->c2_w, r2);
-    if (make_split(h, r2, h->s_c2, ks * C)) return fail(h, -2, "split upload failed");
-    UP(h->c2_b, b2->data);
-  }
-
-  // ---------------- layers ----------------
-  const int DFF = D * c.ff_expansion_factor, ks = c.conv_kernel_size;
-  h->layers.resize(build_encoder ? c.n_layers : 0);
-  for (int li = 0; li < (build_encoder ? c.n_layers : 0); ++li) {
-    LayerW& L = h->layers[li];
-    memset(&L, 0, sizeof L);
-    const std::string p = "encoder.layers." + std::to_string(li) + ".";
-#define LN_(dstw, dstb, name)                 \
-  {                                           \
-    NEED(w_, p + name + ".weight", D);        \
-    NEED(b_, p + name + ".bias", D);          \
-    UP(dstw, w_->data);                       \
-    UP(dstb, b_->data);                       \
-  }
-#define LIN_(dstw, dstb, name, nout, nin)                 \
-  {                                                       \
-    NEED(w_, p + name + ".weight", (int64_t)(nout) * (nin)); \
-    NEED(b_, p + name + ".bias", nout);                   \
-    UP(dstw, w_->data);                                   \
-    UP(dstb, b_->data);                                   \
-  }
-    LN_(L.ln_ff1_w, L.ln_ff1_b, "norm_feed_forward1");
-#define LINS_(dstw, dstb, dsts, name, nout, nin)                                     \
-  {                                                                                  \
-    NEED(w_, p + name + ".weight", (int64_t)(nout) * (nin));                         \
-    NEED(b_, p + name + ".bias", nout);                                              \
-    UP(dstw, w_->data);                                                              \
-    UP(dstb, b_->data);                                                              \
-    if (make_split(h, w_->data, dsts, nin)) return fail(h, -2, "split upload failed"); \
-  }
-    LINS_(L.ff1_w1, L.ff1_b1, L.s_ff1_w1, "feed_forward1.linear1", DFF, D);
-    LINS_(L.ff1_w2, L.ff1_b2, L.s_ff1_w2, "feed_forward1.linear2", D, DFF);
-    LN_(L.ln_att_w, L.ln_att_b, "norm_self_att");
-    {
-      NEED(wq, p + "self_attn.linear_q.weight", (int64_t)D * D);
-      NEED(bq, p + "self_attn.linear_q.bias", D);
-      NEED(wk, p + "self_attn.linear_k.weight", (int64_t)D * D);
-      NEED(bk, p + "self_attn.linear_k.bias", D);
-      NEED(wv, p + "self_attn.linear_v.weight", (int64_t)D * D);
-      NEED(bv, p + "self_attn.linear_v.bias", D);
-      std::vector<float> w(wq->data), b(bq->data);
-      w.insert(w.end(), wk->data.begin(), wk->data.end());
-      w.insert(w.end(), wv->data.begin(), wv->data.end());
-      b.insert(b.end(), bk->data.begin(), bk->data.end());
-      b.insert(b.end(), bv->data.begin(), bv->data.end());
-      UP(L.wqkv, w);
-      UP(L.bqkv, b);
-      if (make_split(h, w, L.s_wqkv, D)) return fail(h, -2, "split upload failed");
-    }
-    LINS_(L.wo, L.bo, L.s_wo, "self_attn.linear_out", D, D);
-    if (c.self_attention_model == GAM_ATT_REL_POS) {
-      NEED(wp, p + "self_attn.linear_pos.weight", (int64_t)D * D);
-      NEED(pu, p + "self_attn.pos_bias_u", D);
-      NEED(pv, p + "self_attn.pos_bias_v", D);
-      UP(L.wpos, wp->data);
-      if (make_split(h, wp->data, L.s_wpos, D)) return fail(h, -2, "split upload failed");
-      UP(L.pos_u, pu->data);
-      UP(L.pos_v, pv->data);
-    }
-    LN_(L.ln_conv_w, L.ln_conv_b, "norm_conv");
-    LINS_(L.pw1_w, L.pw1_b, L.s_pw1, "conv.pointwise_conv1", 2 * D, D);
-    LIN_(L.dw_w, L.dw_b, "conv.depthwise_conv", D, ks);
-    {
-      NEED(g, p + "conv.batch_norm.weight", D);
-      NEED(be, p + "conv.batch_norm.bias", D);
-      if (c.conv_norm_type == GAM_NORM_BATCH) {
-        NEED(rm, p + "conv.batch_norm.running_mean", D);
-        NEED(rv, p + "conv.batch_norm.running_var", D);
-        std::vector<float> sc(D), sh(D);
-        for (int i = 0; i < D; ++i) {
-          const float inv = 1.0f / sqrtf(rv->data[i] + 1e-5f);
-          sc[i] = g->data[i] * inv;
-          sh[i] = be->data[i] - rm->data[i] * sc[i];
-        }
-        UP(L.cn_scale, sc);
-        UP(L.cn_shift, sh);
-      } else {
-        UP(L.cn_scale, g->data);
-        UP(L.cn_shift, be->data);
-      }
-    }
-    LINS_(L.pw2_w, L.pw2_b, L.s_pw2, "conv.pointwise_conv2", D, D);
-    LN_(L.ln_ff2_w, L.ln_ff2_b, "norm_feed_forward2");
-    LINS_(L.ff2_w1, L.ff2_b1, L.s_ff2_w1, "feed_forward2.linear1", DFF, D);
-    LINS_(L.ff2_w2, L.ff2_b2, L.s_ff2_w2, "feed_forward2.linear2", D, DFF);
-    LN_(L.ln_out_w, L.ln_out_b, "norm_out");
-#undef LN_
-#undef LIN_
-#undef LINS_
-  }
-
-  // ---------------- rotary table (encoder.py:342-355; base = pos_emb_max_len) ----------------
-  if (!build_encoder) {
-  } else if (c.self_attention_model == GAM_ATT_ROTARY) {
-    const int half = dk / 2, n = c.pos_emb_max_len;
-    std::vector<float> cs((size_t)n * half), sn((size_t)n * half);
-    for (int i = 0; i < half; ++i) {
-      const float inv_freq = 1.0f / powf((float)n, (float)(2 * i) / (float)dk);
-      for (int t = 0; t < n; ++t) {
-        const float fr = (float)t * inv_freq;
-        cs[(size_t)t * half + i] = (float)cos((double)fr);
-        sn[(size_t)t * half + i] = (float)sin((double)fr);
-      }
-    }
-    UP(h->rot_cos, cs);
-    UP(h->rot_sin, sn);
-  } else {
-    // RelPositionalEmbedding.create_pe (encoder.py:312-327): pe(r)[2i] = sin(r * w_i),
-    // pe(r)[2i+1] = cos(r * w_i), w_i = exp(2i * -(ln 10000 / D)); rows ascending in r
-    const int n = c.pos_emb_max_len;
-    std::vector<float> pe((size_t)(2 * n - 1) * D);
-    for (int i = 0; i < D / 2; ++i) {
-      const float w = expf((float)(2 * i) * (float)(-(log(10000.0) / D)));
-      for (int r = -(n - 1); r <= n - 1; ++r) {
-        const float ang = (float)r * w;
-        pe[(size_t)(r + n - 1) * D + 2 * i] = (float)sin((double)ang);
-        pe[(size_t)(r + n - 1) * D + 2 * i + 1] = (float)cos((double)ang);
-      }
-    }
-    UP(h->rel_pe, pe);
-    // its sp32 copy, split by the kernel that splits every other fp32 operand (D % 32 == 0: a row starts on a 32-element block)
-    HIPCHK(h, hipMalloc(&h->rel_pe_sp, pe.size() * sizeof(float)));
-    h->owned.push_back(h->rel_pe_sp);
-    hipLaunchKernelGGL(gam_to_sp32_kernel, dim3((int)std::min<size_t>((pe.size() / 4 + 255) / 256, 4096)), dim3(256), 0, nullptr, h->rel_pe,
-                       reinterpret_cast<_Float16*>(h->rel_pe_sp), pe.size() / 4, (const float*)nullptr, D);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(nullptr));
-  }
-
   h->has_encoder = build_encoder;
-
-  // ---------------- heads ----------------
-  const bool build_head = find(h, "head.decoder_layers.0.weight") != nullptr || find(h, "head.joint.enc.weight") != nullptr ||
-                          (c.head_type == GAM_HEAD_EMO && find(h, "head.weight") != nullptr);
-  h->has_head = build_head;
-  if (!build_head) {
-  } else if (c.head_type == GAM_HEAD_CTC) {
-    NEED(w, "head.decoder_layers.0.weight", (int64_t)c.num_classes * D);
-    NEED(b, "head.decoder_layers.0.bias", c.num_classes);
-    UP(h->ctc_w, w->data);
-    UP(h->ctc_b, b->data);
-  } else if (c.head_type == GAM_HEAD_EMO) {
-    NEED(w, "head.weight", (int64_t)c.num_classes * D);
-    NEED(b, "head.bias", c.num_classes);
-    UP(h->emo_w, w->data);
-    UP(h->emo_b, b->data);
-  } else if (c.head_type == GAM_HEAD_RNNT) {
-    const int V = c.num_classes, PH = c.pred_hidden, JH = c.joint_hidden;
-    NEED(emb, "head.decoder.embed.weight", (int64_t)V * PH);
-    NEED(wih, "head.decoder.lstm.weight_ih_l0", (int64_t)4 * PH * PH);
-    NEED(whh, "head.decoder.lstm.weight_hh_l0", (int64_t)4 * PH * PH);
-    NEED(bih, "head.decoder.lstm.bias_ih_l0", 4 * PH);
-    NEED(bhh, "head.decoder.lstm.bias_hh_l0", 4 * PH);
-    NEED(wp, "head.joint.pred.weight", (int64_t)JH * PH);
-    NEED(bp, "head.joint.pred.bias", JH);
-    NEED(we, "head.joint.enc.weight", (int64_t)JH * D);
-    NEED(bee, "head.joint.enc.bias", JH);
-    NEED(wo, "head.joint.joint_net.1.weight", (int64_t)V * JH);
-    NEED(bo, "head.joint.joint_net.1.bias", V);
-    std::vector<float> tab((size_t)(V + 1) * 4 * PH), whh_t((size_t)PH * 4 * PH), wp_t((size_t)PH * JH);
-    for (int v = 0; v <= V; ++v)
-      for (int r = 0; r < 4 * PH; ++r) {
-        float acc = 0.f;
-        if (v < V) {
-          const float* wr = &wih->data[(size_t)r * PH];
-          const float* e = &emb->data[(size_t)v * PH];
-          for (int k = 0; k < PH; ++k) acc = fmaf(wr[k], e[k], acc);
-        }
-        tab[(size_t)v * 4 * PH + r] = (acc + bih->data[r]) + bhh->data[r];
-      }
-    for (int r = 0; r < 4 * PH; ++r)
-      for (int k = 0; k < PH; ++k) whh_t[(size_t)k * 4 * PH + r] = whh->data[(size_t)r * PH + k];
-    for (int r = 0; r < JH; ++r)
-      for (int k = 0; k < PH; ++k) wp_t[(size_t)k * JH + r] = wp->data[(size_t)r * PH + k];
-    std::vector<float> whh_q((size_t)PH * 4 * PH), wp_q((size_t)PH * JH);
-    for (int r = 0; r < 4 * PH; ++r)
-      for (int k = 0; k < PH; ++k) whh_q[((size_t)(k / 4) * 4 * PH + r) * 4 + (k & 3)] = whh->data[(size_t)r * PH + k];
-    for (int r = 0; r < JH; ++r)
-      for (int k = 0; k < PH; ++k) wp_q[((size_t)(k / 4) * JH + r) * 4 + (k & 3)] = wp->data[(size_t)r * PH + k];
-    if (c.pred_rnn_layers > 1) {   // nn.LSTM layers 1 .. L-1 (decoder.py:78-83): transposed like W_hh, biases summed
-      const int LX = c.pred_rnn_layers - 1;
-      std::vector<float> wih_x((size_t)LX * PH * 4 * PH), whh_x((size_t)LX * PH * 4 * PH), bias_x((size_t)LX * 4 * PH);
-      for (int l = 1; l <= LX; ++l) {
-        const std::string sfx = "_l" + std::to_string(l);
-        NEED(wi, "head.decoder.lstm.weight_ih" + sfx, (int64_t)4 * PH * PH);
-        NEED(wh, "head.decoder.lstm.weight_hh" + sfx, (int64_t)4 * PH * PH);
-        NEED(bi, "head.decoder.lstm.bias_ih" + sfx, 4 * PH);
-        NEED(bh, "head.decoder.lstm.bias_hh" + sfx, 4 * PH);
-        const size_t o = (size_t)(l - 1) * PH * 4 * PH;
-        for (int r = 0; r < 4 * PH; ++r) {
-          for (int k = 0; k < PH; ++k) {
-            wih_x[o + (size_t)k * 4 * PH + r] = wi->data[(size_t)r * PH + k];
-            whh_x[o + (size_t)k * 4 * PH + r] = wh->data[(size_t)r * PH + k];
-          }
-          bias_x[(size_t)(l - 1) * 4 * PH + r] = bi->data[r] + bh->data[r];
-        }
-      }
-      UP(h->lstm_wih_x, wih_x);
-      UP(h->lstm_whh_x, whh_x);
-      UP(h->lstm_bias_x, bias_x);
-    }
-    UP(h->lstm_whh_q, whh_q);
-    UP(h->jn_pred_q, wp_q);
-    UP(h->lstm_tab, tab);
-    UP(h->lstm_whh_t, whh_t);
-    UP(h->jn_pred_t, wp_t);
-    UP(h->jn_pred_b, bp->data);
-    UP(h->jn_pred_w, wp->data);
-    UP(h->jn_enc_w, we->data);
-    UP(h->jn_enc_b, bee->data);
-    UP(h->jn_out_w, wo->data);
-    UP(h->jn_out_b, bo->data);
-  }
-  HIPCHK(h, hipMalloc(&h->range_flag, 64));
-  HIPCHK(h, hipMemset(h->range_flag, 0, 64));
+  h->has_head = find(h, "head.decoder_layers.0.weight") != nullptr || find(h, "head.joint.enc.weight") != nullptr ||
+                (c.head_type == GAM_HEAD_EMO && find(h, "head.weight") != nullptr);
+  if (h->has_head)
+    if (int r = fin_head(h)) return r;
+  const std::vector<int> zeros(16, 0);   // the range flag: one int in a 64-byte line of its own
+  h->range_flag = (int*)dev_upload(h, zeros.data(), 64, 64);
+  if (!h->range_flag) return fail(h, -2, "device upload failed (h->range_flag)");
   h->staged.clear();
   h->finalized = true;
   return 0;
@@ -1136,14 +1160,9 @@ static int enc_plan(gam_handle* h, int B, int64_t T, int n_layers_run, const int
 // Everything the call touches exists behind this function: the stem, the layers and a capture allocate nothing.
 static int enc_workspace(gam_handle* h, const EncPlan& p, EncBufs& w) {
   const size_t B = p.B, N = p.N, D = p.D, Ta = p.Ta;
-  if (p.B > h->lens_cap) {
-    if (h->lens) HIPCHK(h, hipFree(h->lens));
-    h->lens = nullptr;
-    HIPCHK(h, hipMalloc(&h->lens, (size_t)4 * B * sizeof(int)));
-    h->lens_cap = p.B;
-    ++h->ws_generation;   // captured graphs hold the old pointer
-  }
-  w.len0 = h->lens; w.len1 = h->lens + h->lens_cap; w.len2 = h->lens + 2 * h->lens_cap; w.elen = h->lens + 3 * h->lens_cap;
+  if (int r = ensure(h, h->lens, 4 * B)) return r;
+  const size_t maxB = h->lens.cap / 4;
+  w.len0 = h->lens.as<int>(); w.len1 = w.len0 + maxB; w.len2 = w.len0 + 2 * maxB; w.elen = w.len0 + 3 * maxB;
   if (int r = ensure(h, h->x, N * D)) return r;
   if (int r = ensure(h, h->y, N * D)) return r;
   if (int r = ensure(h, h->yr, N * D)) return r;
@@ -1825,23 +1844,15 @@ int gam_set_keywords(gam_handle* h, const int32_t* tokens, const int32_t* offset
   if (n_keywords == 0) {
     h->kw_K = h->kw_ntok = 0;
     h->kw_max_tok = -1;
-    if (h->kw_dev) HIPCHK(h, hipFree(h->kw_dev));
-    h->kw_dev = nullptr;
-    h->kw_cap = 0;
+    HIPCHK(h, h->kw_dev.release());
     return 0;
   }
   std::vector<int> flat((size_t)n_keywords + 1 + ntok + n_keywords);
   memcpy(flat.data(), offsets, ((size_t)n_keywords + 1) * sizeof(int));
   memcpy(flat.data() + n_keywords + 1, tokens, (size_t)ntok * sizeof(int));
   memcpy(flat.data() + n_keywords + 1 + ntok, min_score, (size_t)n_keywords * sizeof(float));
-  if (flat.size() > h->kw_cap) {
-    if (h->kw_dev) HIPCHK(h, hipFree(h->kw_dev));
-    h->kw_dev = nullptr;
-    h->kw_cap = 0;
-    HIPCHK(h, hipMalloc(&h->kw_dev, flat.size() * sizeof(int)));
-    h->kw_cap = flat.size();
-  }
-  HIPCHK(h, hipMemcpy(h->kw_dev, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (int r = ensure_table(h, h->kw_dev, flat.size())) return r;
+  HIPCHK(h, hipMemcpy(h->kw_dev.p, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
   h->kw_K = n_keywords;
   h->kw_ntok = ntok;
   h->kw_max_tok = max_tok;
@@ -1854,7 +1865,7 @@ static int ctc_kws_check(gam_handle* h, int B, int64_t Tp, int V, int max_hits, 
   if (Tp > GAM_KWS_MAX_T) return fail(h, -1, "keyword search: T'=%lld frames exceed the limit %d", (long long)Tp, GAM_KWS_MAX_T);
   if (max_hits < 1 || max_hits > GAM_KWS_MAX_HITS)
     return fail(h, -1, "keyword search: max_hits=%d outside [1, %d]", max_hits, GAM_KWS_MAX_HITS);
-  if (!h->kw_dev || h->kw_K <= 0) return fail(h, -1, "keyword search: no keyword set (gam_set_keywords)");
+  if (!h->kw_dev.p || h->kw_K <= 0) return fail(h, -1, "keyword search: no keyword set (gam_set_keywords)");
   if (h->kw_max_tok > V - 2) return fail(h, -1, "keyword search: keyword token id %d outside [0, %d] for V=%d", h->kw_max_tok, V - 2, V);
   if ((int64_t)B * ((h->kw_K + GAM_KWS_WAVES - 1) / GAM_KWS_WAVES) > 2147483647ll)
     return fail(h, -1, "keyword search: B=%d x %d keywords exceed the grid", B, h->kw_K);
@@ -1877,7 +1888,7 @@ static int ctc_kws_launch(gam_handle* h, const float* lp, const int32_t* enc_len
   const int K = h->kw_K;
   GamKwsArgs a;
   a.lp = lp; a.enc_len = enc_len; a.mb = reinterpret_cast<const float2*>(h->kws_mb.p);
-  a.kw_off = h->kw_dev; a.kw_tok = h->kw_dev + K + 1; a.kw_min = reinterpret_cast<const float*>(h->kw_dev + K + 1 + h->kw_ntok);
+  a.kw_off = h->kw_dev.as<int>(); a.kw_tok = a.kw_off + K + 1; a.kw_min = reinterpret_cast<const float*>(a.kw_tok + h->kw_ntok);
   a.B = B; a.Tp = (int)Tp; a.V = V; a.K = K; a.max_hits = max_hits;
   a.hit_frames = hit_frames; a.hit_score = hit_score; a.n_hits = n_hits; a.dense_score = dense_score; a.dense_start = dense_start;
   ProfScope ps(h, s, GAM_PF_DECODE, (double)rows * K * 64.0 * 4.0);
@@ -1909,14 +1920,14 @@ int gam_op_ctc_kws(gam_handle* h, const float* log_probs, const int32_t* enc_len
 // ---- what the two beam searches share (gam_search.h): the handle's hotwords and LM as kernel arguments, the common checks, the launch
 static GamHwArgs hw_args(const gam_handle* h, bool hw_lds) {
   GamHwArgs a;
-  a.trie = h->hw_trie; a.nodes = h->hw_nodes; a.words = h->hw_words; a.lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
+  a.trie = h->hw_trie.as<int>(); a.nodes = h->hw_nodes; a.words = h->hw_words; a.lds = hw_lds ? 1 : 0; a.beta = h->hw_boost;
   return a;
 }
 static GamLmArgs lm_args(const gam_handle* h) {
   GamLmArgs a;
-  a.lm_cls = h->lm_cls;
-  a.lm_wt = reinterpret_cast<const uint4*>(h->lm_wt);
-  a.lm_ng = reinterpret_cast<const uint4*>(h->lm_ng);
+  a.lm_cls = h->lm_cls.as<int>();
+  a.lm_wt = h->lm_wt.as<const uint4>();
+  a.lm_ng = h->lm_ng.as<const uint4>();
   a.lm_wmask = h->lm_wslots - 1; a.lm_wprobe = h->lm_wprobe; a.lm_nmask = h->lm_nslots - 1; a.lm_nprobe = h->lm_nprobe;
   a.lm_m = h->lm_order - 1; a.lm_bos = h->lm_bos; a.lm_eos = h->lm_eos; a.lm_unk = h->lm_unk;
   a.lm_unk_logp = h->lm_unk_logp; a.lm_alpha = h->lm_alpha; a.lm_beta = h->lm_beta;
@@ -1927,9 +1938,9 @@ static GamLmArgs lm_args(const gam_handle* h) {
 static int beam_check(gam_handle* h, const char* name, int W, int V, bool null_buffer, const char* lm_fmt) {
   if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "%s: beam width W=%d outside [1, %d]", name, W, GAM_BEAM_MAX_W);
   if (null_buffer) return fail(h, -1, "%s: NULL buffer", name);
-  if (h->hw_trie && h->hw_max_tok > V - 2)
+  if (h->hw_trie.p && h->hw_max_tok > V - 2)
     return fail(h, -1, "%s: hotword token id %d outside [0, %d] for V=%d", name, h->hw_max_tok, V - 2, V);
-  if (h->lm_ng && h->lm_V != V) return fail(h, -1, lm_fmt, h->lm_V, V);
+  if (h->lm_ng.p && h->lm_V != V) return fail(h, -1, lm_fmt, h->lm_V, V);
   return 0;
 }
 // The N-best calls' own check (n_hyp != NULL marks an N-best call): 1 <= N <= W <= 32.
@@ -1960,8 +1971,8 @@ static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_le
   if (nbest)
     if (int r = nbest_check(h, "CTC beam search", W, N, n_hyp)) return r;
   const int K = std::min(W, V - 1);
-  const bool lm = h->lm_ng != nullptr;
-  const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
+  const bool lm = h->lm_ng.p != nullptr;
+  const bool hw_lds = h->hw_trie.p && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
   const size_t sm = gam_beam_lds_bytes(W, K, V, hw_lds ? h->hw_words : 0, lm);
   if (int r = ensure(h, h->beam_nodes, (size_t)B * Tp * W * 2 + 64)) return r;
   GamBeamArgs a;
@@ -2064,19 +2075,11 @@ int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offset
   if (n_phrases == 0) {
     h->hw_nodes = h->hw_words = 0;
     h->hw_max_tok = -1;
-    if (h->hw_trie) HIPCHK(h, hipFree(h->hw_trie));
-    h->hw_trie = nullptr;
-    h->hw_cap = 0;
+    HIPCHK(h, h->hw_trie.release());
     return 0;
   }
-  if (flat.size() > h->hw_cap) {
-    if (h->hw_trie) HIPCHK(h, hipFree(h->hw_trie));
-    h->hw_trie = nullptr;
-    h->hw_cap = 0;
-    HIPCHK(h, hipMalloc(&h->hw_trie, flat.size() * sizeof(int)));
-    h->hw_cap = flat.size();
-  }
-  HIPCHK(h, hipMemcpy(h->hw_trie, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (int r = ensure_table(h, h->hw_trie, flat.size())) return r;
+  HIPCHK(h, hipMemcpy(h->hw_trie.p, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
   h->hw_nodes = nn;
   h->hw_words = (int)flat.size();
   h->hw_max_tok = max_tok;
@@ -2084,12 +2087,8 @@ int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offset
   return 0;
 }
 
-static void lm_free(gam_handle* h) {
-  if (h->lm_cls) (void)hipFree(h->lm_cls);
-  if (h->lm_wt) (void)hipFree(h->lm_wt);
-  if (h->lm_ng) (void)hipFree(h->lm_ng);
-  h->lm_cls = nullptr;
-  h->lm_wt = h->lm_ng = nullptr;
+static void lm_clear(gam_handle* h) {
+  h->lm_cls = DevBuf(); h->lm_wt = DevBuf(); h->lm_ng = DevBuf();   // (the tables they held are freed)
   h->lm_V = 0;
 }
 
@@ -2117,18 +2116,17 @@ int gam_set_lm(gam_handle* h, const int32_t* token_class, int V, const void* wor
   HIPCHK(h, hipSetDevice(h->device));
   // a decode-class kernel still in flight may read the current tables
   if (h->dec_evt != nullptr && h->dec_evt_set) HIPCHK(h, hipEventSynchronize(h->dec_evt));
-  lm_free(h);
+  lm_clear(h);
   if (ngram_slots == 0) return 0;
   const size_t wb = (size_t)word_slots * 16, nbytes = (size_t)ngram_slots * 16;
-  if (hipMalloc(&h->lm_cls, (size_t)V * sizeof(int)) != hipSuccess || hipMalloc(&h->lm_wt, wb) != hipSuccess ||
-      hipMalloc(&h->lm_ng, nbytes) != hipSuccess) {
-    lm_free(h);
+  if (h->lm_cls.alloc((size_t)V) != hipSuccess || h->lm_wt.alloc(wb / 4) != hipSuccess || h->lm_ng.alloc(nbytes / 4) != hipSuccess) {
+    lm_clear(h);
     return fail(h, -1, "LM: cannot allocate %zu bytes of device tables", (size_t)V * 4 + wb + nbytes);
   }
-  if (hipMemcpy(h->lm_cls, token_class, (size_t)V * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->lm_wt, word_table, wb, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->lm_ng, ngram_table, nbytes, hipMemcpyHostToDevice) != hipSuccess) {
-    lm_free(h);
+  if (hipMemcpy(h->lm_cls.p, token_class, (size_t)V * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->lm_wt.p, word_table, wb, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->lm_ng.p, ngram_table, nbytes, hipMemcpyHostToDevice) != hipSuccess) {
+    lm_clear(h);
     return fail(h, -1, "LM: copying the tables to the device failed");
   }
   h->lm_V = V;
@@ -2317,13 +2315,13 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
     return r;
   if (nbest)
     if (int r = nbest_check(h, "RNN-T beam search", W, N, n_hyp)) return r;
-  const bool lm = h->lm_ng != nullptr;
+  const bool lm = h->lm_ng.p != nullptr;
   const int K = std::min(W, V - 1);
   const size_t base = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, 0, lm ? V : 0);
   if (base > 160 * 1024)
     return fail(h, -1, "RNN-T beam search: W=%d, S=%d, H=%d, L=%d%s need %zu bytes of LDS (> 160 KiB)", W, max_symbols, H, L,
                 lm ? " with the LM" : "", base);
-  const bool hw_lds = h->hw_trie && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX && base + (size_t)h->hw_words * 4 <= 160 * 1024;
+  const bool hw_lds = h->hw_trie.p && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX && base + (size_t)h->hw_words * 4 <= 160 * 1024;
   const size_t sm = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, hw_lds ? h->hw_words : 0, lm ? V : 0);
   const size_t per = (gam_rb_ws_floats(W, max_symbols, V, H, JH, L) + 63) & ~(size_t)63;
   if (int r = ensure(h, h->rb_ws, per * B + 64)) return r;
