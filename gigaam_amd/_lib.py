@@ -70,6 +70,8 @@ SIGNATURES = {
     "gam_ctc_align_star": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_align_star": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_align_long_star": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gam_op_ctc_stitch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "gam_op_ctc_greedy_long": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
     "gam_set_ctc_align_workspace": (C.c_int, [_P, C.c_int64]),
     "gam_tune_ctc_align_long": (C.c_int, [C.c_int, C.c_int]),
     "gam_ctc_kws": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),

@@ -35,6 +35,7 @@
 #include "gam_pack.h"
 #include "gam_resample.h"
 #include "gam_stem.h"
+#include "gam_stitch.h"
 
 namespace {
 
@@ -156,6 +157,7 @@ struct gam_handle {
   DevBuf align_star;                    // wildcard emissions of gam_ctc_align_star, B x T' floats (gam_ctc_star_row_kernel)
   DevBuf align_bp;                      // CTC alignment backpointers when they do not fit the kernel's LDS (gam_align.h)
   DevBuf align_long_ws;                 // long-utterance CTC alignment (gam_align_long.h): backpointers | edges | rows | offsets | path | ctrl
+  DevBuf greedy_long_ws;                // long-utterance CTC greedy decode (gam_stitch.h): labels [T] | block counts -> offsets, as ints
   size_t al_ws_limit = GAM_AL_WS_DEFAULT;   // bytes that workspace may take (gam_set_ctc_align_workspace; GAM_CTC_ALIGN_WS at gam_create)
   DevBuf beam_nodes;                    // CTC beam search prefix-trie nodes, B x T' x W (gam_beam.h)
   DevBuf rb_ws, rb_nodes;               // RNN-T beam search: predictor-state slots + logit rows, prefix-trie nodes (gam_rnnt_beam.h)
@@ -1795,6 +1797,50 @@ int gam_op_ctc_align_long_star(gam_handle* h, const float* log_probs, int64_t T,
   if (T > 0 && !star_lp) return fail(h, -1, "long CTC alignment: NULL buffer");
   return ctc_align_long_launch(h, log_probs, T, V, true, star_lp, targets, U, frame_labels, tok_first, tok_last, score, loglik,
                                status, s);
+}
+
+// Windowed longform (gam_stitch.h).  Decode class both; neither synchronises with the host.
+int gam_op_ctc_stitch(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* lo,
+                      const int32_t* hi, const int64_t* dst, float* out, int64_t T_total, int32_t* status, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (B < 1 || B > 65535 || Tp < 1 || Tp > 2147483647ll || V < 1 || T_total < 0)
+    return fail(h, -1, "CTC stitch: bad shape B=%d T'=%lld V=%d T_total=%lld", B, (long long)Tp, V, (long long)T_total);
+  if (!log_probs || !enc_len || !lo || !hi || !dst || !status || (T_total > 0 && !out)) return fail(h, -1, "CTC stitch: NULL buffer");
+  GamStitchArgs a;
+  a.lp = log_probs; a.enc_len = enc_len; a.lo = lo; a.hi = hi; a.dst = reinterpret_cast<const long long*>(dst); a.out = out; a.status = status;
+  a.Tp = Tp; a.T_total = T_total; a.V = V;
+  // 16 floats per thread and pass at the widest access; the grid stride covers whatever the cap leaves over
+  const int64_t chunks = std::min<int64_t>(std::max<int64_t>((Tp * V + 4095) / 4096, 1), 4096);
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)B * Tp * V * 8.0);
+  hipLaunchKernelGGL(gam_ctc_stitch_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int gam_op_ctc_greedy_long(gam_handle* h, const float* log_probs, int64_t T, int V, int32_t* ids, int32_t* frames, int32_t* count,
+                           void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (T < 0 || T > 2147483647ll || V < 2 || V > GAM_BEAM_MAX_V)
+    return fail(h, -1, "long CTC greedy decode: bad shape T=%lld V=%d (2 <= V <= %d)", (long long)T, V, GAM_BEAM_MAX_V);
+  if (!count || (T > 0 && (!log_probs || !ids || !frames))) return fail(h, -1, "long CTC greedy decode: NULL buffer");
+  const bool per_thread = V <= 64 && (V & 1) == 0;      // the two argmax forms of gam_ctc_greedy_kernel
+  const int fb = per_thread ? GAM_GL_FB : GAM_GL_FBW;
+  const int nblk = (int)((T + fb - 1) / fb);
+  if (int r = ensure(h, h->greedy_long_ws, (size_t)T + (size_t)nblk + 64)) return r;
+  int* lab = h->greedy_long_ws.as<int>();
+  int* blk = lab + T;
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)T * V * 4.0);
+  if (nblk > 0) {
+    if (per_thread) hipLaunchKernelGGL(gam_ctc_greedy_long_labels_kernel<GAM_GL_FB>, dim3(nblk), dim3(GAM_GL_FB), 0, s, log_probs, (long long)T, V, lab, blk);
+    else hipLaunchKernelGGL(gam_ctc_greedy_long_labels_kernel<GAM_GL_FBW>, dim3(nblk), dim3(GAM_GL_FB), 0, s, log_probs, (long long)T, V, lab, blk);
+  }
+  hipLaunchKernelGGL(gam_ctc_greedy_long_scan_kernel, dim3(1), dim3(GAM_GL_SCAN_NT), 0, s, blk, nblk, count);
+  if (nblk > 0) {
+    if (per_thread) hipLaunchKernelGGL(gam_ctc_greedy_long_compact_kernel<GAM_GL_FB>, dim3(nblk), dim3(GAM_GL_FB), 0, s, lab, blk, (long long)T, ids, frames);
+    else hipLaunchKernelGGL(gam_ctc_greedy_long_compact_kernel<GAM_GL_FBW>, dim3(nblk), dim3(GAM_GL_FBW), 0, s, lab, blk, (long long)T, ids, frames);
+  }
+  HIPCHK(h, hipGetLastError());
+  return 0;
 }
 
 int gam_set_ctc_align_workspace(gam_handle* h, int64_t bytes) {

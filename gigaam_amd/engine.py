@@ -826,6 +826,37 @@ class HipEngine:
                 self._check(rc, "gam_op_ctc_align_long_star")
             return self._finish(out, consume_flag)
 
+    def op_ctc_stitch(self, log_probs: Tensor, enc_len: Tensor, lo: Tensor, hi: Tensor, dst: Tensor, out: Tensor) -> Tensor:
+        """gam_op_ctc_stitch: rows ``lo[b] <= t < min(hi[b], enc_len[b])`` of every utterance of log_probs f32 [B, T', V] go to
+        ``out[dst[b] + t - lo[b]]`` (f32 [T_total, V] on the device, written in place), bit for bit; no host sync.  ``lo`` / ``hi`` i32
+        [B], ``dst`` i64 [B].  Returns status i32 [B] on the device: 1 where nothing was clipped and the rows fit ``out``."""
+        log_probs, enc_len, b, tp, v = self._in_log_probs(log_probs, enc_len)
+        lo, hi, dst = self._dev(lo, torch.int32), self._dev(hi, torch.int32), self._dev(dst, torch.int64)
+        if not (lo.numel() == hi.numel() == dst.numel() == enc_len.numel() == b):
+            raise GigaAMHipError(f"enc_len / lo / hi / dst must hold {b} entries each")
+        if (not out.is_cuda or out.device != self.device or out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != v
+                or not out.is_contiguous()):
+            raise GigaAMHipError(f"out must be a contiguous f32 [T_total, {v}] tensor on {self.device}")
+        status = torch.empty((b,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_ctc_stitch(self._h, _ptr(log_probs), _ptr(enc_len), b, tp, v, _ptr(lo), _ptr(hi), _ptr(dst), _ptr(out),
+                                            out.shape[0], _ptr(status), self._stream())
+        self._check(rc, "gam_op_ctc_stitch")
+        return status
+
+    def op_ctc_greedy_long(self, log_probs: Tensor, consume_flag: bool = False) -> Decoded:
+        """gam_op_ctc_greedy_long: the CTC greedy decode of ONE utterance of any length, log-probs f32 [T, V] (used as they are),
+        spread over the whole GPU (gam_stitch.h); no host sync.  Returns a ``Decoded`` of one row with room for T tokens:
+        ``collect`` reads it like any greedy decode.  ``consume_flag``: as ``op_ctc_align_long``."""
+        log_probs = self._dev(log_probs, torch.float32)
+        t, v = log_probs.shape
+        out = Decoded.packed(self.device, 1, t)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_ctc_greedy_long(self._h, _ptr(log_probs), t, v, _ptr(out.ids), _ptr(out.frames), _ptr(out.counts),
+                                                 self._stream())
+            self._check(rc, "gam_op_ctc_greedy_long")
+            return self._finish(out, consume_flag)
+
     def set_ctc_align_workspace(self, nbytes: int = 0) -> None:
         """Bytes of workspace ``op_ctc_align_long`` may take (gam_set_ctc_align_workspace; 0: the default, 3 GiB).  A call that needs
         more is an error that names the needed and the allowed bytes."""

@@ -780,7 +780,9 @@ class GigaAMASR(GigaAM):
     def transcribe_longform(self, wav_file: str, word_timestamps: bool = False, fr_batch_size: int = 16,
                             fr_num_workers: int = 0, *, beam_size: Optional[int] = None,
                             hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
-                            lm_weight: float = 0.5, word_bonus: float = 1.0, **kwargs: Any) -> LongformTranscriptionResult:
+                            lm_weight: float = 0.5, word_bonus: float = 1.0, chunk_length_s: float = 20.0,
+                            stride_length_s: Optional[float] = None, pause_s: float = 1.0, max_segment_s: float = 22.0,
+                            **kwargs: Any) -> LongformTranscriptionResult:
         """Segment -> zero-padded batches of ``fr_batch_size`` -> transcribe -> stitch
         (reference model.py:195-259).  The reference segments with pyannote's VAD
         (gated third-party model, not installable here); pass ``speech_regions=[(s,e),..]``,
@@ -793,7 +795,20 @@ class GigaAMASR(GigaAM):
         double-buffered ``feeder.BatchFeeder`` (one staging thread is enough to keep the GPU busy).
 
         ``beam_size`` / ``hotwords`` / ``hotword_boost`` / ``lm`` / ``lm_weight`` / ``word_bonus``: as for ``transcribe`` (CTC prefix
-        beam search on every chunk; each chunk starts its own LM history at <s>)."""
+        beam search on every chunk; each chunk starts its own LM history at <s>).
+
+        ``vad="windows"`` (CTC heads) needs no speech detector: the recording is cut into overlapping windows of ``chunk_length_s``
+        seconds, ``stride_length_s`` seconds (default: a sixth of the chunk) at each inner window edge are dropped, and what is left is
+        decoded as ONE utterance (``_transcribe_windows``); ``pause_s`` / ``max_segment_s`` cut its words into segments."""
+        if isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows":
+            if beam_size is not None or hotwords is not None or lm is not None:
+                raise ValueError('vad="windows" decodes greedily: the beam kernel stops at 8192 frames, so beam_size / hotwords / lm over '
+                                 "the stitched stream are not available")
+            if set(kwargs) - {"vad"}:
+                raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(set(kwargs) - {"vad"})}): there are no speech '
+                                 "regions to give or to pack")
+            return self._transcribe_windows(wav_file, word_timestamps, fr_batch_size, chunk_length_s, stride_length_s, pause_s,
+                                            max_segment_s)
         from .vad_utils import segment_audio_file
 
         beam_kw = {} if self._beam_width(beam_size, hotwords, lm) is None else dict(beam_size=beam_size, hotwords=hotwords,
@@ -841,9 +856,141 @@ class GigaAMASR(GigaAM):
             eng.range_flag()     # a flag left behind by earlier direct engine use must not cost this file an fp32 rerun
         return LongformTranscriptionResult(segments=self._with_f32_fallback(run, "the file was"))
 
+    # ---- longform without a speech detector: overlapping windows stitched on the device (windows.py, gam_stitch.h)
+    def _plan_windows(self, wav_file: str, chunk_length_s: float, stride_length_s: Optional[float]):
+        """(the file's samples as one CPU tensor, the window plan): every error that needs no GPU work is raised here."""
+        from .windows import plan_windows
+
+        if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
+            raise TypeError("windowed longform needs a CTC head")
+        eng = self.head.engine
+        audio = load_audio(wav_file, SAMPLE_RATE)
+        frame_samples = int(eng.cfg.hop_length) * int(eng.cfg.subsampling_factor)
+        return audio, plan_windows(int(audio.shape[0]), frame_samples, lambda n: eng.enc_frames(eng.feat_frames(n)), chunk_length_s,
+                                   stride_length_s, SAMPLE_RATE)
+
+    def _stitched_log_probs(self, audio: Tensor, plan, fr_batch_size: int) -> Tuple[Tensor, Tensor]:
+        """The windows of ``plan`` (views of ``audio``) through the feeder, the encoder (packed rows: host lengths) and the CTC head,
+        batch by batch; each batch's kept frames go straight into one preallocated [T_total, V] buffer (gam_op_ctc_stitch).  The window
+        tables are uploaded once, nothing is read back.  Returns (the stream, the stitch statuses i32 [windows]), both on the device."""
+        from .feeder import BatchFeeder
+
+        eng, dev, ws = self.head.engine, self._device, plan.windows
+        lo = torch.tensor([w.lo for w in ws], dtype=torch.int32).to(dev)
+        hi = torch.tensor([w.hi for w in ws], dtype=torch.int32).to(dev)
+        dst = torch.tensor([w.dst for w in ws], dtype=torch.int64).to(dev)
+        out = torch.empty((plan.t_total, int(eng.cfg.num_classes)), dtype=torch.float32, device=dev)
+        status: List[Tensor] = []
+        feeder = BatchFeeder([audio[w.start:w.stop] for w in ws], fr_batch_size, dev)
+        o = 0
+        for wav, lens in feeder:
+            b = wav.shape[0]
+            encoded, encoded_len = self._encode(wav, lens, getattr(feeder, "host_lengths", None))
+            status.append(eng.op_ctc_stitch(eng.ctc_head(encoded), encoded_len, lo[o:o + b], hi[o:o + b], dst[o:o + b], out))
+            o += b
+        return out, torch.cat(status)
+
+    @staticmethod
+    def _check_stitch(status: Tensor) -> None:
+        if not bool(status.cpu().all()):
+            raise GigaAMHipError("windowed longform: the host length formula and the device disagree on a window's encoder frames "
+                                 f"(stitch statuses {status.cpu().tolist()})")
+
+    def _transcribe_windows(self, wav_file: str, word_timestamps: bool, fr_batch_size: int, chunk_length_s: float,
+                            stride_length_s: Optional[float], pause_s: float, max_segment_s: float) -> LongformTranscriptionResult:
+        """``transcribe_longform(vad="windows")``: plan -> stitched log-probs -> gam_op_ctc_greedy_long -> ONE collect.  Words follow
+        ``frames_to_words``' rule on file times (each time taken in the window its frame was kept from, rounded to 3 decimals);
+        segments are runs of words (windows.segment_words).  The defaults of ``stride_length_s``, ``pause_s`` and ``max_segment_s``
+        are conventions, not measurements."""
+        from .decoding import RangeOverflow
+        from .timestamps_utils import longform_words
+        from .windows import segment_words
+
+        audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
+        if not plan.windows:
+            return LongformTranscriptionResult(segments=[])
+        eng = self.head.engine
+
+        def run():
+            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size)
+            rows, flag = HipEngine.collect(eng.op_ctc_greedy_long(lp_all, consume_flag=True))
+            if flag:
+                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+            self._check_stitch(status)
+            return rows[0]
+
+        if eng.gemm_mode != "f32":
+            eng.range_flag()     # (as the other longform paths: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
+        ids, frames = self._with_f32_fallback(run, "the file was")
+        wins, local, _ = plan.locate(frames)
+        words, _ = longform_words(self.decoding.tokenizer, ids, wins, local, [(w.start_s, w.start_s) for w in plan.windows],
+                                  [w.shift for w in plan.windows])
+        return LongformTranscriptionResult(segments=[
+            Segment(text=" ".join(w.text for w in run_), start=run_[0].start, end=run_[-1].end, words=run_ if word_timestamps else None)
+            for run_ in segment_words(words, pause_s, max_segment_s)])
+
+    def _align_windows(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int, wildcard: Optional[str],
+                       wildcard_penalty: float, chunk_length_s: float, stride_length_s: Optional[float]) -> LongformAlignmentResult:
+        """``align_longform(vad="windows")``: the same plan and the same stitch, then gam_op_ctc_align_long on the stream.  A token's
+        segment is the window its frame was kept from, its frame the local frame inside that window; ``segments`` holds one Segment
+        per window over the time span of its kept frames (they tile the file) with the words that start there."""
+        from .decoding import RangeOverflow
+        from .timestamps_utils import longform_words
+
+        tok = self.decoding.tokenizer
+        if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
+            raise TypeError("windowed longform needs a CTC head")
+        (ids,), penalty = self._wildcard_setup([text], wildcard, wildcard_penalty)
+        wid = self.wildcard_id
+        text_out = tok.decode(ids) if penalty is None else _wildcard.text_of(tok, ids, wid, wildcard)
+        audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
+        if not plan.windows:
+            if ids:
+                raise ValueError(f"the recording holds no encoder frame: the text ({len(ids)} tokens) cannot be aligned to it")
+            return LongformAlignmentResult(text=text_out, words=[], token_ids=ids, token_segments=[], token_frames=[], token_times=[],
+                                           score=0.0, log_likelihood=0.0, segments=[], feasible=True)
+        eng = self.head.engine
+
+        def run():
+            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size)
+            star = None if penalty is None else eng.ctc_star_row(lp_all, None, penalty)
+            h = eng.op_ctc_align_long(lp_all, ids, consume_flag=True, star=star).host()
+            if h["flag"]:
+                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+            self._check_stitch(status)
+            return h
+
+        if eng.gemm_mode != "f32":
+            eng.range_flag()
+        try:
+            h = self._with_f32_fallback(run, "the file was")
+        except GigaAMHipError as e:
+            if "gam_set_ctc_align_workspace" in str(e):
+                raise ValueError(f"the alignment lattice does not fit the workspace cap: {e}") from e
+            raise
+        if not h["status"]:
+            raise ValueError(f"the text ({len(ids)} tokens) cannot be aligned to this audio: too long for its {plan.t_total} frames")
+        token_segments, token_frames, token_times = plan.locate(h["tok_first"].tolist())
+        origins = [(w.start_s, w.start_s) for w in plan.windows]      # a local frame's time counts from its window's start
+        shifts = [w.shift for w in plan.windows]
+        spans = [(round(a, 3), round(b, 3)) for a, b in plan.spans()]
+        gaps = None
+        if penalty is None:
+            words, segs = longform_words(tok, ids, token_segments, token_frames, origins, shifts)
+        else:
+            last_segments, last_frames, _ = plan.locate(h["tok_last"].tolist())
+            words, segs, gaps = _wildcard.longform_result(tok, ids, token_segments, token_frames, last_segments, last_frames, origins,
+                                                          shifts, wid)
+        segs = [Segment(text=sg.text, start=a, end=b, words=sg.words) for sg, (a, b) in zip(segs, spans)]
+        more = {} if gaps is None else {"gaps": gaps}
+        return LongformAlignmentResult(text=text_out, words=words, token_ids=ids, token_segments=token_segments,
+                                       token_frames=token_frames, token_times=token_times, score=h["score"],
+                                       log_likelihood=h["loglik"], segments=segs, feasible=True, **more)
+
     @torch.inference_mode()
     def align_longform(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int = 16, wildcard: Optional[str] = None,
-                       wildcard_penalty: float = _wildcard.DEFAULT_PENALTY, **kwargs: Any) -> LongformAlignmentResult:
+                       wildcard_penalty: float = _wildcard.DEFAULT_PENALTY, chunk_length_s: float = 20.0,
+                       stride_length_s: Optional[float] = None, **kwargs: Any) -> LongformAlignmentResult:
         """Align ``text`` (a string in the model's vocabulary, or token ids) to a recording of any length: forced alignment of the
         WHOLE text against the WHOLE recording (``align`` stops at 25 s and 1024 tokens).  Segmentation keywords as for
         ``transcribe_longform`` (``speech_regions=``, ``vad=``, the pack_regions keywords; the same pyannote / EnergyVAD default).
@@ -860,7 +1007,16 @@ class GigaAMASR(GigaAM):
 
         Raises ``ValueError`` for characters outside the vocabulary, for a text that no alignment fits into the speech found, for a
         non-empty text when no speech was found, and for a lattice beyond the workspace cap (the message carries the needed and
-        the allowed bytes; ``HipEngine.set_ctc_align_workspace`` / GAM_CTC_ALIGN_WS raise it); ``TypeError`` on RNN-T models."""
+        the allowed bytes; ``HipEngine.set_ctc_align_workspace`` / GAM_CTC_ALIGN_WS raise it); ``TypeError`` on RNN-T models.
+
+        ``vad="windows"``: no speech detector -- the whole recording as overlapping windows of ``chunk_length_s`` / ``stride_length_s``
+        (as ``transcribe_longform``), stitched into one stream and aligned in one go (``_align_windows``): a token's segment is then
+        the window its frame was kept from, and ``segments`` tile the file."""
+        if isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows":
+            if set(kwargs) - {"vad"}:
+                raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(set(kwargs) - {"vad"})}): there are no speech '
+                                 "regions to give or to pack")
+            return self._align_windows(wav_file, text, fr_batch_size, wildcard, wildcard_penalty, chunk_length_s, stride_length_s)
         from .decoding import RangeOverflow
         from .feeder import BatchFeeder
         from .timestamps_utils import compute_frame_shift, concat_frames_to_segments, longform_words

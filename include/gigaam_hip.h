@@ -187,6 +187,28 @@ int gam_op_ctc_align_long_star(gam_handle* h, const float* log_probs, int64_t T,
                                int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, double* score, double* loglik,
                                int32_t* status, void* stream);
 
+/* Windowed longform (gigaam_amd/csrc/gam_stitch.h): a long recording is cut into fixed overlapping windows that are encoded as
+ * batches; the context-starved frames at each window's edges are dropped and the rest becomes ONE [T_total, V] CTC utterance.
+ * gam_op_ctc_stitch copies, for every utterance b of one batch, rows lo[b] <= t < min(hi[b], enc_len[b]) of log_probs[b] to
+ * out[dst[b] + t - lo[b]], bit for bit.  One call per batch writes into the same `out`.
+ *   log_probs f32 [B, T', V], enc_len / lo / hi i32 [B], dst i64 [B], out f32 [T_total, V], status i32 [B]: device arrays.
+ *   status[b] = 1: nothing was clipped (0 <= lo[b], hi[b] <= enc_len[b] clamped to [0, T']) and the destination rows lie inside
+ *   [0, T_total), else 0.  hi[b] <= lo[b] copies nothing and is no error (status 1).  A clipped window still copies its valid rows;
+ *   a window whose destination rows do not all fit copies nothing: no byte outside `out` is written.
+ * Rows are V contiguous floats; accesses are 16 bytes wide where the source and the destination address allow it, 8 or 4 otherwise
+ * (V = 34: rows are 8-byte aligned).  Plain vector stores, no atomics.  1 <= B <= 65535.  Decode class; no host synchronisation. */
+int gam_op_ctc_stitch(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* lo,
+                      const int32_t* hi, const int64_t* dst, float* out, int64_t T_total, int32_t* status, void* stream);
+/* CTCGreedyDecoding.decode of ONE utterance of any length 0 <= T < 2^31 from caller-supplied log-probs f32 [T, V] (read as they are),
+ * spread over the whole GPU: the semantics of gam_ctc_greedy's kernel -- blank = V - 1, per-frame argmax with torch's first-maximum
+ * tie rule, frame t kept iff label[t] != blank && (t == 0 || label[t] != label[t - 1]), outputs in frame order -- as three plain
+ * launches on the stream (labels + per-block keep counts, a scan of the block counts, compaction); no workgroup waits on another.
+ *   ids / frames i32 [T] (the first count[0] entries are written), count i32 [1].  T = 0 gives count = 0.
+ * 2 <= V <= 1025 (an error otherwise, without a launch).  The workspace (T + T / 128 ints at most) is the handle's.  Decode class; no host
+ * synchronisation (workspace growth aside). */
+int gam_op_ctc_greedy_long(gam_handle* h, const float* log_probs, int64_t T, int V, int32_t* ids, int32_t* frames, int32_t* count,
+                           void* stream);
+
 /* Keyword search over the CTC posteriors (gigaam_amd/csrc/gam_kws.h holds the contract): for every (utterance, keyword) pair, where
  * the keyword occurs and how well it scores.  Runs the CTC head, its log-softmax, a row-maximum pre-pass and ONE search kernel (a
  * wave per pair: a CTC Viterbi over the keyword's tokens with a free start and a free end, blank = V - 1).  Emissions are
