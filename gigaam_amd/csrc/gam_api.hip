@@ -536,6 +536,25 @@ struct DecodeScope {
   HIPCHK(h, hipSetDevice((h)->device));  \
   DecodeScope ds(h, s)
 
+// The head precondition of an entry point, made BEFORE GAM_DECODE_ENTRY (a refused call opens no DecodeScope): the handle is finalized
+// (`who` opens that message; NULL: the entry point does not ask) and carries the head `want` (GAM_HEAD_CTC / _RNNT / _EMO).
+int head_check(gam_handle* h, int want, const char* who) {
+  if (!h) return -1;
+  if (who && !h->finalized) return fail(h, -1, "%s before gam_finalize", who);
+  if (h->cfg.head_type != want || !h->has_head)
+    return fail(h, -1, "model has no %s head", want == GAM_HEAD_CTC ? "CTC" : want == GAM_HEAD_RNNT ? "RNN-T" : "emotion");
+  return 0;
+}
+
+// The RNN-T head's weights as kernel arguments: the predictor's, the joint's.  For every argument struct that names these fields (the
+// structs' layouts are their kernels' own).
+template <class Args> void rnnt_pred_weights(const gam_handle* h, Args& a) {
+  a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x; a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x;
+}
+template <class Args> void rnnt_joint_weights(const gam_handle* h, Args& a) {
+  a.wpred_t = h->jn_pred_t; a.bpred = h->jn_pred_b; a.wout = h->jn_out_w; a.bout = h->jn_out_b;
+}
+
 }  // namespace
 
 // ===================================================================================
@@ -1546,9 +1565,8 @@ static int to_tokens(gam_handle* h, const float* encoded, int B, int64_t Tp, hip
   return 0;
 }
 
+// The CTC head's logits [B * Tp, V] into h->logits.  The caller has made the head check (head_check).
 static int ctc_logits(gam_handle* h, const float* encoded, int B, int64_t Tp, hipStream_t s) {
-  if (!h || !h->finalized) return fail(h, -1, "CTC head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_CTC || !h->has_head) return fail(h, -1, "model has no CTC head");
   if (B <= 0 || Tp <= 0) return fail(h, -1, "bad shape B=%d T'=%lld", B, (long long)Tp);
   HIPCHK(h, hipSetDevice(h->device));
   const int D = h->cfg.d_model, V = h->cfg.num_classes;
@@ -1579,12 +1597,14 @@ static int ctc_log_probs(gam_handle* h, const float* encoded, int B, int64_t Tp,
 }
 
 int gam_ctc_head(gam_handle* h, const float* encoded, int B, int64_t Tp, float* log_probs, void* stream) {
+  if (int r = head_check(h, GAM_HEAD_CTC, "CTC head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   return ctc_log_probs(h, encoded, B, Tp, log_probs, s);
 }
 
 int gam_ctc_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int32_t* ids,
                    int32_t* frames, int32_t* counts, void* stream) {
+  if (int r = head_check(h, GAM_HEAD_CTC, "CTC head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   if (int r = ctc_logits(h, encoded, B, Tp, s)) return r;
   const int V = h->cfg.num_classes;
@@ -1643,6 +1663,7 @@ static int ctc_align_launch(gam_handle* h, const float* lp, const int32_t* enc_l
 int gam_ctc_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
                   const int32_t* target_len, int Umax, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last, float* score,
                   float* loglik, int32_t* status, void* stream) {
+  if (int r = head_check(h, GAM_HEAD_CTC, "CTC head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   if (Tp > GAM_ALIGN_MAX_T || Umax < 0 || Umax > GAM_ALIGN_MAX_U)
     return fail(h, -1, "CTC alignment: T'=%lld / Umax=%d beyond the limits (%d / %d)", (long long)Tp, Umax, GAM_ALIGN_MAX_T, GAM_ALIGN_MAX_U);
@@ -1690,6 +1711,7 @@ int gam_op_ctc_star_row(gam_handle* h, const float* log_probs, const int32_t* en
 int gam_ctc_align_star(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
                        const int32_t* target_len, int Umax, float penalty, int32_t* frame_labels, int32_t* tok_first, int32_t* tok_last,
                        float* score, float* loglik, int32_t* status, void* stream) {
+  if (int r = head_check(h, GAM_HEAD_CTC, "CTC head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   if (Tp > GAM_ALIGN_MAX_T || Umax < 0 || Umax > GAM_ALIGN_MAX_U)
     return fail(h, -1, "CTC alignment: T'=%lld / Umax=%d beyond the limits (%d / %d)", (long long)Tp, Umax, GAM_ALIGN_MAX_T, GAM_ALIGN_MAX_U);
@@ -1947,9 +1969,8 @@ static int ctc_kws_launch(gam_handle* h, const float* lp, const int32_t* enc_len
 
 int gam_ctc_kws(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int max_hits, int32_t* hit_frames,
                 float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream) {
+  if (int r = head_check(h, GAM_HEAD_CTC, "CTC head")) return r;
   GAM_DECODE_ENTRY(h, stream);
-  if (!h->finalized) return fail(h, -1, "CTC head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_CTC || !h->has_head) return fail(h, -1, "model has no CTC head");
   const int V = h->cfg.num_classes;
   if (int r = ctc_kws_check(h, B, Tp, V, max_hits, !encoded || !enc_len || !hit_frames || !hit_score || !n_hits)) return r;
   if (int r = ctc_log_probs(h, encoded, B, Tp, nullptr, s)) return r;
@@ -2039,6 +2060,7 @@ static int ctc_beam_launch(gam_handle* h, const float* lp, const int32_t* enc_le
 // gam_ctc_beam / gam_ctc_beam_nbest: the CTC head, its log-softmax in place, the beam kernel.
 static int ctc_beam_run(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int32_t* ids, int32_t* frames,
                         int32_t* counts, float* score, float* logp, void* stream, bool nbest, int N, int32_t* n_hyp) {
+  if (int r = head_check(h, GAM_HEAD_CTC, "CTC head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   if (Tp > GAM_ALIGN_MAX_T || W < 1 || W > GAM_BEAM_MAX_W)
     return fail(h, -1, "CTC beam search: T'=%lld / W=%d beyond the limits (%d / [1, %d])", (long long)Tp, W, GAM_ALIGN_MAX_T, GAM_BEAM_MAX_W);
@@ -2212,132 +2234,175 @@ static int audit_dump(gam_handle* h) {
   }
   return 0;
 }
+// diagnosis build: report the previous decode's log, then clear it and hand it to this launch
+static int rnnt_audit_arm(gam_handle* h, hipStream_t s, GamRnntClusterArgs& ca) {
+  if (int r = audit_dump(h)) return r;
+  h->audit_pending = true; h->audit_last_c = ca.C;
+  if (int r = ensure(h, h->rnnt_audit, 16 + 12 * GAM_RC_AUDIT_CAP)) return r;
+  HIPCHK(h, hipMemsetAsync(h->rnnt_audit.p, 0, 64, s));
+  ca.audit = reinterpret_cast<int*>(h->rnnt_audit.p);
+  return 0;
+}
 #endif
+
+// ---- RNN-T greedy decode: the argument block, the cluster plan, the kernel table, the two launches, the entry point
+static GamRnntArgs rnnt_greedy_args(const gam_handle* h, const int32_t* enc_len, int B, int64_t Tp, int max_symbols, int32_t* ids,
+                                    int32_t* frames, int32_t* counts, float* logits_dump, int32_t* dump_count, int dump_cap) {
+  const gam_config& c = h->cfg;
+  GamRnntArgs a;
+  memset(&a, 0, sizeof a);
+  rnnt_pred_weights(h, a);
+  rnnt_joint_weights(h, a);
+  a.encp = h->encp.p; a.enc_len = enc_len; a.ids = ids; a.frames = frames; a.counts = counts;
+  a.dump = logits_dump; a.dump_count = dump_count; a.dump_cap = logits_dump ? dump_cap : 0;
+  a.B = B; a.Tp = (int)Tp; a.V = c.num_classes; a.H = c.pred_hidden; a.JH = c.joint_hidden; a.L = c.pred_rnn_layers;
+  a.max_symbols = max_symbols; a.cap = (int)Tp * max_symbols;
+  return a;
+}
+
+// What the cluster decode (gam_decode_cluster.h) does with a shape: C workgroups per utterance in 8 utterance columns (one per XCD; the C
+// members of a cluster share an XCD), grid <= one workgroup per CU.  C = 0 (and nothing else set): the one-workgroup kernel decodes it.
+struct RnntClusterPlan {
+  int C;                    // workgroups per utterance
+  int need, nr;             // gate-row slots a thread needs (4 * ceil(H / C) rows over 256 threads), and the kernel's NR that holds them
+  bool resident;            // W_hh rows register-resident (gam_decode_cluster.h RESQ)
+  bool h320;                // H = JH = 320 at compile time (the published heads)
+  int kern;                 // index into rnnt_cluster_kern
+  int wout_slice_in_lds, wpred_slice_in_lds;
+  size_t lds;               // dynamic LDS bytes of a workgroup
+  size_t xg;                // exchange granules of the whole batch
+  unsigned grid;            // workgroups
+};
+
+// Plain values in, no HIP call.  ncu: the device's CUs; cluster: gam_handle::rnnt_cluster (-1 auto); exclusive: GAM_RNNT_EXCLUSIVE.
+static RnntClusterPlan rnnt_cluster_plan(int ncu, int cluster, int exclusive, int B, int H, int JH, int V, int L) {
+  RnntClusterPlan p = {};
+  const int nu8 = gam_cdiv(B, 8);
+  // every member of every cluster must be resident at once (they spin on each other): at most one workgroup per CU
+  // of THIS device, with a few CUs to spare; a partition with fewer CUs gets smaller clusters or the one-workgroup kernel
+  int C = std::min(8, (ncu - 16) / (8 * nu8));
+  if (cluster >= 0) C = std::min(cluster, C);
+  if (C < 1 || JH % 16 != 0 || H % 4 != 0 || L != 1) return p;   // (JH % 16: MFMA k-steps and the LDS-DMA window; L > 1: one-workgroup kernel)
+  const int need = gam_cdiv(4 * gam_cdiv(H, C), 256);
+  if (need > 8) return p;
+  static const int ladder[5] = {1, 2, 3, 5, 8};
+  int col = 0;
+  while (ladder[col] < need) ++col;
+  const int nr = ladder[col];
+  const int nV = gam_cdiv(gam_cdiv(V, C), 16) * 16;
+  const int wout = (size_t)nV * (JH + 4) * 4 + gam_rnnt_cluster_smem(H, JH, V, C, nr, 0) <= 96 * 1024 ? 1 : 0;
+  const int wpred = gam_rnnt_cluster_smem(H, JH, V, C, nr, wout, 1) <= 150 * 1024 ? 1 : 0;
+  size_t lds = gam_rnnt_cluster_smem(H, JH, V, C, nr, wout, wpred);
+  // GAM_RNNT_EXCLUSIVE=1: a decode workgroup asks for the CU's whole LDS (160 KB), so no other workgroup that uses LDS -- of this launch or
+  // of ANOTHER stream's kernel -- is placed beside it.  r05 shipped this as the protection against a perturbation of co-resident decode
+  // workgroups whose mechanism was unknown; r06 found it (hipcc had packed the gate rows' FMA chains into v_pk_fma_f32 op_sel:[0,1,0],
+  // whose low result is wrong in lanes 48..63 beside another wave's MFMAs: gigaam_amd/build.py) and removed the instruction, so the
+  // default is the kernel's own LDS size again; the switch stays as an A/B (profiles/r06_exclusive_ab.txt: no time difference).
+  if (exclusive && lds <= 160 * 1024) lds = 160 * 1024;
+  if (lds > 160 * 1024) return p;
+  p.C = C; p.need = need; p.nr = nr;
+  p.h320 = H == 320 && JH == 320;
+  p.resident = p.h320 && nr == 1;
+  p.kern = p.h320 && col < 4 ? col : 4 + col;
+  p.wout_slice_in_lds = wout; p.wpred_slice_in_lds = wpred; p.lds = lds;
+  p.xg = gam_rnnt_cluster_xgranules(H, JH, C) * (size_t)B;
+  p.grid = (unsigned)(8 * nu8 * C);
+  return p;
+}
+
+// One workgroup per utterance (gam_decode.h): the whole decode when the cluster kernel does not take the shape
+// (GAM_RNNT_CLUSTER=0, a refused cluster launch), and -- with only_failed -- the REPAIR pass behind every cluster
+// launch: a workgroup of it returns at once unless the cluster kernel left its utterance at counts[b] = -1 (a hand-off
+// timed out because a member was not resident: GPU shared with another process / stream, CU-masked partition).  The
+// caller therefore always gets the reference's ids back, without a host round trip and without an exception.
+static int rnnt_single_launch(gam_handle* h, hipStream_t s, const GamRnntArgs& a, int only_failed) {
+  GamRnntArgs f = a;
+  f.only_failed = only_failed;
+  f.wout_in_lds = gam_rnnt_smem(f.H, f.JH, f.V, 1, f.L) <= 96 * 1024 ? 1 : 0;
+  size_t sm = gam_rnnt_smem(f.H, f.JH, f.V, f.wout_in_lds, f.L);
+  if (h->rnnt_exclusive && f.B <= h->ncu && sm <= 160 * 1024) sm = 160 * 1024;   // (owns its CU like a cluster member: rnnt_cluster_plan)
+  static std::atomic<unsigned long long> attr5{0}, attr8{0};
+  HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_greedy_kernel<5>), 160 * 1024, attr5));
+  HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_greedy_kernel<8>), 160 * 1024, attr8));
+  if (sm > 160 * 1024) return fail(h, -1, "RNN-T head too large for the greedy kernel's LDS window");
+  if (4 * f.H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_greedy_kernel<5>, dim3(f.B), dim3(256), sm, s, f);
+  else hipLaunchKernelGGL(gam_rnnt_greedy_kernel<8>, dim3(f.B), dim3(256), sm, s, f);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// The cluster kernel's instantiations, each with the word that raises its LDS limit once per device.  [0..3]: H = JH = 320 at compile
+// time, NR = 1 (resident), 2, 3, 5 (C = 1 there needs 5 slots: no NR = 8); [4..8]: the sizes as arguments, NR = 1, 2, 3, 5, 8.
+static const void* const rnnt_cluster_kern[9] = {
+    (const void*)gam_rnnt_cluster_kernel<1, 80>,     (const void*)gam_rnnt_cluster_kernel<2, 0, 320>, (const void*)gam_rnnt_cluster_kernel<3, 0, 320>,
+    (const void*)gam_rnnt_cluster_kernel<5, 0, 320>, (const void*)gam_rnnt_cluster_kernel<1>,         (const void*)gam_rnnt_cluster_kernel<2>,
+    (const void*)gam_rnnt_cluster_kernel<3>,         (const void*)gam_rnnt_cluster_kernel<5>,         (const void*)gam_rnnt_cluster_kernel<8>};
+static std::atomic<unsigned long long> rnnt_cluster_kern_once[9];
+
+// diagnosis build (-DGAM_RC_TIMING=1), GAM_RNNT_TIMING=1: the per-phase totals the kernel left behind the status word (utterance 0, member 0)
+static int rnnt_timing_report(gam_handle* h, hipStream_t s, const int* status, const RnntClusterPlan& p) {
+  if (!GAM_RC_TIMING || !getenv("GAM_RNNT_TIMING")) return 0;
+  int st[16];
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipMemcpy(st, status, sizeof st, hipMemcpyDeviceToHost));
+  fprintf(stderr, "[gam] rnnt cluster C=%d%s utt0: rounds %d; us: gates %.0f xH %.0f pred %.0f xP %.0f z %.0f joint %.0f xA %.0f comb %.0f ctrl %.0f\n", p.C,
+          p.resident ? " (resident)" : "", st[T_ROUNDS], st[T_GATES] / 100.0, st[T_XH] / 100.0, st[T_PRED] / 100.0, st[T_XP] / 100.0, st[T_Z] / 100.0,
+          st[T_JOINT] / 100.0, st[T_XA] / 100.0, st[T_COMB] / 100.0, st[T_CTRL] / 100.0);
+  return 0;
+}
+
+// The cluster kernel over a planned shape (p.C >= 1).  *refused: the runtime did not take the launch and nothing was enqueued behind the
+// memset; the caller decodes with rnnt_single_launch.
+static int rnnt_cluster_launch(gam_handle* h, hipStream_t s, const GamRnntArgs& a, const RnntClusterPlan& p, bool* refused) {
+  GamRnntClusterArgs ca;
+  memset(&ca, 0, sizeof ca);
+  ca.a = a; ca.whh_q = h->lstm_whh_q; ca.wpred_q = h->jn_pred_q; ca.C = p.C;
+  ca.force_dead = h->rnnt_force_timeout;
+  ca.wout_slice_in_lds = p.wout_slice_in_lds; ca.wpred_slice_in_lds = p.wpred_slice_in_lds;
+  if (int r = ensure(h, h->rnnt_x, p.xg * 2 + 64)) return r;   // (floats: 2 per granule) + status word
+  HIPCHK(h, hipMemsetAsync(h->rnnt_x.p, 0, (p.xg * 2 + 64) * sizeof(float), s));
+  ca.xbuf = reinterpret_cast<unsigned long long*>(h->rnnt_x.p);
+  ca.status = reinterpret_cast<int*>(h->rnnt_x.p + p.xg * 2);
+#if GAM_RC_AUDIT
+  if (int r = rnnt_audit_arm(h, s, ca)) return r;
+#endif
+  // Cooperative launch: the runtime REFUSES a grid that cannot be co-resident on this device (occupancy x CUs)
+  // instead of letting resident members spin on absent ones; what it cannot see (CUs held by another queue) is
+  // what the bounded spins + the repair pass are for.
+  const bool coop = h->rnnt_coop != 0;
+  const void* kern = rnnt_cluster_kern[p.kern];
+  HIPCHK(h, gam_set_max_lds(kern, 160 * 1024, rnnt_cluster_kern_once[p.kern]));
+  void* kargs[] = {&ca};
+  const hipError_t le = coop ? hipLaunchCooperativeKernel(kern, dim3(p.grid), dim3(256), kargs, (unsigned)p.lds, s)
+                             : hipLaunchKernel(kern, dim3(p.grid), dim3(256), kargs, p.lds, s);
+  *refused = le != hipSuccess;
+  if (*refused) {
+    (void)hipGetLastError();
+    static std::atomic<int> warned{0};
+    if (!warned.exchange(1))
+      fprintf(stderr, "[gam] RNN-T cluster decode: %s launch of %u workgroups refused (%s); decoding with one workgroup per utterance\n",
+              coop ? "cooperative" : "plain", p.grid, hipGetErrorString(le));
+    return 0;
+  }
+  return rnnt_timing_report(h, s, ca.status, p);
+}
 
 int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int max_symbols,
                     int32_t* ids, int32_t* frames, int32_t* counts, float* logits_dump, int32_t* dump_count, int dump_cap,
                     void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   if (B <= 0 || Tp <= 0 || max_symbols <= 0) return fail(h, -1, "bad arguments");
   GAM_DECODE_ENTRY(h, stream);
-  const gam_config& c = h->cfg;
-  const int JH = c.joint_hidden;
   if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
-  GamRnntArgs a;
-  memset(&a, 0, sizeof a);
-  a.encp = h->encp.p; a.enc_len = enc_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wpred_t = h->jn_pred_t;
-  a.bpred = h->jn_pred_b; a.wout = h->jn_out_w; a.bout = h->jn_out_b; a.ids = ids; a.frames = frames; a.counts = counts;
-  a.dump = logits_dump; a.dump_count = dump_count; a.B = B; a.Tp = (int)Tp; a.V = c.num_classes; a.H = c.pred_hidden; a.JH = JH;
-  a.max_symbols = max_symbols; a.cap = (int)Tp * max_symbols; a.dump_cap = logits_dump ? dump_cap : 0;
-  a.L = c.pred_rnn_layers; a.wih_x = h->lstm_wih_x; a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x;
+  const GamRnntArgs a = rnnt_greedy_args(h, enc_len, B, Tp, max_symbols, ids, frames, counts, logits_dump, dump_count, dump_cap);
+  const RnntClusterPlan p = rnnt_cluster_plan(h->ncu, h->rnnt_cluster, h->rnnt_exclusive, B, a.H, a.JH, a.V, a.L);
   ProfScope ps(h, s, GAM_PF_DECODE, 0.0);
-  // One workgroup per utterance (gam_decode.h): the whole decode when the cluster kernel does not take the shape
-  // (GAM_RNNT_CLUSTER=0, a refused cooperative launch), and -- with only_failed -- the REPAIR pass behind every cluster
-  // launch: a workgroup of it returns at once unless the cluster kernel left its utterance at counts[b] = -1 (a hand-off
-  // timed out because a member was not resident: GPU shared with another process / stream, CU-masked partition).  The
-  // caller therefore always gets the reference's ids back, without a host round trip and without an exception.
-  auto launch_single = [&](int only_failed) -> int {
-    GamRnntArgs f = a;
-    f.only_failed = only_failed;
-    f.wout_in_lds = gam_rnnt_smem(f.H, f.JH, f.V, 1, f.L) <= 96 * 1024 ? 1 : 0;
-    size_t sm1 = gam_rnnt_smem(f.H, f.JH, f.V, f.wout_in_lds, f.L);
-    if (h->rnnt_exclusive && B <= h->ncu && sm1 <= 160 * 1024) sm1 = 160 * 1024;   // (owns its CU like a cluster member: see below)
-    static std::atomic<unsigned long long> attr5{0}, attr8{0};
-    HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_greedy_kernel<5>), 160 * 1024, attr5));
-    HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_greedy_kernel<8>), 160 * 1024, attr8));
-    if (sm1 > 160 * 1024) return fail(h, -1, "RNN-T head too large for the greedy kernel's LDS window");
-    if (4 * f.H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_greedy_kernel<5>, dim3(B), dim3(256), sm1, s, f);
-    else hipLaunchKernelGGL(gam_rnnt_greedy_kernel<8>, dim3(B), dim3(256), sm1, s, f);
-    HIPCHK(h, hipGetLastError());
-    return 0;
-  };
-  // Cluster decode (gam_decode_cluster.h): C workgroups per utterance, grid <= one workgroup per CU.
-  // (8 utterance columns, one per XCD; C members of a cluster share an XCD.)
-  {
-    const int nu8 = gam_cdiv(B, 8);
-    // every member of every cluster must be resident at once (they spin on each other): at most one workgroup per CU
-    // of THIS device, with a few CUs to spare; a partition with fewer CUs gets smaller clusters or the one-workgroup kernel
-    int C = (h->ncu - 16) / (8 * nu8);
-    C = C > 8 ? 8 : C;
-    if (h->rnnt_cluster >= 0) C = h->rnnt_cluster < C ? h->rnnt_cluster : C;
-    if (C >= 1 && JH % 16 == 0 && a.H % 4 == 0 && a.L == 1) {   // (JH % 16: MFMA k-steps and the LDS-DMA window; L > 1: one-workgroup kernel)
-      GamRnntClusterArgs ca;
-      memset(&ca, 0, sizeof ca);
-      ca.a = a; ca.whh_q = h->lstm_whh_q; ca.wpred_q = h->jn_pred_q; ca.C = C;
-      ca.force_dead = h->rnnt_force_timeout;
-      const int nI = gam_cdiv(a.H, C), need = gam_cdiv(4 * nI, 256);
-      int nr = need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 3 ? 3 : (need <= 5 ? 5 : 8)));
-      const int nV = gam_cdiv(gam_cdiv(a.V, C), 16) * 16;
-      ca.wout_slice_in_lds = (size_t)nV * (JH + 4) * 4 + gam_rnnt_cluster_smem(a.H, JH, a.V, C, nr, 0) <= 96 * 1024 ? 1 : 0;
-      ca.wpred_slice_in_lds = gam_rnnt_cluster_smem(a.H, JH, a.V, C, nr, ca.wout_slice_in_lds, 1) <= 150 * 1024 ? 1 : 0;
-      size_t sm = gam_rnnt_cluster_smem(a.H, JH, a.V, C, nr, ca.wout_slice_in_lds, ca.wpred_slice_in_lds);
-      // GAM_RNNT_EXCLUSIVE=1: a decode workgroup asks for the CU's whole LDS (160 KB), so no other workgroup that uses LDS -- of this launch or
-      // of ANOTHER stream's kernel -- is placed beside it.  r05 shipped this as the protection against a perturbation of co-resident decode
-      // workgroups whose mechanism was unknown; r06 found it (hipcc had packed the gate rows' FMA chains into v_pk_fma_f32 op_sel:[0,1,0],
-      // whose low result is wrong in lanes 48..63 beside another wave's MFMAs: gigaam_amd/build.py) and removed the instruction, so the
-      // default is the kernel's own LDS size again; the switch stays as an A/B (profiles/r06_exclusive_ab.txt: no time difference).
-      if (h->rnnt_exclusive && sm <= 160 * 1024) sm = 160 * 1024;
-      const size_t xg = gam_rnnt_cluster_xgranules(a.H, JH, C) * (size_t)B;
-      if (sm <= 160 * 1024 && need <= 8) {
-        if (int r = ensure(h, h->rnnt_x, xg * 2 + 64)) return r;   // (floats: 2 per granule) + status word
-        HIPCHK(h, hipMemsetAsync(h->rnnt_x.p, 0, (xg * 2 + 64) * sizeof(float), s));
-        ca.xbuf = reinterpret_cast<unsigned long long*>(h->rnnt_x.p);
-        ca.status = reinterpret_cast<int*>(h->rnnt_x.p + xg * 2);
-        const dim3 grid(8 * nu8 * C);
-#if GAM_RC_AUDIT
-        if (int r = audit_dump(h)) return r;
-        h->audit_pending = true; h->audit_last_c = C;
-        if (int r = ensure(h, h->rnnt_audit, 16 + 12 * GAM_RC_AUDIT_CAP)) return r;
-        HIPCHK(h, hipMemsetAsync(h->rnnt_audit.p, 0, 64, s));
-        ca.audit = reinterpret_cast<int*>(h->rnnt_audit.p);
-#endif
-        // Cooperative launch: the runtime REFUSES a grid that cannot be co-resident on this device (occupancy x CUs)
-        // instead of letting resident members spin on absent ones; what it cannot see (CUs held by another queue) is
-        // what the bounded spins + the repair pass below are for.
-        const bool coop = h->rnnt_coop != 0;
-        const void* kern = nullptr;
-        static std::atomic<unsigned long long> at1{0}, at2{0}, at3{0}, at5{0}, at8{0}, at1r{0}, at2c{0}, at3c{0}, at5c{0};
-        std::atomic<unsigned long long>* at = nullptr;
-        const bool resident = nr == 1 && a.H == 320 && JH == 320;   // W_hh rows register-resident (gam_decode_cluster.h RESQ)
-        const bool h320 = a.H == 320 && JH == 320;      // compile-time sizes (the published heads)
-        if (resident) { kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<1, 80>); at = &at1r; }
-        else if (h320 && nr == 2) { kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<2, 0, 320>); at = &at2c; }
-        else if (h320 && nr == 3) { kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<3, 0, 320>); at = &at3c; }
-        else if (h320 && nr == 5) { kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<5, 0, 320>); at = &at5c; }
-        else switch (nr) {
-          case 1: kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<1>); at = &at1; break;
-          case 2: kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<2>); at = &at2; break;
-          case 3: kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<3>); at = &at3; break;
-          case 5: kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<5>); at = &at5; break;
-          default: kern = reinterpret_cast<const void*>(gam_rnnt_cluster_kernel<8>); at = &at8; break;
-        }
-        HIPCHK(h, gam_set_max_lds(kern, 160 * 1024, *at));
-        void* kargs[] = {&ca};
-        hipError_t le = coop ? hipLaunchCooperativeKernel(kern, grid, dim3(256), kargs, (unsigned)sm, s)
-                             : hipLaunchKernel(kern, grid, dim3(256), kargs, sm, s);
-        if (le != hipSuccess) {
-          (void)hipGetLastError();
-          static std::atomic<int> warned{0};
-          if (!warned.exchange(1))
-            fprintf(stderr, "[gam] RNN-T cluster decode: %s launch of %u workgroups refused (%s); decoding with one workgroup per utterance\n",
-                    coop ? "cooperative" : "plain", grid.x, hipGetErrorString(le));
-          return launch_single(0);
-        }
-        if (GAM_RC_TIMING && getenv("GAM_RNNT_TIMING")) {
-          int st[16];
-          HIPCHK(h, hipStreamSynchronize(s));
-          HIPCHK(h, hipMemcpy(st, ca.status, sizeof st, hipMemcpyDeviceToHost));
-          fprintf(stderr, "[gam] rnnt cluster C=%d%s utt0: rounds %d; us: gates %.0f xH %.0f pred %.0f xP %.0f z %.0f joint %.0f xA %.0f comb %.0f ctrl %.0f\n", C,
-                  resident ? " (resident)" : "", st[T_ROUNDS], st[T_GATES] / 100.0, st[T_XH] / 100.0, st[T_PRED] / 100.0, st[T_XP] / 100.0, st[T_Z] / 100.0,
-                  st[T_JOINT] / 100.0, st[T_XA] / 100.0, st[T_COMB] / 100.0, st[T_CTRL] / 100.0);
-        }
-        if (h->rnnt_no_repair) return 0;   // GAM_RNNT_NO_REPAIR=1 (test hook, read at gam_create): leave a failed cluster's counts at -1 (HipEngine.collect then raises)
-        return launch_single(1);   // repair pass: no-op workgroups unless a cluster gave up
-      }
-    }
-  }
-  return launch_single(0);
+  if (p.C == 0) return rnnt_single_launch(h, s, a, 0);
+  bool refused = false;
+  if (int r = rnnt_cluster_launch(h, s, a, p, &refused)) return r;
+  if (refused) return rnnt_single_launch(h, s, a, 0);
+  if (h->rnnt_no_repair) return 0;   // GAM_RNNT_NO_REPAIR=1 (test hook, read at gam_create): leave a failed cluster's counts at -1 (HipEngine.collect then raises)
+  return rnnt_single_launch(h, s, a, 1);   // repair pass: no-op workgroups unless a cluster gave up
 }
 
 // RNN-T beam search over the encoder projection encp [B, Tp, JH] (gam_rnnt_beam.h): one workgroup per utterance; with the handle's LM
@@ -2374,8 +2439,9 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
   if (int r = ensure(h, h->rb_nodes, (size_t)B * Tp * max_symbols * W * 2 + 64)) return r;
   GamRnntBeamArgs a;
   memset(&a, 0, sizeof a);
-  a.encp = encp; a.enc_len = enc_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wpred_t = h->jn_pred_t; a.bpred = h->jn_pred_b;
-  a.wout = h->jn_out_w; a.bout = h->jn_out_b; a.wih_x = h->lstm_wih_x; a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x;
+  rnnt_pred_weights(h, a);
+  rnnt_joint_weights(h, a);
+  a.encp = encp; a.enc_len = enc_len;
   a.Tp = (int)Tp; a.V = V; a.H = H; a.JH = JH; a.L = L; a.W = W; a.K = K; a.S = max_symbols;
   a.hw = hw_args(h, hw_lds);
   a.lm = lm_args(h);
@@ -2395,8 +2461,7 @@ static int rnnt_beam_launch(gam_handle* h, const float* encp, const int32_t* enc
 static int rnnt_beam_run(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols,
                          int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, void* stream, bool nbest, int N,
                          int32_t* n_hyp) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   if (B <= 0 || Tp <= 0 || Tp > GAM_RB_MAX_T || W < 1 || W > GAM_BEAM_MAX_W || max_symbols < 1 || max_symbols > GAM_RB_MAX_S)
     return fail(h, -1, "RNN-T beam search: B=%d T'=%lld / W=%d / S=%d beyond the limits (%d / [1, %d] / [1, %d])", B, (long long)Tp, W,
@@ -2419,16 +2484,14 @@ int gam_rnnt_beam_nbest(gam_handle* h, const float* encoded, const int32_t* enc_
 
 int gam_op_rnnt_beam_nbest(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int N,
                            int32_t* ids, int32_t* frames, int32_t* counts, float* score, float* logp, int32_t* n_hyp, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s, true, N, n_hyp);
 }
 
 int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
                      int32_t* frames, int32_t* counts, float* score, float* logp, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s);
 }
@@ -2472,8 +2535,8 @@ static int rnnt_tf_pp(gam_handle* h, const int32_t* targets, const int32_t* targ
   if (int r = ensure(h, h->ra_pp, (size_t)B * u1 * JH + 64)) return r;
   {
     GamRnntTfArgs a;
-    a.targets = targets; a.target_len = target_len; a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x;
-    a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x; a.g = h->ra_g.p; a.Umax = Umax; a.V = V; a.H = H; a.L = L;
+    rnnt_pred_weights(h, a);
+    a.targets = targets; a.target_len = target_len; a.g = h->ra_g.p; a.Umax = Umax; a.V = V; a.H = H; a.L = L;
     ProfScope ps(h, s, GAM_PF_DECODE, (double)B * u1 * L * 8.0 * H * H * 4.0);
     const size_t sm = gam_ra_tf_lds_bytes(H, L);
     if (4 * H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_tf_predict_kernel<5>, dim3(B), dim3(256), sm, s, a);
@@ -2538,8 +2601,7 @@ static int rnnt_align_launch(gam_handle* h, const float* encp, const int32_t* en
 
 int gam_rnnt_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
                    const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   if (int r = rnnt_align_shape_check(h, B, Tp, Umax, h->cfg.num_classes, !encoded)) return r;
   if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
@@ -2549,8 +2611,7 @@ int gam_rnnt_align(gam_handle* h, const float* encoded, const int32_t* enc_len, 
 int gam_op_rnnt_align(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
                       const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status,
                       float* lattice_out, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   return rnnt_align_launch(h, encp, enc_len, B, Tp, targets, target_len, Umax, tok_frame, score, loglik, status, lattice_out, s);
 }
@@ -2615,9 +2676,7 @@ static int ctc_conf_launch(gam_handle* h, const float* lp, const int32_t* enc_le
 int gam_ctc_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                        const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
                        int32_t* status, void* stream) {
-  if (!h) return -1;
-  if (!h->finalized) return fail(h, -1, "CTC head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_CTC || !h->has_head) return fail(h, -1, "model has no CTC head");
+  if (int r = head_check(h, GAM_HEAD_CTC, "CTC head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   const int V = h->cfg.num_classes;
   if (int r = conf_shape_check(h, "CTC", B, Tp, V, cap, 1 << 24, measure, agg, !encoded)) return r;
@@ -2664,8 +2723,7 @@ static int rnnt_conf_launch(gam_handle* h, const float* encp, const int32_t* enc
 
 int gam_rnnt_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                         const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   if (int r = conf_shape_check(h, "RNN-T", B, Tp, h->cfg.num_classes, cap, GAM_RA_MAX_U, measure, GAM_CF_MEAN, !encoded)) return r;
   if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
@@ -2674,22 +2732,20 @@ int gam_rnnt_confidence(gam_handle* h, const float* encoded, const int32_t* enc_
 
 int gam_op_rnnt_confidence(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                            const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "RNN-T head before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   return rnnt_conf_launch(h, encp, enc_len, B, Tp, ids, frames, counts, cap, measure, conf, status, s);
 }
 
 int gam_rnnt_predict(gam_handle* h, const int32_t* labels, const float* h_in, const float* c_in, int B, float* g_out,
                      float* h_out, float* c_out, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "gam_rnnt_predict before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "gam_rnnt_predict")) return r;
   if (B <= 0 || !g_out || !h_out || !c_out || (h_in == nullptr) != (c_in == nullptr)) return fail(h, -1, "bad gam_rnnt_predict arguments");
   HIPCHK(h, hipSetDevice(h->device));
   const gam_config& c = h->cfg;
   GamPredictArgs a;
+  rnnt_pred_weights(h, a);
   a.label = labels; a.h_in = h_in; a.c_in = c_in; a.g_out = g_out; a.h_out = h_out; a.c_out = c_out;
-  a.gate_tab = h->lstm_tab; a.whh_t = h->lstm_whh_t; a.wih_x = h->lstm_wih_x; a.whh_x = h->lstm_whh_x; a.bias_x = h->lstm_bias_x;
   a.B = B; a.PH = c.pred_hidden; a.V = c.num_classes; a.L = c.pred_rnn_layers;
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(h, s, GAM_PF_DECODE, 0.0);
@@ -2699,8 +2755,7 @@ int gam_rnnt_predict(gam_handle* h, const int32_t* labels, const float* h_in, co
 }
 
 int gam_rnnt_joint(gam_handle* h, const float* enc, const float* dec, int B, int T, int U, float* log_probs, void* stream) {
-  if (!h || !h->finalized) return fail(h, -1, "gam_rnnt_joint before gam_finalize");
-  if (h->cfg.head_type != GAM_HEAD_RNNT || !h->has_head) return fail(h, -1, "model has no RNN-T head");
+  if (int r = head_check(h, GAM_HEAD_RNNT, "gam_rnnt_joint")) return r;
   if (B <= 0 || T <= 0 || U <= 0 || !enc || !dec || !log_probs) return fail(h, -1, "bad gam_rnnt_joint arguments");
   HIPCHK(h, hipSetDevice(h->device));
   const gam_config& c = h->cfg;
@@ -2734,8 +2789,7 @@ int gam_rnnt_joint(gam_handle* h, const float* enc, const float* dec, int B, int
 
 int gam_emo_probs(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, float* probs,
                   void* stream) {
-  if (!h) return -1;
-  if (h->cfg.head_type != GAM_HEAD_EMO || !h->has_head) return fail(h, -1, "model has no emotion head");
+  if (int r = head_check(h, GAM_HEAD_EMO, nullptr)) return r;   // (no finalize message of its own: has_head is set at gam_finalize)
   if (B <= 0 || Tp <= 0 || !encoded || !probs) return fail(h, -1, "bad emotion-head arguments");
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;

@@ -627,7 +627,7 @@ class HipEngine:
         if side is not None:
             for t in (ids, frames, src):
                 t.record_stream(side)
-        if n and min(n) < 0:   # cannot happen: gam_rnnt_greedy repairs failed clusters itself (gam_api.hip launch_single)
+        if n and min(n) < 0:   # cannot happen: gam_rnnt_greedy repairs failed clusters itself (gam_api.hip rnnt_single_launch)
             raise GigaAMHipError("RNN-T decode left an utterance undecoded (counts = -1)")
         return _rows(ids_h.numpy(), fr_h.numpy(), n), flag
 
