@@ -104,6 +104,8 @@ SIGNATURES = {
     "gam_get_gemm_mode": (C.c_int, [_P]),
     "gam_set_rnnt_cluster": (C.c_int, [_P, C.c_int]),
     "gam_get_rnnt_cluster": (C.c_int, [_P]),
+    "gam_rnnt_cluster_plan_info": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int32)]),
+    "gam_rnnt_last_decode": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "gam_debug_buffer_hash": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "gam_range_flag": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
     "gam_range_flag_fetch": (C.c_int, [_P, _P, _P]),

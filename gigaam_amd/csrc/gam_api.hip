@@ -140,6 +140,7 @@ struct gam_handle {
   int rnnt_exclusive = 0;       // GAM_RNNT_EXCLUSIVE=1: decode workgroups ask for their CU's whole LDS, so nothing that uses LDS is placed beside them
                                 // (r05's protection; not needed since r06 removed the packed-fp32 instructions that a neighbour's MFMAs disturbed --
                                 // tests/test_hip_hardening.py runs the decode beside another stream's GEMM both ways)
+  int last_rnnt_c = 0, last_rnnt_kern = -1, last_rnnt_refused = 0;   // what the last gam_rnnt_greedy launched (gam_rnnt_last_decode)
   DevBuf rnnt_x;                // hand-off granules + status word of the cluster kernel
   DevBuf rnnt_audit;            // -DGAM_RC_AUDIT=1 diagnosis builds: the cluster kernel's audit log
   bool audit_pending = false; int audit_last_c = 0; long audit_decodes = 0, audit_hit_decodes = 0;
@@ -2397,9 +2398,11 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
   const GamRnntArgs a = rnnt_greedy_args(h, enc_len, B, Tp, max_symbols, ids, frames, counts, logits_dump, dump_count, dump_cap);
   const RnntClusterPlan p = rnnt_cluster_plan(h->ncu, h->rnnt_cluster, h->rnnt_exclusive, B, a.H, a.JH, a.V, a.L);
   ProfScope ps(h, s, GAM_PF_DECODE, 0.0);
+  h->last_rnnt_c = p.C; h->last_rnnt_kern = p.C ? p.kern : -1; h->last_rnnt_refused = 0;   // (gam_rnnt_last_decode)
   if (p.C == 0) return rnnt_single_launch(h, s, a, 0);
   bool refused = false;
   if (int r = rnnt_cluster_launch(h, s, a, p, &refused)) return r;
+  h->last_rnnt_refused = refused ? 1 : 0;
   if (refused) return rnnt_single_launch(h, s, a, 0);
   if (h->rnnt_no_repair) return 0;   // GAM_RNNT_NO_REPAIR=1 (test hook, read at gam_create): leave a failed cluster's counts at -1 (HipEngine.collect then raises)
   return rnnt_single_launch(h, s, a, 1);   // repair pass: no-op workgroups unless a cluster gave up
@@ -2960,6 +2963,22 @@ int gam_set_rnnt_cluster(gam_handle* h, int workgroups_per_utterance) {
 }
 
 int gam_get_rnnt_cluster(gam_handle* h) { return h ? h->rnnt_cluster : -2; }
+
+int gam_rnnt_cluster_plan_info(int ncu, int cluster, int exclusive, int B, int H, int JH, int V, int L, int32_t* out) {
+  if (!out || B <= 0 || H <= 0 || JH <= 0 || V <= 0 || L <= 0) return -1;
+  const RnntClusterPlan p = rnnt_cluster_plan(ncu, cluster, exclusive, B, H, JH, V, L);
+  memset(out, 0, 8 * sizeof(int32_t));
+  if (p.C == 0) return 0;
+  out[0] = p.C; out[1] = p.nr; out[2] = p.kern; out[3] = p.resident ? 1 : 0;
+  out[4] = p.wout_slice_in_lds; out[5] = p.wpred_slice_in_lds; out[6] = (int32_t)p.lds; out[7] = (int32_t)p.grid;
+  return 0;
+}
+
+int gam_rnnt_last_decode(gam_handle* h, int32_t* out) {
+  if (!h || !out) return -1;
+  out[0] = h->last_rnnt_c; out[1] = h->last_rnnt_kern; out[2] = h->last_rnnt_refused;
+  return 0;
+}
 
 int gam_last_encode_rows(gam_handle* h, int* rows_padded) {
   if (!h) return -1;

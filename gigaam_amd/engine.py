@@ -1226,6 +1226,13 @@ class HipEngine:
         self._check(self.lib.gam_set_rnnt_cluster(self._h, int(n)), "gam_set_rnnt_cluster")
         self._rnnt_cluster_user = int(n)
 
+    def rnnt_last_decode(self) -> Tuple[int, int, bool]:
+        """What the last ``rnnt_greedy`` launched (gam_rnnt_last_decode): (C used -- 0 = the one-workgroup kernel, index of the
+        cluster kernel's instantiation or -1, whether the runtime refused the cluster launch)."""
+        out = (C.c_int32 * 3)()
+        self._check(self.lib.gam_rnnt_last_decode(self._h, out), "gam_rnnt_last_decode")
+        return int(out[0]), int(out[1]), bool(out[2])
+
     def _decode_side_stream(self) -> "torch.cuda.Stream":
         return self.aux_streams(self.device)[0]      # (shared by the engines of a device: see aux_streams)
 

@@ -403,7 +403,7 @@ int gam_op_rnnt_confidence(gam_handle* h, const float* encp, const int32_t* enc_
  * A caller that runs the decode of batch n on a side stream BESIDE the encoder of batch n+1 (the product's RNN-T
  * pipelines do, r05: model.launch_batch) asks for small clusters so that the latency-bound decode holds few CUs.  Every
  * setting holds the reference's bars (ids / frames / step counts exact on the fixtures, log-probs <= 1e-3; tests: C in
- * {0, 1, 2, 3, 5, 8}) and is bit-reproducible run to run; the setting fixes how a member partitions its sums, so two
+ * 0 .. 8) and is bit-reproducible run to run; the setting fixes how a member partitions its sums, so two
  * DIFFERENT settings may resolve a near-tie (top-1 / top-2 margin ~1e-5) differently.  gam_rnnt_greedy is safe to run
  * concurrently with gam_frontend / gam_encode of the SAME handle on another stream (it shares no scratch with them).
  * Decode-class calls of one handle (gam_ctc_head / gam_ctc_greedy / gam_rnnt_greedy / gam_rnnt_joint) share one set of
@@ -417,6 +417,17 @@ int gam_op_rnnt_confidence(gam_handle* h, const float* encp, const int32_t* enc_
 int gam_set_rnnt_cluster(gam_handle* h, int workgroups_per_utterance);
 /* The setting in force (-1 auto, 0 .. 8); -2 for a NULL handle. */
 int gam_get_rnnt_cluster(gam_handle* h);
+/* What gam_rnnt_greedy's planner does with a shape (host code only: no handle, no HIP call).  ncu: the device's compute units; cluster:
+ * the gam_set_rnnt_cluster setting (-1 auto); exclusive: GAM_RNNT_EXCLUSIVE; B utterances; H = pred_hidden, JH = joint_hidden, V classes,
+ * L predictor layers.  out[8] = C (workgroups per utterance), NR (gate-row slots per thread), the index of the cluster kernel's
+ * instantiation (0..3: H = JH = 320 at compile time; 4..8: the sizes as arguments), W_hh register-resident, the W_out slice in LDS, the
+ * W_pred slice in LDS, dynamic LDS bytes of a workgroup, workgroups of the grid.  All zeros (C = 0) when the one-workgroup kernel
+ * decodes the shape. */
+int gam_rnnt_cluster_plan_info(int ncu, int cluster, int exclusive, int B, int H, int JH, int V, int L, int32_t* out);
+/* What the LAST gam_rnnt_greedy call of this handle launched: out[3] = C used (0: the one-workgroup kernel), the index of the cluster
+ * kernel's instantiation (-1 for the one-workgroup kernel), 1 if the runtime refused the cluster launch (the one-workgroup kernel then
+ * decoded the batch).  Host fields; no synchronisation. */
+int gam_rnnt_last_decode(gam_handle* h, int32_t* out);
 
 /* Debug aid (r05): FNV-1a hash over one of the decode's scratch buffers as it sits in device memory (synchronises the
  * device).  which: 0 = token-major copy of the encoder output, 1 = encoder projection, 2 = hand-off granules, 3 = CTC

@@ -11,7 +11,8 @@ contributor with the higher score (ties: the earlier one) and the key of its fir
 Final: best score + committed, ties to the lower beam position.
 With ``lm`` (a ctc_lm_ref.LMSpec, where the word rules are): an extension a.y + v takes ``lm.step(state, v)``; blank candidates and
 the forced advance keep the state; equal y means equal state (asserted at every merge); rank and the final pick add the LM term
-(final: ``lm.final(state)``, the last word and </s>).  score = log p + committed + that term; logp = log p."""
+(final: ``lm.final(state)``, the last word and </s>).  score = log p + committed + that term; logp = log p.
+``greedy_trace`` / ``greedy_ref``: the greedy decode over the same predictor and joint (the tests of gam_rnnt_greedy)."""
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -182,6 +183,37 @@ def beam_search(head, encp, W: int, S: int, T: Optional[int] = None, hotwords: S
 def min_margin(res: Dict[str, object]) -> float:
     """The smallest decision margin of a run: every cut, theta comparison, kept merge and the final pick."""
     return float(min([res["final_margin"]] + list(res["margins"])))
+
+
+def greedy_trace(head, encoded, T: int, S: int) -> Dict[str, object]:
+    """The float64 greedy decode of one utterance (reference decoding.py's loop: at most S symbols per frame, the first maximum
+    wins) with everything it saw: ``ids``, ``frames``, ``margin`` (the smallest top-1 / top-2 margin over its joint steps, inf when
+    there was none), ``lp`` [joint steps, V] (the log-probs of every joint evaluation, in decode order), ``per_frame`` [T] (tokens
+    emitted at each frame)."""
+    encp = encoder_projection(head, encoded)
+    pred = Predictor(head)
+    blank = head["out_w"].shape[0] - 1
+    y, frames, margin, rows, per_frame = (), [], np.inf, [], [0] * T
+    for t in range(T):
+        for _ in range(S):
+            lp = joint_lp(head, encp[t], pred(y))
+            rows.append(lp)
+            k = int(np.argmax(lp))
+            top2 = np.partition(lp, -2)[-2:]
+            margin = min(margin, float(top2[1] - top2[0]))
+            if k == blank:
+                break
+            y += (k,)
+            frames.append(t)
+            per_frame[t] += 1
+    lp = np.stack(rows) if rows else np.zeros((0, blank + 1))
+    return {"ids": list(y), "frames": frames, "margin": margin, "lp": lp, "per_frame": per_frame}
+
+
+def greedy_ref(head, encoded, T: int, S: int) -> Tuple[List[int], List[int], float]:
+    """(ids, frames, smallest top-1 / top-2 margin) of ``greedy_trace``."""
+    r = greedy_trace(head, encoded, T, S)
+    return r["ids"], r["frames"], r["margin"]
 
 
 def exact_loglik(joint, y: Sequence[int], T: int, S: int) -> float:

@@ -424,13 +424,16 @@ def test_batching_edge_cases_v3(revision):
     assert enc.shape[0] == 2 and bool(torch.isfinite(enc).all()) and elen.cpu().tolist() == [5, 8]
 
 
-@pytest.mark.parametrize("cluster", ["0", "1", "2", "3", "5", "8"])
+@pytest.mark.parametrize("cluster", ["0", "1", "2", "3", "4", "5", "6", "7", "8"])
 @pytest.mark.parametrize("case", ["v2_rnnt_l2", "v3_e2e_rnnt_l2_dense"])
 def test_rnnt_cluster_sizes(case, cluster, monkeypatch):
     """The RNN-T decode with C workgroups per utterance (gam_decode_cluster.h) for every way of slicing the hidden
     units / joint rows / classes over the cluster, and the one-workgroup kernel (C = 0): ids, frames, number of joint
-    evaluations and every log-prob against the reference's, exactly as in test_rnnt_ids_frames_and_logits."""
+    evaluations and every log-prob against the reference's, exactly as in test_rnnt_ids_frames_and_logits.  Without the
+    repair pass (GAM_RNNT_NO_REPAIR=1, read at gam_create) and with gam_rnnt_last_decode's word that the requested size ran,
+    so the one-workgroup kernel cannot stand in for a cluster that gave up or a launch the runtime refused."""
     monkeypatch.setenv("GAM_RNNT_CLUSTER", cluster)
+    monkeypatch.setenv("GAM_RNNT_NO_REPAIR", "1")
     ck, wav, wlen, gold = load_case(case)
     eng = _engine(ck)
     ms = ck["cfg"]["decoding"]["max_symbols_per_step"]
@@ -438,6 +441,9 @@ def test_rnnt_cluster_sizes(case, cluster, monkeypatch):
     want = golden_trace(gold)
     enc_ref, elen_ref = torch.from_numpy(gold["encoded"]), torch.from_numpy(gold["enc_len"])
     ids, frames, counts, dump, dcount = eng.rnnt_greedy(enc_ref, elen_ref, ms, dump_cap=max(w.shape[0] for w in want))
+    ran_c, ran_kern, refused = eng.rnnt_last_decode()
+    assert (ran_c, refused) == (int(cluster), False) and (ran_kern >= 0) == (ran_c > 0), (case, cluster, ran_c, ran_kern, refused)
+    assert min(counts.cpu().tolist()) >= 0, (case, cluster, counts.cpu().tolist())     # no cluster gave up
     assert ragged_from_device(ids, frames, counts) == ref
     assert dcount.cpu().tolist() == [w.shape[0] for w in want]
     for i, w in enumerate(want):

@@ -381,26 +381,6 @@ def _greedy512_inputs(L):
     return cfg, sd, encoded, [40, 23, 1, 0]
 
 
-def _greedy_ref(head, encoded, T, S):
-    """The float64 greedy decode of one utterance (reference decoding.py's loop: at most S symbols per frame, the first maximum
-    wins): ids, frames and the smallest top-1 / top-2 margin over its joint steps."""
-    encp = R.encoder_projection(head, encoded)
-    pred = R.Predictor(head)
-    blank = head["out_w"].shape[0] - 1
-    y, frames, margin = (), [], np.inf
-    for t in range(T):
-        for _ in range(S):
-            lp = R.joint_lp(head, encp[t], pred(y))
-            k = int(np.argmax(lp))
-            top2 = np.partition(lp, -2)[-2:]
-            margin = min(margin, float(top2[1] - top2[0]))
-            if k == blank:
-                break
-            y += (k,)
-            frames.append(t)
-    return list(y), frames, margin
-
-
 @pytest.mark.parametrize("L", [1, 2])
 def test_greedy_with_512_hidden_units_matches_float64_reference(L):
     """eng.rnnt_greedy on the one-workgroup kernel (cluster size 0), ragged lengths with 0 and 1: ids, frames and counts are exact for
@@ -416,7 +396,7 @@ def test_greedy_with_512_hidden_units_matches_float64_reference(L):
     ids, frames, counts = dec.ids.cpu().numpy(), dec.frames.cpu().numpy(), dec.counts.cpu().numpy()
     excused, n_tok, n_blank = 0, 0, 0
     for b, T in enumerate(enc_len):
-        want_ids, want_frames, margin = _greedy_ref(head, encoded[b], T, S)
+        want_ids, want_frames, margin = R.greedy_ref(head, encoded[b], T, S)      # (the float64 greedy loop: tests/rnnt_beam_ref.py)
         n_tok += len(want_ids)
         n_blank += T - len(set(want_frames))
         if margin <= GREEDY_MIN_MARGIN:
