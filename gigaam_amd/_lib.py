@@ -77,6 +77,8 @@ SIGNATURES = {
     "gam_ctc_kws": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_kws": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_set_keywords": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "gam_ctc_kws_state_bytes": (C.c_int64, [_P]),
+    "gam_op_ctc_kws_stream": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_set_hotwords": (C.c_int, [_P, _P, _P, C.c_int, C.c_float]),

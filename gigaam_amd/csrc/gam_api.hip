@@ -172,6 +172,7 @@ struct gam_handle {
   // the keyword set of gam_set_keywords (gam_kws.h): offsets [K + 1] | tokens | min_score [K] (f32 bits) in one buffer of ints; empty = no set
   DevBuf kw_dev;
   int kw_K = 0, kw_ntok = 0, kw_max_tok = -1;
+  int kw_gen = 0;                       // counts the successful gam_set_keywords calls (an identical set counts too): a stream state remembers the one it began under
   DevBuf kws_mb;                        // keyword search: per row {maximum, blank's emission}, B x T' x 8 bytes
   // the n-gram LM of gam_set_lm (gam_search.h): token classes [lm_V], word / n-gram table slots (uint4); lm_ng empty = no LM
   DevBuf lm_cls, lm_wt, lm_ng;
@@ -1910,6 +1911,7 @@ int gam_set_keywords(gam_handle* h, const int32_t* tokens, const int32_t* offset
   HIPCHK(h, hipSetDevice(h->device));
   // a decode-class kernel still in flight may read the current set
   if (h->dec_evt != nullptr && h->dec_evt_set) HIPCHK(h, hipEventSynchronize(h->dec_evt));
+  ++h->kw_gen;
   if (n_keywords == 0) {
     h->kw_K = h->kw_ntok = 0;
     h->kw_max_tok = -1;
@@ -1983,6 +1985,49 @@ int gam_op_ctc_kws(gam_handle* h, const float* log_probs, const int32_t* enc_len
   GAM_DECODE_ENTRY(h, stream);
   if (int r = ctc_kws_check(h, B, Tp, V, max_hits, !log_probs || !enc_len || !hit_frames || !hit_score || !n_hits)) return r;
   return ctc_kws_launch(h, log_probs, enc_len, B, Tp, V, max_hits, hit_frames, hit_score, n_hits, dense_score, dense_start, s);
+}
+
+// ---- the same search for one stream fed in pieces (gam_kws.h gam_ctc_kws_stream_kernel).  Decode class as above.
+int64_t gam_ctc_kws_state_bytes(gam_handle* h) {
+  if (!h) return -1;
+  if (!h->kw_dev.p || h->kw_K <= 0) return fail(h, -1, "keyword search: no keyword set (gam_set_keywords)");
+  return (int64_t)h->kw_K * GAM_KWS_ST_WORDS * 4;
+}
+
+int gam_op_ctc_kws_stream(gam_handle* h, const float* log_probs, int64_t n, int V, int64_t t_base, int flags, void* state, int max_hits,
+                          int32_t* hit_frames, float* hit_score, int32_t* n_hits, int32_t* status, float* dense_score,
+                          int32_t* dense_start, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (n < 0 || t_base < 0 || V < 2 || n >= 2147483648ll || t_base >= 2147483648ll || t_base + n >= 2147483648ll)
+    return fail(h, -1, "keyword stream: bad shape n=%lld V=%d t_base=%lld (t_base + n must stay below 2^31)", (long long)n, V,
+                (long long)t_base);
+  if (flags & ~(GAM_KWS_F_BEGIN | GAM_KWS_F_END)) return fail(h, -1, "keyword stream: unknown flags 0x%x", flags);
+  if (max_hits < 1 || max_hits > GAM_KWS_STREAM_MAX_HITS)
+    return fail(h, -1, "keyword stream: max_hits=%d outside [1, %d]", max_hits, GAM_KWS_STREAM_MAX_HITS);
+  if (!h->kw_dev.p || h->kw_K <= 0) return fail(h, -1, "keyword search: no keyword set (gam_set_keywords)");
+  if (h->kw_max_tok > V - 2) return fail(h, -1, "keyword search: keyword token id %d outside [0, %d] for V=%d", h->kw_max_tok, V - 2, V);
+  // (n < 2^31 rows are n / 4 < 2^29 workgroups of the row-maximum pass, and n x V < 2^62 is indexed in 64 bits: no further limit)
+  if ((n > 0 && !log_probs) || !state || !hit_frames || !hit_score || !n_hits || !status) return fail(h, -1, "keyword stream: NULL buffer");
+  if (n > 0) {
+    if (int r = ensure(h, h->kws_mb, (size_t)n * 2 + 64)) return r;
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)n * V * 4.0);
+    hipLaunchKernelGGL(gam_kws_rowmax_kernel, dim3(gam_cdiv(n, 4)), dim3(256), 0, s, log_probs, (const int*)nullptr, (int)n, V, (long)n,
+                       reinterpret_cast<float2*>(h->kws_mb.p));
+    HIPCHK(h, hipGetLastError());
+  }
+  const int K = h->kw_K;
+  GamKwsStreamArgs a;
+  a.lp = log_probs; a.mb = reinterpret_cast<const float2*>(h->kws_mb.p);
+  a.kw_off = h->kw_dev.as<int>(); a.kw_tok = a.kw_off + K + 1; a.kw_min = reinterpret_cast<const float*>(a.kw_tok + h->kw_ntok);
+  a.n = (int)n; a.V = V; a.K = K; a.max_hits = max_hits; a.t_base = (int)t_base; a.flags = flags; a.gen = h->kw_gen;
+  a.state = static_cast<int*>(state); a.hit_frames = hit_frames; a.hit_score = hit_score; a.n_hits = n_hits; a.status = status;
+  a.dense_score = dense_score; a.dense_start = dense_start;
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)n * K * 64.0 * 4.0);
+  const dim3 grid(gam_cdiv(K, GAM_KWS_WAVES)), block(64 * GAM_KWS_WAVES);
+  if (dense_score || dense_start) hipLaunchKernelGGL(gam_ctc_kws_stream_kernel<true>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(gam_ctc_kws_stream_kernel<false>, grid, block, 0, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
 }
 
 // ---- what the two beam searches share (gam_search.h): the handle's hotwords and LM as kernel arguments, the common checks, the launch

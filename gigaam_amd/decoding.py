@@ -109,6 +109,33 @@ def keyword_hits(h, b: int, keywords, texts, frame_shift: float, offset: float =
     return hits, truncated
 
 
+def keyword_stream_hits(h, keywords, texts, plan):
+    """A ``KeywordStreamHits.host()`` dict of a search over the stitched stream of ``plan`` (windows.WindowPlan) -> (``KeywordHit`` list
+    in keyword order, indices of the truncated keywords).  A hit's ``segment`` / ``end_segment`` are the windows its start and end
+    frames were kept from, ``start_frame`` / ``end_frame`` the local frames inside those windows (the dropped ones counted, as
+    ``plan.locate`` reports them); ``start`` = the start window's start + start_frame x its frame shift, ``end`` = the end window's
+    start + (end_frame + 1) x its frame shift."""
+    import math
+    from .types import KeywordHit
+    hits, truncated = [], []
+    mh = h["hit_frames"].shape[1]
+    for k, ids in enumerate(keywords):
+        n = int(h["n_hits"][k])
+        if n > mh:
+            truncated.append(k)
+        n = min(n, mh)
+        fr = h["hit_frames"][k, :n]
+        w0, j0, _ = plan.locate(fr[:, 0].tolist())
+        w1, j1, _ = plan.locate(fr[:, 1].tolist())
+        for r in range(n):
+            sc = float(h["hit_score"][k, r])
+            a, b = plan.windows[w0[r]], plan.windows[w1[r]]
+            hits.append(KeywordHit(keyword=texts[k], keyword_index=k, start=a.start_s + j0[r] * a.shift,
+                                   end=b.start_s + (j1[r] + 1) * b.shift, score=sc, confidence=math.exp(sc / len(ids)),
+                                   start_frame=j0[r], end_frame=j1[r], segment=w0[r], end_segment=w1[r]))
+    return hits, truncated
+
+
 def sort_keyword_hits(hits):
     """By start time, then keyword index (then end time)."""
     return sorted(hits, key=lambda x: (x.start, x.keyword_index, x.end))

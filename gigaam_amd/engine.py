@@ -306,6 +306,101 @@ class KeywordHits(_Packed):
         return self._host_fields(self.whole, dense_score=self.dense_score, dense_start=self.dense_start)
 
 
+class KeywordStreamHits(_Packed):
+    """What ``KeywordStream.finish`` returns: the hits of every keyword over ONE stream as views of ONE i32 device buffer (``whole``) that
+    reaches the host in ONE copy (``host``).  Layout: n_hits [K] | status [K] | hit_frames [K, H, 2] (start, end; stream frames) |
+    hit_score [K, H] (f32 bits) | range flag word.  ``n_hits`` counts every hit of the stream (above H: the first H are listed);
+    ``status`` is that of the stream's LAST call (gam_op_ctc_kws_stream)."""
+    DIMS = ("k", "max_hits")
+    FIELDS = (("n_hits", ("k",), _I32), ("status", ("k",), _I32), ("hit_frames", ("k", "h", 2), _I32), ("hit_score", ("k", "h"), _F32),
+              ("ext", (1,), _I32))
+
+    @classmethod
+    def _dims(cls, k: int, max_hits: int) -> Dict[str, int]:
+        return {"k": k, "h": max(max_hits, 0)}
+
+    def __init__(self, whole: Tensor, k: int, max_hits: int, event=None, stream=None):
+        self.whole, self.event, self.stream = whole, event, stream
+        self._bind(whole, k, max_hits)
+
+    def host(self, check: bool = True) -> Dict[str, Any]:
+        """One blocking D2H of the whole result, on the collect stream behind the END call's completion event -> numpy arrays ``n_hits``
+        [K], ``status`` [K], ``hit_frames`` [K, H, 2], ``hit_score`` [K, H] and ``flag`` (as ``KeywordHits.host``).  A zero in
+        ``status`` -- the library refused a call of this stream for that keyword -- raises ``GigaAMHipError`` unless ``check`` is off."""
+        h = self._host_fields(self.whole)
+        if check and not h["status"].all():
+            raise GigaAMHipError(f"keyword stream: the call was refused for keywords {np.nonzero(h['status'] == 0)[0].tolist()[:8]} (the "
+                                 "state was not begun or has ended, a frame was skipped, or set_keywords was called during the stream)")
+        return h
+
+
+class KeywordStream:
+    """Keyword search over one stream of any length fed in pieces (``HipEngine.kws_stream``; gam_op_ctc_kws_stream): owns the state
+    record and the hit arrays of the keyword set that was at hand when it was made.  ``push`` enqueues the next rows, ``finish`` ends the
+    stream; neither synchronises the host."""
+    BEGIN, END = 1, 2      # include/gigaam_hip.h GAM_KWS_STREAM_BEGIN / _END
+
+    def __init__(self, engine: "HipEngine", max_hits: int = 8):
+        self.engine, self.max_hits = engine, int(max_hits)
+        key = getattr(engine, "_keywords_key", None)
+        self.k = len(key[0]) if key else 0
+        nbytes = int(engine.lib.gam_ctc_kws_state_bytes(engine._h))
+        if nbytes < 0:
+            engine._check(-1, "gam_ctc_kws_state_bytes")
+        if nbytes != self.k * engine.KWS_STATE_WORDS * 4:
+            raise GigaAMHipError(f"keyword stream: {nbytes} state bytes for {self.k} keywords, expected {engine.KWS_STATE_WORDS * 4} each")
+        self.state = torch.zeros((nbytes // 4,), dtype=_I32, device=engine.device)
+        # (max_hits outside [1, 4096] is the library's error at the first push; the buffers only must not be negative)
+        self.out = KeywordStreamHits.empty(engine.device, self.k, self.max_hits)
+        self.t_next, self.begun, self.ended, self.v = 0, False, False, None
+
+    def _call(self, log_probs: Optional[Tensor], v: int, flags: int, dense: bool, overlap: bool):
+        eng = self.engine
+        if self.ended:
+            raise GigaAMHipError("keyword stream: the stream has ended (finish); make a new one with kws_stream()")
+        key = getattr(eng, "_keywords_key", None)
+        if (len(key[0]) if key else 0) != self.k:      # (before BEGIN and before any launch: see op_ctc_kws_stream)
+            raise GigaAMHipError(f"keyword stream: made for {self.k} keywords, the set at hand has {len(key[0]) if key else 0} "
+                                 "(set_keywords was called with another set since kws_stream(); make a new stream)")
+        if not self.begun:
+            flags |= self.BEGIN
+        side = eng._decode_side_stream() if overlap else None
+        if overlap:
+            side.wait_stream(torch.cuda.current_stream(eng.device))
+        with torch.cuda.stream(side) if overlap else torch.cuda.device(eng.device):
+            rows = eng.op_ctc_kws_stream(log_probs, v, self.t_next, flags, self.state, self.out, dense)
+            if overlap:      # allocated on the launch stream, last used on the side stream
+                for t in (log_probs, self.state, self.out.whole):
+                    if t is not None:
+                        t.record_stream(side)
+        self.begun = True
+        self.t_next += 0 if log_probs is None else int(log_probs.shape[0])
+        self.ended = bool(flags & self.END)
+        return rows
+
+    def push(self, log_probs: Tensor, dense: bool = False, overlap: bool = False):
+        """Enqueue the search of the next ``n`` rows (log_probs f32 [n, V], used as they are; n = 0 is legal); the first call begins
+        the stream.  ``overlap``: on the engine's decode SIDE stream, behind everything enqueued on the current stream so far (as
+        ``rnnt_greedy(overlap=True)``) -- the caller's next encoder call then runs beside this search; the library orders the
+        decode-class calls of a handle whatever streams they run on.  ``dense``: returns this call's (dense_score f32, dense_start
+        i32) [K, n], allocated on the stream the call ran on."""
+        log_probs = self.engine._dev(log_probs, torch.float32)
+        if log_probs.dim() != 2:
+            raise GigaAMHipError(f"keyword stream: log_probs must be [n, V], got {tuple(log_probs.shape)}")
+        self.v = int(log_probs.shape[1])
+        return self._call(log_probs, self.v, 0, dense, overlap)
+
+    def finish(self, consume_flag: bool = False) -> KeywordStreamHits:
+        """The END call (no rows: it emits the open candidate), on the current stream -> the stream's ``KeywordStreamHits``.
+        ``consume_flag``: the rows came from this engine's encoder -- move the split-fp16 range flag into the result's flag word."""
+        v = self.v
+        if v is None:      # nothing was pushed: any V that the keyword ids fit
+            v = max((max(p) for p in self.engine._keywords_key[0]), default=0) + 2
+        self._call(None, v, self.END, False, False)
+        with torch.cuda.device(self.engine.device):
+            return self.engine._finish(self.out, consume_flag)
+
+
 class AlignedLong(_Packed):
     """What ``op_ctc_align_long`` returns: every output of the long-utterance alignment as a view of ONE i32 device buffer (``whole``)
     that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: score (f64 bits, 2 words) | loglik (f64 bits, 2 words) |
@@ -1201,6 +1296,39 @@ class HipEngine:
                                          self._stream())
             self._check(rc, "gam_op_ctc_kws")
             return self._finish(out, False)
+
+    MAX_KEYWORD_STREAM_HITS = 4096     # include/gigaam_hip.h gam_op_ctc_kws_stream
+    KWS_STATE_WORDS = 272              # gam_kws.h GAM_KWS_ST_WORDS: gam_ctc_kws_state_bytes / (4 K)
+
+    def op_ctc_kws_stream(self, log_probs: Optional[Tensor], v: int, t_base: int, flags: int, state: Tensor, out: KeywordStreamHits,
+                          dense: bool = False):
+        """gam_op_ctc_kws_stream as it is, on the current stream: rows ``log_probs`` f32 [n, V] (None: n = 0) are stream frames
+        ``t_base`` .., ``flags`` of ``KeywordStream.BEGIN`` / ``END``, ``state`` the i32 buffer of gam_ctc_kws_state_bytes, ``out`` the
+        stream's hit arrays.  ``dense``: returns (dense_score f32, dense_start i32) [K, n].  ``KeywordStream`` is the caller that
+        keeps ``t_base`` and the flags right."""
+        n = 0 if log_probs is None else int(log_probs.shape[0])
+        # The library launches a wave per keyword of the set AT HAND and cannot see how large the caller's buffers are: buffers made
+        # for a set of another size would be read and written out of bounds, so that is refused here, before any launch.  (A set of the
+        # same size but other content is the kernel's refusal: status 0.  No set at all is the library's error.)
+        key = getattr(self, "_keywords_key", None)
+        k_now = len(key[0]) if key else 0
+        if k_now and (out.k != k_now or state.numel() != k_now * self.KWS_STATE_WORDS):
+            raise GigaAMHipError(f"keyword stream: the state and the hit arrays were made for {out.k} keywords, the set at hand has {k_now} "
+                                 "(set_keywords was called with another set since kws_stream(); make a new stream)")
+        ds = torch.empty((out.k, n), dtype=torch.float32, device=self.device) if dense else None
+        dst = torch.empty((out.k, n), dtype=torch.int32, device=self.device) if dense else None
+        rc = self.lib.gam_op_ctc_kws_stream(self._h, _ptr(log_probs if n else None), n, int(v), int(t_base), int(flags), _ptr(state),
+                                            out.max_hits, _ptr(out.hit_frames), _ptr(out.hit_score), _ptr(out.n_hits), _ptr(out.status),
+                                            _ptr(ds), _ptr(dst), self._stream())
+        self._check(rc, "gam_op_ctc_kws_stream")
+        return (ds, dst) if dense else None
+
+    def kws_stream(self, max_hits: int = 8) -> KeywordStream:
+        """A resumable keyword search over one stream of any length (gam_op_ctc_kws_stream) for the set of ``set_keywords``: feed it
+        with ``push``, end it with ``finish``.  Its buffers are sized for the set at hand NOW.  After ``set_keywords`` with a set of another
+        size every call of the stream raises ``GigaAMHipError`` before anything is launched; with another set of the same size the kernel
+        refuses the calls (status 0, ``host()`` raises)."""
+        return KeywordStream(self, max_hits)
 
     def set_lm(self, lm=None, tokenizer=None, weight: float = 0.5, word_bonus: float = 1.0) -> None:
         """An n-gram LM (``lm.NgramLM``) for the beam search, its words spelt by ``tokenizer`` (gam_set_lm); None clears it.

@@ -7,6 +7,7 @@ handle per model.
 """
 from __future__ import annotations
 
+import os
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import torch
@@ -510,13 +511,14 @@ class GigaAMASR(GigaAM):
         return out
 
     # ---- keyword search: does a phrase occur, where, and how sure (gam_ctc_kws)
-    def _keyword_setup(self, keywords, threshold, max_hits: int):
-        """(token-id lists, their text, min_score f32 [K]) of a keyword search; every error that needs no audio is raised here."""
+    def _keyword_setup(self, keywords, threshold, max_hits: int, limit: int = 64):
+        """(token-id lists, their text, min_score f32 [K]) of a keyword search; every error that needs no audio is raised here.
+        ``limit``: the most ``max_hits`` may be (64 per utterance or speech region, 4096 per file on the windowed route)."""
         if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
             raise TypeError("keyword search needs a CTC head")
         ids = self.decoding.keyword_ids(keywords)
-        if not 1 <= int(max_hits) <= 64:
-            raise ValueError(f"max_hits={max_hits} outside [1, 64]")
+        if not 1 <= int(max_hits) <= limit:
+            raise ValueError(f"max_hits={max_hits} outside [1, {limit}]")
         tok = self.decoding.tokenizer
         texts = [w if isinstance(w, str) else tok.decode(i) for w, i in zip(keywords, ids)]
         return ids, texts, _decoding.keyword_min_scores([len(i) for i in ids], threshold)
@@ -574,7 +576,22 @@ class GigaAMASR(GigaAM):
         ``vad=``, the pack_regions keywords; the same pyannote / EnergyVAD default and warnings).  Every speech region's chunk is
         searched as one batch entry; hits come in file time (region start + frame x that region's frame shift) with the region's
         index in ``segment`` and the frames counted inside it; ``max_hits`` and ``truncated`` apply per region.  An occurrence that
-        straddles two regions is NOT found: the regions are searched independently and nothing is stitched."""
+        straddles two regions is NOT found: the regions are searched independently and nothing is stitched.
+
+        ``vad="windows"`` needs no speech detector and loses nothing at a cut: the recording is cut into overlapping windows
+        (keywords ``chunk_length_s=20.0`` / ``stride_length_s=None`` as for ``transcribe_longform``; they belong to this route alone --
+        without ``vad="windows"`` they go with the other keywords to the chunk packer, which refuses them as it always has, so such a
+        call runs exactly what it ran before), their kept frames are stitched into ONE stream and the
+        keywords are searched over that stream, batch by batch beside the next batch's encoder (``_find_keywords_windows``).  There
+        ``max_hits`` (1..4096) and ``truncated`` count per keyword over the whole file; a hit's ``segment`` / ``end_segment`` are the
+        windows its start and end frames were kept from, ``start_frame`` / ``end_frame`` the local frames inside those windows."""
+        if isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows":
+            more = set(kwargs) - {"vad", "chunk_length_s", "stride_length_s"}
+            if more:
+                raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(more)}): there are no speech '
+                                 "regions to give or to pack")
+            return self._find_keywords_windows(wav_file, keywords, threshold, max_hits, fr_batch_size, kwargs.get("chunk_length_s", 20.0),
+                                               kwargs.get("stride_length_s"))
         from .feeder import BatchFeeder
         from .timestamps_utils import compute_frame_shift
         from .vad_utils import segment_audio_file
@@ -869,10 +886,13 @@ class GigaAMASR(GigaAM):
         return audio, plan_windows(int(audio.shape[0]), frame_samples, lambda n: eng.enc_frames(eng.feat_frames(n)), chunk_length_s,
                                    stride_length_s, SAMPLE_RATE)
 
-    def _stitched_log_probs(self, audio: Tensor, plan, fr_batch_size: int) -> Tuple[Tensor, Tensor]:
+    def _stitched_log_probs(self, audio: Tensor, plan, fr_batch_size: int,
+                            after_batch: Optional[Callable[[Tensor], None]] = None) -> Tuple[Tensor, Tensor]:
         """The windows of ``plan`` (views of ``audio``) through the feeder, the encoder (packed rows: host lengths) and the CTC head,
         batch by batch; each batch's kept frames go straight into one preallocated [T_total, V] buffer (gam_op_ctc_stitch).  The window
-        tables are uploaded once, nothing is read back.  Returns (the stream, the stitch statuses i32 [windows]), both on the device."""
+        tables are uploaded once, nothing is read back.  Returns (the stream, the stitch statuses i32 [windows]), both on the device.
+        ``after_batch(rows)``: called behind each batch's stitch with the rows of the stream that batch added (a view; they are
+        contiguous: from the ``dst`` of its first window to the end of its last)."""
         from .feeder import BatchFeeder
 
         eng, dev, ws = self.head.engine, self._device, plan.windows
@@ -887,6 +907,8 @@ class GigaAMASR(GigaAM):
             b = wav.shape[0]
             encoded, encoded_len = self._encode(wav, lens, getattr(feeder, "host_lengths", None))
             status.append(eng.op_ctc_stitch(eng.ctc_head(encoded), encoded_len, lo[o:o + b], hi[o:o + b], dst[o:o + b], out))
+            if after_batch is not None:
+                after_batch(out[ws[o].dst:ws[o + b - 1].dst + ws[o + b - 1].hi - ws[o + b - 1].lo])
             o += b
         return out, torch.cat(status)
 
@@ -928,6 +950,38 @@ class GigaAMASR(GigaAM):
         return LongformTranscriptionResult(segments=[
             Segment(text=" ".join(w.text for w in run_), start=run_[0].start, end=run_[-1].end, words=run_ if word_timestamps else None)
             for run_ in segment_words(words, pause_s, max_segment_s)])
+
+    def _find_keywords_windows(self, wav_file: str, keywords, threshold, max_hits: int, fr_batch_size: int, chunk_length_s: float,
+                               stride_length_s: Optional[float]) -> KeywordSearchResult:
+        """``find_keywords_longform(vad="windows")``: the plan and the stitch of ``_transcribe_windows``; behind each batch's stitch ONE
+        push of the rows that batch added into a resumable search (engine.KeywordStream, gam_op_ctc_kws_stream) -- on the decode side
+        stream, so that batch n's search runs beside batch n + 1's frontend and encoder (GAM_KWS_STREAM_OVERLAP=0: on the launch
+        stream, the A/B switch) --, then the END call and ONE collect."""
+        from .decoding import RangeOverflow
+
+        eng_max = HipEngine.MAX_KEYWORD_STREAM_HITS
+        ids, texts, min_score = self._keyword_setup(keywords, threshold, max_hits, eng_max)
+        audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
+        if not plan.windows:
+            return KeywordSearchResult(hits=[], truncated=[], keywords=list(texts))
+        eng = self.head.engine
+        overlap = os.environ.get("GAM_KWS_STREAM_OVERLAP", "1") != "0"
+
+        def run():
+            eng.set_keywords(ids, min_score)
+            search = eng.kws_stream(int(max_hits))      # (a rerun under GAM_GEMM_F32 starts a new stream: BEGIN)
+            _, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: search.push(rows, overlap=overlap))
+            h = search.finish(consume_flag=True).host()
+            if h["flag"]:
+                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+            self._check_stitch(status)
+            return h
+
+        if eng.gemm_mode != "f32":
+            eng.range_flag()     # (as the other longform paths: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
+        h = self._with_f32_fallback(run, "the file was")
+        hits, truncated = _decoding.keyword_stream_hits(h, ids, texts, plan)
+        return KeywordSearchResult(hits=_decoding.sort_keyword_hits(hits), truncated=truncated, keywords=list(texts))
 
     def _align_windows(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int, wildcard: Optional[str],
                        wildcard_penalty: float, chunk_length_s: float, stride_length_s: Optional[float]) -> LongformAlignmentResult:

@@ -215,7 +215,9 @@ class KeywordHit:
     (``end_frame`` + 1) x frame shift -- the convention of ``transcribe(word_timestamps=True)``; in a longform result they are file
     times and the frames count inside speech region ``segment``.  ``score``: the occurrence's log-likelihood ratio against the
     greedy path (<= 0; 0 where the greedy path spells the keyword); ``confidence`` = exp(score / tokens), the geometric mean of
-    that ratio per token, in (0, 1] -- UNCALIBRATED: a ranking value, not a probability of being right."""
+    that ratio per token, in (0, 1] -- UNCALIBRATED: a ranking value, not a probability of being right.  On the windowed longform route
+    (``find_keywords_longform(vad="windows")``) ``segment`` / ``end_segment`` are the windows the start and the end frame were kept
+    from and ``start_frame`` / ``end_frame`` count inside those windows; elsewhere ``end_segment`` is None."""
     keyword: str
     keyword_index: int
     start: float
@@ -225,6 +227,7 @@ class KeywordHit:
     start_frame: int
     end_frame: int
     segment: Optional[int] = None
+    end_segment: Optional[int] = None
 
 
 @dataclass

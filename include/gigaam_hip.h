@@ -229,6 +229,29 @@ int gam_ctc_kws(gam_handle* h, const float* encoded, const int32_t* enc_len, int
 /* The same from caller-supplied log-probs f32 [B, T', V] (read as they are: no normalisation). */
 int gam_op_ctc_kws(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int max_hits,
                    int32_t* hit_frames, float* hit_score, int32_t* n_hits, float* dense_score, int32_t* dense_start, void* stream);
+/* The same search for ONE stream of any length fed in pieces (resumable; gam_kws.h holds the contract).  Rows 0 .. n-1 of log_probs
+ * f32 [n, V] (read as they are) are stream frames t_base .. t_base + n - 1; every frame the call reports is a stream frame.  `state`
+ * is a caller-owned device buffer of gam_ctc_kws_state_bytes bytes (the keyword set at hand; < 0 when there is none) that carries every
+ * keyword's lattice, open candidate, hit count and next frame from call to call.  flags: GAM_KWS_STREAM_BEGIN starts a stream (the
+ * state's content is ignored; n_hits = 0, all max_hits slots -1 / -inf), GAM_KWS_STREAM_END emits the open candidate behind the last
+ * row and ends it; n = 0 is legal with either, both or none.  hit_frames i32 [K, max_hits, 2], hit_score f32 [K, max_hits] and n_hits
+ * i32 [K] are the SAME arrays in every call of a stream: hits are written as they close, n_hits counts every one (n_hits > max_hits:
+ * the list holds the first max_hits).  status i32 [K]: 1 = the call was accepted for keyword k; 0 = refused and nothing changed (the
+ * state was not begun or has ended, t_base is not its next frame, or gam_set_keywords was called since BEGIN).  dense_score f32 /
+ * dense_start i32 [K, n] (either may be NULL): E_t / S_t of this call's rows.  Errors without a launch: max_hits outside [1, 4096],
+ * n < 0, t_base < 0, t_base + n >= 2^31, V inconsistent with the keyword ids, no keyword set, a NULL required buffer.  No host
+ * synchronisation.  Decode class.
+ * BUFFER SIZES ARE THE CALLER'S: every call launches one wave per keyword of the set AT HAND (K of the last gam_set_keywords), and
+ * state, hit_frames, hit_score, n_hits, status and the dense rows must all be sized for that K at every call -- the library cannot
+ * see their sizes.  Calling with buffers made for a set of another K is the caller's error (out-of-bounds access), not a refusal;
+ * ask gam_ctc_kws_state_bytes again after every gam_set_keywords.  The device refusal covers a set of the SAME K: any successful
+ * gam_set_keywords since BEGIN, an identical re-upload included, makes the state's generation stale. */
+#define GAM_KWS_STREAM_BEGIN 1
+#define GAM_KWS_STREAM_END 2
+int64_t gam_ctc_kws_state_bytes(gam_handle* h);
+int gam_op_ctc_kws_stream(gam_handle* h, const float* log_probs, int64_t n, int V, int64_t t_base, int flags, void* state, int max_hits,
+                          int32_t* hit_frames, float* hit_score, int32_t* n_hits, int32_t* status, float* dense_score,
+                          int32_t* dense_start, void* stream);
 /* The keyword set of gam_ctc_kws: keyword i is tokens[offsets[i] .. offsets[i + 1]) (host arrays; offsets has n_keywords + 1 entries,
  * offsets[0] = 0) and reports the frames whose score reaches min_score[i] (f32 [n_keywords], finite and <= 0; U x ln(p) asks for a
  * geometric-mean likelihood ratio of p per token).  Ids outside [0, V - 2], empty keywords, more than 64 tokens in a keyword, more
