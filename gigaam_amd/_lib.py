@@ -81,6 +81,8 @@ SIGNATURES = {
     "gam_op_ctc_kws_stream": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gam_ctc_beam_stream_bytes": (C.c_int64, [_P, C.c_int, C.c_int64]),
+    "gam_op_ctc_beam_stream": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "gam_set_hotwords": (C.c_int, [_P, _P, _P, C.c_int, C.c_float]),
     "gam_set_lm": (C.c_int, [_P, _P, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.c_float, C.c_float, C.c_float]),

@@ -19,6 +19,7 @@
 #include "gam_kws.h"
 #include "gam_attn.h"
 #include "gam_beam.h"
+#include "gam_beam_stream.h"
 #include "gam_rnnt_beam.h"
 #include "gam_attn16.h"
 #include "gam_comm.h"
@@ -169,6 +170,7 @@ struct gam_handle {
   DevBuf hw_trie;                       // hotword trie of gam_set_hotwords (CSR, gam_search.h), ints: offsets | edges; empty = no hotwords
   int hw_nodes = 0, hw_words = 0, hw_max_tok = -1;
   float hw_boost = 0.f;
+  int hw_gen = 0, lm_gen = 0;           // count the successful gam_set_hotwords / gam_set_lm calls, as kw_gen: a beam stream state remembers both
   // the keyword set of gam_set_keywords (gam_kws.h): offsets [K + 1] | tokens | min_score [K] (f32 bits) in one buffer of ints; empty = no set
   DevBuf kw_dev;
   int kw_K = 0, kw_ntok = 0, kw_max_tok = -1;
@@ -2139,6 +2141,50 @@ int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_le
   return ctc_beam_launch(h, log_probs, enc_len, B, Tp, V, W, ids, frames, counts, score, logp, s);
 }
 
+// ---- the same search for one stream fed in pieces (gam_beam_stream.h gam_ctc_beam_stream_kernel).  Decode class as above; the state
+// record and the node pool are the caller's.
+int64_t gam_ctc_beam_stream_bytes(gam_handle* h, int W, int64_t max_frames) {
+  if (!h) return -1;
+  if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "CTC beam stream: beam width W=%d outside [1, %d]", W, GAM_BEAM_MAX_W);
+  if (max_frames < 0 || max_frames * W >= 2147483648ll)
+    return fail(h, -1, "CTC beam stream: max_frames=%lld x W=%d outside [0, 2^31)", (long long)max_frames, W);
+  return (int64_t)GAM_BEAM_STREAM_HDR_BYTES + max_frames * W * (int64_t)sizeof(int4);
+}
+
+int gam_op_ctc_beam_stream(gam_handle* h, const float* log_probs, int64_t n, int V, int64_t t_base, int flags, int W, void* state,
+                           int64_t state_bytes, int32_t* ids, int32_t* frames, int32_t* count, double* score, double* logp,
+                           int32_t* status, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (n < 0 || t_base < 0 || V < 2 || V > GAM_BEAM_MAX_V || n >= 2147483648ll || t_base >= 2147483648ll || t_base + n >= 2147483648ll)
+    return fail(h, -1, "CTC beam stream: bad shape n=%lld V=%d t_base=%lld (t_base + n must stay below 2^31)", (long long)n, V,
+                (long long)t_base);
+  if (flags & ~(GAM_BEAM_F_BEGIN | GAM_BEAM_F_END)) return fail(h, -1, "CTC beam stream: unknown flags 0x%x", flags);
+  if (int r = beam_check(h, "CTC beam stream", W, V, (n > 0 && !log_probs) || !state || !ids || !frames || !count || !score || !logp || !status,
+                         "CTC beam stream: the LM's token classes are for V=%d, the log-probs have V=%d"))
+    return r;
+  if (state_bytes < (int64_t)GAM_BEAM_STREAM_HDR_BYTES)
+    return fail(h, -1, "CTC beam stream: state_bytes=%lld below the record's %zu (gam_ctc_beam_stream_bytes)", (long long)state_bytes,
+                (size_t)GAM_BEAM_STREAM_HDR_BYTES);
+  // the frames the caller's pool holds at this W: the kernel refuses rows beyond them (and a state begun with more)
+  const int64_t max_frames = std::min<int64_t>((state_bytes - (int64_t)GAM_BEAM_STREAM_HDR_BYTES) / ((int64_t)W * (int64_t)sizeof(int4)),
+                                               2147483647ll / W);
+  const int K = std::min(W, V - 1);
+  const bool lm = h->lm_ng.p != nullptr;
+  const bool hw_lds = h->hw_trie.p && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX;
+  const size_t sm = gam_beam_lds_bytes(W, K, V, hw_lds ? h->hw_words : 0, lm);
+  if (sm > 160 * 1024) return fail(h, -1, "CTC beam stream: %zu bytes of LDS exceed the limit %d", sm, 160 * 1024);
+  GamBeamStreamArgs a;
+  a.lp = log_probs; a.n = (int)n; a.t_base = (int)t_base; a.max_frames = (int)max_frames; a.flags = flags;
+  a.V = V; a.W = W; a.K = K; a.hw_gen = h->hw_gen; a.lm_gen = h->lm_gen;
+  a.hw = hw_args(h, hw_lds);
+  a.lm = lm_args(h);
+  a.state = state; a.ids = ids; a.frames = frames; a.count = count; a.score = score; a.logp = logp; a.status = status;
+  static std::atomic<unsigned long long> lds_set[2];
+  static const void* const kern[2] = {(const void*)gam_ctc_beam_stream_kernel<false>, (const void*)gam_ctc_beam_stream_kernel<true>};
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)n * W * (K + 1) * 4.0);
+  return beam_launch(h, kern[lm ? 1 : 0], lds_set[lm ? 1 : 0], sm > 64 * 1024 ? 160 * 1024 : sm, 1, GAM_BEAM_NT, sm, s, &a);
+}
+
 int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offsets, int n_phrases, float boost) {
   if (!h) return -1;
   if (n_phrases < 0 || n_phrases > GAM_BEAM_MAX_PHRASES)
@@ -2186,6 +2232,7 @@ int gam_set_hotwords(gam_handle* h, const int32_t* tokens, const int32_t* offset
   HIPCHK(h, hipSetDevice(h->device));
   // a decode-class kernel still in flight may read the current trie
   if (h->dec_evt != nullptr && h->dec_evt_set) HIPCHK(h, hipEventSynchronize(h->dec_evt));
+  ++h->hw_gen;
   if (n_phrases == 0) {
     h->hw_nodes = h->hw_words = 0;
     h->hw_max_tok = -1;
@@ -2231,6 +2278,7 @@ int gam_set_lm(gam_handle* h, const int32_t* token_class, int V, const void* wor
   // a decode-class kernel still in flight may read the current tables
   if (h->dec_evt != nullptr && h->dec_evt_set) HIPCHK(h, hipEventSynchronize(h->dec_evt));
   lm_clear(h);
+  ++h->lm_gen;
   if (ngram_slots == 0) return 0;
   const size_t wb = (size_t)word_slots * 16, nbytes = (size_t)ngram_slots * 16;
   if (h->lm_cls.alloc((size_t)V) != hipSuccess || h->lm_wt.alloc(wb / 4) != hipSuccess || h->lm_ng.alloc(nbytes / 4) != hipSuccess) {

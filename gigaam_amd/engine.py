@@ -401,6 +401,103 @@ class KeywordStream:
             return self.engine._finish(self.out, consume_flag)
 
 
+class BeamStreamDecoded(_Packed):
+    """What ``BeamStream.finish`` returns: the beam search's result over ONE stream as views of ONE i32 device buffer (``whole``).
+    Layout: score (f64 bits, 2 words) | logp (f64 bits, 2 words) | count | status | ids [max_frames] | frames [max_frames] (stream
+    frames) | range flag word.  ``status`` is that of the stream's LAST call (gam_op_ctc_beam_stream)."""
+    DIMS = ("max_frames",)
+    FIELDS = (("score", (1,), _F64), ("logp", (1,), _F64), ("count", (1,), _I32), ("status", (1,), _I32),
+              ("ids", ("max_frames",), _I32), ("frames", ("max_frames",), _I32), ("ext", (1,), _I32))
+    HEAD_WORDS = 6      # score | logp | count | status: what ``host`` copies first
+
+    @classmethod
+    def _dims(cls, max_frames: int) -> Dict[str, int]:
+        # (at least one word each: the library takes no NULL ids / frames, and an empty view has no address; the attribute keeps
+        # the caller's value)
+        return {"max_frames": max(max_frames, 1)}
+
+    def __init__(self, whole: Tensor, max_frames: int, event=None, stream=None):
+        self.whole, self.event, self.stream = whole, event, stream
+        self._bind(whole, max_frames)
+
+    def host(self, check: bool = True) -> Dict[str, Any]:
+        """The result on the host, on the collect stream behind the END call's completion event: the small block and the flag word
+        first, then only ``count`` entries of ids and of frames -> ``ids`` / ``frames`` (numpy i32 [count]), ``count`` / ``status``
+        (int), ``score`` / ``logp`` (Python floats from the float64 outputs) and ``flag`` (as ``Aligned.host``).  Status 0 -- the
+        library refused the stream's last call -- raises ``GigaAMHipError`` unless ``check`` is off (ids / frames are then empty)."""
+        hw = self.HEAD_WORDS
+
+        def used(first):
+            n = int(first[0][4]) if int(first[0][5]) else 0
+            return (self.ids[:n], self.frames[:n])
+
+        head, ext, ids, frames = _to_host((self.whole[:hw], self.ext), self.event, used, also_record=(self.whole,))
+        status = int(head[5])
+        if check and not status:
+            raise GigaAMHipError("beam stream: the call was refused (the state was not begun or has ended, a frame was skipped, the width "
+                                 "or V changed, set_hotwords / set_lm was called during the stream, or rows beyond max_frames)")
+        return {"ids": ids, "frames": frames, "count": int(ids.shape[0]), "status": status, "score": float(head[:2].view(np.float64)[0]),
+                "logp": float(head[2:4].view(np.float64)[0]), "flag": HipEngine._flag_of(int(ext[-1]))}
+
+
+class BeamStream:
+    """CTC prefix beam search over one stream of any length fed in pieces (``HipEngine.beam_stream``; gam_op_ctc_beam_stream): owns
+    the state record with its node pool and the result.  The hotword set and the LM are those the engine holds at the first ``push``;
+    the kernel refuses the calls that follow a later ``set_hotwords`` / ``set_lm``.  ``push`` enqueues the next rows, ``finish`` ends
+    the stream; neither synchronises the host."""
+    BEGIN, END = 1, 2      # include/gigaam_hip.h GAM_BEAM_STREAM_BEGIN / _END
+
+    def __init__(self, engine: "HipEngine", beam_size: int, max_frames: int):
+        engine._check_beam(beam_size)
+        self.engine, self.beam_size, self.max_frames = engine, int(beam_size), int(max_frames)
+        nbytes = int(engine.lib.gam_ctc_beam_stream_bytes(engine._h, self.beam_size, self.max_frames))
+        if nbytes < 0:
+            engine._check(-1, "gam_ctc_beam_stream_bytes")
+        self.state = torch.zeros(((nbytes + 3) // 4,), dtype=_I32, device=engine.device)
+        self.out = BeamStreamDecoded.empty(engine.device, self.max_frames)
+        self.out.whole[:BeamStreamDecoded.HEAD_WORDS].zero_()      # (a stream refused before its END call has status 0, count 0)
+        self.t_next, self.begun, self.ended, self.v = 0, False, False, None
+
+    def _call(self, log_probs: Optional[Tensor], v: int, flags: int, overlap: bool) -> None:
+        eng = self.engine
+        if self.ended:
+            raise GigaAMHipError("beam stream: the stream has ended (finish); make a new one with beam_stream()")
+        if not self.begun:
+            flags |= self.BEGIN
+        side = eng._decode_side_stream() if overlap else None
+        if overlap:
+            side.wait_stream(torch.cuda.current_stream(eng.device))
+        with torch.cuda.stream(side) if overlap else torch.cuda.device(eng.device):
+            eng.op_ctc_beam_stream(log_probs, v, self.t_next, flags, self.beam_size, self.state, self.out)
+            if overlap:      # allocated on the launch stream, last used on the side stream
+                for t in (log_probs, self.state, self.out.whole):
+                    if t is not None:
+                        t.record_stream(side)
+        self.begun = True
+        self.t_next += 0 if log_probs is None else int(log_probs.shape[0])
+        self.ended = bool(flags & self.END)
+
+    def push(self, log_probs: Tensor, overlap: bool = False) -> None:
+        """Enqueue the search of the next ``n`` rows (log_probs f32 [n, V], used as they are; n = 0 is legal); the first call begins
+        the stream.  ``overlap``: on the engine's decode SIDE stream, behind everything enqueued on the current stream so far (as
+        ``KeywordStream.push``) -- the caller's next encoder call then runs beside this search."""
+        log_probs = self.engine._dev(log_probs, torch.float32)
+        if log_probs.dim() != 2:
+            raise GigaAMHipError(f"beam stream: log_probs must be [n, V], got {tuple(log_probs.shape)}")
+        self.v = int(log_probs.shape[1])
+        self._call(log_probs, self.v, 0, overlap)
+
+    def finish(self, consume_flag: bool = False) -> BeamStreamDecoded:
+        """The END call (no rows: the final pick and the backtrack), on the current stream -> the stream's ``BeamStreamDecoded``.
+        ``consume_flag``: the rows came from this engine's encoder -- move the split-fp16 range flag into the result's flag word."""
+        v = self.v
+        if v is None:      # nothing was pushed: the V of the LM at hand, else any V the hotword ids fit
+            v = self.engine._beam_stream_v()
+        self._call(None, v, self.END, False)
+        with torch.cuda.device(self.engine.device):
+            return self.engine._finish(self.out, consume_flag)
+
+
 class AlignedLong(_Packed):
     """What ``op_ctc_align_long`` returns: every output of the long-utterance alignment as a view of ONE i32 device buffer (``whole``)
     that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: score (f64 bits, 2 words) | loglik (f64 bits, 2 words) |
@@ -1330,6 +1427,39 @@ class HipEngine:
         refuses the calls (status 0, ``host()`` raises)."""
         return KeywordStream(self, max_hits)
 
+    BEAM_STREAM_REBASE = 1024      # gam_beam_stream.h GAM_BEAM_STREAM_REBASE
+
+    def op_ctc_beam_stream(self, log_probs: Optional[Tensor], v: int, t_base: int, flags: int, beam_size: int, state: Tensor,
+                           out: BeamStreamDecoded) -> None:
+        """gam_op_ctc_beam_stream as it is, on the current stream: rows ``log_probs`` f32 [n, V] (None: n = 0) are stream frames
+        ``t_base`` .., ``flags`` of ``BeamStream.BEGIN`` / ``END``, ``state`` the i32 buffer of gam_ctc_beam_stream_bytes, ``out`` the
+        stream's result.  ``BeamStream`` is the caller that keeps ``t_base`` and the flags right."""
+        n = 0 if log_probs is None else int(log_probs.shape[0])
+        # The library sizes the node pool -- and with it how many tokens the END call may write -- from the state's bytes and this W:
+        # it is told no more bytes than ``out.max_frames`` frames take, so that ids / frames [max_frames] hold whatever it writes.
+        nbytes = state.numel() * 4
+        if 1 <= int(beam_size) <= self.MAX_BEAM:
+            nbytes = min(nbytes, int(self.lib.gam_ctc_beam_stream_bytes(self._h, int(beam_size), out.max_frames)))
+        rc = self.lib.gam_op_ctc_beam_stream(self._h, _ptr(log_probs if n else None), n, int(v), int(t_base), int(flags), int(beam_size),
+                                             _ptr(state), nbytes, _ptr(out.ids), _ptr(out.frames), _ptr(out.count), _ptr(out.score),
+                                             _ptr(out.logp), _ptr(out.status), self._stream())
+        self._check(rc, "gam_op_ctc_beam_stream")
+
+    def beam_stream(self, beam_size: int, max_frames: int) -> BeamStream:
+        """A resumable CTC prefix beam search over one stream of at most ``max_frames`` frames (gam_op_ctc_beam_stream), with the
+        hotwords of ``set_hotwords`` and the LM of ``set_lm``: feed it with ``push``, end it with ``finish``.  After a later
+        ``set_hotwords`` / ``set_lm`` the kernel refuses the stream's calls (status 0, ``host()`` raises)."""
+        return BeamStream(self, beam_size, max_frames)
+
+    def _beam_stream_v(self) -> int:
+        """The V of a beam stream's END call when no row was pushed: the LM's, else the head's, else any the hotword ids fit."""
+        if getattr(self, "_lm_key", None) is not None:
+            return self._lm_v
+        if int(self.cfg.num_classes) >= 2:
+            return int(self.cfg.num_classes)
+        key = getattr(self, "_hotwords_key", None)
+        return max((max(p) for p in key[0]), default=0) + 2 if key else 2
+
     def set_lm(self, lm=None, tokenizer=None, weight: float = 0.5, word_bonus: float = 1.0) -> None:
         """An n-gram LM (``lm.NgramLM``) for the beam search, its words spelt by ``tokenizer`` (gam_set_lm); None clears it.
         Re-uploads only when the model, the tokenizer or a parameter changed; a setup call that waits for in-flight decodes."""
@@ -1342,6 +1472,7 @@ class HipEngine:
         else:
             t = lm.device_tables(tokenizer)
             cls = np.ascontiguousarray(t["classes"], dtype=np.int32)
+            self._lm_v = int(cls.shape[0])
             wt, ng = np.ascontiguousarray(t["words"]), np.ascontiguousarray(t["ngrams"])
             rc = self.lib.gam_set_lm(self._h, cls.ctypes.data, int(cls.shape[0]), wt.ctypes.data, int(wt.shape[0]), int(t["word_probe"]),
                                      ng.ctypes.data, int(ng.shape[0]), int(t["ngram_probe"]), int(lm.order), int(lm.bos), int(lm.eos),

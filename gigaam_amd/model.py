@@ -799,7 +799,7 @@ class GigaAMASR(GigaAM):
                             hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
                             lm_weight: float = 0.5, word_bonus: float = 1.0, chunk_length_s: float = 20.0,
                             stride_length_s: Optional[float] = None, pause_s: float = 1.0, max_segment_s: float = 22.0,
-                            **kwargs: Any) -> LongformTranscriptionResult:
+                            stream_search: bool = False, **kwargs: Any) -> LongformTranscriptionResult:
         """Segment -> zero-padded batches of ``fr_batch_size`` -> transcribe -> stitch
         (reference model.py:195-259).  The reference segments with pyannote's VAD
         (gated third-party model, not installable here); pass ``speech_regions=[(s,e),..]``,
@@ -816,14 +816,26 @@ class GigaAMASR(GigaAM):
 
         ``vad="windows"`` (CTC heads) needs no speech detector: the recording is cut into overlapping windows of ``chunk_length_s``
         seconds, ``stride_length_s`` seconds (default: a sixth of the chunk) at each inner window edge are dropped, and what is left is
-        decoded as ONE utterance (``_transcribe_windows``); ``pause_s`` / ``max_segment_s`` cut its words into segments."""
-        if isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows":
-            if beam_size is not None or hotwords is not None or lm is not None:
+        decoded as ONE utterance (``_transcribe_windows``); ``pause_s`` / ``max_segment_s`` cut its words into segments.  With
+        ``stream_search=True`` and at least one of ``beam_size`` / ``hotwords`` / ``lm`` that utterance is decoded by the resumable
+        beam search instead (``_transcribe_windows_beam``): the LM then sees the whole file as ONE history, <s> at its first frame
+        and </s> at its end."""
+        windows = isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows"
+        search = beam_size is not None or hotwords is not None or lm is not None
+        if stream_search and not windows:
+            raise ValueError('stream_search=True searches the stitched stream of vad="windows"; the other routes search chunk by chunk')
+        if windows:
+            if search and not stream_search:
                 raise ValueError('vad="windows" decodes greedily: the beam kernel stops at 8192 frames, so beam_size / hotwords / lm over '
-                                 "the stitched stream are not available")
+                                 "the stitched stream are not available without stream_search=True (the resumable beam search)")
+            if stream_search and not search:
+                raise ValueError("stream_search=True needs beam_size, hotwords or lm: there is nothing to search with")
             if set(kwargs) - {"vad"}:
                 raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(set(kwargs) - {"vad"})}): there are no speech '
                                  "regions to give or to pack")
+            if stream_search:
+                return self._transcribe_windows_beam(wav_file, word_timestamps, fr_batch_size, chunk_length_s, stride_length_s, pause_s,
+                                                     max_segment_s, beam_size, hotwords, hotword_boost, lm, lm_weight, word_bonus)
             return self._transcribe_windows(wav_file, word_timestamps, fr_batch_size, chunk_length_s, stride_length_s, pause_s,
                                             max_segment_s)
         from .vad_utils import segment_audio_file
@@ -925,8 +937,6 @@ class GigaAMASR(GigaAM):
         segments are runs of words (windows.segment_words).  The defaults of ``stride_length_s``, ``pause_s`` and ``max_segment_s``
         are conventions, not measurements."""
         from .decoding import RangeOverflow
-        from .timestamps_utils import longform_words
-        from .windows import segment_words
 
         audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
         if not plan.windows:
@@ -944,12 +954,55 @@ class GigaAMASR(GigaAM):
         if eng.gemm_mode != "f32":
             eng.range_flag()     # (as the other longform paths: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
         ids, frames = self._with_f32_fallback(run, "the file was")
+        return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)
+
+    def _windows_result(self, plan, ids: List[int], frames: List[int], word_timestamps: bool, pause_s: float,
+                        max_segment_s: float) -> LongformTranscriptionResult:
+        """Token ids and their frames of the stitched stream of ``plan`` -> words on file times -> segments."""
+        from .timestamps_utils import longform_words
+        from .windows import segment_words
+
         wins, local, _ = plan.locate(frames)
         words, _ = longform_words(self.decoding.tokenizer, ids, wins, local, [(w.start_s, w.start_s) for w in plan.windows],
                                   [w.shift for w in plan.windows])
         return LongformTranscriptionResult(segments=[
             Segment(text=" ".join(w.text for w in run_), start=run_[0].start, end=run_[-1].end, words=run_ if word_timestamps else None)
             for run_ in segment_words(words, pause_s, max_segment_s)])
+
+    def _transcribe_windows_beam(self, wav_file: str, word_timestamps: bool, fr_batch_size: int, chunk_length_s: float,
+                                 stride_length_s: Optional[float], pause_s: float, max_segment_s: float, beam_size: Optional[int],
+                                 hotwords, hotword_boost: float, lm, lm_weight: float, word_bonus: float) -> LongformTranscriptionResult:
+        """``transcribe_longform(vad="windows", stream_search=True)``: the plan and the stitch of ``_transcribe_windows``; behind each
+        batch's stitch ONE push of the rows that batch added into a resumable beam search (engine.BeamStream, gam_op_ctc_beam_stream)
+        -- on the decode side stream, so that batch n's search runs beside batch n + 1's frontend and encoder
+        (GAM_BEAM_STREAM_OVERLAP=0: on the launch stream, the A/B switch) --, then the END call and ONE collect.  The hotwords and
+        the LM are set as ``transcribe`` sets them; the LM's history is the whole file's."""
+        from .decoding import RangeOverflow
+
+        audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
+        width = self._beam_width(beam_size, hotwords, lm)
+        if not 1 <= width <= HipEngine.MAX_BEAM:
+            raise ValueError(f"beam_size {width} outside [1, {HipEngine.MAX_BEAM}]")
+        if not plan.windows:
+            return LongformTranscriptionResult(segments=[])
+        eng, dec = self.head.engine, self.decoding
+        overlap = os.environ.get("GAM_BEAM_STREAM_OVERLAP", "1") != "0"
+
+        def run():
+            eng.set_hotwords(dec.hotword_ids(hotwords), hotword_boost)
+            eng.set_lm(dec.language_model(lm), dec.tokenizer, lm_weight, word_bonus)
+            search = eng.beam_stream(width, plan.t_total)      # (a rerun under GAM_GEMM_F32 starts a new stream: BEGIN)
+            _, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: search.push(rows, overlap=overlap))
+            h = search.finish(consume_flag=True).host()
+            if h["flag"]:
+                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+            self._check_stitch(status)
+            return h["ids"].tolist(), h["frames"].tolist()
+
+        if eng.gemm_mode != "f32":
+            eng.range_flag()     # (as the other longform paths: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
+        ids, frames = self._with_f32_fallback(run, "the file was")
+        return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)
 
     def _find_keywords_windows(self, wav_file: str, keywords, threshold, max_hits: int, fr_batch_size: int, chunk_length_s: float,
                                stride_length_s: Optional[float]) -> KeywordSearchResult:

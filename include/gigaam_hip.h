@@ -275,6 +275,29 @@ int gam_ctc_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, in
 /* The same from caller-supplied log-probs f32 [B, T', V] (read as they are), 2 <= V <= 1025. */
 int gam_op_ctc_beam(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, int W, int32_t* ids,
                     int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
+/* The same search for ONE stream of any length fed in pieces (resumable; gam_beam_stream.h holds the contract).  Rows 0 .. n-1 of
+ * log_probs f32 [n, V] (read as they are) are stream frames t_base .. t_base + n - 1; every frame the call reports is a stream frame.
+ * `state` is a caller-owned device buffer (16-byte aligned) of gam_ctc_beam_stream_bytes(h, W, max_frames) bytes: the record that
+ * carries the beam from call to call, and behind it the prefix-trie pool of max_frames x W nodes.  flags: GAM_BEAM_STREAM_BEGIN
+ * starts a stream from the empty prefix (the state's content is ignored; with an LM the history starts at <s>), GAM_BEAM_STREAM_END
+ * makes the final pick behind the call's last row (pending hotword bonus dropped, last word and </s> added), backtracks and ends the
+ * stream; n = 0 is legal with either, both or none.  ids / frames i32 [max_frames], count i32 [1], score / logp f64 [1] with
+ * gam_op_ctc_beam's meanings are written by the END call only; a stream that ends without a frame gives count 0, score = logp = 0.
+ * One BEGIN | END call over T <= 1024 frames gives gam_op_ctc_beam's ids, frames and count, and its score and logp once rounded to
+ * f32; however a stream is cut into calls, the result is the same bit for bit.  Beyond 1024 frames the committed hotword bonus and
+ * the LM term are rebased into f64 offsets every 1024 stream frames (gam_beam_stream.h), so they keep their precision over hours.
+ *   status i32 [1]: 1 = the call was accepted; 0 = refused and nothing else written (the state was not begun or has ended, t_base is
+ *   not its next frame, W or V is not what BEGIN saw, gam_set_hotwords or gam_set_lm succeeded since BEGIN -- an identical re-upload
+ *   included --, or t_base + n exceeds the frames the pool holds).
+ * Errors without a launch: W outside [1, 32], V outside [2, 1025], n < 0, t_base < 0, t_base + n >= 2^31, state_bytes below the
+ * record's size, a NULL required buffer, an LM whose classes are not for this V, LDS over the limit.  gam_ctc_beam_stream_bytes is
+ * < 0 for W outside [1, 32], max_frames < 0 or max_frames x W >= 2^31.  Decode class; no host synchronisation. */
+#define GAM_BEAM_STREAM_BEGIN 1
+#define GAM_BEAM_STREAM_END 2
+int64_t gam_ctc_beam_stream_bytes(gam_handle* h, int W, int64_t max_frames);
+int gam_op_ctc_beam_stream(gam_handle* h, const float* log_probs, int64_t n, int V, int64_t t_base, int flags, int W, void* state,
+                           int64_t state_bytes, int32_t* ids, int32_t* frames, int32_t* count, double* score, double* logp,
+                           int32_t* status, void* stream);
 /* N-best of the CTC prefix beam search: the same search (same kernel up to its last frame, same hotwords and LM, same limits), then
  * the N best entries of its final beam instead of the best one, 1 <= N <= W <= 32 (an error otherwise, without a launch).  An entry's
  * value is what gam_ctc_beam's final pick ranks by: log p + committed hotword bonus + LM term with the last word and </s> (a pending
