@@ -62,13 +62,18 @@ class RangeOverflow(RuntimeError):
     directly sees it as an error, never as silently wrong ids."""
 
 
+def check_range(flag) -> None:
+    """Raise ``RangeOverflow`` if ``flag`` -- the range flag a collected result carries -- is set."""
+    if flag:
+        raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+
+
 def _ragged(dec, *rest) -> List[Tuple[List[int], List[int]]]:
     """What decode_device returned (an ``engine.Decoded``; three bare tensors are accepted) -> host lists (one D2H for
     counts + range flag, one for ids / frames)."""
     from .engine import HipEngine
     rows, flag = HipEngine.collect(dec, *rest[:2])
-    if flag:
-        raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+    check_range(flag)
     return rows
 
 
@@ -148,8 +153,7 @@ class _BeamInputs:
         """An ``engine.NBestDecoded`` -> per utterance its hypotheses ``(text, ids, frames, score, logp)``, best first (at most two
         D2H copies: ``NBestDecoded.host``); raises ``RangeOverflow`` like ``finish``."""
         h = dec.host()
-        if h["flag"]:
-            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        check_range(h["flag"])
         return [[(self.tokenizer.decode(i), i, f, float(h["score"][b][r]), float(h["logp"][b][r])) for r, (i, f) in enumerate(rows)]
                 for b, rows in enumerate(h["rows"])]
 
@@ -225,8 +229,7 @@ class CTCGreedyDecoding(_BeamInputs):
         ``NgramLM`` or a path) fuses a word n-gram LM: ``lm_weight`` * ln P(word | history) + ``word_bonus`` per word (gam_set_lm).
         ONE D2H copy; raises ``RangeOverflow`` like ``finish``."""
         h = self.decode_beam_device(head, encoded, lengths, beam_size, hotwords, hotword_boost, lm, lm_weight, word_bonus).host()
-        if h["flag"]:
-            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        check_range(h["flag"])
         return [(self.tokenizer.decode(i), i, f, float(h["score"][k]), float(h["logp"][k])) for k, (i, f) in enumerate(h["rows"])]
 
     @torch.inference_mode()
@@ -289,8 +292,7 @@ class CTCGreedyDecoding(_BeamInputs):
     def finish_keywords(self, dec) -> dict:
         """An ``engine.KeywordHits`` -> its host arrays (ONE D2H copy); raises ``RangeOverflow`` like ``finish``."""
         h = dec.host()
-        if h["flag"]:
-            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        check_range(h["flag"])
         return h
 
     MAX_ALIGN_TOKENS = 1024     # include/gigaam_hip.h gam_ctc_align
@@ -312,8 +314,7 @@ class CTCGreedyDecoding(_BeamInputs):
             h = head.engine.ctc_align(encoded, lengths, targets).host()
         else:
             h = head.engine.ctc_align(encoded, lengths, targets, star_penalty=star_penalty).host()
-        if h["flag"]:
-            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        check_range(h["flag"])
         out = []
         for i, ids in enumerate(targets):
             ok = bool(h["status"][i])
@@ -361,8 +362,7 @@ class RNNTGreedyDecoding:
         if too_long:
             raise ValueError(f"forced alignment takes at most {self.MAX_ALIGN_TOKENS} tokens per utterance (got {max(too_long)})")
         h = head.engine.rnnt_align(encoded, enc_len, targets).host()
-        if h["flag"]:
-            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        check_range(h["flag"])
         out = []
         for i, ids in enumerate(targets):
             ok = bool(h["status"][i])
@@ -419,8 +419,7 @@ class RNNTBeamDecoding(RNNTGreedyDecoding, _BeamInputs):
         ``beam_size`` / ``hotwords`` / ``hotword_boost`` default to this object's.  ONE D2H copy; raises ``RangeOverflow`` like
         ``finish``."""
         h = self.decode_device(head, encoded, enc_len, beam_size=beam_size, hotwords=hotwords, hotword_boost=hotword_boost).host()
-        if h["flag"]:
-            raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+        check_range(h["flag"])
         return [(self.tokenizer.decode(i), i, f, float(h["score"][k]), float(h["logp"][k])) for k, (i, f) in enumerate(h["rows"])]
 
     @torch.inference_mode()

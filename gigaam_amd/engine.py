@@ -334,41 +334,31 @@ class KeywordStreamHits(_Packed):
         return h
 
 
-class KeywordStream:
-    """Keyword search over one stream of any length fed in pieces (``HipEngine.kws_stream``; gam_op_ctc_kws_stream): owns the state
-    record and the hit arrays of the keyword set that was at hand when it was made.  ``push`` enqueues the next rows, ``finish`` ends the
-    stream; neither synchronises the host."""
-    BEGIN, END = 1, 2      # include/gigaam_hip.h GAM_KWS_STREAM_BEGIN / _END
+class _ResumableStream:
+    """One stream of any length fed in pieces to a resumable kernel: the bookkeeping ``KeywordStream`` and ``BeamStream`` share.  Owns
+    the state record (``state``) and the result (``out``), counts the frames (``t_next``), adds BEGIN to the first call and refuses a
+    call after the END one.  A subclass gives ``NAME`` / ``MAKER`` (for the messages), ``BEGIN`` / ``END``, ``_launch`` (the op),
+    ``_empty_v`` (the V of an END call when nothing was pushed) and, if it has one, ``_precheck``."""
 
-    def __init__(self, engine: "HipEngine", max_hits: int = 8):
-        self.engine, self.max_hits = engine, int(max_hits)
-        key = getattr(engine, "_keywords_key", None)
-        self.k = len(key[0]) if key else 0
-        nbytes = int(engine.lib.gam_ctc_kws_state_bytes(engine._h))
-        if nbytes < 0:
-            engine._check(-1, "gam_ctc_kws_state_bytes")
-        if nbytes != self.k * engine.KWS_STATE_WORDS * 4:
-            raise GigaAMHipError(f"keyword stream: {nbytes} state bytes for {self.k} keywords, expected {engine.KWS_STATE_WORDS * 4} each")
-        self.state = torch.zeros((nbytes // 4,), dtype=_I32, device=engine.device)
-        # (max_hits outside [1, 4096] is the library's error at the first push; the buffers only must not be negative)
-        self.out = KeywordStreamHits.empty(engine.device, self.k, self.max_hits)
+    def __init__(self, engine: "HipEngine", state: Tensor, out):
+        self.engine, self.state, self.out = engine, state, out
         self.t_next, self.begun, self.ended, self.v = 0, False, False, None
 
-    def _call(self, log_probs: Optional[Tensor], v: int, flags: int, dense: bool, overlap: bool):
+    def _precheck(self) -> None:
+        """What must hold before BEGIN and before any launch."""
+
+    def _call(self, log_probs: Optional[Tensor], v: int, flags: int, overlap: bool, **kw):
         eng = self.engine
         if self.ended:
-            raise GigaAMHipError("keyword stream: the stream has ended (finish); make a new one with kws_stream()")
-        key = getattr(eng, "_keywords_key", None)
-        if (len(key[0]) if key else 0) != self.k:      # (before BEGIN and before any launch: see op_ctc_kws_stream)
-            raise GigaAMHipError(f"keyword stream: made for {self.k} keywords, the set at hand has {len(key[0]) if key else 0} "
-                                 "(set_keywords was called with another set since kws_stream(); make a new stream)")
+            raise GigaAMHipError(f"{self.NAME}: the stream has ended (finish); make a new one with {self.MAKER}()")
+        self._precheck()
         if not self.begun:
             flags |= self.BEGIN
         side = eng._decode_side_stream() if overlap else None
         if overlap:
             side.wait_stream(torch.cuda.current_stream(eng.device))
         with torch.cuda.stream(side) if overlap else torch.cuda.device(eng.device):
-            rows = eng.op_ctc_kws_stream(log_probs, v, self.t_next, flags, self.state, self.out, dense)
+            rows = self._launch(log_probs, v, flags, **kw)
             if overlap:      # allocated on the launch stream, last used on the side stream
                 for t in (log_probs, self.state, self.out.whole):
                     if t is not None:
@@ -378,27 +368,68 @@ class KeywordStream:
         self.ended = bool(flags & self.END)
         return rows
 
-    def push(self, log_probs: Tensor, dense: bool = False, overlap: bool = False):
+    def push(self, log_probs: Tensor, overlap: bool = False):
         """Enqueue the search of the next ``n`` rows (log_probs f32 [n, V], used as they are; n = 0 is legal); the first call begins
         the stream.  ``overlap``: on the engine's decode SIDE stream, behind everything enqueued on the current stream so far (as
         ``rnnt_greedy(overlap=True)``) -- the caller's next encoder call then runs beside this search; the library orders the
-        decode-class calls of a handle whatever streams they run on.  ``dense``: returns this call's (dense_score f32, dense_start
-        i32) [K, n], allocated on the stream the call ran on."""
+        decode-class calls of a handle whatever streams they run on."""
+        return self._push(log_probs, overlap)
+
+    def _push(self, log_probs: Tensor, overlap: bool, **kw):
         log_probs = self.engine._dev(log_probs, torch.float32)
         if log_probs.dim() != 2:
-            raise GigaAMHipError(f"keyword stream: log_probs must be [n, V], got {tuple(log_probs.shape)}")
+            raise GigaAMHipError(f"{self.NAME}: log_probs must be [n, V], got {tuple(log_probs.shape)}")
         self.v = int(log_probs.shape[1])
-        return self._call(log_probs, self.v, 0, dense, overlap)
+        return self._call(log_probs, self.v, 0, overlap, **kw)
 
-    def finish(self, consume_flag: bool = False) -> KeywordStreamHits:
-        """The END call (no rows: it emits the open candidate), on the current stream -> the stream's ``KeywordStreamHits``.
-        ``consume_flag``: the rows came from this engine's encoder -- move the split-fp16 range flag into the result's flag word."""
-        v = self.v
-        if v is None:      # nothing was pushed: any V that the keyword ids fit
-            v = max((max(p) for p in self.engine._keywords_key[0]), default=0) + 2
-        self._call(None, v, self.END, False, False)
+    def finish(self, consume_flag: bool = False):
+        """The END call (no rows), on the current stream -> the stream's result (``out``).  ``consume_flag``: the rows came from this
+        engine's encoder -- move the split-fp16 range flag into the result's flag word."""
+        self._call(None, self._empty_v() if self.v is None else self.v, self.END, False)
         with torch.cuda.device(self.engine.device):
             return self.engine._finish(self.out, consume_flag)
+
+
+class KeywordStream(_ResumableStream):
+    """Keyword search over one stream of any length fed in pieces (``HipEngine.kws_stream``; gam_op_ctc_kws_stream): owns the state
+    record and the hit arrays of the keyword set that was at hand when it was made.  ``push`` enqueues the next rows, ``finish`` ends the
+    stream (the END call emits the open candidate) and returns its ``KeywordStreamHits``; neither synchronises the host."""
+    BEGIN, END = 1, 2      # include/gigaam_hip.h GAM_KWS_STREAM_BEGIN / _END
+    NAME, MAKER = "keyword stream", "kws_stream"
+
+    def __init__(self, engine: "HipEngine", max_hits: int = 8):
+        self.max_hits = int(max_hits)
+        self.k = self._set_size(engine)
+        nbytes = int(engine.lib.gam_ctc_kws_state_bytes(engine._h))
+        if nbytes < 0:
+            engine._check(-1, "gam_ctc_kws_state_bytes")
+        if nbytes != self.k * engine.KWS_STATE_WORDS * 4:
+            raise GigaAMHipError(f"keyword stream: {nbytes} state bytes for {self.k} keywords, expected {engine.KWS_STATE_WORDS * 4} each")
+        # (max_hits outside [1, 4096] is the library's error at the first push; the buffers only must not be negative)
+        super().__init__(engine, torch.zeros((nbytes // 4,), dtype=_I32, device=engine.device),
+                         KeywordStreamHits.empty(engine.device, self.k, self.max_hits))
+
+    @staticmethod
+    def _set_size(engine: "HipEngine") -> int:
+        key = getattr(engine, "_keywords_key", None)
+        return len(key[0]) if key else 0
+
+    def _precheck(self) -> None:      # (before BEGIN and before any launch: see op_ctc_kws_stream)
+        at_hand = self._set_size(self.engine)
+        if at_hand != self.k:
+            raise GigaAMHipError(f"keyword stream: made for {self.k} keywords, the set at hand has {at_hand} "
+                                 "(set_keywords was called with another set since kws_stream(); make a new stream)")
+
+    def _launch(self, log_probs: Optional[Tensor], v: int, flags: int, dense: bool = False):
+        return self.engine.op_ctc_kws_stream(log_probs, v, self.t_next, flags, self.state, self.out, dense)
+
+    def _empty_v(self) -> int:      # nothing was pushed: any V that the keyword ids fit
+        return max((max(p) for p in self.engine._keywords_key[0]), default=0) + 2
+
+    def push(self, log_probs: Tensor, dense: bool = False, overlap: bool = False):
+        """``_ResumableStream.push``; ``dense``: returns this call's (dense_score f32, dense_start i32) [K, n], allocated on the stream
+        the call ran on."""
+        return self._push(log_probs, overlap, dense=dense)
 
 
 class BeamStreamDecoded(_Packed):
@@ -440,62 +471,29 @@ class BeamStreamDecoded(_Packed):
                 "logp": float(head[2:4].view(np.float64)[0]), "flag": HipEngine._flag_of(int(ext[-1]))}
 
 
-class BeamStream:
+class BeamStream(_ResumableStream):
     """CTC prefix beam search over one stream of any length fed in pieces (``HipEngine.beam_stream``; gam_op_ctc_beam_stream): owns
     the state record with its node pool and the result.  The hotword set and the LM are those the engine holds at the first ``push``;
     the kernel refuses the calls that follow a later ``set_hotwords`` / ``set_lm``.  ``push`` enqueues the next rows, ``finish`` ends
-    the stream; neither synchronises the host."""
+    the stream (the END call makes the final pick and the backtrack) and returns its ``BeamStreamDecoded``; neither synchronises the host."""
     BEGIN, END = 1, 2      # include/gigaam_hip.h GAM_BEAM_STREAM_BEGIN / _END
+    NAME, MAKER = "beam stream", "beam_stream"
 
     def __init__(self, engine: "HipEngine", beam_size: int, max_frames: int):
         engine._check_beam(beam_size)
-        self.engine, self.beam_size, self.max_frames = engine, int(beam_size), int(max_frames)
+        self.beam_size, self.max_frames = int(beam_size), int(max_frames)
         nbytes = int(engine.lib.gam_ctc_beam_stream_bytes(engine._h, self.beam_size, self.max_frames))
         if nbytes < 0:
             engine._check(-1, "gam_ctc_beam_stream_bytes")
-        self.state = torch.zeros(((nbytes + 3) // 4,), dtype=_I32, device=engine.device)
-        self.out = BeamStreamDecoded.empty(engine.device, self.max_frames)
+        super().__init__(engine, torch.zeros(((nbytes + 3) // 4,), dtype=_I32, device=engine.device),
+                         BeamStreamDecoded.empty(engine.device, self.max_frames))
         self.out.whole[:BeamStreamDecoded.HEAD_WORDS].zero_()      # (a stream refused before its END call has status 0, count 0)
-        self.t_next, self.begun, self.ended, self.v = 0, False, False, None
 
-    def _call(self, log_probs: Optional[Tensor], v: int, flags: int, overlap: bool) -> None:
-        eng = self.engine
-        if self.ended:
-            raise GigaAMHipError("beam stream: the stream has ended (finish); make a new one with beam_stream()")
-        if not self.begun:
-            flags |= self.BEGIN
-        side = eng._decode_side_stream() if overlap else None
-        if overlap:
-            side.wait_stream(torch.cuda.current_stream(eng.device))
-        with torch.cuda.stream(side) if overlap else torch.cuda.device(eng.device):
-            eng.op_ctc_beam_stream(log_probs, v, self.t_next, flags, self.beam_size, self.state, self.out)
-            if overlap:      # allocated on the launch stream, last used on the side stream
-                for t in (log_probs, self.state, self.out.whole):
-                    if t is not None:
-                        t.record_stream(side)
-        self.begun = True
-        self.t_next += 0 if log_probs is None else int(log_probs.shape[0])
-        self.ended = bool(flags & self.END)
+    def _launch(self, log_probs: Optional[Tensor], v: int, flags: int) -> None:
+        self.engine.op_ctc_beam_stream(log_probs, v, self.t_next, flags, self.beam_size, self.state, self.out)
 
-    def push(self, log_probs: Tensor, overlap: bool = False) -> None:
-        """Enqueue the search of the next ``n`` rows (log_probs f32 [n, V], used as they are; n = 0 is legal); the first call begins
-        the stream.  ``overlap``: on the engine's decode SIDE stream, behind everything enqueued on the current stream so far (as
-        ``KeywordStream.push``) -- the caller's next encoder call then runs beside this search."""
-        log_probs = self.engine._dev(log_probs, torch.float32)
-        if log_probs.dim() != 2:
-            raise GigaAMHipError(f"beam stream: log_probs must be [n, V], got {tuple(log_probs.shape)}")
-        self.v = int(log_probs.shape[1])
-        self._call(log_probs, self.v, 0, overlap)
-
-    def finish(self, consume_flag: bool = False) -> BeamStreamDecoded:
-        """The END call (no rows: the final pick and the backtrack), on the current stream -> the stream's ``BeamStreamDecoded``.
-        ``consume_flag``: the rows came from this engine's encoder -- move the split-fp16 range flag into the result's flag word."""
-        v = self.v
-        if v is None:      # nothing was pushed: the V of the LM at hand, else any V the hotword ids fit
-            v = self.engine._beam_stream_v()
-        self._call(None, v, self.END, False)
-        with torch.cuda.device(self.engine.device):
-            return self.engine._finish(self.out, consume_flag)
+    def _empty_v(self) -> int:      # nothing was pushed: the V of the LM at hand, else any V the hotword ids fit
+        return self.engine._beam_stream_v()
 
 
 class AlignedLong(_Packed):

@@ -8,6 +8,7 @@ handle per model.
 from __future__ import annotations
 
 import os
+from contextlib import contextmanager
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import torch
@@ -66,6 +67,29 @@ def instantiate(node: Any) -> Any:
     return cls(**kw)
 
 
+@contextmanager
+def _f32_mode(eng: HipEngine):
+    """The engine under GAM_GEMM_F32 for the block; the mode it had comes back whatever the block does."""
+    mode = eng.gemm_mode
+    eng.set_gemm_mode("f32")
+    try:
+        yield
+    finally:
+        eng.set_gemm_mode(mode)
+
+
+def _pipeline(batches, launch: Callable[[int, Any], Any], emit: Callable[[Any], None]) -> None:
+    """The one-batch software pipeline of the chunked longform routes: ``launch(n, batch)`` (device work, no host sync) runs BEFORE
+    ``emit`` brings what ``launch`` returned for batch n - 1 to the host; the last batch is emitted after the loop."""
+    pending: List[Any] = []
+    for n, batch in enumerate(batches):
+        pending.append(launch(n, batch))
+        if len(pending) > 1:
+            emit(pending.pop(0))
+    for handle in pending:
+        emit(handle)
+
+
 class GigaAM(nn.Module):
     _check_range = True   # forward() reads the split-fp16 range flag (one 4-byte D2H + sync) and falls back to fp32
 
@@ -113,12 +137,8 @@ class GigaAM(nn.Module):
             # an activation outside fp16's range reached a split-fp16 GEMM operand (include/gigaam_hip.h,
             # gam_range_flag): the batch is repeated on the exact-fp32 MFMA path, which has no such limit
             self._warn_range("this batch was")
-            mode = eng.gemm_mode
-            eng.set_gemm_mode("f32")
-            try:
+            with _f32_mode(eng):
                 out = self.encoder(features, feature_lengths, host) if host is not None else self.encoder(features, feature_lengths)
-            finally:
-                eng.set_gemm_mode(mode)
         return out
 
     def _host_feat_lengths(self, wav_lengths) -> Optional[list]:
@@ -136,10 +156,10 @@ class GigaAM(nn.Module):
         self.encoder.engine.set_gemm_mode(mode)
 
     @staticmethod
-    def _warn_range(what: str) -> None:
+    def _warn_range(what: str, stacklevel: int = 3) -> None:
         import warnings
         warnings.warn(f"gigaam_amd: activation beyond the split-fp16 GEMM range; {what} recomputed with "
-                      "GAM_GEMM_F32 (set GAM_GEMM_MODE=f32 to use that path throughout)", RuntimeWarning, stacklevel=3)
+                      "GAM_GEMM_F32 (set GAM_GEMM_MODE=f32 to use that path throughout)", RuntimeWarning, stacklevel=stacklevel)
 
     def _encode(self, wav: Tensor, lengths: Tensor, host_lengths=None) -> Tuple[Tensor, Tensor]:
         """Internal twin of ``forward`` for the transcribe paths: fp32 in, fp32 out whatever ``fp16_encoder`` says (the
@@ -149,21 +169,31 @@ class GigaAM(nn.Module):
         feat, flen = self.preprocessor(wav.to(torch.float32), lengths)
         return self.encoder.forward_f32(feat, flen, host)
 
-    def _with_f32_fallback(self, fn: Callable[[], Any], what: str) -> Any:
+    def _encode_batch(self, wav: Tensor, lengths: Tensor) -> Tuple[Tensor, Tensor]:
+        """``_encode`` of a caller's collated batch, moved to the device; as launch_batch: sample counts still on the host (a CPU
+        ``lengths``) give a ragged batch packed rows."""
+        host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
+        return self._encode(wav.to(self._device), lengths.to(self._device), host)
+
+    def _with_f32_fallback(self, fn: Callable[[], Any], what: str, stacklevel: int = 3) -> Any:
         """Run ``fn``; if the decode it collects reports the range flag (decoding.RangeOverflow), warn and run it again
-        under GAM_GEMM_F32."""
-        from .decoding import RangeOverflow
+        under GAM_GEMM_F32.  ``stacklevel``: the warning names the frame that many above ``_warn_range`` (3: this method's caller)."""
         try:
             return fn()
-        except RangeOverflow:
+        except _decoding.RangeOverflow:
             eng = self.encoder.engine
-            self._warn_range(what)
-            mode = eng.gemm_mode
-            eng.set_gemm_mode("f32")
-            try:
+            self._warn_range(what, stacklevel)
+            with _f32_mode(eng):
                 return fn()
-            finally:
-                eng.set_gemm_mode(mode)
+
+    def _file_run(self, run: Callable[[], Any]) -> Any:
+        """The fp32 rerun protocol of every file-level longform route: ``run`` -- the whole file, raising decoding.RangeOverflow on a
+        collected flag -- under ``_with_f32_fallback``.  A flag left behind by earlier direct engine use must not cost the file an
+        fp32 rerun: it is read (that clears it) first."""
+        eng = getattr(self.encoder, "_engine", None)      # (None: not built yet -- then nothing has run on it either)
+        if eng is not None and eng.gemm_mode != "f32":
+            eng.range_flag()
+        return self._with_f32_fallback(run, "the file was", stacklevel=4)      # (the warning names the route, as it always has)
 
     @property
     def _device(self) -> torch.device:
@@ -196,12 +226,8 @@ class GigaAM(nn.Module):
         eng = self.encoder.engine
         if self._check_range and eng.gemm_mode != "f32" and eng.range_flag():
             self._warn_range("this batch was")
-            mode = eng.gemm_mode
-            eng.set_gemm_mode("f32")
-            try:
+            with _f32_mode(eng):
                 out = self._encode(wav, lengths)
-            finally:
-                eng.set_gemm_mode(mode)
         return out
 
 
@@ -409,9 +435,7 @@ class GigaAMASR(GigaAM):
         ctc = isinstance(self.decoding, _decoding.CTCGreedyDecoding)
 
         def run():
-            # as launch_batch: sample counts on the host give a ragged batch packed rows
-            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
-            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            encoded, encoded_len = self._encode_batch(wav, lengths)
             if ctc:
                 dev = self.decoding.decode_nbest_device(self.head, encoded, encoded_len, int(n_best), width, hotwords, hotword_boost, lm,
                                                         lm_weight, word_bonus)
@@ -486,9 +510,7 @@ class GigaAMASR(GigaAM):
         targets, penalty = self._wildcard_setup(texts, wildcard, wildcard_penalty)
 
         def run():
-            # as launch_batch: sample counts on the host give a ragged batch packed rows
-            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
-            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            encoded, encoded_len = self._encode_batch(wav, lengths)
             if penalty is None:
                 return self.decoding.align(self.head, encoded, encoded_len, targets), encoded_len
             return self.decoding.align(self.head, encoded, encoded_len, targets, star_penalty=penalty), encoded_len
@@ -552,9 +574,7 @@ class GigaAMASR(GigaAM):
         ids, texts, min_score = self._keyword_setup(keywords, threshold, max_hits)
 
         def run():
-            # as launch_batch: sample counts on the host give a ragged batch packed rows
-            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
-            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            encoded, encoded_len = self._encode_batch(wav, lengths)
             dec = self.decoding.find_keywords_device(self.head, encoded, encoded_len, ids, min_score, max_hits)
             return self.decoding.finish_keywords(dec), encoded_len
 
@@ -585,11 +605,7 @@ class GigaAMASR(GigaAM):
         keywords are searched over that stream, batch by batch beside the next batch's encoder (``_find_keywords_windows``).  There
         ``max_hits`` (1..4096) and ``truncated`` count per keyword over the whole file; a hit's ``segment`` / ``end_segment`` are the
         windows its start and end frames were kept from, ``start_frame`` / ``end_frame`` the local frames inside those windows."""
-        if isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows":
-            more = set(kwargs) - {"vad", "chunk_length_s", "stride_length_s"}
-            if more:
-                raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(more)}): there are no speech '
-                                 "regions to give or to pack")
+        if self._windows_route(kwargs, ("chunk_length_s", "stride_length_s")):
             return self._find_keywords_windows(wav_file, keywords, threshold, max_hits, fr_batch_size, kwargs.get("chunk_length_s", 20.0),
                                                kwargs.get("stride_length_s"))
         from .feeder import BatchFeeder
@@ -617,22 +633,16 @@ class GigaAMASR(GigaAM):
                     truncated.update(trunc)
                     seg += 1
 
-            pending = None
-            feeder = BatchFeeder(segments, fr_batch_size, self._device)
-            for wav, lens in feeder:
+            def launch(n, batch):
+                wav, lens = batch
                 encoded, encoded_len = self._encode(wav, lens, getattr(feeder, "host_lengths", None))
-                dec = self.decoding.find_keywords_device(self.head, encoded, encoded_len, ids, min_score, max_hits)
-                if pending is not None:
-                    emit(pending)
-                pending = (dec, encoded_len, lens)
-            if pending is not None:
-                emit(pending)
+                return self.decoding.find_keywords_device(self.head, encoded, encoded_len, ids, min_score, max_hits), encoded_len, lens
+
+            feeder = BatchFeeder(segments, fr_batch_size, self._device)
+            _pipeline(feeder, launch, emit)
             return _decoding.sort_keyword_hits(hits), sorted(truncated)
 
-        eng = self.head.engine
-        if eng.gemm_mode != "f32":
-            eng.range_flag()     # (as transcribe_longform: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
-        hits, truncated = self._with_f32_fallback(run, "the file was")
+        hits, truncated = self._file_run(run)
         return KeywordSearchResult(hits=hits, truncated=truncated, keywords=list(texts))
 
     # ---- transducer forced alignment: the same for RNN-T heads (gam_rnnt_align)
@@ -668,8 +678,7 @@ class GigaAMASR(GigaAM):
         targets = [tok.encode(t) if isinstance(t, str) else [int(i) for i in t] for t in texts]
 
         def run():
-            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
-            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            encoded, encoded_len = self._encode_batch(wav, lengths)
             return self.decoding.align(self.head, encoded, encoded_len, targets), encoded_len
 
         rows, encoded_len = self._with_f32_fallback(run, "this batch was")
@@ -730,8 +739,7 @@ class GigaAMASR(GigaAM):
             targets = [tok.encode(t) if isinstance(t, str) else [int(i) for i in t] for t in texts]
 
         def run():
-            host = lengths if (isinstance(lengths, Tensor) and not lengths.is_cuda) else None
-            encoded, encoded_len = self._encode(wav.to(self._device), lengths.to(self._device), host)
+            encoded, encoded_len = self._encode_batch(wav, lengths)
             if targets is not None:
                 rows = [(tok.decode(r[0]), r[0], r[1], r[-1]) for r in self.decoding.align(self.head, encoded, encoded_len, targets)]
             elif width is not None:
@@ -747,8 +755,7 @@ class GigaAMASR(GigaAM):
                 h = eng.ctc_confidence(encoded, encoded_len, ids, frames, measure=measure, aggregation=aggregation).host()
             else:
                 h = eng.rnnt_confidence(encoded, encoded_len, ids, frames, measure=measure).host()
-            if h["flag"]:
-                raise _decoding.RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
+            _decoding.check_range(h["flag"])
             return rows, h, encoded_len
 
         rows, h, encoded_len = self._with_f32_fallback(run, "this batch was")
@@ -772,6 +779,18 @@ class GigaAMASR(GigaAM):
             out.append(ConfidenceResult(text=text, words=scored, token_ids=ids, token_frames=frames, token_confidence=conf,
                                         confidence=aggregate_confidence(conf, aggregation), feasible=True))
         return out
+
+    @staticmethod
+    def _windows_route(kwargs: Dict[str, Any], allowed: Sequence[str] = (), refuse: bool = True) -> bool:
+        """Whether the segmentation keywords of a longform call select ``vad="windows"``; the route takes none but ``allowed`` beside
+        ``vad`` (``ValueError``, unless ``refuse`` is off: a caller with earlier errors to raise asks twice)."""
+        if not (isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows"):
+            return False
+        more = set(kwargs) - {"vad", *allowed}
+        if more and refuse:
+            raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(more)}): there are no speech '
+                             "regions to give or to pack")
+        return True
 
     def _default_vad(self, kwargs: Dict[str, Any], what: str) -> None:
         """The segmentation keywords of the longform calls: ``vad="energy"`` becomes the EnergyVAD stand-in; with neither ``vad`` nor
@@ -820,7 +839,7 @@ class GigaAMASR(GigaAM):
         ``stream_search=True`` and at least one of ``beam_size`` / ``hotwords`` / ``lm`` that utterance is decoded by the resumable
         beam search instead (``_transcribe_windows_beam``): the LM then sees the whole file as ONE history, <s> at its first frame
         and </s> at its end."""
-        windows = isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows"
+        windows = self._windows_route(kwargs, refuse=False)
         search = beam_size is not None or hotwords is not None or lm is not None
         if stream_search and not windows:
             raise ValueError('stream_search=True searches the stitched stream of vad="windows"; the other routes search chunk by chunk')
@@ -830,9 +849,7 @@ class GigaAMASR(GigaAM):
                                  "the stitched stream are not available without stream_search=True (the resumable beam search)")
             if stream_search and not search:
                 raise ValueError("stream_search=True needs beam_size, hotwords or lm: there is nothing to search with")
-            if set(kwargs) - {"vad"}:
-                raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(set(kwargs) - {"vad"})}): there are no speech '
-                                 "regions to give or to pack")
+            self._windows_route(kwargs)
             if stream_search:
                 return self._transcribe_windows_beam(wav_file, word_timestamps, fr_batch_size, chunk_length_s, stride_length_s, pause_s,
                                                      max_segment_s, beam_size, hotwords, hotword_boost, lm, lm_weight, word_bonus)
@@ -867,23 +884,13 @@ class GigaAMASR(GigaAM):
                     else:
                         result.append(Segment(text=text, start=start, end=end))
 
-            pending = None
             n_batches = (len(segments) + fr_batch_size - 1) // fr_batch_size
             feeder = BatchFeeder(segments, fr_batch_size, self._device)                           # pinned, double-buffered H2D
-            for k, (wav, lens) in enumerate(feeder):
-                handle = self.launch_batch(wav, lens, overlap=k + 1 < n_batches, host_lengths=getattr(feeder, "host_lengths", None),
-                                           **beam_kw)   # (RNN-T: decode n beside encoder n+1)
-                if pending is not None:
-                    emit(pending)
-                pending = handle
-            if pending is not None:
-                emit(pending)
+            _pipeline(feeder, lambda n, batch: self.launch_batch(*batch, overlap=n + 1 < n_batches,      # (RNN-T: decode n beside encoder n+1)
+                                                                 host_lengths=getattr(feeder, "host_lengths", None), **beam_kw), emit)
             return result
 
-        eng = getattr(self.encoder, "_engine", None)
-        if eng is not None and eng.gemm_mode != "f32":
-            eng.range_flag()     # a flag left behind by earlier direct engine use must not cost this file an fp32 rerun
-        return LongformTranscriptionResult(segments=self._with_f32_fallback(run, "the file was"))
+        return LongformTranscriptionResult(segments=self._file_run(run))
 
     # ---- longform without a speech detector: overlapping windows stitched on the device (windows.py, gam_stitch.h)
     def _plan_windows(self, wav_file: str, chunk_length_s: float, stride_length_s: Optional[float]):
@@ -930,30 +937,39 @@ class GigaAMASR(GigaAM):
             raise GigaAMHipError("windowed longform: the host length formula and the device disagree on a window's encoder frames "
                                  f"(stitch statuses {status.cpu().tolist()})")
 
+    def _windows_run(self, audio: Tensor, plan, fr_batch_size: int, whole: Optional[Callable[[Tensor], Dict[str, Any]]] = None,
+                     stream=None, overlap: bool = False) -> Dict[str, Any]:
+        """One pass of a windowed route over the stitched stream of ``plan`` -> its result on the host.  Either ``whole(stream)`` -- a
+        one-shot op on the finished [T_total, V] stream, brought to the host (a dict with ``flag``) -- or ``stream``, a resumable
+        search (engine.KeywordStream / BeamStream): ONE push of the rows each batch added behind that batch's stitch (``overlap``: on
+        the decode side stream, beside the next batch's frontend and encoder), then the END call and ONE collect.  Raises
+        decoding.RangeOverflow on the flag, then checks the stitch statuses."""
+        if stream is None:
+            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size)
+            h = whole(lp_all)
+        else:
+            _, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: stream.push(rows, overlap=overlap))
+            h = stream.finish(consume_flag=True).host()
+        _decoding.check_range(h["flag"])
+        self._check_stitch(status)
+        return h
+
     def _transcribe_windows(self, wav_file: str, word_timestamps: bool, fr_batch_size: int, chunk_length_s: float,
                             stride_length_s: Optional[float], pause_s: float, max_segment_s: float) -> LongformTranscriptionResult:
         """``transcribe_longform(vad="windows")``: plan -> stitched log-probs -> gam_op_ctc_greedy_long -> ONE collect.  Words follow
         ``frames_to_words``' rule on file times (each time taken in the window its frame was kept from, rounded to 3 decimals);
         segments are runs of words (windows.segment_words).  The defaults of ``stride_length_s``, ``pause_s`` and ``max_segment_s``
         are conventions, not measurements."""
-        from .decoding import RangeOverflow
-
         audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
         if not plan.windows:
             return LongformTranscriptionResult(segments=[])
         eng = self.head.engine
 
-        def run():
-            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size)
+        def greedy(lp_all: Tensor) -> Dict[str, Any]:
             rows, flag = HipEngine.collect(eng.op_ctc_greedy_long(lp_all, consume_flag=True))
-            if flag:
-                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
-            self._check_stitch(status)
-            return rows[0]
+            return {"rows": rows[0], "flag": flag}
 
-        if eng.gemm_mode != "f32":
-            eng.range_flag()     # (as the other longform paths: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
-        ids, frames = self._with_f32_fallback(run, "the file was")
+        ids, frames = self._file_run(lambda: self._windows_run(audio, plan, fr_batch_size, greedy)["rows"])
         return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)
 
     def _windows_result(self, plan, ids: List[int], frames: List[int], word_timestamps: bool, pause_s: float,
@@ -977,8 +993,6 @@ class GigaAMASR(GigaAM):
         -- on the decode side stream, so that batch n's search runs beside batch n + 1's frontend and encoder
         (GAM_BEAM_STREAM_OVERLAP=0: on the launch stream, the A/B switch) --, then the END call and ONE collect.  The hotwords and
         the LM are set as ``transcribe`` sets them; the LM's history is the whole file's."""
-        from .decoding import RangeOverflow
-
         audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
         width = self._beam_width(beam_size, hotwords, lm)
         if not 1 <= width <= HipEngine.MAX_BEAM:
@@ -988,20 +1002,13 @@ class GigaAMASR(GigaAM):
         eng, dec = self.head.engine, self.decoding
         overlap = os.environ.get("GAM_BEAM_STREAM_OVERLAP", "1") != "0"
 
-        def run():
+        def run():      # (a rerun under GAM_GEMM_F32 comes here again: a new stream, BEGIN)
             eng.set_hotwords(dec.hotword_ids(hotwords), hotword_boost)
             eng.set_lm(dec.language_model(lm), dec.tokenizer, lm_weight, word_bonus)
-            search = eng.beam_stream(width, plan.t_total)      # (a rerun under GAM_GEMM_F32 starts a new stream: BEGIN)
-            _, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: search.push(rows, overlap=overlap))
-            h = search.finish(consume_flag=True).host()
-            if h["flag"]:
-                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
-            self._check_stitch(status)
+            h = self._windows_run(audio, plan, fr_batch_size, stream=eng.beam_stream(width, plan.t_total), overlap=overlap)
             return h["ids"].tolist(), h["frames"].tolist()
 
-        if eng.gemm_mode != "f32":
-            eng.range_flag()     # (as the other longform paths: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
-        ids, frames = self._with_f32_fallback(run, "the file was")
+        ids, frames = self._file_run(run)
         return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)
 
     def _find_keywords_windows(self, wav_file: str, keywords, threshold, max_hits: int, fr_batch_size: int, chunk_length_s: float,
@@ -1010,8 +1017,6 @@ class GigaAMASR(GigaAM):
         push of the rows that batch added into a resumable search (engine.KeywordStream, gam_op_ctc_kws_stream) -- on the decode side
         stream, so that batch n's search runs beside batch n + 1's frontend and encoder (GAM_KWS_STREAM_OVERLAP=0: on the launch
         stream, the A/B switch) --, then the END call and ONE collect."""
-        from .decoding import RangeOverflow
-
         eng_max = HipEngine.MAX_KEYWORD_STREAM_HITS
         ids, texts, min_score = self._keyword_setup(keywords, threshold, max_hits, eng_max)
         audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
@@ -1020,79 +1025,83 @@ class GigaAMASR(GigaAM):
         eng = self.head.engine
         overlap = os.environ.get("GAM_KWS_STREAM_OVERLAP", "1") != "0"
 
-        def run():
+        def run():      # (a rerun under GAM_GEMM_F32 comes here again: a new stream, BEGIN)
             eng.set_keywords(ids, min_score)
-            search = eng.kws_stream(int(max_hits))      # (a rerun under GAM_GEMM_F32 starts a new stream: BEGIN)
-            _, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: search.push(rows, overlap=overlap))
-            h = search.finish(consume_flag=True).host()
-            if h["flag"]:
-                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
-            self._check_stitch(status)
-            return h
+            return self._windows_run(audio, plan, fr_batch_size, stream=eng.kws_stream(int(max_hits)), overlap=overlap)
 
-        if eng.gemm_mode != "f32":
-            eng.range_flag()     # (as the other longform paths: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
-        h = self._with_f32_fallback(run, "the file was")
-        hits, truncated = _decoding.keyword_stream_hits(h, ids, texts, plan)
+        hits, truncated = _decoding.keyword_stream_hits(self._file_run(run), ids, texts, plan)
         return KeywordSearchResult(hits=_decoding.sort_keyword_hits(hits), truncated=truncated, keywords=list(texts))
+
+    # ---- forced alignment of a whole recording: one stream, two ways to produce it (speech regions / windows), one tail
+    def _align_long_setup(self, text: Union[str, List[int]], wildcard: Optional[str], wildcard_penalty: float):
+        """(token ids, the penalty when wildcards are enabled else None, the result's text) of ``align_longform``: every error
+        that needs no audio."""
+        (ids,), penalty = self._wildcard_setup([text], wildcard, wildcard_penalty)
+        tok = self.decoding.tokenizer
+        return ids, penalty, (tok.decode(ids) if penalty is None else _wildcard.text_of(tok, ids, self.wildcard_id, wildcard))
+
+    def _align_stream(self, lp_all: Tensor, ids: List[int], penalty: Optional[float]) -> Dict[str, Any]:
+        """gam_op_ctc_align_long of ``ids`` on a finished [T_total, V] stream (wildcards enabled: with its star row) -> the host dict."""
+        eng = self.head.engine
+        star = None if penalty is None else eng.ctc_star_row(lp_all, None, penalty)
+        return eng.op_ctc_align_long(lp_all, ids, consume_flag=True, star=star).host()
+
+    def _align_long_result(self, ids: List[int], penalty: Optional[float], text_out: str, nothing: Optional[str],
+                           run: Optional[Callable[[], tuple]]) -> LongformAlignmentResult:
+        """The tail of ``align_longform`` on either route.  ``nothing``: set when there is no frame to align to (it says why) -- an
+        empty text then aligns trivially, any other is an error.  Else ``run()`` (under ``_file_run``) produces the stream, aligns it
+        and returns (the host dict of ``op_ctc_align_long``, what the text is too long for when it does not fit, ``locate(stream
+        frames) -> (segments, local frames, times)``, the segments' time origins, their frame shifts, the time spans that re-time the
+        segments or None)."""
+        from .timestamps_utils import longform_words
+
+        tok, wid = self.decoding.tokenizer, self.wildcard_id
+        if nothing is not None:
+            if ids:
+                raise ValueError(f"{nothing}: the text ({len(ids)} tokens) cannot be aligned to it")
+            return LongformAlignmentResult(text=text_out, words=[], token_ids=ids, token_segments=[], token_frames=[], token_times=[],
+                                           score=0.0, log_likelihood=0.0, segments=[], feasible=True)
+        try:
+            h, too_long_for, locate, origins, shifts, spans = self._file_run(run)
+        except GigaAMHipError as e:
+            if "gam_set_ctc_align_workspace" in str(e):
+                raise ValueError(f"the alignment lattice does not fit the workspace cap: {e}") from e
+            raise
+        if not h["status"]:
+            raise ValueError(f"the text ({len(ids)} tokens) cannot be aligned to this audio: too long for {too_long_for}")
+        token_segments, token_frames, token_times = locate(h["tok_first"].tolist())
+        more = {}
+        if penalty is None:
+            words, segs = longform_words(tok, ids, token_segments, token_frames, origins, shifts)
+        else:
+            last_segments, last_frames, _ = locate(h["tok_last"].tolist())
+            words, segs, more["gaps"] = _wildcard.longform_result(tok, ids, token_segments, token_frames, last_segments, last_frames,
+                                                                  origins, shifts, wid)
+        if spans is not None:
+            segs = [Segment(text=sg.text, start=a, end=b, words=sg.words) for sg, (a, b) in zip(segs, spans)]
+        return LongformAlignmentResult(text=text_out, words=words, token_ids=ids, token_segments=token_segments,
+                                       token_frames=token_frames, token_times=token_times, score=h["score"],
+                                       log_likelihood=h["loglik"], segments=segs, feasible=True, **more)
 
     def _align_windows(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int, wildcard: Optional[str],
                        wildcard_penalty: float, chunk_length_s: float, stride_length_s: Optional[float]) -> LongformAlignmentResult:
         """``align_longform(vad="windows")``: the same plan and the same stitch, then gam_op_ctc_align_long on the stream.  A token's
         segment is the window its frame was kept from, its frame the local frame inside that window; ``segments`` holds one Segment
         per window over the time span of its kept frames (they tile the file) with the words that start there."""
-        from .decoding import RangeOverflow
-        from .timestamps_utils import longform_words
-
-        tok = self.decoding.tokenizer
         if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
             raise TypeError("windowed longform needs a CTC head")
-        (ids,), penalty = self._wildcard_setup([text], wildcard, wildcard_penalty)
-        wid = self.wildcard_id
-        text_out = tok.decode(ids) if penalty is None else _wildcard.text_of(tok, ids, wid, wildcard)
+        ids, penalty, text_out = self._align_long_setup(text, wildcard, wildcard_penalty)
         audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
         if not plan.windows:
-            if ids:
-                raise ValueError(f"the recording holds no encoder frame: the text ({len(ids)} tokens) cannot be aligned to it")
-            return LongformAlignmentResult(text=text_out, words=[], token_ids=ids, token_segments=[], token_frames=[], token_times=[],
-                                           score=0.0, log_likelihood=0.0, segments=[], feasible=True)
-        eng = self.head.engine
+            return self._align_long_result(ids, penalty, text_out, "the recording holds no encoder frame", None)
 
         def run():
-            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size)
-            star = None if penalty is None else eng.ctc_star_row(lp_all, None, penalty)
-            h = eng.op_ctc_align_long(lp_all, ids, consume_flag=True, star=star).host()
-            if h["flag"]:
-                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
-            self._check_stitch(status)
-            return h
+            h = self._windows_run(audio, plan, fr_batch_size, lambda lp_all: self._align_stream(lp_all, ids, penalty))
+            origins = [(w.start_s, w.start_s) for w in plan.windows]      # a local frame's time counts from its window's start
+            return (h, f"its {plan.t_total} frames", plan.locate, origins, [w.shift for w in plan.windows],
+                    [(round(a, 3), round(b, 3)) for a, b in plan.spans()])
 
-        if eng.gemm_mode != "f32":
-            eng.range_flag()
-        try:
-            h = self._with_f32_fallback(run, "the file was")
-        except GigaAMHipError as e:
-            if "gam_set_ctc_align_workspace" in str(e):
-                raise ValueError(f"the alignment lattice does not fit the workspace cap: {e}") from e
-            raise
-        if not h["status"]:
-            raise ValueError(f"the text ({len(ids)} tokens) cannot be aligned to this audio: too long for its {plan.t_total} frames")
-        token_segments, token_frames, token_times = plan.locate(h["tok_first"].tolist())
-        origins = [(w.start_s, w.start_s) for w in plan.windows]      # a local frame's time counts from its window's start
-        shifts = [w.shift for w in plan.windows]
-        spans = [(round(a, 3), round(b, 3)) for a, b in plan.spans()]
-        gaps = None
-        if penalty is None:
-            words, segs = longform_words(tok, ids, token_segments, token_frames, origins, shifts)
-        else:
-            last_segments, last_frames, _ = plan.locate(h["tok_last"].tolist())
-            words, segs, gaps = _wildcard.longform_result(tok, ids, token_segments, token_frames, last_segments, last_frames, origins,
-                                                          shifts, wid)
-        segs = [Segment(text=sg.text, start=a, end=b, words=sg.words) for sg, (a, b) in zip(segs, spans)]
-        more = {} if gaps is None else {"gaps": gaps}
-        return LongformAlignmentResult(text=text_out, words=words, token_ids=ids, token_segments=token_segments,
-                                       token_frames=token_frames, token_times=token_times, score=h["score"],
-                                       log_likelihood=h["loglik"], segments=segs, feasible=True, **more)
+        return self._align_long_result(ids, penalty, text_out, None, run)
 
     @torch.inference_mode()
     def align_longform(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int = 16, wildcard: Optional[str] = None,
@@ -1119,28 +1128,18 @@ class GigaAMASR(GigaAM):
         ``vad="windows"``: no speech detector -- the whole recording as overlapping windows of ``chunk_length_s`` / ``stride_length_s``
         (as ``transcribe_longform``), stitched into one stream and aligned in one go (``_align_windows``): a token's segment is then
         the window its frame was kept from, and ``segments`` tile the file."""
-        if isinstance(kwargs.get("vad"), str) and kwargs["vad"] == "windows":
-            if set(kwargs) - {"vad"}:
-                raise ValueError(f'vad="windows" takes no segmentation keywords (got {sorted(set(kwargs) - {"vad"})}): there are no speech '
-                                 "regions to give or to pack")
+        if self._windows_route(kwargs):
             return self._align_windows(wav_file, text, fr_batch_size, wildcard, wildcard_penalty, chunk_length_s, stride_length_s)
-        from .decoding import RangeOverflow
         from .feeder import BatchFeeder
-        from .timestamps_utils import compute_frame_shift, concat_frames_to_segments, longform_words
+        from .timestamps_utils import compute_frame_shift, concat_frames_to_segments
         from .vad_utils import segment_audio_file
 
         self._require_ctc()
-        tok = self.decoding.tokenizer
-        (ids,), penalty = self._wildcard_setup([text], wildcard, wildcard_penalty)
-        wid = self.wildcard_id
-        text_out = tok.decode(ids) if penalty is None else _wildcard.text_of(tok, ids, wid, wildcard)
+        ids, penalty, text_out = self._align_long_setup(text, wildcard, wildcard_penalty)
         self._default_vad(kwargs, "align_longform")
         segments, boundaries = segment_audio_file(wav_file, SAMPLE_RATE, device=self._device, **kwargs)
         if not segments:
-            if ids:
-                raise ValueError(f"no speech found in the recording: the text ({len(ids)} tokens) cannot be aligned to it")
-            return LongformAlignmentResult(text=text_out, words=[], token_ids=ids, token_segments=[], token_frames=[], token_times=[],
-                                           score=0.0, log_likelihood=0.0, segments=[], feasible=True)
+            return self._align_long_result(ids, penalty, text_out, "no speech found in the recording", None)
         eng = self.head.engine
 
         def run():
@@ -1153,38 +1152,12 @@ class GigaAMASR(GigaAM):
                 valid = torch.arange(lp.shape[1], device=lp.device)[None, :] < encoded_len[:, None]
                 rows.append(lp[valid])                                             # each utterance's valid rows, utterance after utterance
                 seg_frames.append(encoded_len)
-            lp_all = torch.cat(rows, dim=0)
-            if penalty is None:
-                out = eng.op_ctc_align_long(lp_all, ids, consume_flag=True)
-            else:
-                out = eng.op_ctc_align_long(lp_all, ids, consume_flag=True, star=eng.ctc_star_row(lp_all, None, penalty))
-            h = out.host()
-            if h["flag"]:
-                raise RangeOverflow("activation beyond the split-fp16 GEMM range (repeat under GAM_GEMM_F32)")
-            return h, torch.cat(seg_frames).tolist()
+            h = self._align_stream(torch.cat(rows, dim=0), ids, penalty)
+            _decoding.check_range(h["flag"])
+            n = torch.cat(seg_frames).tolist()
+            shifts = [compute_frame_shift(int(seg.shape[0]), int(k)) if k else 0.0 for seg, k in zip(segments, n)]
+            starts = [b[0] for b in boundaries]
+            return (h, f"the speech found ({sum(n)} frames)", lambda frames: concat_frames_to_segments(frames, n, starts, shifts),
+                    boundaries, shifts, None)
 
-        if eng.gemm_mode != "f32":
-            eng.range_flag()     # (as transcribe_longform: a flag left behind by earlier direct engine use must not cost an fp32 rerun)
-        try:
-            h, seg_frames = self._with_f32_fallback(run, "the file was")
-        except GigaAMHipError as e:
-            if "gam_set_ctc_align_workspace" in str(e):
-                raise ValueError(f"the alignment lattice does not fit the workspace cap: {e}") from e
-            raise
-        if not h["status"]:
-            raise ValueError(f"the text ({len(ids)} tokens) cannot be aligned to this audio: too long for the speech found "
-                             f"({sum(seg_frames)} frames)")
-        shifts = [compute_frame_shift(int(seg.shape[0]), int(n)) if n else 0.0 for seg, n in zip(segments, seg_frames)]
-        token_segments, token_frames, token_times = concat_frames_to_segments(h["tok_first"].tolist(), seg_frames,
-                                                                              [b[0] for b in boundaries], shifts)
-        if penalty is None:
-            words, segs = longform_words(tok, ids, token_segments, token_frames, boundaries, shifts)
-            return LongformAlignmentResult(text=text_out, words=words, token_ids=ids, token_segments=token_segments,
-                                           token_frames=token_frames, token_times=token_times, score=h["score"],
-                                           log_likelihood=h["loglik"], segments=segs, feasible=True)
-        last_segments, last_frames, _ = concat_frames_to_segments(h["tok_last"].tolist(), seg_frames, [b[0] for b in boundaries], shifts)
-        words, segs, gaps = _wildcard.longform_result(tok, ids, token_segments, token_frames, last_segments, last_frames, boundaries,
-                                                      shifts, wid)
-        return LongformAlignmentResult(text=text_out, words=words, token_ids=ids, token_segments=token_segments,
-                                       token_frames=token_frames, token_times=token_times, score=h["score"],
-                                       log_likelihood=h["loglik"], segments=segs, feasible=True, gaps=gaps)
+        return self._align_long_result(ids, penalty, text_out, None, run)
