@@ -143,8 +143,6 @@ struct gam_handle {
                                 // tests/test_hip_hardening.py runs the decode beside another stream's GEMM both ways)
   int last_rnnt_c = 0, last_rnnt_kern = -1, last_rnnt_refused = 0;   // what the last gam_rnnt_greedy launched (gam_rnnt_last_decode)
   DevBuf rnnt_x;                // hand-off granules + status word of the cluster kernel
-  DevBuf rnnt_audit;            // -DGAM_RC_AUDIT=1 diagnosis builds: the cluster kernel's audit log
-  bool audit_pending = false; int audit_last_c = 0; long audit_decodes = 0, audit_hit_decodes = 0;
   // The decode class owns ONE set of scratch per handle (tok / logits / encp / rnnt_x / jz / jp / jl / dec_splitk_ws).  Every decode-class
   // entry point records dec_evt behind its last launch; a decode-class call on ANOTHER stream waits for it first (DecodeScope), so two
   // decodes of one handle are ordered whatever streams the caller puts them on (an overlapped decode on the side stream followed
@@ -612,16 +610,9 @@ int gam_create(const gam_config* cfg, int device_id, gam_handle** out) {
   return 0;
 }
 
-#if GAM_RC_AUDIT
-static int audit_dump(gam_handle* h);
-#endif
 void gam_destroy(gam_handle* h) {
   if (!h) return;
   hipSetDevice(h->device);
-#if GAM_RC_AUDIT
-  audit_dump(h);
-  fprintf(stderr, "[gam-audit] total: %ld of %ld cluster decodes logged at least one entry\n", h->audit_hit_decodes, h->audit_decodes);
-#endif
   for (auto& e : h->prof_events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (auto& g : h->graphs)
     if (g.second.exec) hipGraphExecDestroy(g.second.exec);
@@ -2299,46 +2290,6 @@ int gam_set_lm(gam_handle* h, const int32_t* token_class, int V, const void* wor
   return 0;
 }
 
-#if GAM_RC_AUDIT
-// diagnosis build: print what the PREVIOUS cluster decode's audit logged (called before the next decode reuses the log, and at destroy --
-// never right behind the launch: a host sync there would remove the very overlap under test)
-static int audit_dump(gam_handle* h) {
-  if (h->rnnt_audit.p == nullptr || !h->audit_pending) return 0;
-  h->audit_pending = false;
-  static std::vector<int> au(16 + 12 * GAM_RC_AUDIT_CAP);
-  HIPCHK(h, hipDeviceSynchronize());
-  HIPCHK(h, hipMemcpy(au.data(), h->rnnt_audit.p, 64, hipMemcpyDeviceToHost));
-  const int n = au[0];
-  h->audit_decodes++;
-  if (n > 0) {
-    h->audit_hit_decodes++;
-    const int m = n < GAM_RC_AUDIT_CAP ? n : GAM_RC_AUDIT_CAP;
-    HIPCHK(h, hipMemcpy(au.data(), h->rnnt_audit.p, (16 + 12 * (size_t)m) * sizeof(int), hipMemcpyDeviceToHost));
-    int by_site[16] = {0};
-    for (int k = 0; k < m; ++k) by_site[au[16 + 12 * k] & 15]++;
-    fprintf(stderr, "[gam-audit] decode %ld C=%d entries %d; by site:", h->audit_decodes, h->audit_last_c, n);
-    for (int k = 1; k < 16; ++k) if (by_site[k]) fprintf(stderr, " s%d=%d", k, by_site[k]);
-    fprintf(stderr, "\n");
-    for (int k = 0; k < m && k < 24; ++k) {
-      const int* e = au.data() + 16 + 12 * k;
-      float x0, x1; memcpy(&x0, e + 6, 4); memcpy(&x1, e + 7, 4);
-      fprintf(stderr, "[gam-audit]   site %d utt %d member %d xc %d tid %d idx %d: %.9g (%08x) vs %.9g (%08x)  aux %08x %08x\n", e[0], e[1], e[2], e[3], e[4], e[5],
-              x0, (unsigned)e[6], x1, (unsigned)e[7], (unsigned)e[8], (unsigned)e[9]);
-    }
-  }
-  return 0;
-}
-// diagnosis build: report the previous decode's log, then clear it and hand it to this launch
-static int rnnt_audit_arm(gam_handle* h, hipStream_t s, GamRnntClusterArgs& ca) {
-  if (int r = audit_dump(h)) return r;
-  h->audit_pending = true; h->audit_last_c = ca.C;
-  if (int r = ensure(h, h->rnnt_audit, 16 + 12 * GAM_RC_AUDIT_CAP)) return r;
-  HIPCHK(h, hipMemsetAsync(h->rnnt_audit.p, 0, 64, s));
-  ca.audit = reinterpret_cast<int*>(h->rnnt_audit.p);
-  return 0;
-}
-#endif
-
 // ---- RNN-T greedy decode: the argument block, the cluster plan, the kernel table, the two launches, the entry point
 static GamRnntArgs rnnt_greedy_args(const gam_handle* h, const int32_t* enc_len, int B, int64_t Tp, int max_symbols, int32_t* ids,
                                     int32_t* frames, int32_t* counts, float* logits_dump, int32_t* dump_count, int dump_cap) {
@@ -2457,9 +2408,6 @@ static int rnnt_cluster_launch(gam_handle* h, hipStream_t s, const GamRnntArgs& 
   HIPCHK(h, hipMemsetAsync(h->rnnt_x.p, 0, (p.xg * 2 + 64) * sizeof(float), s));
   ca.xbuf = reinterpret_cast<unsigned long long*>(h->rnnt_x.p);
   ca.status = reinterpret_cast<int*>(h->rnnt_x.p + p.xg * 2);
-#if GAM_RC_AUDIT
-  if (int r = rnnt_audit_arm(h, s, ca)) return r;
-#endif
   // Cooperative launch: the runtime REFUSES a grid that cannot be co-resident on this device (occupancy x CUs)
   // instead of letting resident members spin on absent ones; what it cannot see (CUs held by another queue) is
   // what the bounded spins + the repair pass are for.

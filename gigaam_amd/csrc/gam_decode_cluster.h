@@ -42,7 +42,6 @@ struct GamRnntClusterArgs {
   int wout_slice_in_lds;     // this member's class slice of W_out is cached in LDS
   int wpred_slice_in_lds;    // this member's rows of W_pred are cached in LDS ([H/4][nP][4]): the step's pp no longer waits on L2
   int force_dead;            // test hook (GAM_RNNT_FORCE_TIMEOUT=1): odd utterances report a failed hand-off without decoding
-  int* audit;                // -DGAM_RC_AUDIT=1 builds only: [0] = entries logged, entry k at [16 + 12 k] (null in production)
 };
 
 #define GAM_RC_WIN 16
@@ -61,28 +60,6 @@ enum { T_GATES = 1, T_XH, T_PRED, T_XP, T_Z, T_JOINT, T_XA, T_COMB, T_CTRL, T_RO
 // "every load issued so far has landed", as a compiler barrier too: keeps a batch of independent loads TOGETHER in front of
 // their uses (hipcc otherwise sinks each load into the conditional block that consumes it: one L2 round trip per load)
 #define GAM_RC_LOADS_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-// r06 diagnosis (-DGAM_RC_AUDIT=1, never a production build): every phase of the round is computed TWICE by the same thread from freshly
-// re-read inputs and every piece of LDS-held state is checked against a register copy kept by the thread that wrote it; any difference is
-// logged as (site, utterance, member, exchange counter, thread, index, four words).  Sites: 1 gate row recomputed differs (words: first,
-// second, xor of weight bits xor, xor of h bits xor)   2 gates[] read back != written   3 cell update recomputed differs   4 W_pred row
-// recomputed differs   5 committed h / c in LDS != the writer's register copy (index 0 h, 1 c)   6 candidate h' in LDS != register copy
-// 7 pp in LDS != register copy   8 window row in LDS (LDS-DMA) != the same row loaded from global   9 joint tile recomputed differs
-// 10 gate_tab row re-loaded != the prefetched one
-#ifndef GAM_RC_AUDIT
-#define GAM_RC_AUDIT 0
-#endif
-#define GAM_RC_AUDIT_CAP 4096
-#if GAM_RC_AUDIT
-__device__ __forceinline__ void gam_rc_audit_log(int* au, int site, int b, int cm, unsigned xc, int tid, int idx, float x0, float x1, unsigned x2, unsigned x3) {
-  const int k = atomicAdd(au, 1);
-  if (k < GAM_RC_AUDIT_CAP) {
-    int* e = au + 16 + 12 * k;
-    e[0] = site; e[1] = b; e[2] = cm; e[3] = (int)xc; e[4] = tid; e[5] = idx;
-    e[6] = __float_as_int(x0); e[7] = __float_as_int(x1); e[8] = (int)x2; e[9] = (int)x3;
-  }
-}
-#define GAM_RC_LOG(site, idx, x0, x1, x2, x3) gam_rc_audit_log(g.audit, site, b, cm, xc, tid, idx, x0, x1, x2, x3)
-#endif
 
 __device__ __forceinline__ void gam_rc_put(unsigned long long* p, float v, unsigned tag) {
   const unsigned long long w = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v);
@@ -224,9 +201,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
   int t = 0, sym = 0;
   bool need_pred = true;
   unsigned xc = 0;     // exchange counter = tag
-#if GAM_RC_AUDIT
-  float au_h[2] = {0.f, 0.f}, au_c[2] = {0.f, 0.f}, au_hn[2] = {0.f, 0.f}, au_cn[2] = {0.f, 0.f}, au_pp[2] = {0.f, 0.f};   // (nI, nP <= 512)
-#endif
   int par_h = 0, par_p = 0, par_a = 0;
   bool dead = g.force_dead && (b & 1);
 
@@ -238,20 +212,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
     tacc[T_ROUNDS] += 1;
 #endif
     if (need_pred) {
-#if GAM_RC_AUDIT
-      {
-        int k = 0;
-        for (int ii = tid; i0 + ii < i1; ii += 256, ++k) {
-          if (__float_as_uint(h_s[i0 + ii]) != __float_as_uint(au_h[k])) GAM_RC_LOG(5, 2 * ii, h_s[i0 + ii], au_h[k], 0u, 0u);
-          if (__float_as_uint(c_s[ii]) != __float_as_uint(au_c[k])) GAM_RC_LOG(5, 2 * ii + 1, c_s[ii], au_c[k], 0u, 0u);
-        }
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-          const float tv = a.gate_tab[(size_t)label * 4 * H + grow[j]];
-          if (__float_as_uint(tv) != __float_as_uint(tabv[j])) GAM_RC_LOG(10, j, tv, tabv[j], (unsigned)label, 0u);
-        }
-      }
-#endif
       // ---- LSTM gates of my units: tab[label] + W_hh.h, k ascending (same fmaf chain as the 1-workgroup kernel)
       {
         float acc[NR];
@@ -295,56 +255,9 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
           }
         }
         }
-#if GAM_RC_AUDIT
-        if constexpr (RESQ == 0) {   // second pass: the same sums from re-loaded weights and re-read h
-          float acc2[NR];
-          unsigned wx[2] = {0u, 0u}, hx[2] = {0u, 0u};
-#pragma unroll
-          for (int j = 0; j < NR; ++j) acc2[j] = tabv[j];
-          constexpr int KU2 = NR == 1 ? 40 : (NR == 2 ? 20 : (NR == 3 ? 12 : (NR == 5 ? 8 : 4)));
-          for (int pass = 0; pass < 2; ++pass) {   // pass 0 recomputes; pass 1 only re-reads (a third look at the same words)
-            for (int q0 = 0; q0 < HQ; q0 += KU2) {
-              f32x4 w[KU2][NR];
-#pragma unroll
-              for (int u = 0; u < KU2; ++u) {
-                const int q = q0 + u < HQ ? q0 + u : HQ - 1;
-#pragma unroll
-                for (int j = 0; j < NR; ++j) w[u][j] = gam_rc_glb4(g.whh_q + ((size_t)q * 4 * H + grow[j]) * 4);
-              }
-#pragma unroll
-              for (int u = 0; u < KU2; ++u) {
-                if (q0 + u < HQ) {
-                  const f32x4 hv = *reinterpret_cast<const f32x4*>(h_s + 4 * (q0 + u));
-                  hx[pass] ^= __float_as_uint(hv.x) ^ (__float_as_uint(hv.y) * 3u) ^ (__float_as_uint(hv.z) * 5u) ^ (__float_as_uint(hv.w) * 7u);
-#pragma unroll
-                  for (int j = 0; j < NR; ++j) {
-                    wx[pass] ^= (__float_as_uint(w[u][j].x) ^ (__float_as_uint(w[u][j].y) * 3u) ^ (__float_as_uint(w[u][j].z) * 5u) ^ (__float_as_uint(w[u][j].w) * 7u)) * (unsigned)(2 * j + 1);
-                    if (pass == 0) {
-                      acc2[j] = fmaf(w[u][j].x, hv.x, acc2[j]);
-                      acc2[j] = fmaf(w[u][j].y, hv.y, acc2[j]);
-                      acc2[j] = fmaf(w[u][j].z, hv.z, acc2[j]);
-                      acc2[j] = fmaf(w[u][j].w, hv.w, acc2[j]);
-                    }
-                  }
-                }
-              }
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < NR; ++j)
-            if (gok[j] && (__float_as_uint(acc2[j]) != __float_as_uint(acc[j]) || wx[0] != wx[1] || hx[0] != hx[1]))
-              GAM_RC_LOG(1, j, acc[j], acc2[j], wx[0] ^ wx[1], hx[0] ^ hx[1]);
-        }
-#endif
 #pragma unroll
         for (int j = 0; j < NR; ++j)
           if (gok[j]) gates[tid + 256 * j] = acc[j];
-#if GAM_RC_AUDIT
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NR; ++j)
-          if (gok[j] && __float_as_uint(gates[tid + 256 * j]) != __float_as_uint(acc[j])) GAM_RC_LOG(2, j, gates[tid + 256 * j], acc[j], 0u, 0u);
-#endif
       }
       __syncthreads();
     GAM_RC_MARK(T_GATES);
@@ -353,16 +266,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
         float cn, hn;
         gam_lstm_cell<true>(gates[ii], gates[nI + ii], gates[2 * nI + ii], gates[3 * nI + ii], c_s[ii], cn, hn);
         cn_s[ii] = cn;
-#if GAM_RC_AUDIT
-        {
-          const volatile float* gv = gates;
-          const volatile float* cv = c_s;
-          float cn2, hn2;
-          gam_lstm_cell<true>(gv[ii], gv[nI + ii], gv[2 * nI + ii], gv[3 * nI + ii], cv[ii], cn2, hn2);
-          if (__float_as_uint(cn2) != __float_as_uint(cn) || __float_as_uint(hn2) != __float_as_uint(hn)) GAM_RC_LOG(3, ii, hn, hn2, __float_as_uint(cn), __float_as_uint(cn2));
-          au_hn[ii >> 8] = hn; au_cn[ii >> 8] = cn;
-        }
-#endif
         if (C > 1) gam_rc_put(xh + par_h * H + i0 + ii, hn, xc);
         else hn_s[i0 + ii] = hn;
       }
@@ -378,13 +281,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
       }
       __syncthreads();
     GAM_RC_MARK(T_XH);
-#if GAM_RC_AUDIT
-      {
-        int k = 0;
-        for (int ii = tid; i0 + ii < i1; ii += 256, ++k)
-          if (__float_as_uint(hn_s[i0 + ii]) != __float_as_uint(au_hn[k])) GAM_RC_LOG(6, ii, hn_s[i0 + ii], au_hn[k], 0u, 0u);
-      }
-#endif
       if (dead_s[0]) { dead = true; break; }
       // ---- my rows of W_pred.h' + b_pred
       {
@@ -408,27 +304,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
                 }
             }
             red[rr] = acc;
-#if GAM_RC_AUDIT
-            {
-              float acc2 = a.bpred[r];
-              for (int q0 = 0; q0 < HQ; q0 += 16) {
-                f32x4 w[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                  const int q = q0 + u < HQ ? q0 + u : HQ - 1;
-                  if (wpl != nullptr) w[u] = gam_rc_lds4(wpl + ((size_t)q * nP + rr) * 4);
-                  else w[u] = gam_rc_glb4(g.wpred_q + ((size_t)q * JH + r) * 4);
-                }
-#pragma unroll
-                for (int u = 0; u < 16; ++u)
-                  if (q0 + u < HQ) {
-                    const f32x4 hv = *reinterpret_cast<const f32x4*>(hn_s + 4 * (q0 + u));
-                    acc2 = fmaf(w[u].x, hv.x, acc2); acc2 = fmaf(w[u].y, hv.y, acc2); acc2 = fmaf(w[u].z, hv.z, acc2); acc2 = fmaf(w[u].w, hv.w, acc2);
-                  }
-              }
-              if (__float_as_uint(acc2) != __float_as_uint(acc)) GAM_RC_LOG(4, rr, acc, acc2, 0u, 0u);
-            }
-#endif
           }
         } else {
           const int rr = tid % nP, part = tid / nP;
@@ -463,9 +338,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
         for (int p = 1; p < P; ++p) v += red[p * nP + rr];
         if (C > 1) gam_rc_put(xp + par_p * JH + r0 + rr, v, xc);
         else pp[r0 + rr] = v;
-#if GAM_RC_AUDIT
-        au_pp[rr >> 8] = v;
-#endif
       }
       if (C > 1) {
         for (int i = tid; i < JH; i += 512) {
@@ -488,24 +360,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
     // (the window's encoder-projection rows were fetched when t was decided, at the end of the previous round)
     __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0): my wave's LDS-DMA loads have landed ...
     __syncthreads();                      // ... and so have everyone else's
-#if GAM_RC_AUDIT
-    {
-      int k = 0;
-      for (int rr = tid; r0 + rr < r1; rr += 256, ++k)
-        if (__float_as_uint(pp[r0 + rr]) != __float_as_uint(au_pp[k])) GAM_RC_LOG(7, rr, pp[r0 + rr], au_pp[k], 0u, 0u);
-      const int Wn = len - t < GAM_RC_WIN ? len - t : GAM_RC_WIN;
-      for (int idx = tid; idx < GAM_RC_WIN * JQ; idx += 256) {
-        const int f = idx / JQ, q = idx - f * JQ;
-        int tt = t + (f < Wn ? f : Wn - 1);
-        tt = tt < 0 ? 0 : (tt < a.Tp ? tt : a.Tp - 1);
-        const f32x4 ev = *reinterpret_cast<const f32x4*>(zenc + 4 * idx);
-        const f32x4 gv = *reinterpret_cast<const f32x4*>(a.encp + ((size_t)b * a.Tp + tt) * JH + 4 * q);
-        if (__float_as_uint(ev.x) != __float_as_uint(gv.x) || __float_as_uint(ev.y) != __float_as_uint(gv.y) || __float_as_uint(ev.z) != __float_as_uint(gv.z) ||
-            __float_as_uint(ev.w) != __float_as_uint(gv.w))
-          GAM_RC_LOG(8, idx, ev.x, gv.x, (unsigned)t, (unsigned)tt);
-      }
-    }
-#endif
     for (int idx = tid; idx < GAM_RC_WIN * JQ; idx += 256) {
       const int f = idx / JQ, q = idx - f * JQ;
       const f32x4 ev = *reinterpret_cast<const f32x4*>(zenc + 4 * idx);
@@ -550,18 +404,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
       if (wout_l != nullptr) tile([](const float* p) { return gam_rc_lds4(p); }, wout_l + (size_t)(vc - v0) * WLD + 4 * lg4, false);
       else tile([](const float* p) { return gam_rc_glb4(p); }, a.wout + (size_t)vc * JH + 4 * lg4, true);
       acc = (acc + acc1) + (acc2 + acc3);
-#if GAM_RC_AUDIT
-      {
-        const f32x4 first = acc;
-        acc = (f32x4){0.f, 0.f, 0.f, 0.f}; acc1 = acc; acc2 = acc; acc3 = acc;
-        if (wout_l != nullptr) tile([](const float* p) { return gam_rc_lds4(p); }, wout_l + (size_t)(vc - v0) * WLD + 4 * lg4, false);
-        else tile([](const float* p) { return gam_rc_glb4(p); }, a.wout + (size_t)vc * JH + 4 * lg4, true);
-        acc = (acc + acc1) + (acc2 + acc3);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (__float_as_uint(first[r]) != __float_as_uint(acc[r])) GAM_RC_LOG(9, nt * 64 + lane, first[r], acc[r], (unsigned)r, 0u);
-      }
-#endif
       if (v < v1) {   // C/D: col = lane&15 = class, row = 4*(lane>>4) + r = frame
         const float bo = gam_rc_glb1(a.bout + v);
 #pragma unroll
@@ -673,9 +515,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_cluster_kernel(GamRnntClusterArg
 #pragma unroll
       for (int j = 0; j < NR; ++j) tabv[j] = gam_rc_glb1(a.gate_tab + (size_t)label * 4 * H + grow[j]);   // lands while the round finishes
       { float* x = h_s; h_s = hn_s; hn_s = x; x = c_s; c_s = cn_s; cn_s = x; }   // commit (h', c'): swap the buffers
-#if GAM_RC_AUDIT
-      au_h[0] = au_hn[0]; au_h[1] = au_hn[1]; au_c[0] = au_cn[0]; au_c[1] = au_cn[1];
-#endif
       need_pred = true;
       if (sym >= a.max_symbols) { t = te + 1; sym = 0; }   // frame advances regardless (decoding.py:189-205)
       else t = te;

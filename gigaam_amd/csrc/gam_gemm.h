@@ -3,10 +3,15 @@
 //   C[M,N] = epilogue( A[M,K] . W[N,K]^T )        ("NT": both operands K-contiguous,
 //                                                  W is a torch Linear weight as stored)
 //
-// Every dense contraction of the GigaAM hot path goes through this kernel
-// (reference gigaam/encoder.py: Linear 12288->768 :127, FFN :419-424, q/k/v/out
-// :145-148, pointwise convs :379,394; decoder.py heads), and so do the three
-// convolution-shaped ones as implicit GEMMs:
+// This kernel serves what the split-fp16 LDS-DMA kernel (gam_gemm_sp.h, the default
+// mode's encoder GEMMs) does not (gemm() in gam_api.hip):
+//   * the exact mode (GAM_GEMM_F32): every dense contraction of the encoder
+//     (reference gigaam/encoder.py: Linear 12288->768 :127, FFN :419-424, q/k/v/out
+//     :145-148, pointwise convs :379,394) and the convolution-shaped ones below;
+//   * the decode heads (decoder.py) in every mode;
+//   * in the split modes, the GEMMs whose operands are not in the sp32 layout --
+//     shapes the LDS-DMA kernel cannot take.
+// The convolution-shaped contractions run as implicit GEMMs:
 //   * a_mode 1  -- the 3x3/stride-2 Conv2d #2 of the stem (encoder.py:59-69) over a
 //                  zero-bordered channels-last image, K index = (kh,kw,c)
 //   * a_mode 0 with lda < K -- overlapping rows: the stride-2 Conv1d stem of v3 models
@@ -14,8 +19,7 @@
 //                  log-mel frontend (lda = hop = 160)
 //
 // Arithmetic is exact fp32 (MFMA f32 == an fmaf chain): parity with the reference's
-// fp32 CPU path is the first gate, and the fp32 matrix rate (157 TFLOP/s) already
-// exceeds what the 2000x real-time target needs.
+// fp32 CPU path is the first gate.
 //
 // Tiling: 128x128x32 block tile, 256 threads = 4 waves (2x2), each wave 64x64 = 2x2
 // MFMA tiles of 32x32; LDS rows padded to 36 floats (9 x 16 B, odd) so both the
@@ -72,7 +76,6 @@ struct GamGemmArgs {
   int a_fmt;            // format of the Asp operand as its producer wrote it: 1 = sp32 (hi, lo) lines, 2 = plain fp16 rows
   int h16;              // GAM_GEMM_F16 (opt-in speed mode): plain-fp16 operands, one MFMA per product; K / lda / conv_c are HALVED by the caller
   int ntiles;           // set by the launcher
-  int dbg;              // experiment switches (GAM_SP_DBG), 0 in production
   float wscale_inv;     // 2^-wshift, applied to the accumulator in the epilogue
   // split-fp16 modes: per-row pre-scale of the A operand (gam_common.h gam_row_scale).  The producing kernel stored row m
   // multiplied by 2^e_m (sp32 or fp32 alike); a_rs[m] = 2^-e_m multiplies row m's accumulators in the epilogue.
@@ -82,9 +85,7 @@ struct GamGemmArgs {
   // value beyond fp16's range written to C sets *range_flag (gam_common.h gam_range_note); may be null.
   int* range_flag;
   int c_guard;
-  long long* tlog;      // instrumented builds (GAM_SP_INSTRUMENT, GAM_SP_DBG & 16): per-workgroup timeline, 8 words per tile
-  int prio;             // LDS-DMA GEMM: s_setprio 1 for the later-dispatched half of the waves (GAM_SP_PRIO, A/B switch)
-  int tile_order;       // LDS-DMA GEMM: 0 = n innermost (the default), G > 0 = groups of G column tiles outermost (GAM_SP_ORDER, r05 experiment)
+  long long* tlog;      // instrumented builds (GAM_SP_INSTRUMENT with GAM_SP_TLOG=1): per-workgroup timeline, 8 words per tile; else null
 };
 
 #define GAM_GEMM_BM 128

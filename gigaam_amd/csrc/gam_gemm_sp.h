@@ -40,7 +40,7 @@
 // those of a 128 x 128 tile; the k-tile after next lands while the current one is multiplied.
 // Why this MFMA shape: same cycles per FLOP as 32x32x16, same LDS bytes, but under the power cap the chip holds a higher clock
 // on it (measurements: profiles/mfma16_gemm_ab.md).
-// MT in {2,3,4} and NW in {2,4} are picked per launch (gam_gemm_sp_pick) to minimise the tail of the
+// MT in {2,3,4} and NW in {2,4} are picked per launch (gam_gemm_sp_plan) to minimise the tail of the
 // last round of tiles.
 #pragma once
 #include "gam_gemm.h"
@@ -50,19 +50,16 @@
 #include <vector>
 #endif
 
-// -DGAM_SP_INSTRUMENT=1 compiles the GAM_SP_DBG experiment switches in (1: skip the epilogue, 2: one
-// k-tile only, 4: clock64 counters of the k-tile's first half / barrier / second half, written into the last C row, 8: drop the in-loop barrier).
-// They produced profiles/r01_gemm_sp_clock_random_vs_zero.txt; production builds carry none of it.
+// -DGAM_SP_INSTRUMENT=1 is the one instrumented build: the per-workgroup timeline, turned on at run time by GAM_SP_TLOG=1 -- wall clock
+// (100 MHz) at entry / operands of the first two k-tiles landed / main loop done / epilogue done, shader clock around the loop -- into
+// g.tlog[tile * 8 ..]; the launcher prints the distribution (tools/gemm_sp_test.py; profiles/r03_gemm_timeline.txt).  It measures and
+// changes nothing the kernel computes; production builds carry none of it.
 #ifndef GAM_SP_INSTRUMENT
 #define GAM_SP_INSTRUMENT 0
 #endif
-#define GAM_SP_DBG(g) (GAM_SP_INSTRUMENT ? (g).dbg : 0)
-// GAM_SP_DBG & 16 (instrumented builds): per-workgroup timeline -- wall clock (100 MHz) at entry / operands of the first two
-// k-tiles landed / main loop done / epilogue done, shader clock around the loop -- into g.tlog[tile * 8 ..]; the launcher
-// prints the distribution (tools/gemm_sp_test.py; profiles/r03_gemm_timeline.txt).
 #if GAM_SP_INSTRUMENT
 #define GAM_SP_TL(i)                                                                  \
-  if ((GAM_SP_DBG(g) & 16) && g.tlog != nullptr && threadIdx.x == 0) {                        \
+  if (g.tlog != nullptr && threadIdx.x == 0) {                                        \
     g.tlog[(size_t)lid * 8 + (i)] = wall_clock64();                                   \
     if ((i) == 1 || (i) == 2) g.tlog[(size_t)lid * 8 + 4 + (i)] = clock64();          \
     if ((i) == 0) g.tlog[(size_t)lid * 8 + 7] = blockIdx.x;                            \
@@ -130,15 +127,6 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
     // row tile on one XCD -- they share the A patch -- measured worse: conv2 0.955 of the padded launch against 0.905, r06_packed_rows_ab.txt.)
     tm = bid / nbn;
     tn = bid % nbn;
-  }
-  if (GAM_SP_INSTRUMENT && g.tile_order > 0 && nbn % g.tile_order == 0 && !g.skip_pad) {   // (r05 experiment, instrumented builds only)
-    // r05 experiment (GAM_SP_ORDER = G): groups of G column tiles OUTERMOST -- an XCD's contiguous share of the tile sequence
-    // then stays inside one group, i.e. G x BN rows of W (G = 3, BN = 256, K = 768: 2.4 MB, resident in the XCD's 4 MB L2)
-    // while the row tiles stream past; same tiles, same arithmetic: bit-identical results (profiles/r05_gemm_tile_order.txt)
-    const int G = g.tile_order, nbm = (g.M + BM - 1) / BM;
-    const int grp = lid / (nbm * G), rem = lid - grp * (nbm * G);
-    tm = rem / G;
-    tn = grp * G + rem % G;
   }
   const int m0 = tm * BM;
   const int n0 = tn * BN;
@@ -256,7 +244,7 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
   // Everything that is not an MFMA is issued one or two items at a time BETWEEN MFMAs: an LDS-DMA piece
   // costs the issuing wave ~60+ cycles, and with the whole refill issued in one block after the barrier
   // both waves of a SIMD sat in it together and the matrix pipe idled ~600 of every 3500 cycles
-  // (clock64 instrumentation, GAM_SP_INSTRUMENT build with GAM_SP_DBG=4).
+  // (clock64 counters around the halves of the k-tile, profiles/r01_gemm_sp_clock_random_vs_zero.txt).
   gam_half8 fah[2 * MT], fal[2 * MT], fwh[4], fwl[4];
   constexpr int NTERM = H16 ? 2 : 3;
   constexpr int QM = 2 * NTERM * MT;  // MFMAs per quadrant: terms x MT x 2 blocks
@@ -331,11 +319,6 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
     }
   };
 
-  long long t_bar = 0, t_mm0 = 0, t_mm1 = 0, t_start = 0, w_start = 0;
-  if (GAM_SP_DBG(g) & 4) { t_start = clock64(); w_start = wall_clock64(); }
-  // static priority for the later-dispatched half of the workgroup's waves (the arbitration loser on every half:
-  // MI355X_MICROARCH.md "Two waves per SIMD", item 4)
-  if (GAM_SP_INSTRUMENT && g.prio && wave >= NWAVES / 2) __builtin_amdgcn_s_setprio(1);   // (r02 experiment, instrumented builds only)
   // in-loop wait: everything but the newest (NS - 2) k-tiles' DMA pieces of this wave has landed (vmcnt counts in issue order)
   constexpr int VMW = (NS - 2) * NG;
   static_assert(VMW < 64, "vmcnt field");
@@ -353,39 +336,26 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
   for (int q = 0; q < 2 * MT; ++q) GAM_SP_RDA(0, q, gam_smem_sp);
 #pragma unroll
   for (int q = 0; q < 4; ++q) GAM_SP_RDW(0, q, gam_smem_sp);
-  const int nk_run = (GAM_SP_DBG(g) & 2) ? 1 : nk;
   int s_cur = 0;       // LDS stage of k-tile kt
-  for (int kt = 0; kt < nk_run; ++kt) {
+  for (int kt = 0; kt < nk; ++kt) {
     const int s_nxt = s_cur + 1 == NS ? 0 : s_cur + 1;
     const unsigned char* st = gam_smem_sp + s_cur * Cfg::STAGE;
     const unsigned char* sn = gam_smem_sp + s_nxt * Cfg::STAGE;
-    long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    if (GAM_SP_DBG(g) & 4) c0 = clock64();
     half0(st);
-    if (GAM_SP_DBG(g) & 4) c1 = clock64();
     // vmcnt by hand: this wave's DMA pieces of tile kt+1 have landed (hipcc does not order an LDS-DMA against the
     // ds_reads behind a later barrier); lgkmcnt(0): this wave's last reads of tile kt are in registers
     if constexpr (NS == 2) {
       __builtin_amdgcn_s_waitcnt(0x0070);
-      if (!(GAM_SP_DBG(g) & 8)) __syncthreads();
+      __syncthreads();
     } else {
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VMW) : "memory");
     }
-    if (GAM_SP_DBG(g) & 4) c2 = clock64();
     // Unconditional (one copy of the MFMA stream; a second, DMA-less copy behind a branch made hipcc
     // double-buffer the accumulators): past the end the reads fetch stale LDS that is never used
     // and the DMA re-fetches the last k-tile into a stage nobody reads again (drained before the epilogue).
     // The refill goes to the stage of tile kt: every wave has read its last fragments before the barrier above.
     half1(sn, s_cur);
-    if (GAM_SP_DBG(g) & 4) { c3 = clock64(); t_mm0 += c1 - c0; t_bar += c2 - c1; t_mm1 += c3 - c2; }
     s_cur = s_nxt;
-  }
-  if ((GAM_SP_DBG(g) & 4) && lane == 0 && (lid == 0 || lid == (int)gridDim.x - 1)) {
-    // [total clk, total wall(100 MHz), first half, barrier, second half] of one wave
-    float* d = g.C + (size_t)(g.M - 1) * g.ldc + (lid == 0 ? 0 : 64) + wave * 8;
-    d[0] = (float)(clock64() - t_start); d[1] = (float)(wall_clock64() - w_start);
-    d[2] = (float)t_mm0; d[3] = (float)t_bar; d[4] = (float)t_mm1;
-    return;
   }
 #undef GAM_SPLD
 #undef GAM_SP_RDW
@@ -397,7 +367,6 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
   GAM_SP_TL(2);
 
   const int mw = m0 + wm * (BM / 2), nw = n0 + wn * 64;
-  if ((GAM_SP_DBG(g) & 1) && acc[0][0][0] != 123.456f) return;
 
   // ---- epilogue, straight from the accumulators.  The MFMAs run with the operands SWAPPED (W fragment as the A
   //      operand, activation fragment as B), i.e. they accumulate C^T blocks: lane l then owns ONE row of C per block row
@@ -511,7 +480,6 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
           v[hf] = t;
         }
         if (g.c_guard) { gam_range_note(g.range_flag, v[0].x, v[0].y, v[0].z, v[0].w); gam_range_note(g.range_flag, v[1].x, v[1].y, v[1].z, v[1].w); }
-        if ((GAM_SP_DBG(g) & 32) && v[0].x != 123.456f) continue;   // (experiment: the whole epilogue except its global stores)
         if (g.c_split == 2) {   // plain fp16 rows (the one-term mode's operand format): 8 halfs = one 16-byte store
           _Float16* cp = reinterpret_cast<_Float16*>(g.C) + orow * g.ldc + ecol;
           const gam_half4 h0 = __builtin_convertvector(v[0], gam_half4), h1 = __builtin_convertvector(v[1], gam_half4);
@@ -544,7 +512,7 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
   }
 #undef GAM_SP_LDR
 #if GAM_SP_INSTRUMENT
-  if (GAM_SP_DBG(g) & 16) { __builtin_amdgcn_s_waitcnt(0x0070); __syncthreads(); }   // stores issued AND acknowledged by every wave
+  if (g.tlog != nullptr) { __builtin_amdgcn_s_waitcnt(0x0070); __syncthreads(); }   // stores issued AND acknowledged by every wave
   GAM_SP_TL(3);
 #endif
 }
@@ -588,7 +556,6 @@ struct GamSpForce {
 // tile classes with a three-stage instantiation: the 4-wave tiles (128-wide) and the 128 x 256 8-wave tile (3 x 48 KB)
 static inline bool gam_sp_has_ns3(int mt, int nw) { return (nw == 2 && (mt == 2 || mt == 3)) || (nw == 4 && mt == 2); }
 static inline GamSpForce& gam_sp_force() { static GamSpForce f; return f; }
-static inline int gam_env_int_once(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
 static inline double gam_gemm_sp_model(int M, int N, int K, int a_mode, int t, int w, int S, int ncu, int ns = 2) {
   // least-squares fit (log error) to the 810 points of profiles/r03_smallm_sweep.txt -- five layer shapes x six row counts x
   // every (MT, NW, S) -- r.m.s. 10 %, the planned configuration within 1 % of the best measured one on average (worst 11 %).
@@ -680,20 +647,12 @@ static inline hipError_t gam_launch_gemm_sp(const GamGemmArgs& a_in, int act, hi
   if (a.splitk <= 1) { a.splitk = 0; a.partial = nullptr; }
   const int grid = gam_cdiv(a.M, 64 * mt) * gam_cdiv(a.N, 64 * nw);
   a.ntiles = grid;
-  // the experiment switches GAM_SP_DBG / GAM_SP_PRIO / GAM_SP_ORDER exist in -DGAM_SP_INSTRUMENT=1 builds only: the production kernel
-  // carries none of their branches and the launcher reads no environment variable for them
-#if GAM_SP_INSTRUMENT
-  static const int dbg = gam_env_int_once("GAM_SP_DBG"), prio = gam_env_int_once("GAM_SP_PRIO"), order = gam_env_int_once("GAM_SP_ORDER");   // (thread-safe one-time init)
-#else
-  constexpr int dbg = 0, prio = 0, order = 0;
-#endif
-  a.dbg = dbg;
-  a.prio = prio;
-  a.tile_order = order;
 #if GAM_SP_INSTRUMENT
   static long long* tl_dev = nullptr;
   static int tl_cap = 0;
-  if (dbg & 16) {
+  static const bool tl_on = getenv("GAM_SP_TLOG") != nullptr;   // (thread-safe one-time init)
+  a.tlog = nullptr;
+  if (tl_on) {
     if (grid > tl_cap) { if (tl_dev) (void)hipFree(tl_dev); (void)hipMalloc(&tl_dev, (size_t)grid * 64); tl_cap = grid; }
     (void)hipMemsetAsync(tl_dev, 0, (size_t)grid * 64, stream);
     a.tlog = tl_dev;
@@ -732,7 +691,7 @@ static inline hipError_t gam_launch_gemm_sp(const GamGemmArgs& a_in, int act, hi
   }
 #undef GAM_LSP
 #if GAM_SP_INSTRUMENT
-  if ((dbg & 16) && getenv("GAM_SP_TLOG")) {
+  if (tl_on) {
     std::vector<long long> t((size_t)grid * 8);
     (void)hipStreamSynchronize(stream);
     (void)hipMemcpy(t.data(), tl_dev, t.size() * 8, hipMemcpyDeviceToHost);

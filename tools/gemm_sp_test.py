@@ -27,7 +27,7 @@ def main():
     elif len(sys.argv) > 1:      # "M,N,K,act;M,N,K,act;..."
         shapes = [tuple(int(v) for v in t.split(",")) for t in sys.argv[1].split(";") if t]
     engs = [("sp", engine())]
-    tlog = bool(os.environ.get("GAM_SP_TLOG"))    # instrumented library + GAM_SP_DBG=16: the launcher prints a timeline per call
+    tlog = bool(os.environ.get("GAM_SP_TLOG"))    # instrumented library (-DGAM_SP_INSTRUMENT=1): the launcher prints a timeline per call
     torch.manual_seed(0)
     for (m, n, k, act) in shapes:
         a = torch.randn(m, k, device="cuda")
@@ -61,14 +61,6 @@ def main():
             ms = e.profile_read()["gemm"]["ms"] / reps
             e.profile_enable(0)
             line += f" | {name}: {ms*1e3:8.1f} us {2.0*m*n*k/ms/1e9:6.1f} TF err {err:.1e}"
-            if int(os.environ.get("GAM_SP_DBG", "0")) & 4:
-                d = out[m - 1].cpu()
-                for base in (0, 64):
-                    for wv in (0, 5):
-                        v = d[base + wv * 8: base + wv * 8 + 5].tolist()
-                        if v[1] > 0:
-                            line += (f"\n    tile@{base} wave{wv}: clk {v[0]:.0f} wall {v[1]:.0f} -> {v[0]/v[1]*100:.0f} MHz;"
-                                     f" per k-tile: mm0 {v[2]/(k/32):.0f} bar {v[3]/(k/32):.0f} issue+rd+mm1 {v[4]/(k/32):.0f} clk")
         print(line, flush=True)
 
 

@@ -1,6 +1,6 @@
 // pkfma_canary.hip (r06 diagnosis) -- is v_pk_fma_f32 reliable in a wave that shares its SIMD with another kernel's MFMA-heavy waves?
 //
-// The audit build of the RNN-T cluster decode (gam_decode_cluster.h, -DGAM_RC_AUDIT=1) showed: beside the small-tile GEMM, a gate row's sum
+// The audit build of the RNN-T cluster decode (every phase of a round computed twice; profiles/r06_ERRATUM.md) showed: beside the small-tile GEMM, a gate row's sum
 // w . h recomputed by the SAME thread from the SAME operands (hashes equal) differs from the first evaluation -- always in groups of 8 / 16
 // consecutive lanes, and ONLY in the row slots that hipcc had packed into the LOW half of a v_pk_fma_f32 (slots 0 and 2 of five; 0 of three);
 // the scalar v_fmac_f32 slot and the high halves never.  Alone on the GPU: never.
