@@ -17,9 +17,11 @@ __global__ __launch_bounds__(256) void gam_log_softmax_kernel(const float* x, fl
   float s = 0.f;
   for (int v = lane; v < V; v += 64) s += expf(xr[v] - mx);
   s = gam_wave_sum(s);
-  const float lse = mx + logf(s);
+  // (x - mx) - log s, not x - (mx + log s): the sum rounds log s to an ulp of mx, and that error is common to the whole row -- at
+  // logits near 1e4 the row's probabilities then sum to exp(+-5e-4)
+  const float ls = logf(s);
   float* yr = y + (size_t)row * V;
-  for (int v = lane; v < V; v += 64) yr[v] = xr[v] - lse;
+  for (int v = lane; v < V; v += 64) yr[v] = (xr[v] - mx) - ls;
 }
 
 // ------------------------------------------------------------------ CTC greedy
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(GAM_CTC_NT) void gam_ctc_greedy_kernel(const float*
         if (x > best || (x == best && v < bi)) { best = x; bi = v; }
       }
       gam_first_max<64>(best, bi);
-      if (lane == 0) lab[t] = bi;
+      if (lane == 0) lab[t] = bi == 0x7fffffff ? 0 : bi;   // no comparable value in the row (all NaN): class 0, as the thread form
     }
   }
   __syncthreads();

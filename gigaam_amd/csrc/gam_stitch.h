@@ -157,7 +157,8 @@ __global__ __launch_bounds__(GAM_GL_FB) void gam_ctc_greedy_long_labels_kernel(c
 #pragma unroll
       for (int r = 0; r < GAM_GL_NR; ++r) {
         gam_first_max<64>(best[r], bi[r]);
-        if (lane == 0 && jb + NWV * r <= (int)nfr) lab[jb + NWV * r] = bi[r];
+        // (no comparable value in the row -- all NaN: class 0, as the thread form)
+        if (lane == 0 && jb + NWV * r <= (int)nfr) lab[jb + NWV * r] = bi[r] == 0x7fffffff ? 0 : bi[r];
       }
     }
   }
