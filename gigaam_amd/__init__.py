@@ -19,9 +19,10 @@ from .audio import decode_audio, read_wav, resample, set_audio_backend
 from .lm import NgramLM
 from .model import GigaAM, GigaAMASR, GigaAMEmo
 from .preprocess import load_audio
-from .types import ConfidenceResult, Gap, KeywordHit, KeywordSearchResult, LongformAlignmentResult, ScoredWord
+from .types import (ConfidenceResult, Gap, KeywordHit, KeywordSearchResult, LongformAlignmentResult, LongformConfidenceResult, ScoredSegment,
+                    ScoredWord)
 
-__all__ = ["GigaAM", "GigaAMASR", "GigaAMEmo", "NgramLM", "ConfidenceResult", "Gap", "KeywordHit", "KeywordSearchResult", "LongformAlignmentResult", "ScoredWord", "load_audio", "decode_audio", "resample", "read_wav", "set_audio_backend", "format_time", "load_model", "model_from_checkpoint"]
+__all__ = ["GigaAM", "GigaAMASR", "GigaAMEmo", "NgramLM", "ConfidenceResult", "Gap", "KeywordHit", "KeywordSearchResult", "LongformAlignmentResult", "LongformConfidenceResult", "ScoredSegment", "ScoredWord", "load_audio", "decode_audio", "resample", "read_wav", "set_audio_backend", "format_time", "load_model", "model_from_checkpoint"]
 
 _CACHE_DIR = os.path.expanduser("~/.cache/gigaam")
 # md5 of the reference's published checkpoints (gigaam/__init__.py:28-41)

@@ -99,6 +99,7 @@ SIGNATURES = {
     "gam_set_rnnt_align_workspace": (C.c_int, [_P, C.c_int64]),
     "gam_ctc_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gam_op_ctc_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gam_op_ctc_confidence_long": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gam_rnnt_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "gam_op_rnnt_confidence": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "gam_emo_probs": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P]),

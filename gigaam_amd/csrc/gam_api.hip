@@ -2735,6 +2735,43 @@ int gam_op_ctc_confidence(gam_handle* h, const float* log_probs, const int32_t* 
   return ctc_conf_launch(h, log_probs, enc_len, B, Tp, V, ids, frames, counts, cap, measure, agg, conf, span, status, s);
 }
 
+// ONE utterance of any length: memset (the validity word), check (validity over the token grid; T to the word beside it), the batch
+// op's row pass with B = 1, the span walk over the token grid.  The workspace is cf_stats, as the batch op's: T x 8 bytes + the two words.
+int gam_op_ctc_confidence_long(gam_handle* h, const float* log_probs, int64_t T, int V, const int32_t* ids, const int32_t* frames,
+                               const int32_t* count, int cap, int measure, int agg, int wildcard, float* conf, int32_t* span,
+                               int32_t* status, void* stream) {
+  GAM_DECODE_ENTRY(h, stream);
+  if (T < 1 || T > 2147483647ll || V < 2 || V > GAM_CF_MAX_V)
+    return fail(h, -1, "long CTC confidence: bad shape T=%lld V=%d (1 <= T < 2^31, 2 <= V <= %d)", (long long)T, V, GAM_CF_MAX_V);
+  if (cap < 0) return fail(h, -1, "long CTC confidence: cap=%d tokens is negative", cap);
+  if (measure != GAM_CF_PROB && measure != GAM_CF_ENTROPY) return fail(h, -1, "long CTC confidence: unknown measure %d (0 prob, 1 entropy)", measure);
+  if (agg < GAM_CF_MEAN || agg > GAM_CF_PROD) return fail(h, -1, "long CTC confidence: unknown aggregation %d (0 mean, 1 min, 2 prod)", agg);
+  if (wildcard != 0 && wildcard != 1) return fail(h, -1, "long CTC confidence: wildcard=%d must be 0 or 1", wildcard);
+  if (!log_probs || !count || !status || (cap > 0 && (!ids || !frames || !conf || !span))) return fail(h, -1, "long CTC confidence: NULL buffer");
+  if (int r = ensure(h, h->cf_stats, (size_t)T * 2 + 64)) return r;
+  GamConfLongArgs a;
+  a.lp = log_probs; a.stats = reinterpret_cast<const int2*>(h->cf_stats.p); a.ctrl = h->cf_stats.as<int>() + (size_t)T * 2; a.ids = ids;
+  a.frames = frames; a.count = count; a.T = (int)T; a.V = V; a.cap = cap; a.measure = measure; a.agg = agg; a.wildcard = wildcard;
+  a.conf = conf; a.span = span; a.status = status;
+  const unsigned tok_blocks = (unsigned)gam_cdiv(cap > 0 ? cap : 1, 256);
+  HIPCHK(h, hipMemsetAsync(a.ctrl, 0, sizeof(int), s));
+  hipLaunchKernelGGL(gam_ctc_conf_long_check_kernel, dim3(tok_blocks), dim3(256), 0, s, a);
+  HIPCHK(h, hipGetLastError());
+  {
+    GamConfStatArgs sa;
+    sa.lp = log_probs; sa.enc_len = a.ctrl + 1; sa.stats = reinterpret_cast<int2*>(h->cf_stats.p); sa.rows = (int)T; sa.Tp = (int)T; sa.V = V;
+    sa.measure = measure; sa.inv_lnv = (float)(1.0 / std::log((double)V));
+    ProfScope ps(h, s, GAM_PF_DECODE, (double)T * V * 4.0);
+    if (V <= 64) hipLaunchKernelGGL(gam_ctc_conf_stats_kernel<16>, dim3((unsigned)((T + 15) / 16)), dim3(256), 0, s, sa);
+    else hipLaunchKernelGGL(gam_ctc_conf_stats_kernel<64>, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, sa);
+    HIPCHK(h, hipGetLastError());
+  }
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)T * 8.0);
+  hipLaunchKernelGGL(gam_ctc_conf_long_agg_kernel, dim3(tok_blocks), dim3(256), 0, s, a);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // From the encoder projection encp [B, Tp, JH]: the rows are checked, then the teacher-forced predictor and its projection (rnnt_tf_pp,
 // the decoded ids as targets), then the joint at the listed nodes.
 static int rnnt_conf_launch(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,

@@ -1,5 +1,6 @@
-// gam_confidence.h -- token confidence of a finished decode (gam_ctc_confidence / gam_op_ctc_confidence / gam_rnnt_confidence /
-// gam_op_rnnt_confidence).  A post-pass: it reads what the decoders and the alignments returned and changes none of their kernels.
+// gam_confidence.h -- token confidence of a finished decode (gam_ctc_confidence / gam_op_ctc_confidence / gam_op_ctc_confidence_long /
+// gam_rnnt_confidence / gam_op_rnnt_confidence).  A post-pass: it reads what the decoders and the alignments returned and changes none
+// of their kernels.
 //
 // The contract (shared with tests/confidence_ref.py, float64).  For utterance b: T = enc_len[b], U = counts[b] decoded tokens
 // ids[0..U) at frames[0..U) (the meaning the greedy decodes, the beam searches and the alignments give them), blank = V - 1.
@@ -27,7 +28,8 @@
 // (GAM_CF_NV class tiles in flight, the next k-step prefetched) and carries per node an online
 // (m, S = sum e^(l - m), A = sum e^(l - m) l): H = m + ln S - A / S, ln p(token) = l_token - m - ln S.  One float per token is
 // stored; the logits never reach memory and no [nodes, V] buffer exists.
-// Limits (host errors): V <= 1025, T' <= 8192; RNN-T: cap <= 1024 tokens per utterance, pred_hidden and joint_hidden <= 512.
+// Limits (host errors): V <= 1025; the batch ops T' <= 8192 (gam_op_ctc_confidence_long below: one utterance, 1 <= T < 2^31); RNN-T:
+// cap <= 1024 tokens per utterance, pred_hidden and joint_hidden <= 512.
 #pragma once
 #include "gam_rnnt_align.h"
 
@@ -134,6 +136,22 @@ struct GamConfAggArgs {
   int* status;             // [B]
 };
 
+// Token `id` entered at frame f0 of ONE utterance (lp [T, V], st [T]); the next token's frame, or T, is `lim`: its confidence, and in `n`
+// the frames of its span.  The one span walk of both aggregation kernels (the same statements in the same order: the same bits).
+__device__ __forceinline__ float gam_ctc_conf_span(const float* lp, const int2* st, int V, int measure, int agg, int id, int f0, int lim,
+                                                   int& n_out) {
+  float acc = measure == GAM_CF_PROB ? gam_conf_clamp01(gam_fast_exp(lp[(size_t)f0 * V + id])) : __int_as_float(st[f0].y);
+  int n = 1;
+  for (int f = f0 + 1; f < lim; ++f, ++n) {
+    const int2 s = st[f];
+    if (s.x != id) break;
+    const float x = __int_as_float(s.y);
+    acc = agg == GAM_CF_MEAN ? acc + x : (agg == GAM_CF_MIN ? fminf(acc, x) : acc * x);
+  }
+  n_out = n;
+  return agg == GAM_CF_MEAN ? acc / (float)n : acc;
+}
+
 __global__ __launch_bounds__(256) void gam_ctc_conf_agg_kernel(GamConfAggArgs a) {
   __shared__ int bad;
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -165,19 +183,61 @@ __global__ __launch_bounds__(256) void gam_ctc_conf_agg_kernel(GamConfAggArgs a)
       sp[u] = 0;
       continue;
     }
-    const int id = y[u], f0 = fr[u], lim = u + 1 < U ? fr[u + 1] : T;
-    float acc = a.measure == GAM_CF_PROB ? gam_conf_clamp01(gam_fast_exp(a.lp[((size_t)b * a.Tp + f0) * a.V + id]))
-                                         : __int_as_float(st[f0].y);
-    int n = 1;
-    for (int f = f0 + 1; f < lim; ++f, ++n) {
-      const int2 s = st[f];
-      if (s.x != id) break;
-      const float x = __int_as_float(s.y);
-      acc = a.agg == GAM_CF_MEAN ? acc + x : (a.agg == GAM_CF_MIN ? fminf(acc, x) : acc * x);
-    }
-    cf[u] = a.agg == GAM_CF_MEAN ? acc / (float)n : acc;
+    int n;
+    cf[u] = gam_ctc_conf_span(a.lp + (size_t)b * a.Tp * a.V, st, a.V, a.measure, a.agg, y[u], fr[u], u + 1 < U ? fr[u + 1] : T, n);
     sp[u] = n;
   }
+}
+
+// ------------------------------------------------------------------ CTC, ONE utterance of any length (gam_op_ctc_confidence_long)
+// The contract above on one row with T in place of enc_len[b], plus the wildcard id V (`wildcard` = 1): a valid entry whose frame takes
+// part in the increasing check and bounds its predecessor's span, itself not scored (conf -1, span 0).  Validity spans the whole grid,
+// so it has a launch of its own: the stream zeroes ctrl[0], gam_ctc_conf_long_check_kernel ORs it and writes the clamped T to ctrl[1]
+// (the enc_len word of gam_ctc_conf_stats_kernel, run with B = 1 and Tp = T), gam_ctc_conf_long_agg_kernel reads ctrl[0] and walks one
+// span per thread with gam_ctc_conf_span: the batch op's statements, hence its bits on any stream the batch op takes.
+struct GamConfLongArgs {
+  const float* lp;         // [T, V]
+  const int2* stats;       // [T]
+  int* ctrl;               // [0] the list is invalid, [1] T (behind the stats in the handle's workspace)
+  const int* ids;          // [cap]
+  const int* frames;       // [cap]
+  const int* count;        // [1]
+  int T, V, cap, measure, agg, wildcard;
+  float* conf;             // [cap]
+  int* span;               // [cap]
+  int* status;             // [1]
+};
+
+__global__ __launch_bounds__(256) void gam_ctc_conf_long_check_kernel(GamConfLongArgs a) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  const int U = a.count[0];
+  const bool ulen_ok = U >= 0 && U <= a.cap;
+  if (u == 0) {
+    a.ctrl[1] = a.T;
+    if (!ulen_ok) atomicOr(&a.ctrl[0], 1);
+  }
+  if (ulen_ok && u < U) {
+    const int v = a.ids[u], f = a.frames[u], prev = u > 0 ? a.frames[u - 1] : -1;
+    const bool id_ok = (v >= 0 && v <= a.V - 2) || (a.wildcard && v == a.V);
+    if (!id_ok || f < 0 || f >= a.T || f <= prev) atomicOr(&a.ctrl[0], 1);
+  }
+}
+
+__global__ __launch_bounds__(256) void gam_ctc_conf_long_agg_kernel(GamConfLongArgs a) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  const bool valid = a.ctrl[0] == 0;      // (valid: 0 <= U <= cap, every id and frame in range)
+  if (u == 0) a.status[0] = valid ? 1 : 0;
+  if (u >= a.cap) return;
+  const int U = a.count[0];
+  const int id = valid && u < U ? a.ids[u] : a.V;
+  if (id == a.V) {                        // past the list, an invalid list, or a wildcard
+    a.conf[u] = -1.f;
+    a.span[u] = 0;
+    return;
+  }
+  int n;
+  a.conf[u] = gam_ctc_conf_span(a.lp, a.stats, a.V, a.measure, a.agg, id, a.frames[u], u + 1 < U ? a.frames[u + 1] : a.T, n);
+  a.span[u] = n;
 }
 
 // ------------------------------------------------------------------ RNN-T 1: rows checked, outputs preset

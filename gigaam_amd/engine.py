@@ -1186,6 +1186,52 @@ class HipEngine:
             self._check(rc, "gam_op_ctc_confidence")
             return self._finish(out, False)
 
+    def _confidence_long_tokens(self, decoded, frames, count) -> Tuple[Tensor, Tensor, Tensor]:
+        """``decoded``: a ``Decoded`` of one row or a ``BeamStreamDecoded`` (their ids, frames and count are used where they are), or
+        ids as an i32 tensor or an int list; ``frames`` (a tensor or a list) replaces the result's own, and is needed beside bare
+        ids; ``count`` (a device word, or an int) defaults to the ids' length -> device i32 ids, frames [cap], count [1]."""
+        if isinstance(decoded, Decoded):
+            if decoded.ids.shape[0] != 1:
+                raise GigaAMHipError(f"long token confidence: a decode of one utterance, not of {decoded.ids.shape[0]}")
+            ids, own, cnt = decoded.ids.reshape(-1), decoded.frames.reshape(-1), decoded.counts
+        elif isinstance(decoded, BeamStreamDecoded):
+            ids, own, cnt = decoded.ids, decoded.frames, decoded.count
+        else:
+            ids = (decoded if isinstance(decoded, Tensor) else torch.tensor([int(i) for i in decoded], dtype=torch.int32)).reshape(-1)
+            own, cnt = None, None
+        if frames is None:
+            frames = own
+        if frames is None:
+            raise GigaAMHipError("long token confidence: ids without frames")
+        frames = (frames if isinstance(frames, Tensor) else torch.tensor([int(f) for f in frames], dtype=torch.int32)).reshape(-1)
+        if frames.numel() != ids.numel():
+            raise GigaAMHipError(f"long token confidence: {ids.numel()} ids and {frames.numel()} frames")
+        if count is None:
+            count = cnt if cnt is not None else ids.numel()
+        count = count.reshape(-1)[:1] if isinstance(count, Tensor) else torch.tensor([int(count)], dtype=torch.int32)
+        return self._dev(ids, torch.int32), self._dev(frames, torch.int32), self._dev(count, torch.int32)
+
+    def op_ctc_confidence_long(self, log_probs: Tensor, decoded=None, frames=None, count=None, measure: str = "prob",
+                               aggregation: str = "mean", wildcard: bool = False, consume_flag: bool = False) -> "Confidence":
+        """gam_op_ctc_confidence_long: the token confidences of ONE utterance of any length, log-probs f32 [T, V] (used as they are);
+        no host sync.  ``decoded``: what ``op_ctc_greedy_long`` or ``BeamStream.finish`` returned (read where it lies on the device:
+        no round trip), or ids as a tensor or a list with ``frames`` -- for an aligned text ``AlignedLong.tok_first`` -- and ``count``
+        (default: the ids' length).  ``wildcard``: id V is the aligners' wildcard -- it bounds its neighbour's span and is itself not
+        scored (conf -1, span 0).  Returns a ``Confidence`` of one row; on at most 8192 frames its conf, span and status are
+        bit-identical to ``op_ctc_confidence`` with B = 1.  ``consume_flag``: as ``op_ctc_align_long``."""
+        m, a = self._confidence_codes(measure, aggregation)
+        log_probs = self._dev(log_probs, torch.float32)
+        if log_probs.dim() != 2:
+            raise GigaAMHipError(f"long token confidence: log_probs must be [T, V], got {tuple(log_probs.shape)}")
+        t, v = log_probs.shape
+        ids, fr, cnt = self._confidence_long_tokens(decoded, frames, count)
+        out = Confidence.empty(self.device, 1, ids.numel(), True)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_ctc_confidence_long(self._h, _ptr(log_probs), t, v, _ptr(ids), _ptr(fr), _ptr(cnt), out.cap, m, a,
+                                                     1 if wildcard else 0, _ptr(out.conf), _ptr(out.span), _ptr(out.status), self._stream())
+            self._check(rc, "gam_op_ctc_confidence_long")
+            return self._finish(out, consume_flag)
+
     def rnnt_confidence(self, encoded: Tensor, enc_len: Tensor, decoded, frames=None, counts=None, measure: str = "prob") -> "Confidence":
         """Token confidences of a finished RNN-T decode (gam_rnnt_confidence): the encoder projection, the teacher-forced predictor
         over the decoded ids and the joint at the nodes (frames[u], ids[:u]) the tokens were emitted from, no host sync.  ``decoded``:

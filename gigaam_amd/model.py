@@ -22,8 +22,8 @@ from . import wildcard as _wildcard
 from ._lib import GigaAMHipError
 from .engine import HipEngine, build_config
 from .preprocess import SAMPLE_RATE, load_audio
-from .types import (AlignmentResult, ConfidenceResult, Hypothesis, KeywordSearchResult, LongformAlignmentResult, LongformTranscriptionResult, NBestResult,
-                    ScoredWord, Segment, TranscriptionResult, Word, nbest_posteriors)
+from .types import (AlignmentResult, ConfidenceResult, Hypothesis, KeywordSearchResult, LongformAlignmentResult, LongformConfidenceResult,
+                    LongformTranscriptionResult, NBestResult, ScoredWord, Segment, TranscriptionResult, Word, nbest_posteriors)
 
 LONGFORM_THRESHOLD = 25 * SAMPLE_RATE
 
@@ -938,18 +938,20 @@ class GigaAMASR(GigaAM):
                                  f"(stitch statuses {status.cpu().tolist()})")
 
     def _windows_run(self, audio: Tensor, plan, fr_batch_size: int, whole: Optional[Callable[[Tensor], Dict[str, Any]]] = None,
-                     stream=None, overlap: bool = False) -> Dict[str, Any]:
+                     stream=None, overlap: bool = False, ended: Optional[Callable[[Tensor, Any], Dict[str, Any]]] = None) -> Dict[str, Any]:
         """One pass of a windowed route over the stitched stream of ``plan`` -> its result on the host.  Either ``whole(stream)`` -- a
         one-shot op on the finished [T_total, V] stream, brought to the host (a dict with ``flag``) -- or ``stream``, a resumable
         search (engine.KeywordStream / BeamStream): ONE push of the rows each batch added behind that batch's stitch (``overlap``: on
-        the decode side stream, beside the next batch's frontend and encoder), then the END call and ONE collect.  Raises
-        decoding.RangeOverflow on the flag, then checks the stitch statuses."""
+        the decode side stream, beside the next batch's frontend and encoder), then the END call and ONE collect -- or, with ``ended``,
+        ``ended(stream, result)``: a pass over the finished stream that reads the search's result on the device, and brings both to
+        the host.  Raises decoding.RangeOverflow on the flag, then checks the stitch statuses."""
         if stream is None:
             lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size)
             h = whole(lp_all)
         else:
-            _, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: stream.push(rows, overlap=overlap))
-            h = stream.finish(consume_flag=True).host()
+            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: stream.push(rows, overlap=overlap))
+            out = stream.finish(consume_flag=True)
+            h = out.host() if ended is None else ended(lp_all, out)
         _decoding.check_range(h["flag"])
         self._check_stitch(status)
         return h
@@ -1084,10 +1086,13 @@ class GigaAMASR(GigaAM):
                                        log_likelihood=h["loglik"], segments=segs, feasible=True, **more)
 
     def _align_windows(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int, wildcard: Optional[str],
-                       wildcard_penalty: float, chunk_length_s: float, stride_length_s: Optional[float]) -> LongformAlignmentResult:
+                       wildcard_penalty: float, chunk_length_s: float, stride_length_s: Optional[float],
+                       align: Optional[Callable[[Tensor, List[int], Optional[float]], Dict[str, Any]]] = None) -> LongformAlignmentResult:
         """``align_longform(vad="windows")``: the same plan and the same stitch, then gam_op_ctc_align_long on the stream.  A token's
         segment is the window its frame was kept from, its frame the local frame inside that window; ``segments`` holds one Segment
-        per window over the time span of its kept frames (they tile the file) with the words that start there."""
+        per window over the time span of its kept frames (they tile the file) with the words that start there.  ``align``: what aligns
+        the finished stream in place of ``_align_stream`` (``confidence_longform``: the alignment and the confidence pass behind it)."""
+        align = align or self._align_stream
         if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
             raise TypeError("windowed longform needs a CTC head")
         ids, penalty, text_out = self._align_long_setup(text, wildcard, wildcard_penalty)
@@ -1096,7 +1101,7 @@ class GigaAMASR(GigaAM):
             return self._align_long_result(ids, penalty, text_out, "the recording holds no encoder frame", None)
 
         def run():
-            h = self._windows_run(audio, plan, fr_batch_size, lambda lp_all: self._align_stream(lp_all, ids, penalty))
+            h = self._windows_run(audio, plan, fr_batch_size, lambda lp_all: align(lp_all, ids, penalty))
             origins = [(w.start_s, w.start_s) for w in plan.windows]      # a local frame's time counts from its window's start
             return (h, f"its {plan.t_total} frames", plan.locate, origins, [w.shift for w in plan.windows],
                     [(round(a, 3), round(b, 3)) for a, b in plan.spans()])
@@ -1130,6 +1135,13 @@ class GigaAMASR(GigaAM):
         the window its frame was kept from, and ``segments`` tile the file."""
         if self._windows_route(kwargs):
             return self._align_windows(wav_file, text, fr_batch_size, wildcard, wildcard_penalty, chunk_length_s, stride_length_s)
+        return self._align_regions(wav_file, text, fr_batch_size, wildcard, wildcard_penalty, kwargs)
+
+    def _align_regions(self, wav_file: str, text: Union[str, List[int]], fr_batch_size: int, wildcard: Optional[str], wildcard_penalty: float,
+                       kwargs: Dict[str, Any],
+                       align: Optional[Callable[[Tensor, List[int], Optional[float]], Dict[str, Any]]] = None) -> LongformAlignmentResult:
+        """``align_longform`` over speech regions (its docstring); ``align``: as ``_align_windows``."""
+        align = align or self._align_stream
         from .feeder import BatchFeeder
         from .timestamps_utils import compute_frame_shift, concat_frames_to_segments
         from .vad_utils import segment_audio_file
@@ -1152,7 +1164,7 @@ class GigaAMASR(GigaAM):
                 valid = torch.arange(lp.shape[1], device=lp.device)[None, :] < encoded_len[:, None]
                 rows.append(lp[valid])                                             # each utterance's valid rows, utterance after utterance
                 seg_frames.append(encoded_len)
-            h = self._align_stream(torch.cat(rows, dim=0), ids, penalty)
+            h = align(torch.cat(rows, dim=0), ids, penalty)
             _decoding.check_range(h["flag"])
             n = torch.cat(seg_frames).tolist()
             shifts = [compute_frame_shift(int(seg.shape[0]), int(k)) if k else 0.0 for seg, k in zip(segments, n)]
@@ -1161,3 +1173,217 @@ class GigaAMASR(GigaAM):
                     boundaries, shifts, None)
 
         return self._align_long_result(ids, penalty, text_out, None, run)
+
+    # ---- token / word / segment confidence over a whole recording (gam_op_ctc_confidence_long; per chunk: the batch passes)
+    @torch.inference_mode()
+    def confidence_longform(self, wav_file: str, text: Optional[Union[str, List[int]]] = None, *, measure: str = "prob",
+                            aggregation: str = "mean", fr_batch_size: int = 16, wildcard: Optional[str] = None,
+                            wildcard_penalty: float = _wildcard.DEFAULT_PENALTY, beam_size: Optional[int] = None,
+                            hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
+                            lm_weight: float = 0.5, word_bonus: float = 1.0, stream_search: bool = False, chunk_length_s: float = 20.0,
+                            stride_length_s: Optional[float] = None, pause_s: float = 1.0, max_segment_s: float = 22.0,
+                            **kwargs: Any) -> LongformConfidenceResult:
+        """``confidence`` on a recording of any length: how sure the model is of each token, word and segment.  Words (text, start,
+        end), segments, token ids, ``token_segments`` / ``token_frames`` / ``token_times`` and gaps are exactly those of
+        ``transcribe_longform(..., word_timestamps=True)`` (without ``text``) or of ``align_longform(...)`` (with ``text``: a KNOWN,
+        with ``wildcard=`` partial, transcript) under the same arguments; confidence only adds numbers.  ``measure`` /
+        ``aggregation``: as ``confidence``; a wildcard belongs to no word, has ``token_confidence`` None and is left out of every
+        aggregate.  Segmentation keywords, ``chunk_length_s`` / ``stride_length_s`` / ``pause_s`` / ``max_segment_s``, the beam keywords
+        and ``stream_search``: as ``transcribe_longform``; ``wildcard`` / ``wildcard_penalty``: as ``align_longform``.
+
+        ``vad="windows"`` (CTC heads): the stitched stream is decoded greedily (gam_op_ctc_greedy_long), searched
+        (``stream_search=True``: the resumable beam search) or aligned (``text``), and ONE pass over the whole stream
+        (gam_op_ctc_confidence_long) scores the tokens where the decode or the alignment left them on the device.  Speech regions with
+        ``text`` (CTC heads): the concatenated region stream of ``align_longform``, aligned, then the same pass.  Speech regions
+        without ``text`` (CTC and RNN-T heads): each feeder batch is decoded as ``transcribe_longform`` decodes it -- an RNN-T batch on
+        the launch stream with full-size clusters, as ``confidence_batch`` decodes it -- and scored on the same encoder output by the
+        batch pass of ``confidence_batch``.
+
+        Raises ``ValueError`` for an unknown measure or aggregation (before any audio is read), for beam options together with
+        ``text``, and whatever ``transcribe_longform`` / ``align_longform`` raise for the same arguments; ``TypeError`` for
+        ``vad="windows"`` or ``text`` on an RNN-T model (there is no long transducer alignment) and for per-call beam options there;
+        ``GigaAMHipError`` if the pass rejects the token list."""
+        HipEngine._confidence_codes(measure, aggregation)
+        search = beam_size is not None or hotwords is not None or lm is not None
+        is_ctc = isinstance(self.decoding, _decoding.CTCGreedyDecoding)
+        windows = self._windows_route(kwargs, refuse=False)
+        if text is not None:
+            if search or stream_search:
+                raise ValueError("beam search options select a decode; they cannot be combined with a given text")
+            if not is_ctc and not windows:
+                raise TypeError("confidence_longform with a text needs a CTC head: there is no long transducer alignment")
+            return self._confidence_long_text(wav_file, text, measure, aggregation, fr_batch_size, wildcard, wildcard_penalty,
+                                              chunk_length_s, stride_length_s, kwargs)
+        if wildcard is not None or wildcard_penalty is not _wildcard.DEFAULT_PENALTY:
+            raise ValueError("wildcard / wildcard_penalty belong to a given text")
+        if stream_search and not windows:
+            raise ValueError('stream_search=True searches the stitched stream of vad="windows"; the other routes search chunk by chunk')
+        if windows:
+            if search and not stream_search:
+                raise ValueError('vad="windows" decodes greedily: the beam kernel stops at 8192 frames, so beam_size / hotwords / lm over '
+                                 "the stitched stream are not available without stream_search=True (the resumable beam search)")
+            if stream_search and not search:
+                raise ValueError("stream_search=True needs beam_size, hotwords or lm: there is nothing to search with")
+            self._windows_route(kwargs)
+            beam = (beam_size, hotwords, hotword_boost, lm, lm_weight, word_bonus) if stream_search else None
+            return self._confidence_windows(wav_file, measure, aggregation, fr_batch_size, chunk_length_s, stride_length_s, pause_s,
+                                            max_segment_s, beam)
+        width = self._beam_width(beam_size, hotwords, lm)
+        beam = None if width is None else (width, hotwords, hotword_boost, lm, lm_weight, word_bonus)
+        return self._confidence_regions(wav_file, measure, aggregation, fr_batch_size, beam, kwargs)
+
+    def _confidence_host(self, cf, n: int) -> List[float]:
+        """The first ``n`` token confidences of a one-row ``engine.Confidence`` on the host; status 0 is an error."""
+        h = cf.host()
+        if not int(h["status"][0]):
+            raise GigaAMHipError("the confidence pass rejected the token list of the recording")
+        return [float(c) for c in h["conf"][0, :n]]
+
+    def _confidence_windows(self, wav_file: str, measure: str, aggregation: str, fr_batch_size: int, chunk_length_s: float,
+                            stride_length_s: Optional[float], pause_s: float, max_segment_s: float, beam) -> LongformConfidenceResult:
+        """``confidence_longform(vad="windows")`` without text: the plan, the stitch and the decode of ``_transcribe_windows`` (``beam``:
+        of ``_transcribe_windows_beam``), then gam_op_ctc_confidence_long on the stream the stitch left, fed by the decode's device
+        result; the collects come after both."""
+        from .timestamps_utils import score_longform
+
+        audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s)
+        eng, dec = self.head.engine, self.decoding
+        if beam is not None:
+            width = self._beam_width(beam[0], beam[1], beam[3])
+            if not 1 <= width <= HipEngine.MAX_BEAM:
+                raise ValueError(f"beam_size {width} outside [1, {HipEngine.MAX_BEAM}]")
+        if not plan.windows:
+            return LongformConfidenceResult(text="", segments=[], words=[], token_ids=[], token_segments=[], token_frames=[],
+                                            token_times=[], token_confidence=[], confidence=None)
+
+        def greedy(lp_all: Tensor) -> Dict[str, Any]:
+            out = eng.op_ctc_greedy_long(lp_all, consume_flag=True)
+            cf = eng.op_ctc_confidence_long(lp_all, out, measure=measure, aggregation=aggregation)
+            rows, flag = HipEngine.collect(out)
+            return {"ids": rows[0][0], "frames": rows[0][1], "flag": flag, "cf": cf}
+
+        def searched(lp_all: Tensor, out) -> Dict[str, Any]:
+            cf = eng.op_ctc_confidence_long(lp_all, out, measure=measure, aggregation=aggregation)
+            h = out.host()
+            return {"ids": h["ids"].tolist(), "frames": h["frames"].tolist(), "flag": h["flag"], "cf": cf}
+
+        def run():
+            if beam is None:
+                h = self._windows_run(audio, plan, fr_batch_size, greedy)
+            else:      # (a rerun under GAM_GEMM_F32 comes here again: a new stream, BEGIN)
+                _, hotwords, hotword_boost, lm, lm_weight, word_bonus = beam
+                eng.set_hotwords(dec.hotword_ids(hotwords), hotword_boost)
+                eng.set_lm(dec.language_model(lm), dec.tokenizer, lm_weight, word_bonus)
+                overlap = os.environ.get("GAM_BEAM_STREAM_OVERLAP", "1") != "0"
+                h = self._windows_run(audio, plan, fr_batch_size, stream=eng.beam_stream(width, plan.t_total), overlap=overlap,
+                                      ended=searched)
+            return h["ids"], h["frames"], self._confidence_host(h["cf"], len(h["ids"]))
+
+        ids, frames, conf = self._file_run(run)
+        base = self._windows_result(plan, ids, frames, True, pause_s, max_segment_s)
+        wins, local, times = plan.locate(frames)
+        token_conf, words, segments, total = score_longform(dec.tokenizer, ids, conf, base.words, base.segments, aggregation)
+        return LongformConfidenceResult(text=base.text, segments=segments, words=words, token_ids=ids, token_segments=list(wins),
+                                        token_frames=list(local), token_times=list(times), token_confidence=token_conf, confidence=total)
+
+    def _confidence_long_text(self, wav_file: str, text: Union[str, List[int]], measure: str, aggregation: str, fr_batch_size: int,
+                              wildcard: Optional[str], wildcard_penalty: float, chunk_length_s: float, stride_length_s: Optional[float],
+                              kwargs: Dict[str, Any]) -> LongformConfidenceResult:
+        """``confidence_longform`` with a text, on either route of ``align_longform``: its alignment, and behind it on the same stream
+        gam_op_ctc_confidence_long with the text's ids at ``tok_first`` as the alignment left them on the device (wildcards enabled:
+        ``wildcard=`` set); ONE result is assembled from ``align_longform``'s own."""
+        from .timestamps_utils import score_longform
+
+        eng = self.head.engine if isinstance(self.decoding, _decoding.CTCGreedyDecoding) else None
+        got: Dict[str, Any] = {}
+
+        def align(lp_all: Tensor, ids: List[int], penalty: Optional[float]) -> Dict[str, Any]:
+            star = None if penalty is None else eng.ctc_star_row(lp_all, None, penalty)
+            al = eng.op_ctc_align_long(lp_all, ids, consume_flag=True, star=star)
+            cf = eng.op_ctc_confidence_long(lp_all, ids, frames=al.tok_first, measure=measure, aggregation=aggregation,
+                                            wildcard=penalty is not None) if ids else None
+            h = al.host()
+            got["cf"] = cf if h["status"] else None      # (a text that does not fit: the caller raises; its frames are no token list)
+            return h
+
+        if self._windows_route(kwargs):
+            base = self._align_windows(wav_file, text, fr_batch_size, wildcard, wildcard_penalty, chunk_length_s, stride_length_s, align)
+        else:
+            base = self._align_regions(wav_file, text, fr_batch_size, wildcard, wildcard_penalty, kwargs, align)
+        ids = base.token_ids
+        conf = self._confidence_host(got["cf"], len(ids)) if got.get("cf") is not None else [0.0] * len(ids)
+        wid = self.wildcard_id
+        token_conf, words, segments, total = score_longform(self.decoding.tokenizer, ids, conf, base.words, base.segments, aggregation, wid)
+        return LongformConfidenceResult(text=base.text, segments=segments, words=words, token_ids=ids, token_segments=base.token_segments,
+                                        token_frames=base.token_frames, token_times=base.token_times, token_confidence=token_conf,
+                                        confidence=total, gaps=base.gaps, score=base.score, log_likelihood=base.log_likelihood)
+
+    def _confidence_regions(self, wav_file: str, measure: str, aggregation: str, fr_batch_size: int, beam: Optional[tuple],
+                            kwargs: Dict[str, Any]) -> LongformConfidenceResult:
+        """``confidence_longform`` over speech regions without text: the segmentation, the feeder and the one-batch pipeline of
+        ``transcribe_longform``; per batch ONE encoder run, the decode, and behind it the batch pass of ``confidence_batch`` on the
+        decode's device result.  ``beam``: (width, hotwords, hotword_boost, lm, lm_weight, word_bonus) of a CTC beam search, or None.
+        A segment per chunk; a token's segment is its chunk, its frame the chunk's local frame."""
+        from .engine import _to_host
+        from .feeder import BatchFeeder
+        from .timestamps_utils import aggregate_confidence, compute_frame_shift, frames_to_words, score_longform
+        from .vad_utils import segment_audio_file
+
+        is_ctc = isinstance(self.decoding, _decoding.CTCGreedyDecoding)
+        self._default_vad(kwargs, "confidence_longform")
+        segments, boundaries = segment_audio_file(wav_file, SAMPLE_RATE, device=self._device, **kwargs)
+        out = LongformConfidenceResult(text="", segments=[], words=[], token_ids=[], token_segments=[], token_frames=[], token_times=[],
+                                       token_confidence=[], confidence=None)
+        if not segments:
+            return out
+        eng, tok = self.head.engine, self.decoding.tokenizer
+
+        def run():
+            chunks: List[tuple] = []
+
+            def launch(n, batch):
+                wav, lens = batch
+                encoded, encoded_len = self._encode(wav, lens, getattr(feeder, "host_lengths", None))
+                if beam is None:
+                    dev_out = self.decoding.decode_device(self.head, encoded, encoded_len)
+                else:
+                    dev_out = self.decoding.decode_beam_device(self.head, encoded, encoded_len, *beam)
+                if is_ctc:
+                    cf = eng.ctc_confidence(encoded, encoded_len, dev_out, measure=measure, aggregation=aggregation)
+                else:
+                    cf = eng.rnnt_confidence(encoded, encoded_len, dev_out, measure=measure)
+                return dev_out, cf, list(feeder.host_lengths), encoded_len
+
+            def emit(pending) -> None:
+                dev_out, cf, wl, encoded_len = pending
+                rows = self.decoding.finish(dev_out)
+                h = cf.host()
+                _decoding.check_range(h["flag"])
+                el = _to_host((encoded_len,), cf.event)[0].tolist()
+                for i, (text, ids, frames) in enumerate(rows):
+                    if not int(h["status"][i]):
+                        raise GigaAMHipError(f"confidence pass rejected the tokens of chunk {len(chunks)}")
+                    chunks.append((text, ids, frames, [float(c) for c in h["conf"][i, :len(ids)]], int(wl[i]), int(el[i])))
+
+            feeder = BatchFeeder(segments, fr_batch_size, self._device)
+            _pipeline(feeder, launch, emit)
+            return chunks
+
+        # chunk by chunk, as transcribe_longform builds its segments: a word never runs from one chunk's tokens into the next's
+        for k, (text, ids, frames, conf, wl, el) in enumerate(self._file_run(run)):
+            start, end = boundaries[k]
+            shift = compute_frame_shift(wl, el) if el else 0.0
+            words = [Word(text=w.text, start=round(w.start + start, 3), end=round(w.end + start, 3))
+                     for w in frames_to_words(tok, ids, frames, shift)]
+            token_conf, scored, (segment,), _ = score_longform(tok, ids, conf, words, [Segment(text=text, start=start, end=end, words=words)],
+                                                               aggregation)
+            out.segments.append(segment)
+            out.words += scored
+            out.token_ids += ids
+            out.token_segments += [k] * len(ids)
+            out.token_frames += frames
+            out.token_times += [start + f * shift for f in frames]
+            out.token_confidence += token_conf
+        out.text = " ".join(sg.text for sg in out.segments)
+        out.confidence = aggregate_confidence(out.token_confidence, aggregation)
+        return out

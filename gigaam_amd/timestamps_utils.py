@@ -2,11 +2,11 @@
 Pure host-side string work over the exact ``frames`` the HIP decoders emit."""
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 from .decoding import Tokenizer
 from .preprocess import SAMPLE_RATE
-from .types import Segment, Word
+from .types import ScoredSegment, ScoredWord, Segment, Word
 
 
 def compute_frame_shift(audio_length_samples: int, seq_len: int) -> float:
@@ -83,6 +83,33 @@ def aggregate_confidence(values: List[float], aggregation: str):
     for v in values:
         out *= float(v)
     return out
+
+
+def score_longform(tokenizer: Tokenizer, token_ids: Sequence[int], conf: Sequence[float], words: Sequence[Word],
+                   segments: Sequence[Segment], aggregation: str, wildcard_id: Optional[int] = None):
+    """Confidences added to a finished longform result.  ``words`` are the words a longform route built from ``token_ids`` (in order:
+    ``frames_to_words`` / ``longform_words`` on each wildcard-free run), ``segments`` hold those same ``Word`` objects, ``conf`` one
+    value per token (what stands at a wildcard is not read).  Returns (token confidences with None at the wildcards, ``ScoredWord``
+    per word, ``ScoredSegment`` per segment, the file's confidence): a word aggregates its tokens (``word_token_groups``), a segment
+    the tokens of its words, the file every token that is no wildcard; None where there is no token."""
+    ids = [int(i) for i in token_ids]
+    token_conf = [None if i == wildcard_id else float(c) for i, c in zip(ids, conf)]
+    groups: List[List[int]] = []
+    a = 0
+    for b in [k for k, i in enumerate(ids) if i == wildcard_id] + [len(ids)]:      # word groups run by run: no word spans a wildcard
+        groups += [[a + k for k in g] for g in word_token_groups(tokenizer, ids[a:b])]
+        a = b + 1
+    if len(groups) != len(words):
+        raise ValueError(f"{len(words)} words for {len(groups)} word groups of the token list")
+    scored = [ScoredWord(text=w.text, start=w.start, end=w.end, confidence=aggregate_confidence([token_conf[k] for k in g], aggregation))
+              for w, g in zip(words, groups)]
+    index = {id(w): k for k, w in enumerate(words)}
+    out_segments = []
+    for sg in segments:
+        ks = [index[id(w)] for w in sg.words or []]
+        out_segments.append(ScoredSegment(text=sg.text, start=sg.start, end=sg.end, words=[scored[k] for k in ks],
+                                          confidence=aggregate_confidence([token_conf[t] for k in ks for t in groups[k]], aggregation)))
+    return token_conf, scored, out_segments, aggregate_confidence([c for c in token_conf if c is not None], aggregation)
 
 
 def concat_frames_to_segments(frames: Sequence[int], seg_frames: Sequence[int], seg_starts: Sequence[float],

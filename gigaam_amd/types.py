@@ -210,6 +210,48 @@ class LongformAlignmentResult:
 
 
 @dataclass
+class ScoredSegment:
+    """A ``Segment`` whose words carry confidences; ``confidence``: the aggregation over the tokens of its words, None without any."""
+    text: str
+    start: float
+    end: float
+    words: List[ScoredWord]
+    confidence: Optional[float]
+
+
+@dataclass
+class LongformConfidenceResult:
+    """``GigaAMASR.confidence_longform``: the transcript of a recording of any length -- the model's own decode, or a known (partial)
+    text placed by forced alignment -- with a confidence in [0, 1] per token, per word, per segment and for the file.  Words
+    (text, start, end), segments, ``token_ids`` and ``gaps`` are those of ``transcribe_longform(word_timestamps=True)`` (without text)
+    or ``align_longform`` (with text) under the same arguments; ``token_segments`` / ``token_frames`` / ``token_times`` as in
+    ``LongformAlignmentResult``.  ``token_confidence``: per token as ``ConfidenceResult.token_confidence``, None at a wildcard, which
+    belongs to no word and is left out of every aggregate; ``confidence``: the aggregation over all scored tokens, None without any.
+    ``score`` / ``log_likelihood``: the alignment's, None without text."""
+    text: str
+    segments: List[ScoredSegment]
+    words: List[ScoredWord]
+    token_ids: List[int]
+    token_segments: List[int]
+    token_frames: List[int]
+    token_times: List[float]
+    token_confidence: List[Optional[float]]
+    confidence: Optional[float]
+    gaps: List[Gap] = field(default_factory=list)
+    score: Optional[float] = None
+    log_likelihood: Optional[float] = None
+
+    def __str__(self) -> str:
+        return self.text
+
+    def __iter__(self) -> Iterator[ScoredSegment]:
+        return iter(self.segments)
+
+    def __len__(self) -> int:
+        return len(self.segments)
+
+
+@dataclass
 class KeywordHit:
     """One occurrence of a keyword (``GigaAMASR.find_keywords``).  ``start`` / ``end``: seconds, ``start_frame`` x frame shift and
     (``end_frame`` + 1) x frame shift -- the convention of ``transcribe(word_timestamps=True)``; in a longform result they are file

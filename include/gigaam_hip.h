@@ -429,7 +429,8 @@ int gam_set_rnnt_align_workspace(gam_handle* h, int64_t bytes);
  * a workspace of the handle, and a span walk per token.  gam_rnnt_confidence runs the encoder projection GEMM, the teacher-forced
  * predictor and its projection GEMM as gam_rnnt_align does (the decoded ids as targets), then a fused joint at the listed nodes that
  * stores one float per token; the logits never reach memory.
- * Limits (an error beyond them): V <= 1025, T' <= 8192; RNN-T: cap <= 1024, pred_hidden and joint_hidden <= 512.  Calling a function of
+ * Limits (an error beyond them): V <= 1025, T' <= 8192 in these batch calls (gam_op_ctc_confidence_long takes one utterance of any
+ * length); RNN-T: cap <= 1024, pred_hidden and joint_hidden <= 512.  Calling a function of
  * the other head family is an error.  Decode class; no host synchronisation. */
 int gam_ctc_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                        const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
@@ -438,6 +439,20 @@ int gam_ctc_confidence(gam_handle* h, const float* encoded, const int32_t* enc_l
 int gam_op_ctc_confidence(gam_handle* h, const float* log_probs, const int32_t* enc_len, int B, int64_t Tp, int V, const int32_t* ids,
                           const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
                           int32_t* status, void* stream);
+/* The CTC pass on ONE utterance of any length, 1 <= T < 2^31 (frames are int32): log_probs f32 [T, V] (read as they are), ids /
+ * frames i32 [cap] and count i32 [1] on the device (a decode's or an alignment's result feeds it with no host round trip), conf f32
+ * [cap], span i32 [cap], status i32 [1].  The contract above on one row with T in place of enc_len[b]: the same step distribution,
+ * measures, clamp, span rule, aggregations and validity -- one bad entry anywhere in the list gives status 0, every conf -1 and every
+ * span 0; count = 0 is status 1.  On a stream of at most 8192 frames conf, span and status are bit-identical to
+ * gam_op_ctc_confidence with B = 1 (both run the same row pass and the same span walk).  wildcard = 1: id V (the aligners' wildcard,
+ * one past blank) is a valid entry -- its frame takes part in the strictly-increasing check and bounds the previous token's span, it
+ * is itself not scored (conf -1, span 0); wildcard = 0: id V is invalid.  Four launches in stream order (validity is grid-wide): a
+ * memset, a check over the tokens, the row pass, one thread per token walking its span -- a token that owns N frames is walked
+ * serially.  Workspace: the handle's, T x 8 bytes plus two words.  Limits (an error beyond them): 1 <= T < 2^31, 2 <= V <= 1025,
+ * cap >= 0.  Needs no head.  Decode class; no host synchronisation. */
+int gam_op_ctc_confidence_long(gam_handle* h, const float* log_probs, int64_t T, int V, const int32_t* ids, const int32_t* frames,
+                               const int32_t* count, int cap, int measure, int agg, int wildcard, float* conf, int32_t* span,
+                               int32_t* status, void* stream);
 int gam_rnnt_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                         const int32_t* frames, const int32_t* counts, int cap, int measure, float* conf, int32_t* status, void* stream);
 /* The same from a caller-supplied encoder projection encp f32 [B, T', joint_hidden], with the handle's predictor and joint weights. */
