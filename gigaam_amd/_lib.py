@@ -116,6 +116,7 @@ SIGNATURES = {
     "gam_range_flag_fetch": (C.c_int, [_P, _P, _P]),
     "gam_op_gemm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gam_op_gemm_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "gam_op_gemm_fmt": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "gam_op_attention": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "gam_op_attention_ex": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gam_op_layernorm": (C.c_int, [_P, C.POINTER(GamLnOp), _P]),

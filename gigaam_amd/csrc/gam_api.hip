@@ -2887,12 +2887,30 @@ int gam_op_gemm(gam_handle* h, const float* A, const float* W, const float* bias
   return gam_op_gemm_ex(h, A, W, bias, nullptr, 1.0f, C, M, N, K, act, stream);
 }
 
+static int op_gemm_impl(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha, float* C, long ldc,
+                        int M, int N, int K, int act, int c_split, int c_guard, void* stream);
+
 int gam_op_gemm_ex(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha, float* C, int M,
                    int N, int K, int act, void* stream) {
   if (!h) return -1;
+  return op_gemm_impl(h, A, W, bias, R, alpha, C, N, M, N, K, act, 0, 0, stream);
+}
+
+int gam_op_gemm_fmt(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha, float* C, int64_t ldc,
+                    int M, int N, int K, int act, int c_split, int c_guard, void* stream) {
+  if (!h) return -1;
+  if (!split_mode(h) || K % 32 != 0 || N % 4 != 0 || ldc < N || c_split < 0 || c_split > 2 || (c_split == 1 && ldc % 32 != 0) ||
+      (c_split == 2 && !(h->gemm_mode == GAM_GEMM_F16 && K % 64 == 0)))
+    return fail(h, -1, "gam_op_gemm_fmt: format %d / pitch %ld not available for this mode and shape (N=%d K=%d)", c_split, (long)ldc, N, K);
+  return op_gemm_impl(h, A, W, bias, R, alpha, C, (long)ldc, M, N, K, act, c_split, c_guard, stream);
+}
+
+static int op_gemm_impl(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha, float* C, long ldc,
+                        int M, int N, int K, int act, int c_split, int c_guard, void* stream) {
   HIPCHK(h, hipSetDevice(h->device));
-  GamGemmArgs g = gemm_args(A, K, W, bias, C, N, M, N, K);
-  g.R = R; g.ldr = N; g.alpha = alpha;
+  GamGemmArgs g = gemm_args(A, K, W, bias, C, ldc, M, N, K);
+  g.R = R; g.ldr = ldc; g.alpha = alpha;
+  g.c_split = c_split; g.c_guard = c_guard;
   hipStream_t s = (hipStream_t)stream;
   // the exact-fp32 kernel: the exact mode, and the shapes the LDS-DMA kernel cannot take (its epilogue moves 4-column pieces)
   if (!split_mode(h) || K % 32 != 0 || N % 4 != 0) return gemm(h, s, g, act);

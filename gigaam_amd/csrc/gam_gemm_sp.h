@@ -101,7 +101,29 @@ __device__ __forceinline__ int gam_sp_key(int row) { return ((row >> 1) & 7) ^ (
 // work, half the operand bytes.  (A first version kept the sp32 operands and fetched only the hi half of every line: a 64-byte
 // piece of each 128-byte line costs the memory path the whole line, and the kernel ran at half the delivery rate --
 // profiles/r04_fastmode.txt.)
-template <int ACT, int MT, int NW, int NS = 2, bool H16 = false>
+//
+// EPI = the epilogue class: which of the epilogue's options this instantiation carries, as compile-time bits.  The options are run-time
+// fields of GamGemmArgs; tested per element or per 16-byte piece inside the unrolled row loop they made the FFN-up epilogue 5205
+// instructions where its class needs 1562 (profiles/gemm_epilogue_classes.md) -- paid with the matrix pipe idle.  The launcher
+// derives the bits from the arguments (gam_sp_epi_bits) and picks the instantiation of the same bits if the encoder's callers can
+// produce them (gam_launch_gemm_sp lists them); everything else runs GAM_EPI_GENERIC, which reads every option from GamGemmArgs at
+// run time.  One body serves both: an option is `GEN ? run-time field : class bit`, a constant wherever the class decides it.  No
+// class changes a rounding -- the order on a value stays acc * rsc + bias -> activation -> mask -> * alpha -> + R -> split, and the
+// multiply a class drops is by exactly 1.0f.
+enum : int {
+  GAM_EPI_SP32 = 1,      // C in the sp32 layout (c_split 1)
+  GAM_EPI_F16 = 2,       // C as plain fp16 rows (c_split 2)
+  GAM_EPI_CFMT = 3,
+  GAM_EPI_RESID = 4,     // + R
+  GAM_EPI_ALPHA = 8,     // alpha != 1
+  GAM_EPI_ROWS = 16,     // row mask and / or row remap (lens != nullptr || remap)
+  GAM_EPI_GUARD = 32,    // range guard on C (c_guard with a flag word)
+  GAM_EPI_TAIL = 64,     // N % 8 == 4: the last 8-column group of a row has its first half only
+  GAM_EPI_PART = 128,    // split-K slice: raw partial sums, no other option applies
+  GAM_EPI_GENERIC = 256  // every option read from GamGemmArgs at run time
+};
+
+template <int ACT, int EPI, int MT, int NW, int NS = 2, bool H16 = false>
 __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(GamGemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gam_smem_sp[];
   using Cfg = GamGemmSpCfg<MT, NW, NS>;
@@ -382,26 +404,48 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
   // and an sp32 / fp16 result as ONE 16-byte store per plane instead of two 8-byte ones (the store path, not the arithmetic, is what
   // an epilogue costs: profiles/r03_gemm_timeline.txt).  On the 32x32x16 shape this took a v_permlane32_swap per register; here it is
   // address arithmetic alone.
+  // The options are compile-time per epilogue class (EPI, above); the range guard keeps a running maximum per lane and tests it
+  // once; a lane's column offsets are computed once and a row adds its pitch once (profiles/gemm_epilogue_classes.md).
+  constexpr bool GEN = (EPI & GAM_EPI_GENERIC) != 0;
+  const bool part = GEN ? g.partial != nullptr : (EPI & GAM_EPI_PART) != 0;
+  const int cfmt = GEN ? g.c_split : (EPI & GAM_EPI_CFMT);
+  const bool resid = !part && (GEN ? g.R != nullptr : (EPI & GAM_EPI_RESID) != 0);
+  const bool scaled = GEN || (EPI & GAM_EPI_ALPHA) != 0;          // (the generic class multiplies by alpha whatever it is: 1.0f is exact)
+  const bool need_bt = !part && (GEN ? (g.lens != nullptr || g.remap) : (EPI & GAM_EPI_ROWS) != 0);
+  const bool guard = GEN ? (g.c_guard && g.range_flag != nullptr) : (EPI & GAM_EPI_GUARD) != 0;
+  const bool tail = GEN ? (g.N & 4) != 0 : (EPI & GAM_EPI_TAIL) != 0;
   const int lrow = lane & 15, lq8 = (lane >> 4) * 8;
   const float accscale = g.wscale_inv;
-  // piece (p, hf): columns nw + 32 p + lq8 + 4 hf .. + 3  =  accumulator block 2 p + hf
+  // Column data, once per lane.  Piece (p, hf): columns ecol0 + 32 p + 4 hf .. + 3  =  accumulator block 2 p + hf.  Group p = 1 lies 32
+  // columns behind group 0 in every format: 128 bytes in fp32 and in sp32 (the next [hi x32 | lo x32] line), 64 in plain fp16.
+  const int ecol0 = nw + lq8;                                    // first of this lane's eight columns of group 0
+  bool c_ok[2], c_both[2];
+#pragma unroll
+  for (int pp = 0; pp < 2; ++pp) {
+    c_ok[pp] = ecol0 + 32 * pp < g.N;
+    c_both[pp] = !tail || ecol0 + 32 * pp + 4 < g.N;             // (N % 8 == 4: the last group has its first half only)
+  }
   f32x4 bv[2][2];
 #pragma unroll
   for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-      const int col = nw + 32 * pp + lq8 + 4 * hf;
+      const int col = ecol0 + 32 * pp + 4 * hf;
       bv[pp][hf] = (g.bias != nullptr && col < g.N) ? *reinterpret_cast<const f32x4*>(g.bias + col) : (f32x4){0.f, 0.f, 0.f, 0.f};   // N % 4 == 0
     }
+  // byte offset of the lane's group 0 inside a row of C, the row pitch and the step to group 1
+  const long c_col = cfmt == 1 ? 2L * ((ecol0 >> 5) * 64 + (ecol0 & 31)) : (cfmt == 2 ? 2L * ecol0 : 4L * ecol0);
+  const long c_pitch = cfmt == 2 ? 2 * g.ldc : 4 * g.ldc;
+  const int c_step = cfmt == 2 ? 64 : 128;
+  unsigned char* const c_base = reinterpret_cast<unsigned char*>(g.C) + c_col;
   // Row data of all 2 MT rows first -- validity, mask, output row, per-row factor -- so that the a_rs / lens loads of every row
   // are in flight together: inside the row loop each would sit behind the previous row's stores (C may alias anything), one
   // exposed L2 round trip per row, and the 16-row blocks make twice as many rows per lane as the 32-row blocks did.
   // (utterance, frame) of a row: ONE division per lane -- a lane's rows are 16 apart, so the next row's pair follows by a
   // conditional subtraction (utterances of fewer than 16 rows divide again); the mask test tt / fdiv >= len is tt >= len fdiv.
-  // A split-K slice needs neither (it stores raw sums of every row below M).  Measured on the small grids, where the epilogue
+  // A split-K slice needs neither (it stores raw sums of every row below M), nor does a class without mask and remap: there the
+  // output row is the row and nothing but the per-row factor is kept.  Measured on the small grids, where the epilogue
   // is a visible share of a launch: profiles/mfma16_gemm_ab.md, section 4.
-  const bool part = g.partial != nullptr;
-  const bool need_bt = !part && (g.lens != nullptr || g.remap);
   bool r_ok[2 * MT], r_masked[2 * MT];
   long r_orow[2 * MT];
   float r_rsc[2 * MT];
@@ -434,38 +478,37 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
 #pragma unroll
     for (int i = 0; i < 2 * MT; ++i) {
       if (!r_ok[i]) continue;
-      float* P = g.partial + ((size_t)blockIdx.y * (size_t)g.M + (size_t)(mw + 16 * i + lrow)) * (size_t)g.N;
+      float* P = g.partial + ((size_t)blockIdx.y * (size_t)g.M + (size_t)(mw + 16 * i + lrow)) * (size_t)g.N + ecol0;
 #pragma unroll
       for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          const int ecol = nw + 32 * pp + lq8 + 4 * hf;
-          if (ecol < g.N) *reinterpret_cast<f32x4*>(P + ecol) = acc[i][2 * pp + hf] * r_rsc[i];
-        }
+        for (int hf = 0; hf < 2; ++hf)
+          if (ecol0 + 32 * pp + 4 * hf < g.N) *reinterpret_cast<f32x4*>(P + 32 * pp + 4 * hf) = acc[i][2 * pp + hf] * r_rsc[i];
     }
   }
   // the four residual pieces of row I -> D; the pieces of row i + 1 are requested BEFORE row i is stored (a lane reads and writes
   // only its own elements, so R == C is safe), which keeps one row of residual in flight behind every row of stores
 #define GAM_SP_LDR(I, D)                                                                          \
-  _Pragma("unroll") for (int pp = 0; pp < 2; ++pp) _Pragma("unroll") for (int hf = 0; hf < 2; ++hf) { \
-    const int col = nw + 32 * pp + lq8 + 4 * hf;                                                  \
-    D[pp][hf] = (r_ok[I] && col < g.N) ? *reinterpret_cast<const f32x4*>(g.R + r_orow[I] * g.ldr + col) : (f32x4){0.f, 0.f, 0.f, 0.f}; \
+  {                                                                                               \
+    const float* rrow_ = g.R + r_orow[I] * g.ldr + ecol0;                                         \
+    _Pragma("unroll") for (int pp = 0; pp < 2; ++pp) _Pragma("unroll") for (int hf = 0; hf < 2; ++hf)  \
+      D[pp][hf] = (r_ok[I] && ecol0 + 32 * pp + 4 * hf < g.N) ? *reinterpret_cast<const f32x4*>(rrow_ + 32 * pp + 4 * hf)  \
+                                                             : (f32x4){0.f, 0.f, 0.f, 0.f};       \
   }
   f32x4 rv[2][2], rn[2][2];
-  const bool resid = g.R != nullptr && !part;
+  float gmax = 0.f;   // range guard: the largest |value| this lane stores (fmaxf drops a NaN, as the per-piece test did; an Inf stays)
   if (resid) GAM_SP_LDR(0, rv);
 #pragma unroll
   for (int i = 0; i < 2 * MT; ++i) {
     if (resid && i + 1 < 2 * MT) GAM_SP_LDR(i + 1, rn);
     const bool masked = r_masked[i];
-    const long orow = r_orow[i];
     const float rsc = r_rsc[i];
     if (r_ok[i] && !part) {
+      unsigned char* const crow = c_base + r_orow[i] * c_pitch;
 #pragma unroll
       for (int pp = 0; pp < 2; ++pp) {
-        const int ecol = nw + 32 * pp + lq8;                 // first of this lane's eight columns
-        if (ecol >= g.N) continue;
-        const bool both = ecol + 4 < g.N;                    // (N % 8 == 4: the last group has its first half only)
+        if (!c_ok[pp]) continue;
+        const bool both = c_both[pp];
         f32x4 v[2];
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
@@ -473,33 +516,35 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
           t = t * rsc + bv[pp][hf];
           if (ACT == GAM_ACT_SILU) { t.x = gam_silu(t.x); t.y = gam_silu(t.y); t.z = gam_silu(t.z); t.w = gam_silu(t.w); }
           if (ACT == GAM_ACT_RELU) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
-          if (masked) t = (f32x4){0.f, 0.f, 0.f, 0.f};
-          t = t * g.alpha;
+          if (need_bt && masked) t = (f32x4){0.f, 0.f, 0.f, 0.f};
+          if (scaled) t = t * g.alpha;
           if (resid) t += rv[pp][hf];
-          if (!both && hf == 1) t = (f32x4){0.f, 0.f, 0.f, 0.f};
+          if (tail && !both && hf == 1) t = (f32x4){0.f, 0.f, 0.f, 0.f};
           v[hf] = t;
         }
-        if (g.c_guard) { gam_range_note(g.range_flag, v[0].x, v[0].y, v[0].z, v[0].w); gam_range_note(g.range_flag, v[1].x, v[1].y, v[1].z, v[1].w); }
-        if (g.c_split == 2) {   // plain fp16 rows (the one-term mode's operand format): 8 halfs = one 16-byte store
-          _Float16* cp = reinterpret_cast<_Float16*>(g.C) + orow * g.ldc + ecol;
+        if (guard) {
+          gmax = fmaxf(gmax, fmaxf(fmaxf(fabsf(v[0].x), fabsf(v[0].y)), fmaxf(fabsf(v[0].z), fabsf(v[0].w))));
+          gmax = fmaxf(gmax, fmaxf(fmaxf(fabsf(v[1].x), fabsf(v[1].y)), fmaxf(fabsf(v[1].z), fabsf(v[1].w))));
+        }
+        unsigned char* const cp = crow + pp * c_step;
+        if (cfmt == 2) {   // plain fp16 rows (the one-term mode's operand format): 8 halfs = one 16-byte store
           const gam_half4 h0 = __builtin_convertvector(v[0], gam_half4), h1 = __builtin_convertvector(v[1], gam_half4);
           if (both) *reinterpret_cast<gam_half8*>(cp) = (gam_half8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
           else *reinterpret_cast<gam_half4*>(cp) = h0;
-        } else if (g.c_split) {
-          _Float16* cp = reinterpret_cast<_Float16*>(g.C) + orow * (2 * g.ldc) + (ecol >> 5) * 64 + (ecol & 31);
+        } else if (cfmt) {   // sp32: the hi plane of the line, the lo plane 64 bytes behind it
           gam_half4 hi0, lo0, hi1, lo1;
           gam_split4(v[0], hi0, lo0);
           gam_split4(v[1], hi1, lo1);
           if (both) {
             *reinterpret_cast<gam_half8*>(cp) = (gam_half8){hi0[0], hi0[1], hi0[2], hi0[3], hi1[0], hi1[1], hi1[2], hi1[3]};
-            *reinterpret_cast<gam_half8*>(cp + 32) = (gam_half8){lo0[0], lo0[1], lo0[2], lo0[3], lo1[0], lo1[1], lo1[2], lo1[3]};
+            *reinterpret_cast<gam_half8*>(cp + 64) = (gam_half8){lo0[0], lo0[1], lo0[2], lo0[3], lo1[0], lo1[1], lo1[2], lo1[3]};
           } else {
             *reinterpret_cast<gam_half4*>(cp) = hi0;
-            *reinterpret_cast<gam_half4*>(cp + 32) = lo0;
+            *reinterpret_cast<gam_half4*>(cp + 64) = lo0;
           }
         } else {
-          *reinterpret_cast<f32x4*>(g.C + orow * g.ldc + ecol) = v[0];
-          if (both) *reinterpret_cast<f32x4*>(g.C + orow * g.ldc + ecol + 4) = v[1];
+          *reinterpret_cast<f32x4*>(cp) = v[0];
+          if (both) *reinterpret_cast<f32x4*>(cp + 16) = v[1];
         }
       }
     }
@@ -510,6 +555,7 @@ __global__ __launch_bounds__(128 * NW, NW == 2 ? 2 : 1) void gam_gemm_sp_kernel(
         for (int hf = 0; hf < 2; ++hf) rv[pp][hf] = rn[pp][hf];
     }
   }
+  if (guard && gmax > GAM_F16_SAFE_MAX) atomicOr(g.range_flag, 1);   // bit 0 iff any stored value is beyond the limit
 #undef GAM_SP_LDR
 #if GAM_SP_INSTRUMENT
   if (g.tlog != nullptr) { __builtin_amdgcn_s_waitcnt(0x0070); __syncthreads(); }   // stores issued AND acknowledged by every wave
@@ -524,14 +570,23 @@ static inline bool gam_gemm_sp_epilogue_ok(const GamGemmArgs& a) {
          (a.R == nullptr || (a.ldr % 4 == 0 && al16(a.R)));
 }
 
-template <int ACT, int MT, int NW, int NS = 2, bool H16 = false>
+template <int ACT, int EPI, int MT, int NW, int NS = 2, bool H16 = false>
 static inline void gam_launch_gemm_sp_t(const GamGemmArgs& a, int grid, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_devs{0};
   constexpr int smem = GamGemmSpCfg<MT, NW, NS>::SMEM;
   static_assert(smem <= 160 * 1024, "LDS stages do not fit a CU");
-  auto kern = gam_gemm_sp_kernel<ACT, MT, NW, NS, H16>;
+  auto kern = gam_gemm_sp_kernel<ACT, EPI, MT, NW, NS, H16>;
   if (gam_set_max_lds(reinterpret_cast<const void*>(kern), smem, attr_devs) != hipSuccess) return;
   hipLaunchKernelGGL(kern, dim3(grid, a.splitk > 1 ? a.splitk : 1), dim3(128 * NW), smem, stream, a);
+}
+
+// The exact epilogue class of a launch (the GAM_EPI_* bits of its arguments as the launcher has normalised them: partial is null
+// unless this is a split-K slice).  A slice stores raw sums: no other option reaches its kernel.
+static inline int gam_sp_epi_bits(const GamGemmArgs& a) {
+  if (a.partial != nullptr) return GAM_EPI_PART;
+  return (a.c_split & GAM_EPI_CFMT) | (a.R != nullptr ? GAM_EPI_RESID : 0) | (a.alpha != 1.0f ? GAM_EPI_ALPHA : 0) |
+         ((a.lens != nullptr || a.remap) ? GAM_EPI_ROWS : 0) | ((a.c_guard && a.range_flag != nullptr) ? GAM_EPI_GUARD : 0) |
+         ((a.N & 7) == 4 ? GAM_EPI_TAIL : 0);
 }
 
 // Tile shape and split-K factor.  NW = 4: (64 MT) x 256 tiles, 8 waves, one workgroup per CU -- fewest bytes per FLOP.
@@ -658,38 +713,70 @@ static inline hipError_t gam_launch_gemm_sp(const GamGemmArgs& a_in, int act, hi
     a.tlog = tl_dev;
   }
 #endif
-#define GAM_LSP(ACTV)                                                            \
-  if (a.h16) {   /* (K, lda, conv_c arrive halved: gam_api.hip gemm()) */        \
-    if (ns == 3) {                                                               \
-      if (nw == 4) gam_launch_gemm_sp_t<ACTV, 2, 4, 3, true>(a, grid, stream);   \
-      else if (mt == 2) gam_launch_gemm_sp_t<ACTV, 2, 2, 3, true>(a, grid, stream); \
-      else gam_launch_gemm_sp_t<ACTV, 3, 2, 3, true>(a, grid, stream);           \
-    } else if (nw == 2) {                                                        \
-      if (mt == 2) gam_launch_gemm_sp_t<ACTV, 2, 2, 2, true>(a, grid, stream);   \
-      else gam_launch_gemm_sp_t<ACTV, 3, 2, 2, true>(a, grid, stream);           \
-    } else switch (mt) {                                                         \
-      case 2: gam_launch_gemm_sp_t<ACTV, 2, 4, 2, true>(a, grid, stream); break; \
-      case 3: gam_launch_gemm_sp_t<ACTV, 3, 4, 2, true>(a, grid, stream); break; \
-      default: gam_launch_gemm_sp_t<ACTV, 4, 4, 2, true>(a, grid, stream); break; \
-    }                                                                            \
-  } else if (ns == 3) {                                                          \
-    if (nw == 4) gam_launch_gemm_sp_t<ACTV, 2, 4, 3>(a, grid, stream);           \
-    else if (mt == 2) gam_launch_gemm_sp_t<ACTV, 2, 2, 3>(a, grid, stream);      \
-    else gam_launch_gemm_sp_t<ACTV, 3, 2, 3>(a, grid, stream);                   \
-  } else if (nw == 2) switch (mt) {                                              \
-    case 2: gam_launch_gemm_sp_t<ACTV, 2, 2>(a, grid, stream); break;            \
-    default: gam_launch_gemm_sp_t<ACTV, 3, 2>(a, grid, stream); break;           \
-  } else switch (mt) {                                                           \
-    case 2: gam_launch_gemm_sp_t<ACTV, 2, 4>(a, grid, stream); break;            \
-    case 3: gam_launch_gemm_sp_t<ACTV, 3, 4>(a, grid, stream); break;            \
-    default: gam_launch_gemm_sp_t<ACTV, 4, 4>(a, grid, stream); break;           \
+  // tile class of the three-term kernel / of the one-term kernel (K, lda, conv_c arrive halved: gam_api.hip gemm())
+#define GAM_LSP(ACTV, EPIV)                                                            \
+  if (ns == 3) {                                                                       \
+    if (nw == 4) gam_launch_gemm_sp_t<ACTV, EPIV, 2, 4, 3>(a, grid, stream);           \
+    else if (mt == 2) gam_launch_gemm_sp_t<ACTV, EPIV, 2, 2, 3>(a, grid, stream);      \
+    else gam_launch_gemm_sp_t<ACTV, EPIV, 3, 2, 3>(a, grid, stream);                   \
+  } else if (nw == 2) switch (mt) {                                                    \
+    case 2: gam_launch_gemm_sp_t<ACTV, EPIV, 2, 2>(a, grid, stream); break;            \
+    default: gam_launch_gemm_sp_t<ACTV, EPIV, 3, 2>(a, grid, stream); break;           \
+  } else switch (mt) {                                                                 \
+    case 2: gam_launch_gemm_sp_t<ACTV, EPIV, 2, 4>(a, grid, stream); break;            \
+    case 3: gam_launch_gemm_sp_t<ACTV, EPIV, 3, 4>(a, grid, stream); break;            \
+    default: gam_launch_gemm_sp_t<ACTV, EPIV, 4, 4>(a, grid, stream); break;           \
   }
-  switch (act) {
-    case GAM_ACT_SILU: GAM_LSP(GAM_ACT_SILU); break;
-    case GAM_ACT_RELU: GAM_LSP(GAM_ACT_RELU); break;
-    default: GAM_LSP(GAM_ACT_NONE); break;
+#define GAM_LSP_H16(ACTV)                                                              \
+  if (ns == 3) {                                                                       \
+    if (nw == 4) gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 2, 4, 3, true>(a, grid, stream);      \
+    else if (mt == 2) gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 2, 2, 3, true>(a, grid, stream); \
+    else gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 3, 2, 3, true>(a, grid, stream);  \
+  } else if (nw == 2) {                                                                \
+    if (mt == 2) gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 2, 2, 2, true>(a, grid, stream);      \
+    else gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 3, 2, 2, true>(a, grid, stream);  \
+  } else switch (mt) {                                                                 \
+    case 2: gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 2, 4, 2, true>(a, grid, stream); break;    \
+    case 3: gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 3, 4, 2, true>(a, grid, stream); break;    \
+    default: gam_launch_gemm_sp_t<ACTV, GAM_EPI_GENERIC, 4, 4, 2, true>(a, grid, stream); break;   \
+  }
+  // The epilogue classes with an instantiation of their own = what the encoder's callers (gam_api.hip) and gam_op_gemm_ex produce in
+  // the default three-term mode, one per (activation, bits) pair x the eight tile classes:
+  //   none | fp32                   pointwise-conv1, the stem's Linear, linear_pos, gam_op_gemm
+  //   none | fp32 + R               attention out, pointwise-conv2
+  //   none | fp32 + R, alpha        FFN down
+  //   none | fp32, guard            q | k | v
+  //   SiLU | sp32, guard            FFN up
+  //   ReLU | sp32, guard, rows      Conv2d #2 of the stem (implicit GEMM), the conv1d stem's first stage (remap)
+  //   none | split-K slice          every split-K launch, whatever its activation: the reduce pass applies it
+  // Anything else -- the one-term mode (fp16 C), the N % 8 == 4 tail, an activation with a residual, the conv1d stem's second stage
+  // -- runs the generic class of its activation: the same code with every option read at run time.  No shape is refused for its class.
+  const int epi = gam_sp_epi_bits(a);
+  const int act_k = epi == GAM_EPI_PART ? GAM_ACT_NONE : act;
+  enum : int { E_PLAIN = 0, E_RES = GAM_EPI_RESID, E_RESA = GAM_EPI_RESID | GAM_EPI_ALPHA, E_GRD = GAM_EPI_GUARD,
+               E_UP = GAM_EPI_SP32 | GAM_EPI_GUARD, E_STEM = GAM_EPI_SP32 | GAM_EPI_GUARD | GAM_EPI_ROWS };
+  if (a.h16) {
+    switch (act) {
+      case GAM_ACT_SILU: GAM_LSP_H16(GAM_ACT_SILU); break;
+      case GAM_ACT_RELU: GAM_LSP_H16(GAM_ACT_RELU); break;
+      default: GAM_LSP_H16(GAM_ACT_NONE); break;
+    }
+  } else if (act_k == GAM_ACT_NONE && epi == E_PLAIN) { GAM_LSP(GAM_ACT_NONE, E_PLAIN);
+  } else if (act_k == GAM_ACT_NONE && epi == E_RES) { GAM_LSP(GAM_ACT_NONE, E_RES);
+  } else if (act_k == GAM_ACT_NONE && epi == E_RESA) { GAM_LSP(GAM_ACT_NONE, E_RESA);
+  } else if (act_k == GAM_ACT_NONE && epi == E_GRD) { GAM_LSP(GAM_ACT_NONE, E_GRD);
+  } else if (act_k == GAM_ACT_SILU && epi == E_UP) { GAM_LSP(GAM_ACT_SILU, E_UP);
+  } else if (act_k == GAM_ACT_RELU && epi == E_STEM) { GAM_LSP(GAM_ACT_RELU, E_STEM);
+  } else if (epi == GAM_EPI_PART) { GAM_LSP(GAM_ACT_NONE, GAM_EPI_PART);
+  } else {
+    switch (act) {
+      case GAM_ACT_SILU: GAM_LSP(GAM_ACT_SILU, GAM_EPI_GENERIC); break;
+      case GAM_ACT_RELU: GAM_LSP(GAM_ACT_RELU, GAM_EPI_GENERIC); break;
+      default: GAM_LSP(GAM_ACT_NONE, GAM_EPI_GENERIC); break;
+    }
   }
 #undef GAM_LSP
+#undef GAM_LSP_H16
 #if GAM_SP_INSTRUMENT
   if (tl_on) {
     std::vector<long long> t((size_t)grid * 8);

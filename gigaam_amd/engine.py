@@ -1647,6 +1647,22 @@ class HipEngine:
         self._check(rc, "gam_op_gemm_ex")
         return out
 
+    def op_gemm_fmt(self, a: Tensor, w: Tensor, out: Tensor, bias: Optional[Tensor] = None, act: int = 0, resid: Optional[Tensor] = None,
+                    alpha: float = 1.0, c_split: int = 0, c_guard: bool = False) -> Tensor:
+        """gam_op_gemm_fmt: op_gemm into the caller's ``out`` (f32 [M, ldc], ldc >= N; ``resid`` has the same pitch and may BE ``out``) in
+        the encoder's output formats -- c_split 0 fp32, 1 sp32 (hi / lo fp16 planes per 32 columns), 2 plain fp16 rows -- with the range
+        guard on the stored values (``range_flag`` reads it).  Split-fp16 modes only."""
+        a = self._dev(a, torch.float32)
+        w = self._dev(w, torch.float32)
+        bias = None if bias is None else self._dev(bias, torch.float32)
+        m, k = a.shape
+        n = w.shape[0]
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_gemm_fmt(self._h, _ptr(a), _ptr(w), _ptr(bias), _ptr(resid), alpha, _ptr(out), out.stride(0), m, n, k, act,
+                                          int(c_split), int(bool(c_guard)), self._stream())
+        self._check(rc, "gam_op_gemm_fmt")
+        return out
+
     def op_attention(self, q: Tensor, k: Tensor, v: Tensor, lens: Optional[Tensor] = None) -> Tensor:
         """q, k, v [B,T,H*48] -> ctx [B,T,H*48]; keys >= lens[b] are masked."""
         q, k, v = (self._dev(t, torch.float32) for t in (q, k, v))

@@ -552,6 +552,12 @@ int gam_op_gemm(gam_handle* h, const float* A, const float* W, const float* bias
  * an R that is not 16-byte aligned (the call fails, nothing is launched); the exact-fp32 kernel reads it element-wise. */
 int gam_op_gemm_ex(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha,
                    float* C, int M, int N, int K, int act, void* stream);
+/* The same with the encoder's output formats and range guard (split-fp16 modes only, K % 32 == 0, N % 4 == 0): C has row pitch ldc
+ * elements (ldc >= N; R, when given, has the same pitch) and is written as fp32 (c_split 0), in the sp32 layout (c_split 1, ldc % 32 == 0:
+ * the 4 bytes of element (row, c) hold its fp16 hi / lo pair, regrouped per 32 columns) or as plain fp16 rows (c_split 2, one-term mode
+ * only, row pitch ldc halfs); c_guard != 0: a stored value beyond 60000 in magnitude sets bit 0 of the handle's range flag. */
+int gam_op_gemm_fmt(gam_handle* h, const float* A, const float* W, const float* bias, const float* R, float alpha,
+                    float* C, int64_t ldc, int M, int N, int K, int act, int c_split, int c_guard, void* stream);
 
 /* Raw attention entry for kernel-level tests: q, k, v, ctx f32 [B*T, H*48] token-major
  * (head h = columns 48h..48h+47), lens i32 [B] valid keys per utterance or NULL (no mask);
