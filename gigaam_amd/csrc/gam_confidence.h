@@ -29,7 +29,7 @@
 // (m, S = sum e^(l - m), A = sum e^(l - m) l): H = m + ln S - A / S, ln p(token) = l_token - m - ln S.  One float per token is
 // stored; the logits never reach memory and no [nodes, V] buffer exists.
 // Limits (host errors): V <= 1025; the batch ops T' <= 8192 (gam_op_ctc_confidence_long below: one utterance, 1 <= T < 2^31); RNN-T:
-// cap <= 1024 tokens per utterance, pred_hidden and joint_hidden <= 512.
+// cap <= 1024 tokens per utterance, pred_hidden and joint_hidden <= 512 (multiples of 16; the pp GEMM takes any such K).
 #pragma once
 #include "gam_rnnt_align.h"
 

@@ -21,6 +21,9 @@
 // Arithmetic is exact fp32 (MFMA f32 == an fmaf chain): parity with the reference's
 // fp32 CPU path is the first gate.
 //
+// K % 4 == 0.  K % 32 != 0 (plain rows with lda >= K only: the decode heads' K = pred_hidden / joint_hidden, multiples of 16): the last k-tile is
+// zero-filled beyond column K.
+//
 // Tiling: 128x128x32 block tile, 256 threads = 4 waves (2x2), each wave 64x64 = 2x2
 // MFMA tiles of 32x32; LDS rows padded to 36 floats (9 x 16 B, odd) so both the
 // ds_write_b128 staging and the ds_read_b128 fragment reads are bank-conflict-free;
@@ -40,7 +43,7 @@ struct GamGemmArgs {
   const float* bias;   // [N] or null
   const float* R;      // residual [*, ldr] or null:  C = R + alpha * act(acc + bias)
   float* C;
-  int M, N, K;         // K % 32 == 0
+  int M, N, K;         // K % 4 == 0; a_mode 1, lda < K and split-K slices: K % 32 == 0
   long lda, ldc, ldr;
   float alpha;
   // A addressing
@@ -204,7 +207,11 @@ __global__ __launch_bounds__(256, 3) void gam_gemm_f32_kernel(GamGemmArgs g) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) { acc00[r] = 0.f; acc01[r] = 0.f; acc10[r] = 0.f; acc11[r] = 0.f; }
 
-  const int nk = g.K / BK;
+  // K % 32 != 0 (a_mode 0 only; the decode heads' K = pred_hidden / joint_hidden, multiples of 16): the last k-tile is partly
+  // filled.  Its loads beyond column K deliver zeros -- products that add +0 -- from an address moved back to the tile's first
+  // column, which lies inside the row (K % 4 == 0).  Full tiles take the loads as they were: K % 32 == 0 runs the same code.
+  const int nkf = g.K / BK;
+  const int nk = (g.K + BK - 1) / BK;
   float4 va0, va1, va2, va3, vb0, vb1, vb2, vb3;
 
 #define GAM_GLOAD(KT)                                                           \
@@ -224,6 +231,22 @@ __global__ __launch_bounds__(256, 3) void gam_gemm_f32_kernel(GamGemmArgs g) {
     vb1 = *reinterpret_cast<const float4*>(pw1 + k0_);                          \
     vb2 = *reinterpret_cast<const float4*>(pw2 + k0_);                          \
     vb3 = *reinterpret_cast<const float4*>(pw3 + k0_);                          \
+  }
+#define GAM_GLOAD_TAIL(KT)                                                      \
+  {                                                                             \
+    const int k0_ = (KT) * BK;                                                  \
+    const bool in_ = k0_ + lc4 < g.K;                                           \
+    const int ko_ = in_ ? k0_ : k0_ - lc4;                                      \
+    const float4 z_ = make_float4(0.f, 0.f, 0.f, 0.f);                          \
+    va0 = *reinterpret_cast<const float4*>(pa0 + ko_);                          \
+    va1 = *reinterpret_cast<const float4*>(pa1 + ko_);                          \
+    va2 = *reinterpret_cast<const float4*>(pa2 + ko_);                          \
+    va3 = *reinterpret_cast<const float4*>(pa3 + ko_);                          \
+    vb0 = *reinterpret_cast<const float4*>(pw0 + ko_);                          \
+    vb1 = *reinterpret_cast<const float4*>(pw1 + ko_);                          \
+    vb2 = *reinterpret_cast<const float4*>(pw2 + ko_);                          \
+    vb3 = *reinterpret_cast<const float4*>(pw3 + ko_);                          \
+    if (!in_) { va0 = z_; va1 = z_; va2 = z_; va3 = z_; vb0 = z_; vb1 = z_; vb2 = z_; vb3 = z_; } \
   }
 #define GAM_LSTORE()                                                            \
   {                                                                             \
@@ -258,18 +281,19 @@ __global__ __launch_bounds__(256, 3) void gam_gemm_f32_kernel(GamGemmArgs g) {
   // next k-tile travels through registers while the current one is multiplied:
   //   barrier | regs -> LDS | barrier | issue global loads of tile kt+1 | 64 MFMAs
   // The two barriers per k-tile are covered by the other resident workgroups' MFMAs.
-  GAM_GLOAD(0);
+  if (nkf > 0) GAM_GLOAD(0) else GAM_GLOAD_TAIL(0);
   const float* Ab = As + wm * 64 * LD + frag;
   const float* Bb = Bs + wn * 64 * LD + frag;
   for (int kt = 0; kt < nk; ++kt) {
     __syncthreads();
     GAM_LSTORE();
     __syncthreads();
-    if (kt + 1 < nk) GAM_GLOAD(kt + 1);
+    if (kt + 1 < nkf) GAM_GLOAD(kt + 1) else if (kt + 1 < nk) GAM_GLOAD_TAIL(kt + 1);
     GAM_COMPUTE(Ab, Bb);
   }
 #undef GAM_COMPUTE
 #undef GAM_GLOAD
+#undef GAM_GLOAD_TAIL
 #undef GAM_LSTORE
 #undef GAM_MFMA
 
@@ -287,7 +311,10 @@ static inline hipError_t gam_launch_gemm(const GamGemmArgs& a_in, int act, hipSt
   GamGemmArgs a = a_in;
   if (a.ldw == 0) a.ldw = a.K;
   if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  if (a.K % GAM_GEMM_BK != 0 || a.K <= 0) return hipErrorInvalidValue;
+  if (a.K <= 0 || a.K % 4 != 0) return hipErrorInvalidValue;
+  // a partly filled last k-tile: plain, non-overlapping rows only (the conv-shaped contractions -- the conv2d gather, the conv1d stem's
+  // and the DFT's overlapping rows with lda < K -- keep K % 32 == 0, and gam_encode keeps refusing a conv1d stem with 5 F % 32 != 0)
+  if (a.K % GAM_GEMM_BK != 0 && (a.a_mode != 0 || a.splitk > 1 || a.lda < a.K)) return hipErrorInvalidValue;
   const int grid = gam_cdiv(a.M, GAM_GEMM_BM) * gam_cdiv(a.N, GAM_GEMM_BN);
   switch (act) {
     case GAM_ACT_SILU: gam_launch_gemm_t<GAM_ACT_SILU>(a, grid, stream); break;

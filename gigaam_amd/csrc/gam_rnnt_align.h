@@ -18,7 +18,8 @@
 // Status 1: aligned (T = 0 with U = 0 included: score = loglik = 0).  Status 0: T = 0 with U > 0, a target id outside [0, V-2],
 // target_len outside [0, Umax], or no path of finite score -- score = loglik = -inf, token frames -1.  Every T >= 1 is feasible
 // for every U.  Token frames past target_len[b] are -1; target entries past target_len[b] are never read.
-// Limits (host errors beyond them): Umax <= 1024, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512 (multiples of 16).
+// Limits (host errors beyond them): Umax <= 1024, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512 (multiples of 16: every head
+// gam_create accepts; the pp GEMM's K = pred_hidden runs with a zero-filled last k-tile when it is no multiple of 32, gam_gemm.h).
 //
 // Three kernels, exact fp32 products like the rest of the RNN-T head (MFMA f32 / fmaf chains, no fp16 terms):
 //  1. gam_rnnt_tf_predict_kernel -- the teacher-forced predictor g[b, u], u = 0..U: ONE launch, one workgroup per utterance, u the

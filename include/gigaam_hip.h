@@ -353,7 +353,7 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
  *   meaning), counts i32 [B] of them.  score f32 [B]: its log p (summed over the alignments the beam merged) + its committed hotword
  *   bonus + its LM term (every word including the last, and weight * ln P(</s> | history)); logp f32 [B]: that log p alone.
  *   enc_len[b] = 0 gives an empty result with score = logp = 0.
- * Limits: W <= 32, max_symbols <= 16, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512, at most 160 KiB of LDS for the
+ * Limits: W <= 32, max_symbols <= 16, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512 (multiples of 16), at most 160 KiB of LDS for the
  * search state (an error beyond them; every W and max_symbols fits at pred_hidden = joint_hidden = 320 with or without the LM).
  * Decode class, like gam_rnnt_greedy; no host synchronisation. */
 int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
@@ -394,7 +394,7 @@ int gam_op_rnnt_beam_nbest(gam_handle* h, const float* encp, const int32_t* enc_
  * a fused joint kernel that stores only (log P(blank), log P(next token)) per lattice node, and the lattice sweep with its backtrack.
  * The lattice workspace is B x T' x (Umax + 1) x 8 bytes; above the handle's limit (gam_set_rnnt_align_workspace) the batch is
  * processed in slices of utterances with the same results; ONE utterance above the limit is an error that names the bytes.
- * Limits: Umax <= 1024, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512 (an error beyond them).  Decode class, like
+ * Limits: Umax <= 1024, T' <= 8192, V <= 1025, pred_hidden and joint_hidden <= 512 and multiples of 16 (an error beyond them).  Decode class, like
  * gam_rnnt_greedy; no host synchronisation. */
 int gam_rnnt_align(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* targets,
                    const int32_t* target_len, int Umax, int32_t* tok_frame, float* score, float* loglik, int32_t* status, void* stream);
@@ -430,7 +430,7 @@ int gam_set_rnnt_align_workspace(gam_handle* h, int64_t bytes);
  * predictor and its projection GEMM as gam_rnnt_align does (the decoded ids as targets), then a fused joint at the listed nodes that
  * stores one float per token; the logits never reach memory.
  * Limits (an error beyond them): V <= 1025, T' <= 8192 in these batch calls (gam_op_ctc_confidence_long takes one utterance of any
- * length); RNN-T: cap <= 1024, pred_hidden and joint_hidden <= 512.  Calling a function of
+ * length); RNN-T: cap <= 1024, pred_hidden and joint_hidden <= 512 (multiples of 16).  Calling a function of
  * the other head family is an error.  Decode class; no host synchronisation. */
 int gam_ctc_confidence(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, const int32_t* ids,
                        const int32_t* frames, const int32_t* counts, int cap, int measure, int agg, float* conf, int32_t* span,
@@ -544,7 +544,7 @@ int gam_range_flag_fetch(gam_handle* h, int32_t* flag_dev, void* stream);
 int gam_get_gemm_mode(const gam_handle* h);
 
 /* Raw GEMM entry for kernel-level tests and the roofline bench (arithmetic = current mode):
- * C[M,N] = act(A[M,K] . W[N,K]^T + bias) (act: 0 none, 1 SiLU, 2 ReLU); K % 32 == 0. */
+ * C[M,N] = act(A[M,K] . W[N,K]^T + bias) (act: 0 none, 1 SiLU, 2 ReLU); K % 4 == 0 (K % 32 != 0: the exact-fp32 kernel in every mode). */
 int gam_op_gemm(gam_handle* h, const float* A, const float* W, const float* bias, float* C,
                 int M, int N, int K, int act, void* stream);
 /* Kernel-level test entry like gam_op_gemm, with the encoder's residual epilogue: C = alpha * act(A . W^T + bias) + R

@@ -151,7 +151,7 @@ def test_gemm_instantiation_matrix(mode):
 def _f32_splitk(m, n, k):
     """The exact-fp32 kernel's split-K rule (gam_api.hip gemm()), transcribed: grids of at most half the chip in 128 x 128 tiles."""
     tiles, nk = math.ceil(m / 128) * math.ceil(n / 128), k // 32
-    if tiles * 2 > 256 or nk < 4:
+    if tiles * 2 > 256 or nk < 4 or k % 32:      # (a partly filled last k-tile is never split)
         return 1
     s = min(16, 256 // tiles, nk // 2)
     while s > 1 and nk % s:
@@ -162,12 +162,16 @@ def _f32_splitk(m, n, k):
 @pytest.mark.gpu
 def test_exact_fp32_kernel_splitk_rule_and_unaligned_n():
     """The exact-fp32 kernel in the f32 mode at shapes on both sides of its split-K rule (S = 2, 12, 16; S = 1 from too many tiles
-    and from stepping nk % S down to 1), and in the f16x3 mode at the N % 4 != 0 shapes the LDS-DMA kernel cannot take."""
+    and from stepping nk % S down to 1), and in the f16x3 mode at the N % 4 != 0 shapes the LDS-DMA kernel cannot take.  The last
+    four f32 shapes have K % 32 == 16 -- the pp and output GEMMs of RNN-T heads with pred_hidden / joint_hidden = 16, 48, 496, 336
+    (tests/rnnt_cluster_cases.py): one k-tile that is half zeros, one and a half, fifteen and a half, ten and a half."""
     cases = {"f32": [(100, 100, 224, 1, True), (60, 300, 160, 2, False), (100, 100, 768, 0, True), (1000, 2000, 768, 2, True),
-                     (1000, 2050, 768, 1, True), (129, 129, 3072, 0, True), (1, 772, 32, 1, True)],
+                     (1000, 2050, 768, 1, True), (129, 129, 3072, 0, True), (1, 772, 32, 1, True),
+                     (7, 16, 16, 0, True), (61, 64, 48, 0, False), (200, 336, 496, 2, True), (40, 130, 336, 1, True)],
              "f16x3": [(257, 34, 768, 0, True), (300, 771, 96, 1, True), (1, 1, 32, 0, False), (16, 770, 3072, 2, True)]}
     assert {_f32_splitk(m, n, k) for (m, n, k, _, _) in cases["f32"]} == {1, 2, 12, 16}
     assert [_f32_splitk(m, n, k) for (m, n, k, _, _) in cases["f32"][:2]] == [1, 1]   # nk = 7, 5: S steps down to 1
+    assert [k % 32 for (_, _, k, _, _) in cases["f32"][-4:]] == [16] * 4
     for mode, shapes in cases.items():
         eng = _engine(mode)
         for (m, n, k, act, bias) in shapes:

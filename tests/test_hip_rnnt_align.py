@@ -85,10 +85,12 @@ def _check(h, b, lat, T, U, errs, what):
 
 @pytest.mark.parametrize("L", [1, 2])
 @pytest.mark.parametrize("kind", ["blank", "dense"])
-@pytest.mark.parametrize("V,H,JH", [(34, 320, 320), (257, 320, 320), (1025, 320, 320), (257, 256, 512), (34, 512, 512)])
+@pytest.mark.parametrize("V,H,JH", [(34, 320, 320), (257, 320, 320), (1025, 320, 320), (257, 256, 512), (34, 512, 512),
+                                    (34, 48, 64), (34, 16, 16), (130, 496, 336), (1025, 320, 512)])
 def test_op_align_matches_float64_reference(V, H, JH, kind, L):
     """Seeded encp and targets: empty target, U = 1, U > T, T = 1, T = 0 with U = 0 and with U > 0, ragged lengths, poisoned padding.
-    pred_hidden = 512 is the only case above 320: the teacher-forced predictor's eight-rows-per-thread instantiation."""
+    pred_hidden = 512 and 496 are the cases above 320: the teacher-forced predictor's eight-rows-per-thread instantiation.  The last
+    four are heads of tests/rnnt_cluster_cases.py; pred_hidden = 48, 16 and 496 make the K of the pp GEMM no multiple of 32."""
     eng, head, _ = _engine(V, L, 14.0 if kind == "blank" else None, H, JH)
     rng = np.random.default_rng(V * 11 + L + H + (1 if kind == "dense" else 0))
     Tp = 40
