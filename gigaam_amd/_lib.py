@@ -87,6 +87,10 @@ SIGNATURES = {
     "gam_set_lm": (C.c_int, [_P, _P, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.c_float, C.c_float, C.c_float]),
     "gam_rnnt_greedy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "gam_rnnt_encp": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P]),
+    "gam_op_rnnt_greedy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P]),
+    "gam_rnnt_greedy_stream_bytes": (C.c_int64, [_P]),
+    "gam_op_rnnt_greedy_stream": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
     "gam_ctc_beam_nbest": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_op_ctc_beam_nbest": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_rnnt_beam_nbest": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),

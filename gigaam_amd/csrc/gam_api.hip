@@ -26,6 +26,7 @@
 #include "gam_common.h"
 #include "gam_convmod.h"
 #include "gam_decode.h"
+#include "gam_rnnt_stream.h"
 #include "gam_rnnt_align.h"
 #include "gam_confidence.h"
 #include "gam_decode_cluster.h"
@@ -1571,12 +1572,14 @@ static int ctc_logits(gam_handle* h, const float* encoded, int B, int64_t Tp, hi
   return gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE);
 }
 
-// The encoder half of the RNN-T joint for a whole batch: encoded [B, D, Tp] -> h->encp [B * Tp, JH] = W_enc f + b_enc.
-static int rnnt_encp(gam_handle* h, const float* encoded, int B, int64_t Tp, hipStream_t s) {
+// The encoder half of the RNN-T joint for a whole batch: encoded [B, D, Tp] -> [B * Tp, JH] = W_enc f + b_enc, into h->encp or, when
+// given, into the caller's `out` (gam_rnnt_encp).
+static int rnnt_encp(gam_handle* h, const float* encoded, int B, int64_t Tp, hipStream_t s, float* out = nullptr) {
   const int D = h->cfg.d_model, JH = h->cfg.joint_hidden;
   if (int r = to_tokens(h, encoded, B, Tp, s)) return r;
-  if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
-  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, h->encp.p, JH, (int)(B * Tp), JH, D);
+  if (!out)
+    if (int r = ensure(h, h->encp, (size_t)B * Tp * JH)) return r;
+  GamGemmArgs g = gemm_args(h->tok.p, D, h->jn_enc_w, h->jn_enc_b, out ? out : h->encp.p, JH, (int)(B * Tp), JH, D);
   return gemm(h, s, g, GAM_ACT_NONE, GAM_PF_DECODE);
 }
 
@@ -2291,14 +2294,14 @@ int gam_set_lm(gam_handle* h, const int32_t* token_class, int V, const void* wor
 }
 
 // ---- RNN-T greedy decode: the argument block, the cluster plan, the kernel table, the two launches, the entry point
-static GamRnntArgs rnnt_greedy_args(const gam_handle* h, const int32_t* enc_len, int B, int64_t Tp, int max_symbols, int32_t* ids,
-                                    int32_t* frames, int32_t* counts, float* logits_dump, int32_t* dump_count, int dump_cap) {
+static GamRnntArgs rnnt_greedy_args(const gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int max_symbols,
+                                    int32_t* ids, int32_t* frames, int32_t* counts, float* logits_dump, int32_t* dump_count, int dump_cap) {
   const gam_config& c = h->cfg;
   GamRnntArgs a;
   memset(&a, 0, sizeof a);
   rnnt_pred_weights(h, a);
   rnnt_joint_weights(h, a);
-  a.encp = h->encp.p; a.enc_len = enc_len; a.ids = ids; a.frames = frames; a.counts = counts;
+  a.encp = encp; a.enc_len = enc_len; a.ids = ids; a.frames = frames; a.counts = counts;
   a.dump = logits_dump; a.dump_count = dump_count; a.dump_cap = logits_dump ? dump_cap : 0;
   a.B = B; a.Tp = (int)Tp; a.V = c.num_classes; a.H = c.pred_hidden; a.JH = c.joint_hidden; a.L = c.pred_rnn_layers;
   a.max_symbols = max_symbols; a.cap = (int)Tp * max_symbols;
@@ -2429,15 +2432,9 @@ static int rnnt_cluster_launch(gam_handle* h, hipStream_t s, const GamRnntArgs& 
   return rnnt_timing_report(h, s, ca.status, p);
 }
 
-int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int max_symbols,
-                    int32_t* ids, int32_t* frames, int32_t* counts, float* logits_dump, int32_t* dump_count, int dump_cap,
-                    void* stream) {
-  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
-  if (B <= 0 || Tp <= 0 || max_symbols <= 0) return fail(h, -1, "bad arguments");
-  GAM_DECODE_ENTRY(h, stream);
-  if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
-  const GamRnntArgs a = rnnt_greedy_args(h, enc_len, B, Tp, max_symbols, ids, frames, counts, logits_dump, dump_count, dump_cap);
-  const RnntClusterPlan p = rnnt_cluster_plan(h->ncu, h->rnnt_cluster, h->rnnt_exclusive, B, a.H, a.JH, a.V, a.L);
+// The decode over a filled argument block: the cluster plan, the cluster launch with its repair pass, or the one-workgroup kernel.
+static int rnnt_greedy_run(gam_handle* h, hipStream_t s, const GamRnntArgs& a) {
+  const RnntClusterPlan p = rnnt_cluster_plan(h->ncu, h->rnnt_cluster, h->rnnt_exclusive, a.B, a.H, a.JH, a.V, a.L);
   ProfScope ps(h, s, GAM_PF_DECODE, 0.0);
   h->last_rnnt_c = p.C; h->last_rnnt_kern = p.C ? p.kern : -1; h->last_rnnt_refused = 0;   // (gam_rnnt_last_decode)
   if (p.C == 0) return rnnt_single_launch(h, s, a, 0);
@@ -2449,6 +2446,78 @@ int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len,
   return rnnt_single_launch(h, s, a, 1);   // repair pass: no-op workgroups unless a cluster gave up
 }
 
+int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp, int max_symbols,
+                    int32_t* ids, int32_t* frames, int32_t* counts, float* logits_dump, int32_t* dump_count, int dump_cap,
+                    void* stream) {
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
+  if (B <= 0 || Tp <= 0 || max_symbols <= 0) return fail(h, -1, "bad arguments");
+  GAM_DECODE_ENTRY(h, stream);
+  if (int r = rnnt_encp(h, encoded, B, Tp, s)) return r;
+  return rnnt_greedy_run(h, s, rnnt_greedy_args(h, h->encp.p, enc_len, B, Tp, max_symbols, ids, frames, counts, logits_dump, dump_count, dump_cap));
+}
+
+// gam_rnnt_greedy from a caller-supplied encoder projection: the same plan, no logits dump.
+int gam_op_rnnt_greedy(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int max_symbols, int32_t* ids,
+                       int32_t* frames, int32_t* counts, void* stream) {
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
+  if (B <= 0 || Tp <= 0 || max_symbols <= 0 || Tp * max_symbols >= 2147483648ll) return fail(h, -1, "bad arguments");
+  if (!encp || !enc_len || !ids || !frames || !counts) return fail(h, -1, "RNN-T greedy decode: NULL buffer");
+  GAM_DECODE_ENTRY(h, stream);
+  return rnnt_greedy_run(h, s, rnnt_greedy_args(h, encp, enc_len, B, Tp, max_symbols, ids, frames, counts, nullptr, nullptr, 0));
+}
+
+// The encoder projection GEMM of gam_rnnt_greedy into the caller's buffer.
+int gam_rnnt_encp(gam_handle* h, const float* encoded, int B, int64_t Tp, float* encp_out, void* stream) {
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
+  if (B <= 0 || Tp <= 0) return fail(h, -1, "bad shape B=%d T'=%lld", B, (long long)Tp);
+  if (!encoded || !encp_out) return fail(h, -1, "RNN-T encoder projection: NULL buffer");
+  GAM_DECODE_ENTRY(h, stream);
+  return rnnt_encp(h, encoded, B, Tp, s, encp_out);
+}
+
+// ---- the greedy decode of one stream fed in pieces (gam_rnnt_stream.h gam_rnnt_greedy_stream_kernel).  Decode class as above; the
+// state record and the result arrays are the caller's.
+int64_t gam_rnnt_greedy_stream_bytes(gam_handle* h) {
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
+  return (int64_t)gam_rnnt_stream_bytes(h->cfg.pred_hidden, h->cfg.pred_rnn_layers);
+}
+
+int gam_op_rnnt_greedy_stream(gam_handle* h, const float* encp, int64_t n, int64_t t_base, int flags, int max_symbols, void* state,
+                              int64_t state_bytes, int32_t* ids, int32_t* frames, int64_t cap, int32_t* count, int32_t* status,
+                              void* stream) {
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
+  if (n < 0 || t_base < 0 || n >= 2147483648ll || t_base >= 2147483648ll || t_base + n >= 2147483648ll)
+    return fail(h, -1, "RNN-T greedy stream: bad shape n=%lld t_base=%lld (t_base + n must stay below 2^31)", (long long)n, (long long)t_base);
+  if (max_symbols < 1 || cap < 0) return fail(h, -1, "RNN-T greedy stream: max_symbols=%d below 1 or cap=%lld below 0", max_symbols, (long long)cap);
+  if (flags & ~(GAM_RNNT_F_BEGIN | GAM_RNNT_F_END)) return fail(h, -1, "RNN-T greedy stream: unknown flags 0x%x", flags);
+  if ((n > 0 && !encp) || !state || !ids || !frames || !count || !status) return fail(h, -1, "RNN-T greedy stream: NULL buffer");
+  const int64_t need_bytes = (int64_t)gam_rnnt_stream_bytes(h->cfg.pred_hidden, h->cfg.pred_rnn_layers);
+  if (state_bytes < need_bytes)
+    return fail(h, -1, "RNN-T greedy stream: state_bytes=%lld below the record's %lld (gam_rnnt_greedy_stream_bytes)", (long long)state_bytes,
+                (long long)need_bytes);
+  GamRnntStreamArgs g;
+  memset(&g, 0, sizeof g);
+  rnnt_pred_weights(h, g.a);
+  rnnt_joint_weights(h, g.a);
+  const gam_config& c = h->cfg;
+  GamRnntArgs& a = g.a;
+  a.encp = encp; a.ids = ids; a.frames = frames;
+  a.B = 1; a.Tp = (int)n; a.V = c.num_classes; a.H = c.pred_hidden; a.JH = c.joint_hidden; a.L = c.pred_rnn_layers;
+  a.max_symbols = max_symbols; a.cap = (int)std::min<int64_t>(cap, 2147483647ll);
+  a.wout_in_lds = gam_rnnt_smem(a.H, a.JH, a.V, 1, a.L) <= 96 * 1024 ? 1 : 0;      // (the batch kernel's rule: rnnt_single_launch)
+  const size_t sm = gam_rnnt_smem(a.H, a.JH, a.V, a.wout_in_lds, a.L);
+  if (sm > 160 * 1024) return fail(h, -1, "RNN-T head too large for the greedy kernel's LDS window");
+  g.n = (int)n; g.t_base = (int)t_base; g.flags = flags; g.state = state; g.count = count; g.status = status;
+  GAM_DECODE_ENTRY(h, stream);
+  static std::atomic<unsigned long long> attr5{0}, attr8{0};
+  HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_greedy_stream_kernel<5>), 160 * 1024, attr5));
+  HIPCHK(h, gam_set_max_lds(reinterpret_cast<const void*>(gam_rnnt_greedy_stream_kernel<8>), 160 * 1024, attr8));
+  ProfScope ps(h, s, GAM_PF_DECODE, 0.0);
+  if (4 * a.H <= 256 * 5) hipLaunchKernelGGL(gam_rnnt_greedy_stream_kernel<5>, dim3(1), dim3(256), sm, s, g);
+  else hipLaunchKernelGGL(gam_rnnt_greedy_stream_kernel<8>, dim3(1), dim3(256), sm, s, g);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
 // RNN-T beam search over the encoder projection encp [B, Tp, JH] (gam_rnnt_beam.h): one workgroup per utterance; with the handle's LM
 // (gam_set_lm) gam_rnnt_beam_kernel<true>.  Decode class (the caller holds a DecodeScope): the state slots, logit rows and prefix-trie
 // nodes are the handle's.  nbest: the <.., true> kernels, ids / frames [B, N, cap] and counts / score / logp [B, N]; else N and n_hyp

@@ -206,39 +206,68 @@ static inline size_t gam_rnnt_smem(int H, int JH, int V, int wout_in_lds, int L 
   return sizeof(float) * f;
 }
 
-template <int NR>   // gate rows per thread: 4*H <= 256*NR
-__global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float gam_smem_rnnt[];
+// The LDS carve of gam_rnnt_smem, of the one-workgroup kernel and of its resumable twin (gam_rnnt_stream.h).
+struct GamRnntLds {
+  float *h_s, *c_s;      // committed state of layer 0
+  float *hn_s, *cn_s;    // candidate state (= g at L = 1)
+  float* gates;          // [4H]
+  float* pp;             // W_pred.g + b_pred  [JH]
+  float* zw;             // [WIN][JH + 4]  relu(enc + pred)   (16-byte aligned: 8H + 2JH floats)
+  float* lgw;            // [WIN][VP + 1]  logits
+  int* lab_s;            // [WIN]
+  float *mx_s, *lse_s;   // [WIN]
+  float* wout_l;         // [V][JH + 4], 16-byte aligned; null: W_out is read from L2
+  float* xs;             // state of layers 1 .. L-1, behind everything else: layer l at xs + (l - 1) * 4H as [h | c | h' | c']
+};
+
+__device__ __forceinline__ GamRnntLds gam_rnnt_carve(float* smem, int H, int JH, int V, int wout_in_lds) {
+  const int VP = (V + 15) / 16 * 16;
+  GamRnntLds s;
+  s.h_s = smem;
+  s.c_s = s.h_s + H;
+  s.hn_s = s.c_s + H;
+  s.cn_s = s.hn_s + H;
+  s.gates = s.cn_s + H;
+  s.pp = s.gates + 4 * H;
+  s.zw = s.pp + 2 * JH;
+  s.lgw = s.zw + GAM_RNNT_WIN * (JH + 4);
+  s.lab_s = reinterpret_cast<int*>(s.lgw + GAM_RNNT_WIN * (VP + 1));
+  s.mx_s = reinterpret_cast<float*>(s.lab_s + GAM_RNNT_WIN);
+  s.lse_s = s.mx_s + GAM_RNNT_WIN;
+  s.wout_l = wout_in_lds ? s.lse_s + GAM_RNNT_WIN + 12 : nullptr;
+  s.xs = s.lse_s + GAM_RNNT_WIN + 12 + (wout_in_lds ? (size_t)V * (JH + 4) : 0);
+  return s;
+}
+
+// W_out into its LDS copy (rows padded to JH + 4).  No barrier: the caller's next one makes it visible.
+__device__ __forceinline__ void gam_rnnt_load_wout(const GamRnntLds& s, const float* wout, int V, int JH, int tid) {
+  if (s.wout_l != nullptr)
+    for (int i = tid; i < V * JH; i += 256) s.wout_l[(i / JH) * (JH + 4) + (i % JH)] = wout[i];
+}
+
+// THE frame / symbol loop of the greedy decode, written once for gam_rnnt_greedy_kernel and gam_rnnt_greedy_stream_kernel: the
+// predictor candidate (gam_rnnt_layer_step), the W_pred product, the 16-frame joint window on the matrix cores, the per-frame
+// first-maximum argmax, the first-non-blank scan, the commit and the max_symbols rule.  The callers differ in three things only:
+//   where frames come from   rows 0 .. len - 1 of `encp` [len, JH];
+//   where tokens go          token n_out at ids[n_out] / frames[n_out] (frame_base + the local frame) while n_out < cap;
+//   where the state starts   the committed (h, c) of every layer in LDS (s.h_s / s.c_s / s.xs), the last label (V: none yet) and
+//   and ends                 n_out -- all left as the last commit made them, the candidate state and W_pred g NOT among them.
+// The loop returns only when frame len - 1 has ended, by a blank or at max_symbols, so `sym` is 0 whenever it returns: the symbols
+// emitted on the current frame are no part of what a caller has to carry.  Every (frame, state) is evaluated with the same
+// arithmetic wherever the window it falls into starts: a window's rows do not depend on each other (row f of the MFMA tile reads row f
+// of zw only), and a short window repeats its last row in the unused ones.  Enters and leaves with the workgroup behind a barrier.
+template <int NR>
+__device__ __forceinline__ void gam_rnnt_greedy_loop(const GamRnntArgs& a, const GamRnntLds& s, const float* encp, int len, int* ids,
+                                                     int* frames, int cap, int frame_base, float* dump, int& label, int& n_out,
+                                                     int& n_dump) {
   const int H = a.H, JH = a.JH, V = a.V, blank = a.V - 1;
-  const int VP = (V + 15) / 16 * 16, ZLD = JH + 4, LLD = VP + 1;
-  float* h_s = gam_smem_rnnt;            // committed state
-  float* c_s = h_s + H;
-  float* hn_s = c_s + H;                 // candidate state (= g)
-  float* cn_s = hn_s + H;
-  float* gates = cn_s + H;               // [4H]
-  float* pp = gates + 4 * H;             // W_pred.g + b_pred  [JH]
-  float* zw = pp + 2 * JH;               // [WIN][ZLD]  relu(enc + pred)   (16-byte aligned: 8H + 2JH floats)
-  float* lgw = zw + GAM_RNNT_WIN * ZLD;  // [WIN][LLD]  logits
-  int* lab_s = reinterpret_cast<int*>(lgw + GAM_RNNT_WIN * LLD);   // [WIN]
-  float* mx_s = reinterpret_cast<float*>(lab_s + GAM_RNNT_WIN);    // [WIN]
-  float* lse_s = mx_s + GAM_RNNT_WIN;                              // [WIN]
-  const int WLD = JH + 4;
-  float* wout_l = a.wout_in_lds ? lse_s + GAM_RNNT_WIN + 12 : nullptr;   // [V][WLD], 16-byte aligned
-  // state of layers 1 .. L-1, behind everything else: layer l at xs + (l - 1) * 4H as [h | c | h' | c']
-  float* xs = lse_s + GAM_RNNT_WIN + 12 + (a.wout_in_lds ? (size_t)V * WLD : 0);
+  const int VP = (V + 15) / 16 * 16, ZLD = JH + 4, LLD = VP + 1, WLD = JH + 4;
+  float *h_s = s.h_s, *c_s = s.c_s, *hn_s = s.hn_s, *cn_s = s.cn_s, *gates = s.gates, *pp = s.pp, *zw = s.zw, *lgw = s.lgw;
+  int* lab_s = s.lab_s;
+  float *mx_s = s.mx_s, *lse_s = s.lse_s, *wout_l = s.wout_l, *xs = s.xs;
   const int L = a.L > 1 ? a.L : 1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lg4 = lane >> 4;
-  const int b = blockIdx.x;
-  if (a.only_failed && a.counts[b] >= 0) return;   // (block-uniform) the cluster kernel finished this utterance
-  int len = a.enc_len[b];
-  len = len < 0 ? 0 : (len > a.Tp ? a.Tp : len);
-
-  for (int i = tid; i < H; i += 256) { h_s[i] = 0.f; c_s[i] = 0.f; }
-  for (int i = tid; i < (L - 1) * 4 * H; i += 256) xs[i] = 0.f;
-  if (wout_l != nullptr)
-    for (int i = tid; i < V * JH; i += 256) wout_l[(i / JH) * WLD + (i % JH)] = a.wout[i];
-  __syncthreads();
 
   // (frame, k) of this thread's window elements, fixed for the whole decode (index clamped: every load
   // is unconditional)
@@ -250,8 +279,6 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
     const int f = idx / JH;
     zfk[u] = (f << 16) | (idx - f * JH);
   }
-  int label = V;       // gate_tab row V: zero embedding (predict(None, None), decoder.py:97-100)
-  int n_out = 0, n_dump = 0;
   int t = 0, sym = 0;  // current frame, symbols already emitted on it
   bool need_pred = true;
 
@@ -303,7 +330,7 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
       for (int u = 0; u < NZ; ++u) {
         const int f = zfk[u] >> 16, k = zfk[u] & 0xffff;
         const int tt = t + (f < W ? f : W - 1);
-        ze[u] = a.encp[((size_t)b * a.Tp + tt) * JH + k];
+        ze[u] = encp[(size_t)tt * JH + k];
       }
 #pragma unroll
       for (int u = 0; u < NZ; ++u) {
@@ -351,7 +378,7 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
       }
       gam_first_max<64>(best, bi);
       float se = 0.f;
-      if (a.dump != nullptr) {
+      if (dump != nullptr) {
         for (int v = lane; v < V; v += 64) se += expf(lr[v] - best);
         se = gam_wave_sum(se);
       }
@@ -363,10 +390,10 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
     for (int f = 0; f < W; ++f)
       if (lab_s[f] != blank) { fstar = f; break; }
     const int n_eval = fstar < W ? fstar + 1 : W;   // joint evaluations the sequential loop performs
-    if (a.dump != nullptr) {
+    if (dump != nullptr) {
       for (int f = 0; f < n_eval; ++f) {
         if (n_dump + f < a.dump_cap) {
-          float* dp = a.dump + ((size_t)b * a.dump_cap + n_dump + f) * V;
+          float* dp = dump + (size_t)(n_dump + f) * V;
           const float lse = lse_s[f];
           for (int v = tid; v < V; v += 256) dp[v] = lgw[f * LLD + v] - lse;
         }
@@ -380,9 +407,9 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
       const int k = lab_s[fstar];
       const int te = t + fstar;
       if (fstar > 0) sym = 0;
-      if (tid == 0 && n_out < a.cap) {
-        a.ids[(size_t)b * a.cap + n_out] = k;
-        a.frames[(size_t)b * a.cap + n_out] = te;
+      if (tid == 0 && n_out < cap) {
+        ids[n_out] = k;
+        frames[n_out] = frame_base + te;
       }
       ++n_out;
       ++sym;
@@ -398,6 +425,29 @@ __global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
     }
     __syncthreads();
   }
+}
+
+template <int NR>   // gate rows per thread: 4*H <= 256*NR
+__global__ __launch_bounds__(256) void gam_rnnt_greedy_kernel(GamRnntArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float gam_smem_rnnt[];
+  const int H = a.H, V = a.V;
+  const GamRnntLds s = gam_rnnt_carve(gam_smem_rnnt, H, a.JH, V, a.wout_in_lds);
+  const int L = a.L > 1 ? a.L : 1;
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x;
+  if (a.only_failed && a.counts[b] >= 0) return;   // (block-uniform) the cluster kernel finished this utterance
+  int len = a.enc_len[b];
+  len = len < 0 ? 0 : (len > a.Tp ? a.Tp : len);
+
+  for (int i = tid; i < H; i += 256) { s.h_s[i] = 0.f; s.c_s[i] = 0.f; }
+  for (int i = tid; i < (L - 1) * 4 * H; i += 256) s.xs[i] = 0.f;
+  gam_rnnt_load_wout(s, a.wout, V, a.JH, tid);
+  __syncthreads();
+
+  int label = V;       // gate_tab row V: zero embedding (predict(None, None), decoder.py:97-100)
+  int n_out = 0, n_dump = 0;
+  gam_rnnt_greedy_loop<NR>(a, s, a.encp + (size_t)b * a.Tp * a.JH, len, a.ids + (size_t)b * a.cap, a.frames + (size_t)b * a.cap, a.cap, 0,
+                           a.dump != nullptr ? a.dump + (size_t)b * a.dump_cap * V : nullptr, label, n_out, n_dump);
   if (tid == 0) {
     a.counts[b] = n_out < a.cap ? n_out : a.cap;
     if (a.dump_count != nullptr) a.dump_count[b] = n_dump;

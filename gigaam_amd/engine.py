@@ -496,6 +496,53 @@ class BeamStream(_ResumableStream):
         return self.engine._beam_stream_v()
 
 
+class RnntGreedyStream(_ResumableStream):
+    """RNN-T greedy decode over one stream of any length fed in pieces (``HipEngine.rnnt_greedy_stream``;
+    gam_op_rnnt_greedy_stream): owns the state record and a one-row packed ``Decoded`` with room for ``max_frames * max_symbols``
+    tokens.  ``push`` enqueues the next rows of the encoder projection (``HipEngine.rnnt_encp``), ``finish`` ends the stream and returns
+    the ``Decoded``, which ``HipEngine.collect`` reads like any greedy decode (frames are stream frames); neither synchronises the
+    host.  ``out.counts`` holds the tokens so far after every accepted call.  ``status`` (i32 [1] on the device) is that of the
+    stream's LAST call: 0 = the library refused it (``check`` raises)."""
+    BEGIN, END = 1, 2      # include/gigaam_hip.h GAM_RNNT_STREAM_BEGIN / _END
+    NAME, MAKER = "RNN-T greedy stream", "rnnt_greedy_stream"
+
+    def __init__(self, engine: "HipEngine", max_frames: int, max_symbols: int):
+        self.max_frames, self.max_symbols = int(max_frames), int(max_symbols)
+        if self.max_frames < 0 or self.max_symbols < 1 or self.max_frames * self.max_symbols >= 2 ** 31:
+            raise GigaAMHipError(f"RNN-T greedy stream: max_frames {max_frames} x max_symbols {max_symbols} outside [0, 2^31)")
+        nbytes = int(engine.lib.gam_rnnt_greedy_stream_bytes(engine._h))
+        if nbytes < 0:
+            engine._check(-1, "gam_rnnt_greedy_stream_bytes")
+        self.state_bytes = nbytes
+        self.cap = max(self.max_frames * self.max_symbols, 1)      # (at least one word: the library takes no NULL ids / frames)
+        # the record, and behind it the status word (one buffer: what a side-stream call must keep alive)
+        state = torch.zeros(((nbytes + 3) // 4 + 1,), dtype=_I32, device=engine.device)
+        super().__init__(engine, state, Decoded.packed(engine.device, 1, self.cap))
+        self.status = state[-1:]
+        self.out.whole.zero_()      # (a stream refused at its first call has count 0)
+
+    def _launch(self, encp_rows: Optional[Tensor], v: int, flags: int) -> None:
+        self.engine.op_rnnt_greedy_stream(encp_rows, self.t_next, flags, self.max_symbols, self.state, self.state_bytes, self.out,
+                                          self.status)
+
+    def _empty_v(self) -> int:
+        return int(self.engine.cfg.joint_hidden)
+
+    def push(self, encp_rows: Tensor, overlap: bool = False):
+        """``_ResumableStream.push`` of rows of the encoder projection, f32 [n, joint_hidden] (n = 0 is legal)."""
+        encp_rows = self.engine._dev(encp_rows, torch.float32)
+        if encp_rows.dim() != 2 or int(encp_rows.shape[1]) != self._empty_v():
+            raise GigaAMHipError(f"{self.NAME}: encp rows must be [n, {self._empty_v()}], got {tuple(encp_rows.shape)}")
+        self.v = self._empty_v()
+        return self._call(encp_rows, self.v, 0, overlap)
+
+    def check(self) -> None:
+        """Raise ``GigaAMHipError`` if the library refused the stream's last call (one blocking one-word copy)."""
+        if not int(_to_host((self.status,), getattr(self.out, "event", None))[0][0]):
+            raise GigaAMHipError("RNN-T greedy stream: the call was refused (the state was not begun or has ended, a frame was skipped, "
+                                 "max_symbols or the head changed, or more rows than max_frames)")
+
+
 class AlignedLong(_Packed):
     """What ``op_ctc_align_long`` returns: every output of the long-utterance alignment as a view of ONE i32 device buffer (``whole``)
     that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: score (f64 bits, 2 words) | loglik (f64 bits, 2 words) |
@@ -1594,6 +1641,47 @@ class HipEngine:
             if overlap:
                 self._check(self.lib.gam_set_rnnt_cluster(self._h, self._rnnt_cluster_user), "gam_set_rnnt_cluster")
         return Decoded(ids, frames, counts, out.ext, evt, st, dump, dcount, whole=whole)
+
+    def rnnt_encp(self, encoded: Tensor) -> Tensor:
+        """[B, d_model, T'] -> the encoder half of the joint, encp f32 [B, T', joint_hidden] = W_enc f + b_enc (gam_rnnt_encp: the
+        projection GEMM ``rnnt_greedy`` runs): what the ``op_rnnt_*`` calls and ``RnntGreedyStream.push`` take.  The RNN-T twin of
+        ``ctc_head``; no host sync."""
+        encoded, _, b, tp = self._in_encoded(encoded, None)
+        out = torch.empty((b, tp, int(self.cfg.joint_hidden)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_rnnt_encp(self._h, _ptr(encoded), b, tp, _ptr(out), self._stream())
+        self._check(rc, "gam_rnnt_encp")
+        return out
+
+    def op_rnnt_greedy(self, encp: Tensor, enc_len: Tensor, max_symbols: int) -> Decoded:
+        """gam_op_rnnt_greedy: ``rnnt_greedy`` from a caller-supplied encoder projection encp f32 [B, T', joint_hidden], on the current
+        stream: the same plan (the cluster setting is honoured, the repair pass runs), no logits dump.  The flag word is 0."""
+        encp, enc_len, b, tp = self._in_encp(encp, enc_len)
+        out = Decoded.packed(self.device, b, tp * int(max_symbols))
+        with torch.cuda.device(self.device):
+            rc = self.lib.gam_op_rnnt_greedy(self._h, _ptr(encp), _ptr(enc_len), b, tp, int(max_symbols), _ptr(out.ids), _ptr(out.frames),
+                                             _ptr(out.counts), self._stream())
+            self._check(rc, "gam_op_rnnt_greedy")
+            return self._finish(out, False)
+
+    def op_rnnt_greedy_stream(self, encp_rows: Optional[Tensor], t_base: int, flags: int, max_symbols: int, state: Tensor,
+                              state_bytes: int, out: Decoded, status: Tensor, cap: Optional[int] = None) -> None:
+        """gam_op_rnnt_greedy_stream as it is, on the current stream: rows ``encp_rows`` f32 [n, joint_hidden] (None: n = 0) are stream
+        frames ``t_base`` .., ``flags`` of ``RnntGreedyStream.BEGIN`` / ``END``, ``state`` the buffer of gam_rnnt_greedy_stream_bytes
+        (``state_bytes`` of it are the record), ``out`` a one-row ``Decoded`` (``cap``: how many of its columns the library may
+        use, default all), ``status`` i32 [1].  ``RnntGreedyStream`` is the caller that keeps ``t_base`` and the flags right."""
+        n = 0 if encp_rows is None else int(encp_rows.shape[0])
+        cap = int(out.ids.shape[1]) if cap is None else min(int(cap), int(out.ids.shape[1]))
+        rc = self.lib.gam_op_rnnt_greedy_stream(self._h, _ptr(encp_rows if n else None), n, int(t_base), int(flags), int(max_symbols),
+                                                _ptr(state), int(state_bytes), _ptr(out.ids), _ptr(out.frames), cap, _ptr(out.counts),
+                                                _ptr(status), self._stream())
+        self._check(rc, "gam_op_rnnt_greedy_stream")
+
+    def rnnt_greedy_stream(self, max_frames: int, max_symbols: int) -> RnntGreedyStream:
+        """A resumable RNN-T greedy decode over one stream of at most ``max_frames`` frames (gam_op_rnnt_greedy_stream): feed it rows
+        of ``rnnt_encp`` with ``push``, end it with ``finish``.  One workgroup, the one-workgroup kernel's arithmetic (cluster size 0);
+        the predictor's state is carried from call to call, so the stream is decoded as ONE utterance wherever it is cut."""
+        return RnntGreedyStream(self, max_frames, max_symbols)
 
     def rnnt_predict(self, labels: Optional[Tensor], state: Optional[Tuple[Tensor, Tensor]], batch_size: int = 1):
         """One predictor step (reference RNNTDecoder.predict, gigaam/decoder.py:85-102): labels i [B] or None (zero input),

@@ -818,7 +818,7 @@ class GigaAMASR(GigaAM):
                             hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
                             lm_weight: float = 0.5, word_bonus: float = 1.0, chunk_length_s: float = 20.0,
                             stride_length_s: Optional[float] = None, pause_s: float = 1.0, max_segment_s: float = 22.0,
-                            stream_search: bool = False, **kwargs: Any) -> LongformTranscriptionResult:
+                            stream_search: bool = False, stream_decode: bool = False, **kwargs: Any) -> LongformTranscriptionResult:
         """Segment -> zero-padded batches of ``fr_batch_size`` -> transcribe -> stitch
         (reference model.py:195-259).  The reference segments with pyannote's VAD
         (gated third-party model, not installable here); pass ``speech_regions=[(s,e),..]``,
@@ -838,9 +838,29 @@ class GigaAMASR(GigaAM):
         decoded as ONE utterance (``_transcribe_windows``); ``pause_s`` / ``max_segment_s`` cut its words into segments.  With
         ``stream_search=True`` and at least one of ``beam_size`` / ``hotwords`` / ``lm`` that utterance is decoded by the resumable
         beam search instead (``_transcribe_windows_beam``): the LM then sees the whole file as ONE history, <s> at its first frame
-        and </s> at its end."""
+        and </s> at its end.
+
+        ``vad="windows", stream_decode=True`` (RNN-T heads) is the same detector-free route for a transducer: the windows' encoder
+        frames are stitched as the encoder half of the joint, and the resumable greedy kernel walks them in order, carrying its
+        predictor state across the seams (``_transcribe_windows_rnnt``): the predictor sees the file as ONE history, where the
+        speech-region route starts a new one per chunk.  It decodes greedily: beam options are errors."""
         windows = self._windows_route(kwargs, refuse=False)
         search = beam_size is not None or hotwords is not None or lm is not None
+        if stream_decode:      # (every error before any audio is read)
+            if stream_search:
+                raise ValueError("stream_search=True is the CTC heads' resumable beam search, stream_decode=True the RNN-T heads' resumable "
+                                 "greedy decode: a call takes one of them")
+            if not windows:
+                raise ValueError('stream_decode=True decodes the stitched stream of vad="windows"; the other routes decode chunk by chunk')
+            if not isinstance(self.decoding, _decoding.RNNTGreedyDecoding):
+                raise TypeError("stream_decode needs an RNN-T head")
+            self._beam_width(beam_size, hotwords, lm)      # (per-call beam options on an RNN-T model: the TypeError they always raise)
+            if isinstance(self.decoding, _decoding.RNNTBeamDecoding):
+                raise ValueError("stream_decode=True decodes greedily: the RNN-T beam kernel stops at 8192 frames, so the beam decoding "
+                                 "selected by set_decoding is not available over the stitched stream (set_decoding() selects greedy again)")
+            self._windows_route(kwargs)
+            return self._transcribe_windows_rnnt(wav_file, word_timestamps, fr_batch_size, chunk_length_s, stride_length_s, pause_s,
+                                                 max_segment_s)
         if stream_search and not windows:
             raise ValueError('stream_search=True searches the stitched stream of vad="windows"; the other routes search chunk by chunk')
         if windows:
@@ -893,11 +913,12 @@ class GigaAMASR(GigaAM):
         return LongformTranscriptionResult(segments=self._file_run(run))
 
     # ---- longform without a speech detector: overlapping windows stitched on the device (windows.py, gam_stitch.h)
-    def _plan_windows(self, wav_file: str, chunk_length_s: float, stride_length_s: Optional[float]):
-        """(the file's samples as one CPU tensor, the window plan): every error that needs no GPU work is raised here."""
+    def _plan_windows(self, wav_file: str, chunk_length_s: float, stride_length_s: Optional[float], rnnt: bool = False):
+        """(the file's samples as one CPU tensor, the window plan): every error that needs no GPU work is raised here.  ``rnnt``: the
+        caller stitches encoder frames for an RNN-T head (``_transcribe_windows_rnnt``) and has made its own head check."""
         from .windows import plan_windows
 
-        if not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
+        if not rnnt and not isinstance(self.decoding, _decoding.CTCGreedyDecoding):
             raise TypeError("windowed longform needs a CTC head")
         eng = self.head.engine
         audio = load_audio(wav_file, SAMPLE_RATE)
@@ -905,27 +926,31 @@ class GigaAMASR(GigaAM):
         return audio, plan_windows(int(audio.shape[0]), frame_samples, lambda n: eng.enc_frames(eng.feat_frames(n)), chunk_length_s,
                                    stride_length_s, SAMPLE_RATE)
 
-    def _stitched_log_probs(self, audio: Tensor, plan, fr_batch_size: int,
-                            after_batch: Optional[Callable[[Tensor], None]] = None) -> Tuple[Tensor, Tensor]:
+    def _stitched_log_probs(self, audio: Tensor, plan, fr_batch_size: int, after_batch: Optional[Callable[[Tensor], None]] = None,
+                            head: Optional[Tuple[Callable[[Tensor], Tensor], int]] = None) -> Tuple[Tensor, Tensor]:
         """The windows of ``plan`` (views of ``audio``) through the feeder, the encoder (packed rows: host lengths) and the CTC head,
         batch by batch; each batch's kept frames go straight into one preallocated [T_total, V] buffer (gam_op_ctc_stitch).  The window
         tables are uploaded once, nothing is read back.  Returns (the stream, the stitch statuses i32 [windows]), both on the device.
         ``after_batch(rows)``: called behind each batch's stitch with the rows of the stream that batch added (a view; they are
-        contiguous: from the ``dst`` of its first window to the end of its last)."""
+        contiguous: from the ``dst`` of its first window to the end of its last).  ``head``: (what makes a batch's rows
+        [B, T', width] from its encoder output, their width) where they are not the CTC head's log-probs -- the encoder frames are the
+        same for either head, only the rows are head-specific (``_transcribe_windows_rnnt``: ``rnnt_encp``, joint_hidden; the stitch
+        copies rows of any width)."""
         from .feeder import BatchFeeder
 
         eng, dev, ws = self.head.engine, self._device, plan.windows
         lo = torch.tensor([w.lo for w in ws], dtype=torch.int32).to(dev)
         hi = torch.tensor([w.hi for w in ws], dtype=torch.int32).to(dev)
         dst = torch.tensor([w.dst for w in ws], dtype=torch.int64).to(dev)
-        out = torch.empty((plan.t_total, int(eng.cfg.num_classes)), dtype=torch.float32, device=dev)
+        rows_of, width = (eng.ctc_head, int(eng.cfg.num_classes)) if head is None else head
+        out = torch.empty((plan.t_total, width), dtype=torch.float32, device=dev)
         status: List[Tensor] = []
         feeder = BatchFeeder([audio[w.start:w.stop] for w in ws], fr_batch_size, dev)
         o = 0
         for wav, lens in feeder:
             b = wav.shape[0]
             encoded, encoded_len = self._encode(wav, lens, getattr(feeder, "host_lengths", None))
-            status.append(eng.op_ctc_stitch(eng.ctc_head(encoded), encoded_len, lo[o:o + b], hi[o:o + b], dst[o:o + b], out))
+            status.append(eng.op_ctc_stitch(rows_of(encoded), encoded_len, lo[o:o + b], hi[o:o + b], dst[o:o + b], out))
             if after_batch is not None:
                 after_batch(out[ws[o].dst:ws[o + b - 1].dst + ws[o + b - 1].hi - ws[o + b - 1].lo])
             o += b
@@ -938,18 +963,19 @@ class GigaAMASR(GigaAM):
                                  f"(stitch statuses {status.cpu().tolist()})")
 
     def _windows_run(self, audio: Tensor, plan, fr_batch_size: int, whole: Optional[Callable[[Tensor], Dict[str, Any]]] = None,
-                     stream=None, overlap: bool = False, ended: Optional[Callable[[Tensor, Any], Dict[str, Any]]] = None) -> Dict[str, Any]:
+                     stream=None, overlap: bool = False, ended: Optional[Callable[[Tensor, Any], Dict[str, Any]]] = None,
+                     head: Optional[Tuple[Callable[[Tensor], Tensor], int]] = None) -> Dict[str, Any]:
         """One pass of a windowed route over the stitched stream of ``plan`` -> its result on the host.  Either ``whole(stream)`` -- a
         one-shot op on the finished [T_total, V] stream, brought to the host (a dict with ``flag``) -- or ``stream``, a resumable
         search (engine.KeywordStream / BeamStream): ONE push of the rows each batch added behind that batch's stitch (``overlap``: on
         the decode side stream, beside the next batch's frontend and encoder), then the END call and ONE collect -- or, with ``ended``,
         ``ended(stream, result)``: a pass over the finished stream that reads the search's result on the device, and brings both to
-        the host.  Raises decoding.RangeOverflow on the flag, then checks the stitch statuses."""
+        the host.  ``head``: as ``_stitched_log_probs``.  Raises decoding.RangeOverflow on the flag, then checks the stitch statuses."""
         if stream is None:
-            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size)
+            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size, head=head)
             h = whole(lp_all)
         else:
-            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: stream.push(rows, overlap=overlap))
+            lp_all, status = self._stitched_log_probs(audio, plan, fr_batch_size, lambda rows: stream.push(rows, overlap=overlap), head=head)
             out = stream.finish(consume_flag=True)
             h = out.host() if ended is None else ended(lp_all, out)
         _decoding.check_range(h["flag"])
@@ -1009,6 +1035,35 @@ class GigaAMASR(GigaAM):
             eng.set_lm(dec.language_model(lm), dec.tokenizer, lm_weight, word_bonus)
             h = self._windows_run(audio, plan, fr_batch_size, stream=eng.beam_stream(width, plan.t_total), overlap=overlap)
             return h["ids"].tolist(), h["frames"].tolist()
+
+        ids, frames = self._file_run(run)
+        return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)
+
+    def _transcribe_windows_rnnt(self, wav_file: str, word_timestamps: bool, fr_batch_size: int, chunk_length_s: float,
+                                 stride_length_s: Optional[float], pause_s: float, max_segment_s: float) -> LongformTranscriptionResult:
+        """``transcribe_longform(vad="windows", stream_decode=True)`` on an RNN-T head: the plan of ``_transcribe_windows``; each feeder
+        batch goes through the encoder and the encoder half of the joint (``rnnt_encp``), and its kept frames are stitched into one
+        [T_total, joint_hidden] buffer; behind each batch's stitch ONE push of the rows that batch added into a resumable greedy decode
+        (engine.RnntGreedyStream, gam_op_rnnt_greedy_stream) -- on the decode side stream, so that batch n's decode runs beside batch
+        n + 1's frontend and encoder (GAM_RNNT_STREAM_OVERLAP=0: on the launch stream, the A/B switch) --, then the END call and ONE
+        collect.  The predictor's state crosses the seams: the file is ONE history.  Words follow ``_windows_result``'s rule; a frame
+        may carry several tokens (up to max_symbols_per_step), which then share its time."""
+        audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s, rnnt=True)
+        if not plan.windows:
+            return LongformTranscriptionResult(segments=[])
+        eng = self.head.engine
+        overlap = os.environ.get("GAM_RNNT_STREAM_OVERLAP", "1") != "0"
+
+        def run():      # (a rerun under GAM_GEMM_F32 comes here again: a new stream, BEGIN)
+            stream = eng.rnnt_greedy_stream(plan.t_total, int(self.decoding.max_symbols))
+
+            def ended(_, out) -> Dict[str, Any]:
+                rows, flag = HipEngine.collect(out)
+                stream.check()
+                return {"rows": rows[0], "flag": flag}
+
+            return self._windows_run(audio, plan, fr_batch_size, stream=stream, overlap=overlap, ended=ended,
+                                     head=(eng.rnnt_encp, int(eng.cfg.joint_hidden)))["rows"]
 
         ids, frames = self._file_run(run)
         return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)

@@ -340,6 +340,37 @@ int gam_set_lm(gam_handle* h, const int32_t* token_class, int V, const void* wor
 int gam_rnnt_greedy(gam_handle* h, const float* encoded, const int32_t* enc_len, int B, int64_t Tp,
                     int max_symbols, int32_t* ids, int32_t* frames, int32_t* counts,
                     float* logits_dump, int32_t* dump_count, int dump_cap, void* stream);
+/* The encoder half of the RNN-T joint ("encp"): encoded f32 [B, d_model, T'] -> encp_out f32 [B, T', joint_hidden] = W_enc f + b_enc,
+ * by the projection GEMM that gam_rnnt_greedy runs (same transpose, same GEMM arguments, same class), written to the caller's buffer:
+ * what gam_op_rnnt_greedy / _beam / _align / _confidence consume.  The RNN-T twin of gam_ctc_head.  Decode class; no host
+ * synchronisation. */
+int gam_rnnt_encp(gam_handle* h, const float* encoded, int B, int64_t Tp, float* encp_out, void* stream);
+/* gam_rnnt_greedy from a caller-supplied encp f32 [B, T', joint_hidden], the counterpart of gam_op_rnnt_beam: the same plan (the
+ * cluster setting of gam_set_rnnt_cluster is honoured, the repair pass runs, gam_rnnt_last_decode is updated), no logits dump. */
+int gam_op_rnnt_greedy(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int max_symbols, int32_t* ids,
+                       int32_t* frames, int32_t* counts, void* stream);
+/* The greedy decode of ONE stream of any length fed in pieces (gigaam_amd/csrc/gam_rnnt_stream.h): one workgroup, the one-workgroup
+ * kernel's frame / symbol loop, so every (frame, state) is evaluated with gam_rnnt_greedy's one-workgroup arithmetic (cluster size 0)
+ * and a stream cut anywhere gives the bits of the uncut one.  Rows 0 .. n - 1 of encp f32 [n, joint_hidden] are stream frames
+ * t_base .. t_base + n - 1.  state: a caller-owned record of gam_rnnt_greedy_stream_bytes(h) bytes (a header and the committed (h, c)
+ * of every predictor layer) that carries the predictor from call to call.  flags: GAM_RNNT_STREAM_BEGIN starts a stream at this
+ * call's t_base (any value >= 0) from predict(None, None), whatever the record held; GAM_RNNT_STREAM_END ends it.  n = 0 is legal with
+ * either flag, both or none.
+ *   ids / frames i32 [cap]: token k of the stream is written at index k by the call that emits it; frames are stream frames.
+ *   count i32 [1]: the tokens so far, written by every accepted call -- the prefix is readable after any call.
+ *   status i32 [1]: 1 = accepted; 0 = refused, nothing else written and the record unchanged.  Refused: the record was not begun or
+ *   has ended (without BEGIN); t_base is not the record's next frame; max_symbols, V, pred_hidden, joint_hidden or the predictor's
+ *   layers differ from what BEGIN recorded; the call could overflow cap (count + n * max_symbols > cap).  The stream carries on with the
+ *   right call afterwards.
+ * Errors without a launch: a head that is not RNN-T; n < 0, t_base < 0 or t_base + n >= 2^31; max_symbols < 1; cap < 0; unknown
+ * flags; state_bytes below the record's size; a NULL buffer (encp may be NULL when n = 0); LDS over the limit.  Decode class; no host
+ * synchronisation. */
+#define GAM_RNNT_STREAM_BEGIN 1
+#define GAM_RNNT_STREAM_END 2
+int64_t gam_rnnt_greedy_stream_bytes(gam_handle* h);
+int gam_op_rnnt_greedy_stream(gam_handle* h, const float* encp, int64_t n, int64_t t_base, int flags, int max_symbols, void* state,
+                              int64_t state_bytes, int32_t* ids, int32_t* frames, int64_t cap, int32_t* count, int32_t* status,
+                              void* stream);
 
 /* RNN-T beam search with hotword boosting and n-gram LM fusion (gigaam_amd/csrc/gam_rnnt_beam.h holds the contract).  Runs the
  * encoder projection GEMM that gam_rnnt_greedy runs, then ONE beam kernel (a workgroup per utterance, t the sequential loop,
