@@ -97,6 +97,9 @@ SIGNATURES = {
     "gam_op_rnnt_beam_nbest": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gam_rnnt_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_rnnt_beam": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "gam_rnnt_beam_stream_bytes": (C.c_int64, [_P, C.c_int, C.c_int, C.c_int64]),
+    "gam_op_rnnt_beam_stream": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P, _P,
+                                          _P, _P, _P]),
     "gam_rnnt_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "gam_op_rnnt_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gam_op_rnnt_lattice_align": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

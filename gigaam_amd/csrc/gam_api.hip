@@ -21,6 +21,7 @@
 #include "gam_beam.h"
 #include "gam_beam_stream.h"
 #include "gam_rnnt_beam.h"
+#include "gam_rnnt_beam_stream.h"
 #include "gam_attn16.h"
 #include "gam_comm.h"
 #include "gam_common.h"
@@ -2607,6 +2608,83 @@ int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, i
   if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
   GAM_DECODE_ENTRY(h, stream);
   return rnnt_beam_launch(h, encp, enc_len, B, Tp, W, max_symbols, ids, frames, counts, score, logp, s);
+}
+
+// ---- the same search for one stream fed in pieces (gam_rnnt_beam_stream.h gam_rnnt_beam_stream_kernel).  Decode class as above; the
+// state record with its slot and node pools is the caller's, the logit rows are the handle's.
+// The limits both stream entries share; K and the head's sizes for the caller.
+static int rnnt_beam_stream_check(gam_handle* h, int W, int max_symbols) {
+  if (int r = head_check(h, GAM_HEAD_RNNT, "RNN-T head")) return r;
+  const gam_config& c = h->cfg;
+  const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden;
+  if (W < 1 || W > GAM_BEAM_MAX_W) return fail(h, -1, "RNN-T beam stream: beam width W=%d outside [1, %d]", W, GAM_BEAM_MAX_W);
+  if (max_symbols < 1 || max_symbols > GAM_RB_MAX_S)
+    return fail(h, -1, "RNN-T beam stream: max_symbols S=%d outside [1, %d]", max_symbols, GAM_RB_MAX_S);
+  if (V < 2 || V > GAM_BEAM_MAX_V) return fail(h, -1, "RNN-T beam stream: V=%d outside [2, %d]", V, GAM_BEAM_MAX_V);
+  if (H > GAM_RB_MAX_H || JH > GAM_RB_MAX_H || H % 16 != 0 || JH % 16 != 0)
+    return fail(h, -1, "RNN-T beam stream: H=%d / JH=%d must be multiples of 16 up to %d", H, JH, GAM_RB_MAX_H);
+  return 0;
+}
+
+int64_t gam_rnnt_beam_stream_bytes(gam_handle* h, int W, int max_symbols, int64_t max_frames) {
+  if (int r = rnnt_beam_stream_check(h, W, max_symbols)) return r;
+  if (max_frames < 0 || max_frames * max_symbols * W >= 2147483648ll)
+    return fail(h, -1, "RNN-T beam stream: max_frames=%lld x S=%d x W=%d outside [0, 2^31)", (long long)max_frames, max_symbols, W);
+  const gam_config& c = h->cfg;
+  return (int64_t)gam_rb_stream_fixed_bytes(W, max_symbols, c.pred_hidden, c.joint_hidden, c.pred_rnn_layers) +
+         max_frames * max_symbols * W * (int64_t)sizeof(int4);
+}
+
+int gam_op_rnnt_beam_stream(gam_handle* h, const float* encp, int64_t n, int64_t t_base, int flags, int W, int max_symbols, void* state,
+                            int64_t state_bytes, int32_t* ids, int32_t* frames, int64_t cap, int32_t* count, double* score, double* logp,
+                            int32_t* status, void* stream) {
+  if (int r = rnnt_beam_stream_check(h, W, max_symbols)) return r;
+  GAM_DECODE_ENTRY(h, stream);
+  const gam_config& c = h->cfg;
+  const int V = c.num_classes, H = c.pred_hidden, JH = c.joint_hidden, L = c.pred_rnn_layers;
+  if (n < 0 || t_base < 0 || n >= 2147483648ll || t_base >= 2147483648ll || t_base + n >= 2147483648ll)
+    return fail(h, -1, "RNN-T beam stream: bad shape n=%lld t_base=%lld (t_base + n must stay below 2^31)", (long long)n, (long long)t_base);
+  if (cap < 0) return fail(h, -1, "RNN-T beam stream: cap=%lld below 0", (long long)cap);
+  if (flags & ~(GAM_RB_F_BEGIN | GAM_RB_F_END)) return fail(h, -1, "RNN-T beam stream: unknown flags 0x%x", flags);
+  if (int r = beam_check(h, "RNN-T beam stream", W, V, (n > 0 && !encp) || !state || !ids || !frames || !count || !score || !logp || !status,
+                         "RNN-T beam stream: the LM's token classes are for V=%d, the model has V=%d"))
+    return r;
+  if (reinterpret_cast<uintptr_t>(state) & 15)      // (the entries' word state and the nodes are int4)
+    return fail(h, -1, "RNN-T beam stream: state %p is not 16-byte aligned", state);
+  const int64_t fixed = (int64_t)gam_rb_stream_fixed_bytes(W, max_symbols, H, JH, L);
+  if (state_bytes < fixed)
+    return fail(h, -1, "RNN-T beam stream: state_bytes=%lld below the record's %lld (gam_rnnt_beam_stream_bytes)", (long long)state_bytes,
+                (long long)fixed);
+  // the frames the caller's node pool holds at this W and S: the kernel refuses rows beyond them (and a record begun with more)
+  const int64_t per_frame = (int64_t)max_symbols * W;
+  const int64_t max_frames = std::min<int64_t>((state_bytes - fixed) / (per_frame * (int64_t)sizeof(int4)), 2147483647ll / per_frame);
+  const bool lm = h->lm_ng.p != nullptr;
+  const int K = std::min(W, V - 1);
+  const size_t base = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, 0, lm ? V : 0);
+  if (base > 160 * 1024)
+    return fail(h, -1, "RNN-T beam stream: W=%d, S=%d, H=%d, L=%d%s need %zu bytes of LDS (> 160 KiB)", W, max_symbols, H, L,
+                lm ? " with the LM" : "", base);
+  const bool hw_lds = h->hw_trie.p && (size_t)h->hw_words * 4 <= GAM_BEAM_HW_LDS_MAX && base + (size_t)h->hw_words * 4 <= 160 * 1024;
+  const size_t sm = gam_rb_lds_bytes(W, K, max_symbols, H, JH, L, hw_lds ? h->hw_words : 0, lm ? V : 0);
+  if (int r = ensure(h, h->rb_ws, gam_rb_stream_ws_floats(W, V) + 64)) return r;
+  GamRnntBeamStreamArgs g;
+  memset(&g, 0, sizeof g);
+  GamRnntBeamArgs& a = g.a;
+  rnnt_pred_weights(h, a);
+  rnnt_joint_weights(h, a);
+  a.encp = encp;
+  a.Tp = (int)n; a.V = V; a.H = H; a.JH = JH; a.L = L; a.W = W; a.K = K; a.S = max_symbols;
+  a.hw = hw_args(h, hw_lds);
+  a.lm = lm_args(h);
+  a.ws = h->rb_ws.p;
+  a.ids = ids; a.frames = frames; a.cap = (int)std::min<int64_t>(cap, 2147483647ll); a.counts = count;
+  g.x.n = (int)n; g.x.t_base = (int)t_base; g.x.max_frames = (int)max_frames; g.x.flags = flags;
+  g.x.hw_gen = h->hw_gen; g.x.lm_gen = h->lm_gen;
+  g.x.state = state; g.x.status = status; g.x.score = score; g.x.logp = logp;
+  static std::atomic<unsigned long long> lds_set[2];
+  static const void* const kern[2] = {(const void*)gam_rnnt_beam_stream_kernel<false>, (const void*)gam_rnnt_beam_stream_kernel<true>};
+  ProfScope ps(h, s, GAM_PF_DECODE, (double)n * ((double)V * JH + 4.0 * H * H) * 4.0);
+  return beam_launch(h, kern[lm ? 1 : 0], lds_set[lm ? 1 : 0], 160 * 1024, 1, GAM_RB_NT, sm, s, &g);
 }
 
 // ---- transducer forced alignment (gam_rnnt_align.h).  Decode class (the caller holds a DecodeScope): every buffer is the handle's.

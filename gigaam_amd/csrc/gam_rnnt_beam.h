@@ -61,7 +61,12 @@
 // of A_{s+1} whose partial word is non-empty, right after its top-W selection, and the next joint phase only adds d to the
 // extensions by class-1/2 tokens (the split of gam_search.h).  The LM state of the A lists and of B (36 B per entry) and the class
 // table [V] i8 lie in LDS after the union region (gam_rb_lm_bytes): 22.4 KiB at W = 32, S = 16, V = 1025.
+//
+// One stream fed in pieces (template <bool STREAM>; gam_rnnt_beam_stream.h holds the contract of that form and its kernel): the same
+// text with every difference behind `if constexpr (STREAM)` -- the beam comes from and goes to a caller-owned record, rows are stream
+// frames, nodes are int4, score / logp are fp64.  The <.., false> instantiations compile what they compiled without it.
 #pragma once
+#include <type_traits>
 #include "gam_search.h"
 
 #define GAM_RB_NT 256
@@ -136,6 +141,48 @@ static inline size_t gam_rb_ws_floats(int W, int S, int V, int H, int JH, int L)
   return gam_rb_pool(W, S) * ((size_t)L * 2 * H + JH) + Wp * (size_t)((V + 3) & ~3);
 }
 
+// ---- the stream form (template <bool STREAM>; gam_rnnt_beam_stream.h holds its contract and its kernel): the record one stream's search
+// is carried in from call to call, and what a call adds to GamRnntBeamArgs.  The batch instantiations read none of it.
+#define GAM_RB_STREAM_REBASE 256          // a power of two
+#define GAM_RB_F_BEGIN 1                  // include/gigaam_hip.h GAM_RNNT_STREAM_BEGIN / _END
+#define GAM_RB_F_END 2
+#define GAM_RB_ST_BEGUN 0x72626d73        // phase words; anything else, zeros included, is "not begun"
+#define GAM_RB_ST_ENDED 0x72626d65
+
+struct GamRbStreamHdr {
+  int phase, W, S, V, H, JH, L;
+  int hw_gen, lm_gen;
+  int nb, ncount;                 // beam size, prefix-trie nodes so far
+  int next, max_frames, t0;       // the next stream frame, the node pool's frames, the frame BEGIN started at
+  int pad0[2];
+  double off, cb_off, lm_off;     // what the renormalisations / the rebases of the committed bonus / of the LM term subtracted so far
+  int pad1[10];
+};
+struct GamRbStreamEntry {         // one entry of A list 0; the LM fields are zeros without the LM, every field is zero beyond the beam
+  unsigned long long h;
+  int len;
+  float sc;
+  int hn;
+  float acc, cb;
+  int node, slot, pad0;
+  unsigned long long wh;
+  int4 ctx;
+  float lm, dl;
+  int cw, pad1;
+};
+static_assert(sizeof(GamRbStreamHdr) == 128 && offsetof(GamRbStreamHdr, off) == 64 && sizeof(GamRbStreamEntry) == 80 &&
+              offsetof(GamRbStreamEntry, ctx) == 48, "RNN-T beam stream state layout");
+#define GAM_RB_STREAM_HDR_BYTES (sizeof(GamRbStreamHdr) + 32 * sizeof(GamRbStreamEntry))      // 2688: the slot pool starts here
+
+struct GamRbStreamArgs {
+  int n, t_base, max_frames, flags;     // max_frames: what the caller's state_bytes hold for this W, S and head
+  int hw_gen, lm_gen;
+  void* state;
+  int* status;           // [1]
+  double* score;         // [1]   (END only, as ids / frames / counts[0] of GamRnntBeamArgs)
+  double* logp;          // [1]
+};
+
 // acc[g][rt] += A[16 rt + i][k] * Wt[k][g * H + j0 + c] over k < H: A rows from LDS (row stride H + 4), Wt k-major with 4H columns.
 // MFMA lane (i = lane & 15, q = lane >> 4): A row i, weight column j0 + i, k = k0 + 4 q + e in the e-th MFMA of a group of four.
 template <int RT>
@@ -157,17 +204,20 @@ __device__ __forceinline__ void gam_rb_gates_mm(f32x4 (&acc)[4][2], const float*
   }
 }
 
-template <int RT, bool LM, bool NBEST>
-__device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a);
+// STREAM: a holds one utterance (encp [n, JH], ids / frames [cap], counts [1], ws = the logit rows alone); x the call and the record.
+template <int RT, bool LM, bool NBEST, bool STREAM>
+__device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a, const GamRbStreamArgs& x);
 
 template <bool LM, bool NBEST = false>
 __global__ __launch_bounds__(GAM_RB_NT) void gam_rnnt_beam_kernel(GamRnntBeamArgs a) {
-  if (a.W > 16) gam_rb_body<2, LM, NBEST>(a);
-  else gam_rb_body<1, LM, NBEST>(a);
+  if (a.W > 16) gam_rb_body<2, LM, NBEST, false>(a, GamRbStreamArgs{});
+  else gam_rb_body<1, LM, NBEST, false>(a, GamRbStreamArgs{});
 }
 
-template <int RT, bool LM, bool NBEST>
-__device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
+template <int RT, bool LM, bool NBEST, bool STREAM>
+__device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a, const GamRbStreamArgs& x) {
+  static_assert(!(STREAM && NBEST), "there is no N-best over a stream");
+  using Node = typename std::conditional<STREAM, int4, int2>::type;      // {parent, token, stream frame, 0} | {parent, token << 13 | frame}
   extern __shared__ uint4 gam_smem_rbeam[];
   unsigned char* p = reinterpret_cast<unsigned char*>(gam_smem_rbeam);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -235,26 +285,66 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
   }
   int* hw_sh = reinterpret_cast<int*>(U + hw_off);
 
-  int T = a.enc_len[b];
-  T = T < 0 ? 0 : (T > Tp ? Tp : T);
-  if (T == 0) {
-    if constexpr (NBEST) gam_beam_emit_empty(a.nb, b, a.counts, a.score, a.logp, tid);
-    else if (tid == 0) {
-      a.counts[b] = 0;
-      a.score[b] = 0.f;
-      a.logp[b] = 0.f;
+  int T;
+  // the stream's call against its record (every thread reads the header before the first barrier; it is written behind the last)
+  GamRbStreamHdr* hdr = nullptr;
+  GamRbStreamEntry* ent = nullptr;
+  bool begin = true;
+  int maxf = 0, t0 = 0, nb0 = 1, ncount0 = 0;
+  double off0 = 0.0, cb_off = 0.0, lm_off = 0.0;
+  if constexpr (STREAM) {
+    hdr = static_cast<GamRbStreamHdr*>(x.state);
+    ent = reinterpret_cast<GamRbStreamEntry*>(hdr + 1);
+    begin = (x.flags & GAM_RB_F_BEGIN) != 0;
+    maxf = x.max_frames; t0 = x.t_base;
+    bool ok = true;
+    if (!begin) {
+      ok = hdr->phase == GAM_RB_ST_BEGUN && hdr->next == x.t_base && hdr->W == W && hdr->S == S && hdr->V == V && hdr->H == H &&
+           hdr->JH == JH && hdr->L == L && hdr->hw_gen == x.hw_gen && hdr->lm_gen == x.lm_gen && hdr->max_frames <= x.max_frames &&
+           hdr->nb >= 0 && hdr->nb <= W && hdr->ncount >= 0;
+      if (ok) {
+        maxf = hdr->max_frames; t0 = hdr->t0; nb0 = hdr->nb; ncount0 = hdr->ncount;
+        off0 = hdr->off; cb_off = hdr->cb_off; lm_off = hdr->lm_off;
+      }
     }
-    return;
+    ok = ok && (long long)x.t_base + x.n - t0 <= (long long)maxf && (long long)x.t_base + x.n < 2147483648ll;
+    if (!ok) {
+      if (tid == 0) x.status[0] = 0;
+      return;
+    }
+    T = x.n;
+  } else {
+    T = a.enc_len[b];
+    T = T < 0 ? 0 : (T > Tp ? Tp : T);
+    if (T == 0) {
+      if constexpr (NBEST) gam_beam_emit_empty(a.nb, b, a.counts, a.score, a.logp, tid);
+      else if (tid == 0) {
+        a.counts[b] = 0;
+        a.score[b] = 0.f;
+        a.logp[b] = 0.f;
+      }
+      return;
+    }
   }
   const int* hw = a.hw.trie;
   if (hw != nullptr && a.hw.lds) {
     for (int i = tid; i < a.hw.words; i += GAM_RB_NT) hw_sh[i] = a.hw.trie[i];
     hw = hw_sh;
   }
-  float* slots = a.ws + (size_t)b * a.ws_stride;
-  float* lg = slots + (size_t)P * SS;                              // [Wp][LGS] logits
-  int2* nodes = a.nodes + (size_t)b * Tp * S * W;
-  const float* encb = a.encp + (size_t)b * Tp * JH;
+  float *slots, *lg;                                               // [P][SS] state slots, [Wp][LGS] logits
+  Node* nodes;
+  const float* encb;
+  if constexpr (STREAM) {     // the slots and the nodes are the record's; the logit rows are scratch
+    slots = reinterpret_cast<float*>(ent + 32);
+    lg = a.ws;
+    nodes = reinterpret_cast<Node*>(slots + (size_t)P * SS);
+    encb = a.encp;
+  } else {
+    slots = a.ws + (size_t)b * a.ws_stride;
+    lg = slots + (size_t)P * SS;
+    nodes = a.nodes + (size_t)b * Tp * S * W;
+    encb = a.encp + (size_t)b * Tp * JH;
+  }
 
   // wave 0: rebuild the free list from the slots the A[0] list (the beam) holds
   auto rebuild_free = [&](int nb) {
@@ -357,10 +447,23 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
     __syncthreads();
   };
 
-  // ---- the empty hypothesis: predict(None, None) into slot 0
+  // ---- the empty hypothesis: predict(None, None) into slot 0   (STREAM without BEGIN: the record's beam instead)
   if constexpr (LM)
     for (int v = tid; v < V; v += GAM_RB_NT) cls_sh[v] = (signed char)a.lm.lm_cls[v];
-  if (tid == 0) {
+  if constexpr (STREAM) {
+    if (!begin && wave == 0) {
+      if (lane < nb0) {
+        const GamRbStreamEntry& e = ent[lane];
+        ah[lane] = e.h; alen[lane] = e.len; asc[lane] = e.sc; ahn[lane] = e.hn; aacc[lane] = e.acc; acb[lane] = e.cb;
+        anode[lane] = e.node; aslot[lane] = min(max(e.slot, 0), P - 1);
+        if constexpr (LM) {
+          mctx[lane] = e.ctx; mwh[lane] = e.wh; mlm[lane] = e.lm; mdl[lane] = e.dl; mcw[lane] = e.cw;
+        }
+      }
+      if (lane == 0) cnt[0] = nb0;
+    }
+  }
+  if (begin && tid == 0) {
     ah[0] = 0ull; alen[0] = 0; asc[0] = 0.f; ahn[0] = 0; aacc[0] = 0.f; acb[0] = 0.f; anode[0] = -1;
     aslot[0] = 0; atok[0] = V; apar[0] = -1;
     cnt[0] = 1;
@@ -370,8 +473,8 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
     }
   }
   __syncthreads();
-  predict(0, 1);
-  if (wave == 0) rebuild_free(1);
+  if (begin) predict(0, 1);
+  if (wave == 0) rebuild_free(begin ? 1 : nb0);
   __syncthreads();
 
   auto brank = [&](int i) {   // rank of B entry i
@@ -379,12 +482,13 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
     if constexpr (LM) r += mlm[64 + i];
     return r;
   };
-  double off = 0.0;        // wave 0: what the renormalisations subtracted so far
-  int ncount = 0;          // wave 0: prefix-trie nodes of this utterance so far
+  double off = off0;       // wave 0: what the renormalisations subtracted so far
+  int ncount = ncount0;    // wave 0: prefix-trie nodes of this utterance so far
   for (int t = 0; t < T; ++t) {
     int nB = 0;            // wave 0: entries of B
     int fptr = 0;          // wave 0: free slots taken this frame
     const float* et = encb + (size_t)t * JH;
+    const int ts = STREAM ? x.t_base + t : t;      // the stream frame: what a node records, what the rebase goes by
     for (int s = 0; s <= S; ++s) {
       const int cur = s & 1, nx = cur ^ 1;
       const int n = cnt[cur];
@@ -538,7 +642,8 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
             const int v = key - r * GAM_BEAM_KEY_STRIDE - 1;
             const int o = cur * 32 + r, d = nx * 32 + lane;
             const int idx = ncount + lane;
-            nodes[idx] = make_int2(anode[o], (v << 13) | t);
+            if constexpr (STREAM) nodes[idx] = make_int4(anode[o], v, ts, 0);
+            else nodes[idx] = make_int2(anode[o], (v << 13) | t);
             ah[d] = ah[o] * GAM_BEAM_HASH_P + (unsigned long long)(v + 1);
             alen[d] = alen[o] + 1;
             asc[d] = csc[q];
@@ -587,13 +692,26 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
         float M = gam_beam_unord((unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sel >> 32), 0));
         if constexpr (LM) M -= mlm[64 + __builtin_amdgcn_readlane((int)(sel & 0xffff), 0)];     // (scores keep O(one frame))
         off += (double)M;
+        float cb0 = 0.f, lm0 = 0.f;      // STREAM, at a rebase frame: the best kept entry's committed bonus and LM term leave every entry's
+        if constexpr (STREAM) {
+          if (ts > 0 && (ts & (GAM_RB_STREAM_REBASE - 1)) == 0) {
+            const int i0 = __builtin_amdgcn_readlane((int)(sel & 0xffff), 0);
+            cb0 = bcb[i0];
+            cb_off += (double)cb0;
+            if constexpr (LM) {
+              lm0 = mlm[64 + i0];
+              lm_off += (double)lm0;
+            }
+          }
+        }
         if (lane < nb) {
           const int i = (int)(sel & 0xffff);
           ah[lane] = bh[i]; alen[lane] = blen[i]; asc[lane] = bsc[i] - M;
-          ahn[lane] = bhn[i]; aacc[lane] = bacc[i]; acb[lane] = bcb[i];
+          ahn[lane] = bhn[i]; aacc[lane] = bacc[i]; acb[lane] = STREAM ? bcb[i] - cb0 : bcb[i];
           anode[lane] = bnode[i]; aslot[lane] = bslot[i];
           if constexpr (LM) {
-            mctx[lane] = mctx[64 + i]; mwh[lane] = mwh[64 + i]; mlm[lane] = mlm[64 + i]; mdl[lane] = mdl[64 + i]; mcw[lane] = mcw[64 + i];
+            mctx[lane] = mctx[64 + i]; mwh[lane] = mwh[64 + i]; mlm[lane] = STREAM ? mlm[64 + i] - lm0 : mlm[64 + i];
+            mdl[lane] = mdl[64 + i]; mcw[lane] = mcw[64 + i];
           }
         }
       }
@@ -608,6 +726,42 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
   // ---- final pick (pending hotword bonus dropped; with the LM the last word and </s> added), backtrack
   if (wave == 0) {
     const int nb = cnt[0];
+    if constexpr (STREAM) {
+      // ---- store the record: all 32 entries (zeros beyond the beam), then the header
+      if (lane < 32) {
+        GamRbStreamEntry e;
+        memset(&e, 0, sizeof e);
+        if (lane < nb) {
+          e.h = ah[lane]; e.len = alen[lane]; e.sc = asc[lane]; e.hn = ahn[lane]; e.acc = aacc[lane]; e.cb = acb[lane];
+          e.node = anode[lane]; e.slot = aslot[lane];
+          if constexpr (LM) {
+            e.wh = mwh[lane]; e.ctx = mctx[lane]; e.lm = mlm[lane]; e.dl = mdl[lane]; e.cw = mcw[lane];
+          }
+        }
+        ent[lane] = e;
+      }
+      const bool end = (x.flags & GAM_RB_F_END) != 0;
+      if (lane == 0) {
+        hdr->phase = end ? GAM_RB_ST_ENDED : GAM_RB_ST_BEGUN;
+        hdr->W = W; hdr->S = S; hdr->V = V; hdr->H = H; hdr->JH = JH; hdr->L = L;
+        hdr->hw_gen = x.hw_gen; hdr->lm_gen = x.lm_gen;
+        hdr->nb = nb; hdr->ncount = ncount;
+        hdr->next = x.t_base + x.n; hdr->max_frames = maxf; hdr->t0 = t0;
+        hdr->pad0[0] = hdr->pad0[1] = 0;
+        hdr->off = off; hdr->cb_off = cb_off; hdr->lm_off = lm_off;
+        for (int i = 0; i < 10; ++i) hdr->pad1[i] = 0;
+        x.status[0] = 1;
+      }
+      if (!end) return;
+      if (x.t_base + x.n == t0) {      // a stream without a frame
+        if (lane == 0) {
+          a.counts[0] = 0;
+          x.score[0] = 0.0;
+          x.logp[0] = 0.0;
+        }
+        return;
+      }
+    }
     float val = lane < nb ? asc[lane] + acb[lane] : -INFINITY;
     float lmf = 0.f;
     if constexpr (LM) {
@@ -636,24 +790,39 @@ __device__ __forceinline__ void gam_rb_body(const GamRnntBeamArgs& a) {
     if (best < 0) {
       if (lane == 0) {
         a.counts[b] = 0;
-        a.score[b] = -INFINITY;
-        a.logp[b] = -INFINITY;
+        if constexpr (STREAM) {
+          x.score[0] = -(double)INFINITY;
+          x.logp[0] = -(double)INFINITY;
+        } else {
+          a.score[b] = -INFINITY;
+          a.logp[b] = -INFINITY;
+        }
       }
     } else if (lane == best) {
       const double lp_ = (double)asc[lane] + off;
-      a.logp[b] = (float)lp_;
-      if constexpr (LM) a.score[b] = (float)(lp_ + (double)acb[lane] + (double)lmf);
-      else a.score[b] = (float)(lp_ + (double)acb[lane]);
+      if constexpr (STREAM) {      // fp64, with what the rebases took out
+        x.logp[0] = lp_;
+        x.score[0] = (LM ? lp_ + (double)acb[lane] + (double)lmf : lp_ + (double)acb[lane]) + cb_off + lm_off;
+      } else {
+        a.logp[b] = (float)lp_;
+        if constexpr (LM) a.score[b] = (float)(lp_ + (double)acb[lane] + (double)lmf);
+        else a.score[b] = (float)(lp_ + (double)acb[lane]);
+      }
       const int n = alen[lane] < a.cap ? alen[lane] : a.cap;
       a.counts[b] = n;
       int* ids = a.ids + (size_t)b * a.cap;
       int* fr = a.frames + (size_t)b * a.cap;
       int node = anode[lane];
       for (int i = alen[lane] - 1; i >= 0; --i) {
-        const int2 e = nodes[node];
+        const Node e = nodes[node];
         if (i < n) {
-          ids[i] = e.y >> 13;
-          fr[i] = e.y & 8191;
+          if constexpr (STREAM) {
+            ids[i] = e.y;
+            fr[i] = e.z;
+          } else {
+            ids[i] = e.y >> 13;
+            fr[i] = e.y & 8191;
+          }
         }
         node = e.x;
       }

@@ -543,6 +543,44 @@ class RnntGreedyStream(_ResumableStream):
                                  "max_symbols or the head changed, or more rows than max_frames)")
 
 
+class RnntBeamStream(_ResumableStream):
+    """RNN-T beam search over one stream of any length fed in pieces (``HipEngine.rnnt_beam_stream``; gam_op_rnnt_beam_stream): owns
+    the state record -- the beam, the predictor-state slots and the node pool of ``max_frames * max_symbols * beam_size`` nodes -- and
+    the result, a ``BeamStreamDecoded`` whose one dimension is ``cap = max_frames * max_symbols`` tokens.  The hotword set and the LM
+    are those the engine holds at the first ``push``; the kernel refuses the calls that follow a later ``set_hotwords`` / ``set_lm``.
+    ``push`` enqueues the next rows of the encoder projection (``HipEngine.rnnt_encp``), ``finish`` ends the stream (the END call makes
+    the final pick and the backtrack) and returns the ``BeamStreamDecoded`` (frames are stream frames); neither synchronises the host."""
+    BEGIN, END = 1, 2      # include/gigaam_hip.h GAM_RNNT_STREAM_BEGIN / _END
+    NAME, MAKER = "RNN-T beam stream", "rnnt_beam_stream"
+
+    def __init__(self, engine: "HipEngine", beam_size: int, max_frames: int, max_symbols: int):
+        engine._check_beam(beam_size, max_symbols)
+        self.beam_size, self.max_frames, self.max_symbols = int(beam_size), int(max_frames), int(max_symbols)
+        nbytes = int(engine.lib.gam_rnnt_beam_stream_bytes(engine._h, self.beam_size, self.max_symbols, self.max_frames))
+        if nbytes < 0:
+            engine._check(-1, "gam_rnnt_beam_stream_bytes")
+        self.state_bytes = nbytes
+        self.cap = self.max_frames * self.max_symbols
+        super().__init__(engine, torch.zeros(((nbytes + 3) // 4,), dtype=_I32, device=engine.device),
+                         BeamStreamDecoded.empty(engine.device, self.cap))
+        self.out.whole[:BeamStreamDecoded.HEAD_WORDS].zero_()      # (a stream refused before its END call has status 0, count 0)
+
+    def _launch(self, encp_rows: Optional[Tensor], v: int, flags: int) -> None:
+        self.engine.op_rnnt_beam_stream(encp_rows, self.t_next, flags, self.beam_size, self.max_symbols, self.state, self.state_bytes,
+                                        self.out)
+
+    def _empty_v(self) -> int:
+        return int(self.engine.cfg.joint_hidden)
+
+    def push(self, encp_rows: Tensor, overlap: bool = False):
+        """``_ResumableStream.push`` of rows of the encoder projection, f32 [n, joint_hidden] (n = 0 is legal)."""
+        encp_rows = self.engine._dev(encp_rows, torch.float32)
+        if encp_rows.dim() != 2 or int(encp_rows.shape[1]) != self._empty_v():
+            raise GigaAMHipError(f"{self.NAME}: encp rows must be [n, {self._empty_v()}], got {tuple(encp_rows.shape)}")
+        self.v = self._empty_v()
+        return self._call(encp_rows, self.v, 0, overlap)
+
+
 class AlignedLong(_Packed):
     """What ``op_ctc_align_long`` returns: every output of the long-utterance alignment as a view of ONE i32 device buffer (``whole``)
     that reaches the host in ONE copy (``host``), like ``Aligned``.  Layout: score (f64 bits, 2 words) | loglik (f64 bits, 2 words) |
@@ -1682,6 +1720,30 @@ class HipEngine:
         of ``rnnt_encp`` with ``push``, end it with ``finish``.  One workgroup, the one-workgroup kernel's arithmetic (cluster size 0);
         the predictor's state is carried from call to call, so the stream is decoded as ONE utterance wherever it is cut."""
         return RnntGreedyStream(self, max_frames, max_symbols)
+
+    RNNT_BEAM_STREAM_REBASE = 256      # gam_rnnt_beam.h GAM_RB_STREAM_REBASE
+
+    def op_rnnt_beam_stream(self, encp_rows: Optional[Tensor], t_base: int, flags: int, beam_size: int, max_symbols: int, state: Tensor,
+                            state_bytes: int, out: BeamStreamDecoded, cap: Optional[int] = None) -> None:
+        """gam_op_rnnt_beam_stream as it is, on the current stream: rows ``encp_rows`` f32 [n, joint_hidden] (None: n = 0) are stream
+        frames ``t_base`` .., ``flags`` of ``RnntBeamStream.BEGIN`` / ``END``, ``state`` the i32 buffer of gam_rnnt_beam_stream_bytes
+        (``state_bytes`` of it are the record), ``out`` the stream's result (``cap``: how many of its token columns the library may
+        use, default all).  ``RnntBeamStream`` is the caller that keeps ``t_base`` and the flags right."""
+        n = 0 if encp_rows is None else int(encp_rows.shape[0])
+        cap = int(out.max_frames) if cap is None else min(int(cap), int(out.max_frames))
+        rc = self.lib.gam_op_rnnt_beam_stream(self._h, _ptr(encp_rows if n else None), n, int(t_base), int(flags), int(beam_size),
+                                              int(max_symbols), _ptr(state), min(int(state_bytes), state.numel() * 4), _ptr(out.ids),
+                                              _ptr(out.frames), cap, _ptr(out.count), _ptr(out.score), _ptr(out.logp), _ptr(out.status),
+                                              self._stream())
+        self._check(rc, "gam_op_rnnt_beam_stream")
+
+    def rnnt_beam_stream(self, beam_size: int, max_frames: int, max_symbols: int) -> RnntBeamStream:
+        """A resumable RNN-T beam search over one stream of at most ``max_frames`` frames (gam_op_rnnt_beam_stream), with the hotwords
+        of ``set_hotwords`` and the LM of ``set_lm``: feed it rows of ``rnnt_encp`` with ``push``, end it with ``finish``.  One
+        workgroup; the beam with every hypothesis's predictor, hotword and LM state is carried from call to call, so the stream is
+        searched as ONE utterance wherever it is cut.  After a later ``set_hotwords`` / ``set_lm`` the kernel refuses the stream's
+        calls (status 0, ``host()`` raises)."""
+        return RnntBeamStream(self, beam_size, max_frames, max_symbols)
 
     def rnnt_predict(self, labels: Optional[Tensor], state: Optional[Tuple[Tensor, Tensor]], batch_size: int = 1):
         """One predictor step (reference RNNTDecoder.predict, gigaam/decoder.py:85-102): labels i [B] or None (zero input),

@@ -818,7 +818,8 @@ class GigaAMASR(GigaAM):
                             hotwords: Optional[Sequence[Union[str, List[int]]]] = None, hotword_boost: float = 2.0, lm=None,
                             lm_weight: float = 0.5, word_bonus: float = 1.0, chunk_length_s: float = 20.0,
                             stride_length_s: Optional[float] = None, pause_s: float = 1.0, max_segment_s: float = 22.0,
-                            stream_search: bool = False, stream_decode: bool = False, **kwargs: Any) -> LongformTranscriptionResult:
+                            stream_search: bool = False, stream_decode: Union[bool, str] = False,
+                            **kwargs: Any) -> LongformTranscriptionResult:
         """Segment -> zero-padded batches of ``fr_batch_size`` -> transcribe -> stitch
         (reference model.py:195-259).  The reference segments with pyannote's VAD
         (gated third-party model, not installable here); pass ``speech_regions=[(s,e),..]``,
@@ -843,7 +844,11 @@ class GigaAMASR(GigaAM):
         ``vad="windows", stream_decode=True`` (RNN-T heads) is the same detector-free route for a transducer: the windows' encoder
         frames are stitched as the encoder half of the joint, and the resumable greedy kernel walks them in order, carrying its
         predictor state across the seams (``_transcribe_windows_rnnt``): the predictor sees the file as ONE history, where the
-        speech-region route starts a new one per chunk.  It decodes greedily: beam options are errors."""
+        speech-region route starts a new one per chunk.  It decodes greedily: beam options are errors.
+
+        ``vad="windows", stream_decode="beam"`` walks the same stitched rows with the resumable beam search
+        (``_transcribe_windows_rnnt_beam``) for a model that ``set_decoding(beam_size= / hotwords= / lm=)`` has put into beam mode:
+        the width, the hotwords and the LM are the decoding object's; the predictor and the LM see the file as ONE history."""
         windows = self._windows_route(kwargs, refuse=False)
         search = beam_size is not None or hotwords is not None or lm is not None
         if stream_decode:      # (every error before any audio is read)
@@ -855,6 +860,14 @@ class GigaAMASR(GigaAM):
             if not isinstance(self.decoding, _decoding.RNNTGreedyDecoding):
                 raise TypeError("stream_decode needs an RNN-T head")
             self._beam_width(beam_size, hotwords, lm)      # (per-call beam options on an RNN-T model: the TypeError they always raise)
+            if isinstance(stream_decode, str):
+                if stream_decode != "beam":
+                    raise ValueError(f'stream_decode={stream_decode!r}: True (the resumable greedy decode) or "beam" (the resumable beam search)')
+                if not isinstance(self.decoding, _decoding.RNNTBeamDecoding):
+                    raise ValueError('stream_decode="beam" needs a beam search: select one with set_decoding(beam_size=...)')
+                self._windows_route(kwargs)
+                return self._transcribe_windows_rnnt_beam(wav_file, word_timestamps, fr_batch_size, chunk_length_s, stride_length_s, pause_s,
+                                                          max_segment_s)
             if isinstance(self.decoding, _decoding.RNNTBeamDecoding):
                 raise ValueError("stream_decode=True decodes greedily: the RNN-T beam kernel stops at 8192 frames, so the beam decoding "
                                  "selected by set_decoding is not available over the stitched stream (set_decoding() selects greedy again)")
@@ -1064,6 +1077,29 @@ class GigaAMASR(GigaAM):
 
             return self._windows_run(audio, plan, fr_batch_size, stream=stream, overlap=overlap, ended=ended,
                                      head=(eng.rnnt_encp, int(eng.cfg.joint_hidden)))["rows"]
+
+        ids, frames = self._file_run(run)
+        return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)
+
+    def _transcribe_windows_rnnt_beam(self, wav_file: str, word_timestamps: bool, fr_batch_size: int, chunk_length_s: float,
+                                      stride_length_s: Optional[float], pause_s: float, max_segment_s: float) -> LongformTranscriptionResult:
+        """``transcribe_longform(vad="windows", stream_decode="beam")`` on an RNN-T head in beam mode (``set_decoding``): the plan,
+        the stitch and the pushes of ``_transcribe_windows_rnnt`` into a resumable beam search (engine.RnntBeamStream,
+        gam_op_rnnt_beam_stream) with the decoding object's width, hotwords and LM, set as the RNN-T ``transcribe`` sets them
+        (GAM_RNNT_STREAM_OVERLAP=0: pushes on the launch stream, the A/B switch); then the END call and ONE collect.  The predictor
+        and the LM see the file as ONE history: <s> at its first frame, </s> at its end."""
+        audio, plan = self._plan_windows(wav_file, chunk_length_s, stride_length_s, rnnt=True)
+        if not plan.windows:
+            return LongformTranscriptionResult(segments=[])
+        eng, dec = self.head.engine, self.decoding
+        overlap = os.environ.get("GAM_RNNT_STREAM_OVERLAP", "1") != "0"
+
+        def run():      # (a rerun under GAM_GEMM_F32 comes here again: a new stream, BEGIN)
+            eng.set_hotwords(dec.hotword_ids(dec.hotwords), dec.hotword_boost)
+            eng.set_lm(dec.lm, dec.tokenizer, dec.lm_weight, dec.word_bonus)
+            h = self._windows_run(audio, plan, fr_batch_size, stream=eng.rnnt_beam_stream(dec.beam_size, plan.t_total, int(dec.max_symbols)),
+                                  overlap=overlap, head=(eng.rnnt_encp, int(eng.cfg.joint_hidden)))
+            return h["ids"].tolist(), h["frames"].tolist()
 
         ids, frames = self._file_run(run)
         return self._windows_result(plan, ids, frames, word_timestamps, pause_s, max_segment_s)

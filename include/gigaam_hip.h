@@ -393,6 +393,30 @@ int gam_rnnt_beam(gam_handle* h, const float* encoded, const int32_t* enc_len, i
  * predictor and joint weights, hotwords and LM. */
 int gam_op_rnnt_beam(gam_handle* h, const float* encp, const int32_t* enc_len, int B, int64_t Tp, int W, int max_symbols, int32_t* ids,
                      int32_t* frames, int32_t* counts, float* score, float* logp, void* stream);
+/* The same search over ONE stream of any length fed in pieces (gigaam_amd/csrc/gam_rnnt_beam_stream.h): one workgroup, the batch
+ * kernel's own search text, so a stream of fewer frames than the rebase period in one BEGIN | END call gives gam_op_rnnt_beam's bits,
+ * and a stream cut anywhere gives the bits of the uncut one.  Rows 0 .. n - 1 of encp f32 [n, joint_hidden] are stream frames
+ * t_base .. t_base + n - 1.  state: a caller-owned record of gam_rnnt_beam_stream_bytes(h, W, max_symbols, max_frames) bytes (a
+ * header, the beam, the predictor-state slots and a prefix-trie pool of max_frames * max_symbols * W nodes of 16 bytes) that carries
+ * the search -- the predictor, the hotword and the LM state of every hypothesis -- from call to call.  flags: GAM_RNNT_STREAM_BEGIN
+ * starts a stream at this call's t_base (any value >= 0) from the empty hypothesis, whatever the record held; GAM_RNNT_STREAM_END
+ * makes the final pick and the backtrack behind the call's rows.  n = 0 is legal with either flag, both or none.  The hotword set and
+ * the LM are the handle's at BEGIN.
+ *   ids / frames i32 [cap], count i32 [1], score / logp f64 [1]: written by the END call alone; at most cap tokens (the first ones),
+ *   frames are stream frames; score = logp + committed bonus + LM term.  A stream without a frame: count 0, score = logp = 0.
+ *   status i32 [1]: 1 = accepted; 0 = refused, nothing else written and the record unchanged.  Refused without BEGIN: the record was
+ *   not begun or has ended; t_base is not the record's next frame; W, max_symbols or the head's sizes differ from what BEGIN recorded;
+ *   gam_set_hotwords or gam_set_lm was called since BEGIN.  Refused with or without BEGIN: more frames since BEGIN than the record's
+ *   node pool holds.  The stream carries on with the right call afterwards.
+ * Errors without a launch: a head that is not RNN-T; W, max_symbols, V, pred_hidden or joint_hidden outside gam_rnnt_beam's limits;
+ * n < 0, t_base < 0 or t_base + n >= 2^31; cap < 0; unknown flags; state_bytes below the record's size without nodes; a state that is not 16-byte aligned; a NULL buffer
+ * (encp may be NULL when n = 0); an LM whose classes are not for this V; a hotword id >= V - 1; LDS over the limit.
+ * gam_rnnt_beam_stream_bytes is < 0 outside the limits (max_frames * max_symbols * W must stay below 2^31).  Decode class; no host
+ * synchronisation. */
+int64_t gam_rnnt_beam_stream_bytes(gam_handle* h, int W, int max_symbols, int64_t max_frames);
+int gam_op_rnnt_beam_stream(gam_handle* h, const float* encp, int64_t n, int64_t t_base, int flags, int W, int max_symbols, void* state,
+                            int64_t state_bytes, int32_t* ids, int32_t* frames, int64_t cap, int32_t* count, double* score, double* logp,
+                            int32_t* status, void* stream);
 
 /* N-best of the RNN-T beam search: the same search (same kernel up to its last frame, same hotwords and LM, same limits), then the N
  * best entries of its final beam instead of the best one, 1 <= N <= W <= 32 (an error otherwise, without a launch).  An entry's value
